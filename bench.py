@@ -14,6 +14,11 @@ over N >= 2; --prompts-per-gpu overrides.  Inputs (ids, weights, initial latents
 region.  EVERY timed step's latents are kept and checked after the timed region (finite, and within REL_STEP_TOL of the
 first step's: the workload repeats the same inputs); a violation prints the per-step table and exits non-zero.
 Prints ONE JSON line on rank 0.
+
+A plain run sets up, warms up, times the steps and prints the line.  --full adds the side measurements, each of which
+takes work of its own outside the timed steps: the CPU baseline and the forward check against the CPU oracle, the live
+rocprofv3 --pmc traffic passes, the per-kernel rooflines and (N = 1) the 8-prompt scale_origin.  --dump-outputs DIR
+writes the last timed step's outputs (latents, images) as float32 .npy files for output-by-output comparison of builds.
 """
 import argparse
 import json
@@ -37,6 +42,8 @@ UNET_TFLOP_SD21_768 = 2.149              # 1074.6 GMAC, SD
 PEAK_BF16_TFLOPS = 2500.0                # MI355X dense bf16 MFMA (MI355X_MICROARCH.md)
 REL_STEP_TOL = 1e-6                      # rel-L2 of a step's final latents vs the first timed step's: same inputs every step and
                                          # fixed-order reductions everywhere, so the steps are bit-identical (0 expected)
+DUMP_BUDGET_BYTES = 60 * 10**6           # --dump-outputs: the arrays of all ranks together (within 64 MB with the .npy headers)
+DUMP_SAMPLE_SEED = 0
 
 
 def gpu_state_dict(builder, cfg, dev, seed):
@@ -314,6 +321,27 @@ class ClockSampler:
             "samples": max(len(self.clk), len(self.pow)), "source": self.source}
 
 
+def dump_outputs(out_dir, latents, images, rank, world):
+  """What generate_images(..., decode=True) returned to its caller in the last timed step, as float32 .npy files: latents.npy
+  (all ranks' final latents, written by rank 0) and images.npy (this rank's uint8 images as float32; images_rank<r>.npy when
+  N > 1).  Images beyond this rank's share of DUMP_BUDGET_BYTES are replaced by a sample at fixed seeded positions of the
+  flattened array (images.npy 1-D, positions in images_sample_index.npy as float64): the same positions for the same shape."""
+  import numpy as np
+  os.makedirs(out_dir, exist_ok=True)
+  lat = latents.float().cpu().numpy()
+  if rank == 0:
+    np.save(os.path.join(out_dir, "latents.npy"), lat)
+  tag = "" if world == 1 else f"_rank{rank}"
+  img = images.cpu().numpy().astype(np.float32)
+  share = (DUMP_BUDGET_BYTES - lat.nbytes) // world
+  if img.nbytes > share:
+    cap = share // (4 + 8)                # a float32 value and its float64 position per sampled element
+    idx = np.sort(np.random.default_rng(DUMP_SAMPLE_SEED).choice(img.size, size=cap, replace=False))
+    np.save(os.path.join(out_dir, f"images_sample_index{tag}.npy"), idx.astype(np.float64))
+    img = img.reshape(-1)[idx]
+  np.save(os.path.join(out_dir, f"images{tag}.npy"), img)
+
+
 def respawn_under_torchrun(a):
   """`python bench.py --gpus N` without a launcher: re-execute under torch.distributed.run, one rank per GPU."""
   with socket.socket() as sk:
@@ -334,6 +362,10 @@ def main():
   ap.add_argument("--prompts-per-gpu", type=int, default=0, help="default: 4 at --gpus 1 (BASELINE configs[1]), 8 at --gpus > 1 (configs[2]), 16 with --config c5 (configs[4])")
   ap.add_argument("--total-prompts", type=int, default=0, help="global batch (default prompts-per-gpu x gpus); any value: uneven and empty shards are "
                   "legal (contiguous split, first B %% N ranks take one more)")
+  ap.add_argument("--full", action="store_true", help="also run the side measurements: cpu_baseline + forward_check, roofline.traffic "
+                  "(rocprofv3 --pmc passes), roofline_kernels and the N = 1 line's scale_origin (each has its --no-* switch below)")
+  ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="write the last timed step's outputs to DIR/<name>.npy (float32, "
+                  f"at most {DUMP_BUDGET_BYTES // 10**6} MB in all: a fixed seeded sample of the images beyond that)")
   ap.add_argument("--no-scale-origin", action="store_true", help="skip the 8-prompts-per-GPU side measurement of the N = 1 line")
   ap.add_argument("--infer-steps", type=int, default=50)
   ap.add_argument("--prompt-len", type=int, default=24)
@@ -351,6 +383,8 @@ def main():
   ap.add_argument("--scale-origin-value", type=float, default=0.0, help="images/s of the N = 1 line's scale_origin (8 prompts on one GPU): the "
                   "N > 1 line then carries efficiency_vs_scale_origin = value / (N x this)")
   a = ap.parse_args()
+  if a.steps < 1:
+    ap.error("--steps must be at least 1")
 
   if a.share_gpu:
     # test rig: several ranks on ONE GPU.  The UNet's in-kernel GroupNorm finishes wait inside a launch and need the device's CUs to themselves
@@ -391,11 +425,12 @@ def main():
   P_local = hi - lo                        # == P unless --total-prompts makes the shards uneven
   P_max = (B_total + world - 1) // world
   # the N = 1 headline line also carries the 8-prompts-per-GPU figure (the per-GPU load of the N > 1 lines): the origin of the
-  # driver's 1 -> 8 GPU weak-scaling curve must be measured at the same per-GPU work as its other points
+  # driver's 1 -> 8 GPU weak-scaling curve must be measured at the same per-GPU work as its other points.  The pipeline is sized for
+  # it with or without --full, so that the timed steps run on the same workspaces in both kinds of run.
   want_origin = (world == 1 and a.config == "c2" and not a.small and not a.no_scale_origin and not a.child_pmc and
                  a.total_prompts == 0 and P != 8)
   t_build0 = time.time()
-  want_cpu = world == 1 and not a.no_cpu_baseline and not a.child_pmc and not a.small
+  want_cpu = a.full and world == 1 and not a.no_cpu_baseline and not a.child_pmc and not a.small
   g = build_model(dev, opt_cfg, unet_cfg, max(P_max, 8 if want_origin else 1), vae_cfg, keep_unet_cpu=want_cpu)
   torch.cuda.synchronize()
   t_build = time.time() - t_build0
@@ -487,6 +522,8 @@ def main():
     dt = float(tt.item())
   if a.child_pmc:
     return
+  if a.dump_outputs:
+    dump_outputs(a.dump_outputs, kept[-1][0], kept[-1][1], rank, world)
 
   # every timed step must have produced the same finite result (same inputs each step; no atomics on the path)
   ref_lat, ref_img = kept[0][0].float(), kept[0][1].float()
@@ -517,7 +554,7 @@ def main():
   max_rel = max(r[3] for r in table)
 
   scale_origin = None
-  if want_origin and rank == 0:
+  if a.full and want_origin and rank == 0:
     # same model, same loop, 8 prompts on the GPU (UNet batch 16): BASELINE configs[2]'s per-GPU share
     ids8 = synth.synthetic_prompt_ids(8, a.prompt_len, seed=0)[:, :a.prompt_len]
     lat8 = synth.initial_latents(8, 4, unet_cfg.sample_size, seed=1337).to(dev)
@@ -558,8 +595,8 @@ def main():
       per_call = P_local / ((P_local + 7) // 8)                                        # (average over the chunks of this rank)
     flop_per_call = tflop_fwd * 2 * (a.infer_steps + 1) * per_call
     achieved = flop_per_call / (unet_ms * 1e-3)
-    traffic, traffic_detail = (None, "skipped (--no-pmc or N > 1)")
-    if world == 1 and not a.no_pmc and not a.small and a.config == "c2":
+    traffic, traffic_detail = (None, "skipped (no --full, --no-pmc or N > 1)")
+    if a.full and world == 1 and not a.no_pmc and not a.small and a.config == "c2":
       del kept
       traffic, traffic_detail = pmc_traffic_live(a)
     cfg_name = "configs[1]" if (world == 1 and P == 4) else ("configs[2]" if P == 8 else "custom")
@@ -616,9 +653,9 @@ def main():
     rec["sclk_mhz_mean"] = clocks["sclk_mhz_mean"] if clocks else None
     rec["power_w_mean"] = clocks["power_w_mean"] if clocks else None
     rec["clocks"] = clocks
-    if want_origin:
+    if a.full and want_origin:
       rec["scale_origin"] = scale_origin
-    if world == 1 and not a.small and a.config == "c2":
+    if a.full and world == 1 and not a.small and a.config == "c2":
       rec["roofline_kernels"] = kernel_rooflines(dev)
     if per_rank is not None:
       rec["per_rank"] = per_rank

@@ -154,3 +154,30 @@ def test_install_as_gill_aliases_the_reference_import_names():
   root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
   r = subprocess.run([sys.executable, "-c", code], capture_output=True, text=True, cwd=root, timeout=300)
   assert r.returncode == 0 and "ok" in r.stdout, r.stderr[-2000:]
+
+
+def test_bench_dump_outputs_float32_and_budget(tmp_path, monkeypatch):
+  """bench.py --dump-outputs: the last step's (latents, uint8 images) as float32 .npy, exact; past the byte budget the images become
+  a sample at seeded positions that are the same in every run of the same shape (two builds compare position for position)."""
+  import numpy as np
+  import bench
+  lat = torch.randn(4, 4, 8, 8).bfloat16()
+  img = torch.randint(0, 256, (4, 16, 16, 3), dtype=torch.uint8)
+  bench.dump_outputs(str(tmp_path / "a"), lat, img, 0, 1)
+  got_lat, got_img = np.load(tmp_path / "a" / "latents.npy"), np.load(tmp_path / "a" / "images.npy")
+  assert got_lat.dtype == np.float32 and np.array_equal(got_lat, lat.float().numpy())
+  assert got_img.dtype == np.float32 and np.array_equal(got_img, img.numpy().astype(np.float32))
+  assert sorted(os.listdir(tmp_path / "a")) == ["images.npy", "latents.npy"]
+  budget = lat.numel() * 4 + 2 * 1200                                 # two ranks, 1200 bytes each for their images: a sample
+  monkeypatch.setattr(bench, "DUMP_BUDGET_BYTES", budget)
+  for d in ("b", "c"):
+    for rank in (0, 1):
+      bench.dump_outputs(str(tmp_path / d), lat, img, rank, 2)
+  arrays = {f: np.load(tmp_path / "b" / f) for f in os.listdir(tmp_path / "b")}
+  assert sorted(arrays) == ["images_rank0.npy", "images_rank1.npy", "images_sample_index_rank0.npy", "images_sample_index_rank1.npy",
+                            "latents.npy"]
+  assert sum(a.nbytes for a in arrays.values()) <= budget and all(a.dtype in (np.float32, np.float64) for a in arrays.values())
+  idx = arrays["images_sample_index_rank0.npy"]
+  assert len(idx) == 100 and len(np.unique(idx)) == 100
+  assert np.array_equal(arrays["images_rank0.npy"], img.numpy().reshape(-1)[idx.astype(np.int64)].astype(np.float32))
+  assert np.array_equal(idx, np.load(tmp_path / "c" / "images_sample_index_rank0.npy"))
