@@ -43,6 +43,12 @@ class gill_unet_config(C.Structure):
               ("fp8_convs", C.c_int32)]
 
 
+class gill_decode_rule(C.Structure):
+  _fields_ = [("n_ret", C.c_int32), ("ret_ids", C.c_int32 * 16), ("n_gen", C.c_int32), ("gen_ids", C.c_int32 * 16),
+              ("step", C.c_int32), ("min_word_tokens", C.c_int32), ("ret_eq_gen", C.c_int32),
+              ("ret_scale", C.c_double), ("gen_scale", C.c_double), ("filter_value", C.c_double)]
+
+
 class gill_clip_config(C.Structure):
   _fields_ = [(n, C.c_int32) for n in ("image_size", "patch_size", "hidden_size", "num_layers", "num_heads", "intermediate_size",
                                        "max_batch")]
@@ -66,6 +72,10 @@ SYMBOLS: Dict[str, Tuple[object, List[object]]] = {
   "gill_opt_forward_cached": (_i, [_vp, _vp, _i, _i, _i, _vp, _vp]),
   "gill_opt_img_hidden": (_i, [_vp, _vp, C.POINTER(C.c_int32), _i, _i, _i, _vp, _vp, _vp]),
   "gill_opt_last_logits": (_i, [_vp, _vp, _i, _i, _vp, _vp]),
+  "gill_opt_next_token": (_i, [_vp, _vp, _i, _i, C.POINTER(gill_decode_rule), _vp, _vp, _i, _i, _vp, _vp, _vp]),
+  "gill_opt_pick_token": (_i, [_vp, _vp, _i, C.POINTER(gill_decode_rule), _vp, _i, _i, _vp, _vp, _vp]),
+  "gill_opt_decode_logits": (_i, [_vp, _vp, _i, _i, C.POINTER(gill_decode_rule), _vp, _vp]),
+  "gill_opt_filter_logits": (_i, [_vp, _vp, _vp, _i, C.c_double, C.c_double, C.c_double, _i, _vp]),
   "gill_clip_create": (_i, [C.POINTER(_vp), C.POINTER(gill_clip_config), C.POINTER(gill_tensor), _i]),
   "gill_clip_destroy": (None, [_vp]),
   "gill_clip_forward": (_i, [_vp, _vp, _i, _vp, _vp]),

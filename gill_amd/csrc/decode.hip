@@ -1,0 +1,226 @@
+// On-device decision of the generate loop (gill/models.py:471-520): the [IMG] logit rule, the greedy pick with the [IMG]
+// forcing and the next step's input embeddings, and the temperature + top-p filter of the sampled path.
+//
+// Every kernel is one workgroup per row of the (B, vocab) fp32 logits; workgroups never wait for each other and no value is
+// summed through atomics, so each output is a fixed function of its row: bit-repeatable.
+#include "ops.h"
+
+namespace {
+
+constexpr int kPickThreads = 1024;
+constexpr int kFilterThreads = 1024;
+constexpr int kFilterPerThread = 64;    // the row lives in registers: vocab <= 1024 * 64
+
+// The reference's surgery on one row, in its order (:476-489), by one thread: ids may repeat or overlap, and a later
+// assignment reads what an earlier one wrote, exactly as the sequence of torch index assignments does.
+__device__ void apply_rule_row(float* __restrict__ row, const DecodeRuleDev& r) {
+  for (int j = 1; j < r.n_ret; ++j) row[r.ret[j]] = r.filter_value;
+  for (int j = 1; j < r.n_gen; ++j) row[r.gen[j]] = r.filter_value;
+  if (!r.special) return;
+  if (r.suppress) {
+    for (int j = 0; j < r.n_ret; ++j) row[r.ret[j]] = r.filter_value;
+    for (int j = 0; j < r.n_gen; ++j) row[r.gen[j]] = r.filter_value;
+    return;
+  }
+  if (r.do_ret_scale) row[r.ret[0]] = fabsf(row[r.ret[0]]) * r.ret_scale;
+  if (r.do_gen_scale) row[r.gen[0]] = fabsf(row[r.gen[0]]) * r.gen_scale;
+}
+
+// torch.argmax order: NaN above every number (the first NaN wins), then larger value, then smaller index.  A total order,
+// so the reduction tree does not change the winner.
+__device__ __forceinline__ bool argmax_better(float va, int ia, float vb, int ib) {
+  const bool na = va != va, nb = vb != vb;
+  if (na || nb) return na && nb ? ia < ib : na;
+  return va == vb ? ia < ib : va > vb;
+}
+
+template <bool PICK>
+__global__ __launch_bounds__(kPickThreads) void decode_rule_pick_kernel(float* __restrict__ logits, int V, DecodeRuleDev r,
+                                                                        const bf16_t* __restrict__ table, int D,
+                                                                        int64_t* __restrict__ tokens, int ld, int col,
+                                                                        int32_t* __restrict__ n_out, int force,
+                                                                        bf16_t* __restrict__ next_embeds) {
+  const int row = blockIdx.x, tid = threadIdx.x;
+  float* x = logits + (size_t)row * V;
+  if (tid == 0) apply_rule_row(x, r);
+  if (!PICK) return;
+  __syncthreads();    // workgroup-scope release / acquire: the rule's stores are visible to every wave below
+
+  float bv = -INFINITY;
+  int bi = 0x7fffffff;
+  for (int c = tid; c < V; c += kPickThreads) {
+    const float v = x[c];
+    if (argmax_better(v, c, bv, bi)) { bv = v; bi = c; }
+  }
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) {
+    const float ov = __shfl_xor(bv, o, 64);
+    const int oi = __shfl_xor(bi, o, 64);
+    if (argmax_better(ov, oi, bv, bi)) { bv = ov; bi = oi; }
+  }
+  __shared__ float wv[kPickThreads / 64];
+  __shared__ int wi[kPickThreads / 64];
+  __shared__ int64_t emit[kDecodeMaxIds];
+  __shared__ int n_emit;
+  if ((tid & 63) == 0) { wv[tid >> 6] = bv; wi[tid >> 6] = bi; }
+  __syncthreads();
+  if (tid == 0) {
+    for (int w = 1; w < kPickThreads / 64; ++w)
+      if (argmax_better(wv[w], wi[w], bv, bi)) { bv = wv[w]; bi = wi[w]; }
+    int n = 1;
+    emit[0] = bi;
+    if (force && bi == r.ret0_raw) {       // :518-520 (force is set by the host for B == 1 only)
+      if (r.ret_eq_gen) {
+        n = r.n_ret;
+        for (int j = 0; j < n; ++j) emit[j] = r.ret_raw[j];
+      } else {
+        n = -1;                            // the reference's AssertionError: the host raises it when it reads the count
+      }
+    }
+    n_emit = n;
+    for (int j = 0; j < n; ++j) tokens[(size_t)row * ld + col + j] = emit[j];
+    if (row == 0) *n_out = n;
+  }
+  __syncthreads();
+  // input_embeddings(next_token): the bf16 rows copied as embed_rows_bf16_kernel copies them (same clamp of the id)
+  const int n = n_emit;
+  for (int j = 0; j < n; ++j) {
+    int64_t id = emit[j];
+    if (id < 0) id = 0;
+    if (id >= r.vocab) id = r.vocab - 1;
+    const uint32_t* e = reinterpret_cast<const uint32_t*>(table + (size_t)id * D);
+    uint32_t* o = reinterpret_cast<uint32_t*>(next_embeds + (size_t)(row + j) * D);
+    for (int c = tid; c < D / 2; c += kPickThreads) o[c] = e[c];
+  }
+}
+
+// Fixed-order sum over the workgroup, result in every thread.  `red` is double-buffered by the caller's parity so that one
+// barrier per call suffices.
+__device__ __forceinline__ float block_sum_fixed(float v, float* red, int& parity) {
+  v = wave_sum(v);
+  float* buf = red + parity * (kFilterThreads / 64);
+  parity ^= 1;
+  if ((threadIdx.x & 63) == 0) buf[threadIdx.x >> 6] = v;
+  __syncthreads();
+  float s = 0.f;
+#pragma unroll
+  for (int w = 0; w < kFilterThreads / 64; ++w) s += buf[w];
+  return s;
+}
+
+__device__ __forceinline__ float block_max(float v, float* red, int& parity) {
+  v = wave_max(v);
+  float* buf = red + parity * (kFilterThreads / 64);
+  parity ^= 1;
+  if ((threadIdx.x & 63) == 0) buf[threadIdx.x >> 6] = v;
+  __syncthreads();
+  float m = buf[0];
+#pragma unroll
+  for (int w = 1; w < kFilterThreads / 64; ++w) m = fmaxf(m, buf[w]);
+  return m;
+}
+
+// out = in / t, then filter_value on every token the reference's sort / softmax / cumsum rule drops (:503-512): the token at
+// sorted position j stays iff j == 0 or the probability mass before it is <= top_p.  With e = exp(y - max) the mass before a
+// token is the sum of e over the tokens with a larger e, over Z = sum(e); as a function of a threshold k on the bits of e
+// (non-negative floats: the bits are ordered like the values) that mass never grows with k, so the kept tokens are those with
+// bits(e) >= K, K the smallest k whose mass is <= top_p, found by bisection.  Each candidate's mass is a fixed-order sum over
+// the row held in registers.  Tokens whose e round to one fp32 value are kept or dropped together.
+template <bool RECIP>
+__device__ __forceinline__ float divide(float x, float t, float inv_t) { return RECIP ? x * inv_t : __fdiv_rn(x, t); }
+
+template <bool RECIP>
+__global__ __launch_bounds__(kFilterThreads) void decode_filter_kernel(const float* __restrict__ in, float* __restrict__ out, int V,
+                                                                       float t, float inv_t, int do_top_p, float top_p,
+                                                                       float filter_value) {
+  const int row = blockIdx.x, tid = threadIdx.x;
+  const float* x = in + (size_t)row * V;
+  float* y = out + (size_t)row * V;
+  if (!do_top_p) {
+    for (int c = tid; c < V; c += kFilterThreads) y[c] = divide<RECIP>(x[c], t, inv_t);
+    return;
+  }
+  __shared__ float red[2 * (kFilterThreads / 64)];
+  int parity = 0;
+  float e[kFilterPerThread];
+  float mx = -INFINITY;
+#pragma unroll
+  for (int i = 0; i < kFilterPerThread; ++i) {
+    const int c = tid + i * kFilterThreads;
+    float v = -INFINITY;
+    if (c < V) {
+      v = divide<RECIP>(x[c], t, inv_t);
+      y[c] = v;                   // kept tokens keep this value; the last pass overwrites the dropped ones
+    }
+    e[i] = v;
+    mx = fmaxf(mx, v);
+  }
+  mx = block_max(mx, red, parity);
+  float z = 0.f;
+#pragma unroll
+  for (int i = 0; i < kFilterPerThread; ++i) {
+    e[i] = e[i] == -INFINITY ? 0.f : __expf(e[i] - mx);
+    z += e[i];
+  }
+  z = block_sum_fixed(z, red, parity);
+  const float bound = top_p * z;
+  // smallest k in [0, bits(1.0)] with mass(e > k) <= top_p; mass(e > bits(1.0)) = 0
+  uint32_t lo = 0, hi = __float_as_uint(1.0f);
+  while (lo < hi) {
+    const uint32_t mid = lo + ((hi - lo) >> 1);
+    float s = 0.f;
+#pragma unroll
+    for (int i = 0; i < kFilterPerThread; ++i) s += __float_as_uint(e[i]) > mid ? e[i] : 0.f;
+    s = block_sum_fixed(s, red, parity);
+    if (s <= bound) hi = mid; else lo = mid + 1;
+  }
+  // the dropped tokens, from the values this thread stored above (e recomputed bit for bit; a rolled loop, so the compiler does
+  // not keep 64 addresses alive across the bisection)
+  for (int c = tid; c < V; c += kFilterThreads) {
+    const float v = y[c];
+    const float ev = v == -INFINITY ? 0.f : __expf(v - mx);
+    if (__float_as_uint(ev) < lo) y[c] = filter_value;
+  }
+}
+
+}  // namespace
+
+int decode_rule_pick_launch(float* logits, int B, int V, const DecodeRuleDev& r, const bf16_t* table, int D, int64_t* tokens,
+                            int ld, int col, int32_t* n_out, bf16_t* next_embeds, hipStream_t s) {
+  GILL_REQUIRE(B >= 1 && V >= 1 && D % 2 == 0, "decode pick: bad shape");
+  GILL_REQUIRE(tokens && n_out && next_embeds && table, "decode pick: null argument");
+  const int force = B == 1;
+  GILL_REQUIRE(col >= 0 && col + (force ? (r.n_ret > 1 ? r.n_ret : 1) : 1) <= ld, "decode pick: token buffer too short");
+  hipLaunchKernelGGL(decode_rule_pick_kernel<true>, dim3(B), dim3(kPickThreads), 0, s, logits, V, r, table, D, tokens, ld, col,
+                     n_out, force, next_embeds);
+  GILL_CHECK_HIP(hipGetLastError());
+  return 0;
+}
+
+int decode_rule_launch(float* logits, int B, int V, const DecodeRuleDev& r, hipStream_t s) {
+  GILL_REQUIRE(B >= 1 && V >= 1, "decode rule: bad shape");
+  hipLaunchKernelGGL(decode_rule_pick_kernel<false>, dim3(B), dim3(64), 0, s, logits, V, r, nullptr, 0, nullptr, 0, 0, nullptr, 0,
+                     nullptr);
+  GILL_CHECK_HIP(hipGetLastError());
+  return 0;
+}
+
+int decode_filter_launch(const float* in, float* out, int B, int V, double temperature, int reciprocal, double top_p,
+                         double filter_value, hipStream_t s) {
+  GILL_REQUIRE(B >= 1 && V >= 1 && in && out, "decode filter: bad argument");
+  GILL_REQUIRE(temperature != 0, "decode filter: temperature must not be 0");
+  const int do_top_p = top_p < 1.0;
+  GILL_REQUIRE(!do_top_p || top_p > 0, "decode filter: top_p must be > 0");
+  GILL_REQUIRE(!do_top_p || V <= kFilterThreads * kFilterPerThread, "decode filter: top-p needs vocab <= 65536");
+  GILL_REQUIRE(in != out, "decode filter: out of place only");
+  const float t = (float)temperature;
+  const float inv_t = 1.0f / t;    // torch's rule for a device tensor divided by a host scalar: a * (1 / b), both in fp32
+  if (reciprocal)
+    hipLaunchKernelGGL(decode_filter_kernel<true>, dim3(B), dim3(kFilterThreads), 0, s, in, out, V, t, inv_t, do_top_p, (float)top_p,
+                       (float)filter_value);
+  else
+    hipLaunchKernelGGL(decode_filter_kernel<false>, dim3(B), dim3(kFilterThreads), 0, s, in, out, V, t, inv_t, do_top_p, (float)top_p,
+                       (float)filter_value);
+  GILL_CHECK_HIP(hipGetLastError());
+  return 0;
+}

@@ -269,6 +269,28 @@ int conv_out_launch(const bf16_t* x, const bf16_t* w /*[Cout][9][Cin]*/, const f
                     int Cout, float* y, hipStream_t s);
 // skinny GEMV-ish: out[M][N] (f32) = x[M][K] (bf16) . W[N][K]^T ; M <= 8, any N (lm_head)
 int skinny_gemm_launch(const bf16_t* x, const bf16_t* W, int M, int N, int K, float* out, hipStream_t s);
+// ---- decode decision of the generate loop (decode.hip; models.py:471-520) ----
+constexpr int kDecodeMaxIds = 16;
+struct DecodeRuleDev {          // gill_decode_rule resolved on the host: ids in [0, vocab), conditions evaluated
+  int vocab;
+  int n_ret, n_gen;
+  int ret[kDecodeMaxIds], gen[kDecodeMaxIds];       // normalised like a torch index (negative counts from the end)
+  int64_t ret_raw[kDecodeMaxIds];                   // as given: what the forced step emits (:520)
+  int64_t ret0_raw;
+  int special;                  // ids present and ret[0] != -1 and gen[0] != -1 (:478)
+  int suppress;                 // step < min_word_tokens (:479)
+  int do_ret_scale, do_gen_scale;
+  float ret_scale, gen_scale, filter_value;
+  int ret_eq_gen;
+};
+// rule + torch.argmax per row (in place), then the [IMG] forcing of B == 1, the emitted ids into tokens[b][col ..], their count
+// (-1: forced [IMG0] with ret != gen) into *n_out and their bf16 embedding rows into next_embeds row b + j
+int decode_rule_pick_launch(float* logits, int B, int V, const DecodeRuleDev& r, const bf16_t* table, int D, int64_t* tokens,
+                            int ld, int col, int32_t* n_out, bf16_t* next_embeds, hipStream_t s);
+int decode_rule_launch(float* logits, int B, int V, const DecodeRuleDev& r, hipStream_t s);   // the rule only, in place
+// out = in / temperature (reciprocal: in * fp32(1 / temperature)), then the top-p filter when top_p < 1
+int decode_filter_launch(const float* in, float* out, int B, int V, double temperature, int reciprocal, double top_p,
+                         double filter_value, hipStream_t s);
 // classifier-free guidance + PLMS update on fp32 NCHW latents (see unet.hip for the coefficient layout)
 // One row per UNet call of a denoise loop, computed on the host once per call of gill_sd_denoise and read by the
 // device: the loop's only per-step inputs.  The step index itself lives on the device (SdLoopArgs::ctr), so replaying one

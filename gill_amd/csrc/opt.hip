@@ -381,10 +381,85 @@ extern "C" int gill_opt_img_hidden(gill_opt* m, const int64_t* ids, const int32_
 
 extern "C" int gill_opt_last_logits(gill_opt* m, const float* hidden, int B, int T, float* logits_out, void* stream) {
   GILL_REQUIRE(m && hidden && logits_out, "null argument");
-  GILL_REQUIRE(B >= 1 && B <= 8, "last_logits supports B <= 8");
+  GILL_REQUIRE(B >= 1 && T >= 1, "bad shape");
   hipStream_t s = (hipStream_t)stream;
-  const int D = m->cfg.hidden_size;
-  for (int b = 0; b < B; ++b)
-    GILL_TRY(cast_f32_to_bf16_launch(hidden + ((size_t)b * T + (T - 1)) * D, m->last_bf + (size_t)b * D, D, s));
-  return skinny_gemm_launch(m->last_bf, m->lm_head, B, m->cfg.vocab_size, D, logits_out, s);
+  const int D = m->cfg.hidden_size, V = m->cfg.vocab_size;
+  // the GEMV takes 8 rows per launch (last_bf holds 8); its rows are independent, so chunking leaves every row's bits as they are
+  for (int b0 = 0; b0 < B; b0 += 8) {
+    const int nb = B - b0 < 8 ? B - b0 : 8;
+    for (int b = 0; b < nb; ++b)
+      GILL_TRY(cast_f32_to_bf16_launch(hidden + ((size_t)(b0 + b) * T + (T - 1)) * D, m->last_bf + (size_t)b * D, D, s));
+    GILL_TRY(skinny_gemm_launch(m->last_bf, m->lm_head, nb, V, D, logits_out + (size_t)b0 * V, s));
+  }
+  return 0;
+}
+
+// gill_decode_rule -> the kernel's form: ids normalised and range-checked like a torch index, the conditions of :478-489
+// evaluated once (the scale tests in double precision, as Python compares the floats)
+static int resolve_rule(const gill_opt* m, const gill_decode_rule* rule, DecodeRuleDev* r) {
+  GILL_REQUIRE(rule, "null rule");
+  GILL_REQUIRE(rule->n_ret >= 0 && rule->n_ret <= kDecodeMaxIds && rule->n_gen >= 0 && rule->n_gen <= kDecodeMaxIds,
+               "rule: at most 16 retrieval / generation ids");
+  const int V = m->cfg.vocab_size;
+  *r = DecodeRuleDev{};
+  r->vocab = V;
+  r->n_ret = rule->n_ret;
+  r->n_gen = rule->n_gen;
+  for (int j = 0; j < rule->n_ret; ++j) {
+    const int id = rule->ret_ids[j];
+    GILL_REQUIRE(id >= -V && id < V, "rule: retrieval id out of the vocabulary");
+    r->ret[j] = id < 0 ? id + V : id;
+    r->ret_raw[j] = id;
+  }
+  for (int j = 0; j < rule->n_gen; ++j) {
+    const int id = rule->gen_ids[j];
+    GILL_REQUIRE(id >= -V && id < V, "rule: generation id out of the vocabulary");
+    r->gen[j] = id < 0 ? id + V : id;
+  }
+  r->ret0_raw = rule->n_ret > 0 ? rule->ret_ids[0] : INT64_MIN;
+  r->special = (rule->n_ret > 0 || rule->n_gen > 0) && rule->n_ret > 0 && rule->n_gen > 0 && rule->ret_ids[0] != -1 &&
+               rule->gen_ids[0] != -1;
+  r->suppress = rule->step < rule->min_word_tokens;
+  r->do_ret_scale = rule->ret_scale > 1.0;
+  r->do_gen_scale = rule->gen_scale > 1.0;
+  r->ret_scale = (float)rule->ret_scale;
+  r->gen_scale = (float)rule->gen_scale;
+  r->filter_value = (float)rule->filter_value;
+  r->ret_eq_gen = rule->ret_eq_gen != 0;
+  return 0;
+}
+
+extern "C" int gill_opt_pick_token(gill_opt* m, float* logits, int B, const gill_decode_rule* rule, int64_t* tokens, int ld,
+                                   int col, int32_t* n_out, void* next_embeds_bf16, void* stream) {
+  GILL_REQUIRE(m && logits && tokens && n_out && next_embeds_bf16, "null argument");
+  DecodeRuleDev r;
+  GILL_TRY(resolve_rule(m, rule, &r));
+  return decode_rule_pick_launch(logits, B, m->cfg.vocab_size, r, m->embed, m->cfg.hidden_size, tokens, ld, col, n_out,
+                                 (bf16_t*)next_embeds_bf16, (hipStream_t)stream);
+}
+
+extern "C" int gill_opt_next_token(gill_opt* m, const float* hidden, int B, int T, const gill_decode_rule* rule, float* logits_out,
+                                   int64_t* tokens, int ld, int col, int32_t* n_out, void* next_embeds_bf16, void* stream) {
+  GILL_REQUIRE(m && rule && tokens && n_out && next_embeds_bf16, "null argument");
+  DecodeRuleDev r;
+  GILL_TRY(resolve_rule(m, rule, &r));   // argument errors before anything is enqueued
+  GILL_TRY(gill_opt_last_logits(m, hidden, B, T, logits_out, stream));
+  return decode_rule_pick_launch(logits_out, B, m->cfg.vocab_size, r, m->embed, m->cfg.hidden_size, tokens, ld, col, n_out,
+                                 (bf16_t*)next_embeds_bf16, (hipStream_t)stream);
+}
+
+extern "C" int gill_opt_decode_logits(gill_opt* m, const float* hidden, int B, int T, const gill_decode_rule* rule, float* logits_out,
+                                      void* stream) {
+  GILL_REQUIRE(m && rule, "null argument");
+  DecodeRuleDev r;
+  GILL_TRY(resolve_rule(m, rule, &r));
+  GILL_TRY(gill_opt_last_logits(m, hidden, B, T, logits_out, stream));
+  return decode_rule_launch(logits_out, B, m->cfg.vocab_size, r, (hipStream_t)stream);
+}
+
+extern "C" int gill_opt_filter_logits(gill_opt* m, const float* in, float* out, int B, double temperature, double top_p,
+                                      double filter_value, int reciprocal, void* stream) {
+  GILL_REQUIRE(m, "null handle");
+  return decode_filter_launch(in, out, B, m->cfg.vocab_size, temperature, reciprocal != 0, top_p, filter_value,
+                              (hipStream_t)stream);
 }

@@ -395,6 +395,28 @@ class GILLModel(nn.Module):
     last_output_logit = None
     return output, full_labels, last_embedding, last_output_logit, visual_embs, visual_embs_norm, input_embs_norm, llm_hidden_states
 
+  # The decision of the generate loop (:471-520) runs on the device: the [IMG] logit rule, the greedy pick, the [IMG] forcing and
+  # the next step's embeddings (gill_opt_next_token), and the rule, the temperature and the top-p filter of the sampled path
+  # (gill_opt_decode_logits / gill_opt_filter_logits).  False runs the reference's host decision instead (A/B and test arm).
+  decode_on_device = True
+  _decode_host_waits = 0      # instrumentation: host waits inside the loop of the last generate() call
+
+  def _decode_rule(self, step: int, min_word_tokens: int, ret_scale_factor: float, gen_scale_factor: float,
+                   filter_value: float):
+    """gill_decode_rule of loop step `step` (the arguments of :476-489)."""
+    ret, gen = list(self.retrieval_token_idx), list(self.gen_token_idx)
+    if len(ret) > 16 or len(gen) > 16:
+      raise NotImplementedError('the on-device decode rule takes at most 16 retrieval / generation token ids')
+    r = N.gill_decode_rule()
+    r.n_ret, r.n_gen = len(ret), len(gen)
+    for j, v in enumerate(ret):
+      r.ret_ids[j] = int(v)
+    for j, v in enumerate(gen):
+      r.gen_ids[j] = int(v)
+    r.step, r.min_word_tokens, r.ret_eq_gen = int(step), int(min_word_tokens), int(ret == gen)
+    r.ret_scale, r.gen_scale, r.filter_value = float(ret_scale_factor), float(gen_scale_factor), float(filter_value)
+    return r
+
   def generate(self, embeddings=torch.FloatTensor, max_len: int = 32, temperature: float = 0.0, top_p: float = 1.0,
                min_word_tokens: int = 0, ret_scale_factor: float = 1.0, gen_scale_factor: float = 1.0,
                filter_value: float = -float('Inf'), use_kv_cache: bool = True):
@@ -402,7 +424,14 @@ class GILLModel(nn.Module):
     whole sequence through the LM at every step; with use_kv_cache (default) only the tokens appended since the last
     step go through the layers, against keys/values cached in the native handle — causal attention makes the hidden
     states of earlier positions independent of later tokens, so the outputs are the same up to rounding.
-    Outputs: out (N,T) token ids, output_embeddings list of hidden_states[-1], output_logits list (N, vocab)."""
+    With decode_on_device (default) the logit rule and the pick run in libgill_amd: greedy decoding at batch > 1 never
+    waits for the device inside the loop, at batch 1 it reads one 4-byte count per step (the [IMG] forcing decides how
+    many tokens the next forward takes).  Outputs: out (N,T) token ids, output_embeddings list of hidden_states[-1],
+    output_logits list (N, vocab) — CPU tensors when top_p == 1 (:471-472), device tensors otherwise."""
+    self._decode_host_waits = 0
+    if self.decode_on_device and temperature == 0.0 and top_p == 1.0:
+      return self._generate_greedy_device(embeddings, max_len, min_word_tokens, ret_scale_factor, gen_scale_factor,
+                                          filter_value, use_kv_cache)
     with torch.no_grad():
       out = None
       output_embeddings = []
@@ -411,11 +440,7 @@ class GILLModel(nn.Module):
       vocab = self.opt_cfg.vocab_size
       hidden = None
       if use_kv_cache:
-        # the cache lives in the handle: size it for the longest sequence this call can produce — every one of the max_len
-        # steps may emit [IMG0] and so append all len(retrieval_token_idx) forced tokens (:518-520) — capped at the LM's
-        # position table.  The handle is never rebuilt mid-sequence (_lm_forward_hidden_cached raises instead).
-        grow = max(1, len(self.retrieval_token_idx))
-        self._opt_native(embeddings.shape[0], min(embeddings.shape[1] + max_len * grow, self.opt_cfg.max_positions))
+        self._size_kv_cache(embeddings, max_len)
       for i in range(max_len):
         if use_kv_cache:
           past = 0 if hidden is None else hidden.shape[1]
@@ -426,43 +451,69 @@ class GILLModel(nn.Module):
         for idx in self.args.text_emb_layers:
           output_embeddings.append(hidden.to(embeddings.dtype))                # :467-468
         B, T, D = hidden.shape
-        if B > 8:
-          raise NotImplementedError('generate(): batch <= 8')
         logits = torch.empty((B, vocab), device=dev, dtype=torch.float32)
-        with torch.cuda.device(dev):
-          N.check(N.lib().gill_opt_last_logits(self._opt_handle, N.ptr(hidden), B, T, N.ptr(logits), N.current_stream()))
-        if top_p == 1.0:
-          logits = logits.cpu()                                                # :471-472
-        output_logits.append(logits)
-        logits[:, self.retrieval_token_idx[1:]] = filter_value                 # :476-477
-        logits[:, self.gen_token_idx[1:]] = filter_value
-        if (self.retrieval_token_idx or self.gen_token_idx) and self.retrieval_token_idx[0] != -1 and self.gen_token_idx[0] != -1:
-          if i < min_word_tokens:
-            logits[:, self.retrieval_token_idx] = filter_value
-            logits[:, self.gen_token_idx] = filter_value
-          else:
-            if ret_scale_factor > 1:
-              logits[:, self.retrieval_token_idx[0]] = logits[:, self.retrieval_token_idx[0]].abs() * ret_scale_factor
-            if gen_scale_factor > 1:
-              logits[:, self.gen_token_idx[0]] = logits[:, self.gen_token_idx[0]].abs() * gen_scale_factor
-        if temperature == 0.0:
-          if top_p != 1.0:
+        if self.decode_on_device:
+          # :470-512 in libgill_amd: lm_head + rule (in place: what output_logits holds), then division + top-p out of place;
+          # the draw stays torch.multinomial on the device the reference's tensor is on
+          rule = self._decode_rule(i, min_word_tokens, ret_scale_factor, gen_scale_factor, filter_value)
+          with torch.cuda.device(dev):
+            N.check(N.lib().gill_opt_decode_logits(self._opt_handle, N.ptr(hidden), B, T, C.byref(rule), N.ptr(logits),
+                                                   N.current_stream()))
+          if temperature == 0.0:
             raise ValueError('top_p cannot be set if temperature is 0 (greedy decoding).')
-          next_token = torch.argmax(logits, keepdim=True, dim=-1)
-        else:
-          logits = logits / temperature
           if top_p < 1.0:
             assert top_p > 0, f'top_p should be above 0, got {top_p} instead.'
-            sorted_logits, sorted_indices = torch.sort(logits, descending=True)
-            cumulative_probs = torch.cumsum(torch.softmax(sorted_logits, dim=-1), dim=-1)
-            remove = cumulative_probs > top_p
-            remove[..., 1:] = remove[..., :-1].clone()
-            remove[..., 0] = 0
-            for j in range(sorted_indices.shape[0]):
-              logits[j, sorted_indices[j, remove[j, :]]] = filter_value
-          next_token = torch.multinomial(logits.exp(), 1)
+          probs_in = torch.empty_like(logits)
+          with torch.cuda.device(dev):
+            N.check(N.lib().gill_opt_filter_logits(self._opt_handle, N.ptr(logits), N.ptr(probs_in), B, float(temperature),
+                                                   float(top_p), float(filter_value), int(top_p != 1.0), N.current_stream()))
+          if top_p == 1.0:
+            logits, probs_in = logits.cpu(), probs_in.cpu()                    # :471-472: the host tensors of the reference
+            self._decode_host_waits += 1
+          output_logits.append(logits)
+          next_token = torch.multinomial(probs_in.exp(), 1)
+        else:
+          with torch.cuda.device(dev):
+            N.check(N.lib().gill_opt_last_logits(self._opt_handle, N.ptr(hidden), B, T, N.ptr(logits), N.current_stream()))
+          if top_p == 1.0:
+            logits = logits.cpu()                                              # :471-472
+            self._decode_host_waits += 1
+          output_logits.append(logits)
+          logits[:, self.retrieval_token_idx[1:]] = filter_value               # :476-477
+          logits[:, self.gen_token_idx[1:]] = filter_value
+          if (self.retrieval_token_idx or self.gen_token_idx) and self.retrieval_token_idx[0] != -1 and self.gen_token_idx[0] != -1:
+            if i < min_word_tokens:
+              logits[:, self.retrieval_token_idx] = filter_value
+              logits[:, self.gen_token_idx] = filter_value
+            else:
+              if ret_scale_factor > 1:
+                logits[:, self.retrieval_token_idx[0]] = logits[:, self.retrieval_token_idx[0]].abs() * ret_scale_factor
+              if gen_scale_factor > 1:
+                logits[:, self.gen_token_idx[0]] = logits[:, self.gen_token_idx[0]].abs() * gen_scale_factor
+          if temperature == 0.0:
+            if top_p != 1.0:
+              raise ValueError('top_p cannot be set if temperature is 0 (greedy decoding).')
+            next_token = torch.argmax(logits, keepdim=True, dim=-1)
+          else:
+            logits = logits / temperature
+            if top_p < 1.0:
+              assert top_p > 0, f'top_p should be above 0, got {top_p} instead.'
+              sorted_logits, sorted_indices = torch.sort(logits, descending=True)
+              cumulative_probs = torch.cumsum(torch.softmax(sorted_logits, dim=-1), dim=-1)
+              remove = cumulative_probs > top_p
+              remove[..., 1:] = remove[..., :-1].clone()
+              remove[..., 0] = 0
+              for j in range(sorted_indices.shape[0]):
+                logits[j, sorted_indices[j, remove[j, :]]] = filter_value
+            next_token = torch.multinomial(logits.exp(), 1)
         # Force generation of the remaining [IMG] tokens if [IMG0] is generated (batch 1 only, :518-520).
-        if next_token.shape[0] == 1 and next_token.item() == self.retrieval_token_idx[0]:
+        if next_token.shape[0] == 1:
+          if next_token.is_cuda:
+            self._decode_host_waits += 1
+          forced = next_token.item() == self.retrieval_token_idx[0]
+        else:
+          forced = False
+        if forced:
           assert self.retrieval_token_idx == self.gen_token_idx, (self.retrieval_token_idx, self.gen_token_idx)
           next_token = torch.tensor(self.retrieval_token_idx)[None, :].long().to(dev)
         else:
@@ -472,6 +523,72 @@ class GILLModel(nn.Module):
         embeddings = torch.cat([embeddings, next_embedding.to(embeddings.dtype)], dim=1)
     return out, output_embeddings, output_logits
 
+  def _size_kv_cache(self, embeddings: Tensor, max_len: int):
+    # the cache lives in the handle: size it for the longest sequence this call can produce — every one of the max_len
+    # steps may emit [IMG0] and so append all len(retrieval_token_idx) forced tokens (:518-520) — capped at the LM's
+    # position table.  The handle is never rebuilt mid-sequence (_lm_forward_hidden_cached raises instead).
+    grow = max(1, len(self.retrieval_token_idx))
+    self._opt_native(embeddings.shape[0], min(embeddings.shape[1] + max_len * grow, self.opt_cfg.max_positions))
+
+  def _generate_greedy_device(self, embeddings: Tensor, max_len: int, min_word_tokens: int, ret_scale_factor: float,
+                              gen_scale_factor: float, filter_value: float, use_kv_cache: bool):
+    """generate() at temperature 0 with the decision in libgill_amd (gill_opt_next_token).  The picked ids go to a device
+    token buffer, their embeddings to the next step's input; the post-rule logits go to pinned host memory by asynchronous
+    copies, and the one synchronisation is at the end.  At batch 1 the count of emitted ids (1, or the 8 forced [IMG] ids)
+    is read back each step: the next forward's length depends on it."""
+    with torch.no_grad():
+      output_embeddings = []
+      output_logits = []
+      dev = embeddings.device
+      vocab = self.opt_cfg.vocab_size
+      B0, _, D = embeddings.shape
+      grow = max(1, len(self.retrieval_token_idx)) if B0 == 1 else 1      # ids one step can emit (:518-520: batch 1 only)
+      tokens = torch.empty((B0, max(1, max_len * grow)), device=dev, dtype=torch.int64)
+      nxt = torch.empty((B0, grow, D), device=dev, dtype=torch.bfloat16)
+      n_dev = torch.empty(1, device=dev, dtype=torch.int32)
+      n_host = torch.empty(1, dtype=torch.int32, pin_memory=True)
+      host_logits = torch.empty((max_len, B0, vocab), dtype=torch.float32, pin_memory=True) if max_len > 0 else None
+      ev = torch.cuda.Event()
+      col = 0
+      hidden = None
+      new_embeds = None
+      if use_kv_cache:
+        self._size_kv_cache(embeddings, max_len)
+      for i in range(max_len):
+        if use_kv_cache:
+          past = 0 if hidden is None else hidden.shape[1]
+          new_hidden = self._lm_forward_hidden_cached(embeddings if hidden is None else new_embeds, past)
+          hidden = new_hidden if hidden is None else torch.cat([hidden, new_hidden], dim=1)
+        else:
+          hidden = self._lm_forward_hidden(embeddings)                         # :465
+        for idx in self.args.text_emb_layers:
+          output_embeddings.append(hidden.to(embeddings.dtype))                # :467-468
+        B, T, _ = hidden.shape
+        logits = torch.empty((B, vocab), device=dev, dtype=torch.float32)
+        rule = self._decode_rule(i, min_word_tokens, ret_scale_factor, gen_scale_factor, filter_value)
+        with torch.cuda.device(dev):
+          N.check(N.lib().gill_opt_next_token(self._opt_handle, N.ptr(hidden), B, T, C.byref(rule), N.ptr(logits), N.ptr(tokens),
+                                              tokens.shape[1], col, N.ptr(n_dev), N.ptr(nxt), N.current_stream()))
+          host_logits[i].copy_(logits, non_blocking=True)                      # :471-472, the post-rule values (:476-489)
+          output_logits.append(host_logits[i])
+          if B == 1:
+            n_host.copy_(n_dev, non_blocking=True)
+            ev.record()
+            ev.synchronize()
+            self._decode_host_waits += 1
+            n = int(n_host[0])
+            if n < 0:
+              raise AssertionError((self.retrieval_token_idx, self.gen_token_idx))   # :519
+          else:
+            n = 1
+        col += n
+        new_embeds = nxt[:, :n].to(embeddings.dtype)
+        if not use_kv_cache:
+          embeddings = torch.cat([embeddings, new_embeds], dim=1)
+      if max_len > 0:
+        torch.cuda.current_stream(dev).synchronize()                           # the pinned logits are complete
+    out = tokens[:, :col].clone() if max_len > 0 else None
+    return out, output_embeddings, output_logits
 
 class GILL(nn.Module):
   def __init__(self, tokenizer, model_args: Optional[GILLArgs] = None, path_array: Optional[List[str]] = None,

@@ -82,8 +82,50 @@ int gill_opt_img_hidden(gill_opt* h, const int64_t* ids, const int32_t* last_idx
                         void* raw_out_bf16, void* emb_out_bf16, void* stream);
 
 /* logits[:, -1, :] of the tied lm_head for the generate loop (models.py:470):
- *   hidden (B,T,D) fp32 from gill_opt_forward -> logits_out (B, vocab) fp32.  B <= 8. */
+ *   hidden (B,T,D) fp32 from gill_opt_forward -> logits_out (B, vocab) fp32.  Any B >= 1: the rows go through the GEMV
+ *   8 at a time, each row's arithmetic independent of the others (a row's logits do not depend on B). */
 int gill_opt_last_logits(gill_opt* h, const float* hidden, int B, int T, float* logits_out, void* stream);
+
+/* The decision half of the generate loop, on the device (models.py:471-520).
+ * gill_decode_rule holds the arguments of the [IMG] logit rule (:476-489) as GILLModel.generate has them:
+ *   ret_ids / gen_ids = retrieval_token_idx / gen_token_idx (at most 16 each; negative ids index from the end, as in torch),
+ *   step = the loop index i, min_word_tokens, ret_scale / gen_scale / filter_value = the Python floats,
+ *   ret_eq_gen = (retrieval_token_idx == gen_token_idx), the assert at :519. */
+typedef struct gill_decode_rule {
+  int32_t n_ret;
+  int32_t ret_ids[16];
+  int32_t n_gen;
+  int32_t gen_ids[16];
+  int32_t step;
+  int32_t min_word_tokens;
+  int32_t ret_eq_gen;
+  double ret_scale;
+  double gen_scale;
+  double filter_value;
+} gill_decode_rule;
+
+/* Greedy step (:470-491, :498, :518-529): lm_head as gill_opt_last_logits -> logits_out (B, vocab) fp32, the rule applied in
+ * place (what output_logits holds, :472-477), torch.argmax per row; at B == 1 a pick equal to ret_ids[0] emits all n_ret ids
+ * (:518-520).  The emitted ids go to tokens (B, ld) int64 at columns col.., their count (1, or n_ret; -1 when [IMG0] was picked
+ * with ret_eq_gen == 0: the reference's AssertionError) to *n_out (device int32), and their input_embeddings rows (bf16, as
+ * gill_opt_embed) to next_embeds: row b at B > 1 ((B,1,D)), rows 0..n-1 at B == 1 ((1,max(1,n_ret),D)).  No host wait. */
+int gill_opt_next_token(gill_opt* h, const float* hidden, int B, int T, const gill_decode_rule* rule, float* logits_out,
+                        int64_t* tokens, int ld, int col, int32_t* n_out, void* next_embeds_bf16, void* stream);
+
+/* The same decision on caller-supplied logits (B, vocab) fp32, modified in place (:476-498, :518-520). */
+int gill_opt_pick_token(gill_opt* h, float* logits, int B, const gill_decode_rule* rule, int64_t* tokens, int ld, int col,
+                        int32_t* n_out, void* next_embeds_bf16, void* stream);
+
+/* Sampled step, first half (:470-489): lm_head + the rule in place -> logits_out (B, vocab) fp32. */
+int gill_opt_decode_logits(gill_opt* h, const float* hidden, int B, int T, const gill_decode_rule* rule, float* logits_out,
+                           void* stream);
+
+/* Sampled step, second half (:500-512): out = in / temperature, then filter_value on every token the sort / softmax / cumsum
+ * top-p rule removes (only when top_p < 1; vocab <= 65536).  reciprocal = 0: correctly rounded fp32 division (torch on the
+ * CPU); reciprocal = 1: in * fp32(1 / temperature) (torch on the GPU for a tensor divided by a Python float).  Out of place,
+ * deterministic: the same input gives the same bits on every call. */
+int gill_opt_filter_logits(gill_opt* h, const float* in, float* out, int B, double temperature, double top_p,
+                           double filter_value, int reciprocal, void* stream);
 
 /* ------------------------------------------------------------------------------------------
  * Image prompts — the frozen CLIP vision tower (transformers CLIPVisionModel built at gill/models.py:78-96 and called by
