@@ -4,9 +4,15 @@ The reference builds `StableDiffusionPipeline.from_pretrained("runwayml/stable-d
 (gill/models.py:550-551) and calls it as
     self.sd_pipe(prompt_embeds=gen_emb[i:i+8], generator=generator, guidance_scale=..., num_inference_steps=...).images
 (gill/models.py:730-731); the loop it runs is restated in-tree at gill/custom_sd.py:567-651.
-`GillSDPipeline` keeps that call signature (prompt_embeds / negative_prompt_embeds / latents / generator /
-guidance_scale / num_inference_steps / output_type) and runs the UNet + PNDM loop in libgill_amd
-(gill_sd_denoise: csrc/unet.hip).
+`GillSDPipeline` keeps that call signature (prompt / negative_prompt / prompt_embeds / negative_prompt_embeds / latents /
+generator / guidance_scale / num_inference_steps / num_images_per_prompt / output_type / return_prompts_only) and runs the UNet +
+PNDM loop in libgill_amd (gill_sd_denoise: csrc/unet.hip).
+
+Text prompts (`prompt=`, `negative_prompt=`: _encode_prompt, gill/custom_sd.py:224-373) run through the CLIP text tower in libgill_amd
+(gill_clip_text_forward: csrc/cliptext.hip) when the pipeline was built with text-encoder weights (`text_state=` / a model directory
+with `text_encoder/`) and a tokenizer; tokenisation itself stays with the CPU tokenizer object.  `truncate_side` and
+`return_prompts_only` are the reference's two additions to the stock pipeline (custom_sd.py:90, :268-298, :496, :589-604).  A pipeline
+built without text-encoder weights is driven by `prompt_embeds` alone, as `GILL.generate_images` drives it.
 
 `output_type` defaults to "pil" like the reference's (gill/custom_sd.py:491) when the handle holds VAE weights (a UNet-only
 handle defaults to "latent"); "latent" (what `GILL.generate_images` passes: the hot path hands latents to the all-gather) returns
@@ -24,7 +30,7 @@ from typing import Dict, List, Optional, Union
 import torch
 
 from . import _native as N
-from .synth import UNetConfig, VAEConfig
+from .synth import ClipTextConfig, UNetConfig, VAEConfig
 
 
 @dataclass
@@ -34,10 +40,18 @@ class PipelineOutput:
 
 
 class GillSDPipeline:
-  def __init__(self, unet_state: Dict[str, torch.Tensor], cfg: UNetConfig, uncond_embeds: torch.Tensor,
+  def __init__(self, unet_state: Dict[str, torch.Tensor], cfg: UNetConfig, uncond_embeds: Optional[torch.Tensor],
                device: Union[str, torch.device] = "cuda", max_batch: int = 16,
-               vae_state: Optional[Dict[str, torch.Tensor]] = None, vae_cfg: Optional[VAEConfig] = None):
+               vae_state: Optional[Dict[str, torch.Tensor]] = None, vae_cfg: Optional[VAEConfig] = None,
+               text_state: Optional[Dict[str, torch.Tensor]] = None, text_cfg: Optional[ClipTextConfig] = None, tokenizer=None,
+               text_max_batch: Optional[int] = None):
+    """text_state / text_cfg: the CLIP text tower (state-dict names of the published text_encoder files, `text_model.` prefix);
+    tokenizer: a Hugging Face style tokenizer object (CLIPTokenizer).  Without text_state nothing is allocated for text and
+    `prompt=` raises.  uncond_embeds may be None only when text_state and tokenizer are given: it is then the native encoding of ""."""
     self.cfg = cfg
+    self.truncate_side = "right"        # custom_sd.py:90, :169 ('left': keep the tail of an over-long prompt)
+    self.tokenizer = tokenizer
+    self.text_encoder = None
     self.device = torch.device(device if str(device) != "cuda" else "cuda:0")
     if self.device.type != "cuda":
       raise N.GillNativeError("GillSDPipeline runs only on an MI355X through libgill_amd")
@@ -46,6 +60,17 @@ class GillSDPipeline:
     # gill_amd.configure_hip_runtime() first; a caller that did not gets ONE RuntimeWarning here instead of a silent 1.2 % (README "Runtime setting")
     from . import configure_hip_runtime
     configure_hip_runtime(warn=True)
+    if text_state is not None:
+      from .clip_text import GillClipTextEncoder
+      tc = text_cfg or ClipTextConfig.sd15()
+      if tc.hidden_size != cfg.cross_attention_dim or tc.max_positions < cfg.ctx_len:
+        raise ValueError(f"text encoder (width {tc.hidden_size}, {tc.max_positions} positions) does not fit the UNet's context "
+                         f"({cfg.ctx_len} x {cfg.cross_attention_dim})")
+      self.text_encoder = GillClipTextEncoder(text_state, tc, self.device, max_batch=text_max_batch or max_batch)
+    if uncond_embeds is None:
+      if self.text_encoder is None or self.tokenizer is None:
+        raise ValueError("uncond_embeds=None needs text-encoder weights and a tokenizer to encode the empty prompt")
+      uncond_embeds = self.encode_prompt_ids(self._tokenize([""]), dtype=torch.bfloat16)
     self.uncond_embeds = uncond_embeds.to(self.device, torch.bfloat16).reshape(1, cfg.ctx_len, cfg.cross_attention_dim).contiguous()
     ccfg = N.gill_unet_config(in_channels=cfg.in_channels, out_channels=cfg.out_channels,
                               layers_per_block=cfg.layers_per_block, cross_attention_dim=cfg.cross_attention_dim,
@@ -105,7 +130,12 @@ class GillSDPipeline:
   # ---- construction from a local diffusers directory (no diffusers import: safetensors + json only)
   @classmethod
   def from_pretrained(cls, model_dir: str, uncond_embeds: Optional[torch.Tensor] = None, device="cuda", max_batch: int = 16,
-                      **_ignored):
+                      tokenizer=None, text_max_batch: Optional[int] = None, **_ignored):
+    """When `text_encoder/model.safetensors` and its `config.json` exist they are loaded into the native text tower, with the
+    tokenizer from `tokenizer=` or `tokenizer/` (transformers.CLIPTokenizer: plumbing).  The default negative embedding comes from,
+    in this order: `uncond_embeds=`; `uncond_embeds.safetensors`; the native tower on ""; the transformers host forward, only when
+    there are no text-encoder weights the native tower can load.  The third arm replaces what used to be that host computation
+    (fp32 torch on the CPU): its values agree with it to the rounding of the tower's bf16 GEMM operands, not bit for bit."""
     from safetensors.torch import load_file
     with open(os.path.join(model_dir, "unet", "config.json")) as f:
       c = json.load(f)
@@ -128,8 +158,24 @@ class GillSDPipeline:
       # offline cache of CLIP-text("") (1,77,ctx_dim): what _encode_prompt computes for the empty negative prompt
       # (custom_sd.py:319-357), for machines without the text encoder / tokenizer files
       uncond_embeds = load_file(upath)["uncond_embeds"]
-    if uncond_embeds is None:
-      # CLIP-text("") — plumbing through transformers when its files are on disk
+    text_sd, text_cfg = None, None
+    tdir = os.path.join(model_dir, "text_encoder")
+    if os.path.exists(os.path.join(tdir, "model.safetensors")) and os.path.exists(os.path.join(tdir, "config.json")):
+      with open(os.path.join(tdir, "config.json")) as f:
+        tc = json.load(f)
+      text_cfg = ClipTextConfig(vocab_size=tc["vocab_size"], hidden_size=tc["hidden_size"], num_layers=tc["num_hidden_layers"],
+                                num_heads=tc["num_attention_heads"], intermediate_size=tc["intermediate_size"],
+                                max_positions=tc.get("max_position_embeddings", 77), hidden_act=tc.get("hidden_act", "quick_gelu"),
+                                use_attention_mask=bool(tc.get("use_attention_mask", False)))
+      text_sd = load_file(os.path.join(tdir, "model.safetensors"))
+      if tokenizer is None and os.path.isdir(os.path.join(model_dir, "tokenizer")):
+        from transformers import CLIPTokenizer
+        tokenizer = CLIPTokenizer.from_pretrained(os.path.join(model_dir, "tokenizer"))
+    if uncond_embeds is None and text_sd is not None and tokenizer is None:
+      raise ValueError(f"{model_dir} has text-encoder weights but neither tokenizer= nor a tokenizer/ directory to encode the empty "
+                       "negative prompt with; pass one of them, uncond_embeds=, or add uncond_embeds.safetensors")
+    if uncond_embeds is None and text_sd is None:
+      # CLIP-text("") on the host — only for directories whose text encoder the native tower cannot load (no safetensors file)
       from transformers import CLIPTextModel, CLIPTokenizer
       tok = CLIPTokenizer.from_pretrained(os.path.join(model_dir, "tokenizer"))
       enc = CLIPTextModel.from_pretrained(os.path.join(model_dir, "text_encoder"))
@@ -145,7 +191,8 @@ class GillSDPipeline:
                           block_out_channels=tuple(vc["block_out_channels"]), layers_per_block=vc["layers_per_block"],
                           norm_num_groups=vc["norm_num_groups"], latent_size=cfg.sample_size)   # scaling 0.18215: custom_sd.py:387
       vae_sd = load_file(os.path.join(vdir, "diffusion_pytorch_model.safetensors"))
-    pipe = cls(sd, cfg, uncond_embeds, device, max_batch, vae_state=vae_sd, vae_cfg=vae_cfg)
+    pipe = cls(sd, cfg, uncond_embeds, device, max_batch, vae_state=vae_sd, vae_cfg=vae_cfg, text_state=text_sd, text_cfg=text_cfg,
+               tokenizer=tokenizer, text_max_batch=text_max_batch)    # uncond_embeds None here: the native tower encodes ""
     sdir = os.path.join(model_dir, "safety_checker")
     if os.path.exists(os.path.join(sdir, "model.safetensors")):     # the reference's from_pretrained loads it by default
       from .safety import GillSafetyChecker
@@ -170,6 +217,7 @@ class GillSDPipeline:
       if getattr(self, "_vae", None):
         N.lib().gill_vae_destroy(self._vae)
         self._vae = None
+      self.text_encoder = None
     except Exception:
       pass
 
@@ -204,17 +252,81 @@ class GillSDPipeline:
         latents = torch.randn(shape, generator=generator, device=gdev, dtype=torch.float32)
     return latents.to(self.device, torch.float32).contiguous()
 
+  # ---- text prompts (custom_sd.py:224-373)
+  def encode_prompt_ids(self, ids: torch.Tensor, dtype: torch.dtype = torch.float32) -> torch.Tensor:
+    """text_encoder(input_ids)[0] (custom_sd.py:305-309): ids (B,77) from the tokenizer -> (B,77,D) on the device, float32 or
+    bfloat16 (the rounding of the former, from the same pass).  Any B: rows go through the tower in chunks of its max_batch."""
+    if self.text_encoder is None:
+      raise N.GillNativeError("this pipeline was built without text-encoder weights (pass text_state= / use from_pretrained)")
+    return self.text_encoder(ids, dtype=dtype)
+
+  def _tokenize(self, texts) -> torch.Tensor:
+    return self.tokenizer(texts, padding="max_length", max_length=self.tokenizer.model_max_length, truncation=True,
+                          return_tensors="pt").input_ids
+
+  def _prompt_ids(self, prompt) -> torch.Tensor:
+    """custom_sd.py:266-284: the ids the text encoder sees for `prompt` (str | list[str])."""
+    if self.truncate_side not in ("left", "right"):
+      raise ValueError(f"truncate_side must be 'left' or 'right', got {self.truncate_side!r}")
+    if self.truncate_side == "left":
+      # keep the tail: decode the last model_max_length ids in front of the closing token and tokenise those again (:268-275)
+      untruncated = self.tokenizer(prompt, padding="longest", return_tensors="pt").input_ids
+      mml = self.tokenizer.model_max_length
+      if untruncated.shape[-1] > mml:
+        prompt = self.tokenizer.batch_decode(untruncated[:, -1 - mml:-1])
+    return self._tokenize(prompt)
+
+  def _negative_texts(self, prompt, negative_prompt, batch_size: int) -> List[str]:
+    """custom_sd.py:320-337 (the type check compares with the prompt as the caller passed it)."""
+    if negative_prompt is None:
+      return [""] * batch_size
+    if type(prompt) is not type(negative_prompt):
+      raise TypeError(f"`negative_prompt` should be the same type to `prompt`, but got {type(negative_prompt)} != {type(prompt)}.")
+    if isinstance(negative_prompt, str):
+      return [negative_prompt]
+    if batch_size != len(negative_prompt):
+      raise ValueError(f"`negative_prompt`: {negative_prompt} has batch size {len(negative_prompt)}, but `prompt`: {prompt} has batch "
+                       f"size {batch_size}. Please make sure that passed `negative_prompt` matches the batch size of `prompt`.")
+    return negative_prompt
+
   @torch.no_grad()
   def __call__(self, prompt=None, height=None, width=None, num_inference_steps: int = 50, guidance_scale: float = 7.5,
                negative_prompt=None, num_images_per_prompt: int = 1, eta: float = 0.0, generator=None,
                latents: Optional[torch.Tensor] = None, prompt_embeds: Optional[torch.Tensor] = None,
                negative_prompt_embeds: Optional[torch.Tensor] = None, output_type: Optional[str] = None, return_dict: bool = True,
-               **_ignored):
-    if prompt is not None:
+               return_prompts_only: bool = False, **_ignored):
+    text = getattr(self, "text_encoder", None) is not None
+    if prompt is not None and not text:
       raise ValueError("GillSDPipeline is driven by prompt_embeds (gill/models.py:730); text prompts need the CLIP text "
                        "encoder, which is outside this path")
-    if prompt_embeds is None:
+    # diffusers' check_inputs (custom_sd.py:572-574)
+    if prompt is not None and prompt_embeds is not None:
+      raise ValueError(f"Cannot forward both `prompt`: {prompt} and `prompt_embeds`: {prompt_embeds}. Please make sure to only forward "
+                       "one of the two.")
+    if prompt is None and prompt_embeds is None:
       raise ValueError("Provide either `prompt` or `prompt_embeds`. Cannot leave both `prompt` and `prompt_embeds` undefined.")
+    if prompt is not None and not isinstance(prompt, (str, list)):
+      raise ValueError(f"`prompt` has to be of type `str` or `list` but is {type(prompt)}")
+    if text and negative_prompt is not None and negative_prompt_embeds is not None:
+      raise ValueError(f"Cannot forward both `negative_prompt`: {negative_prompt} and `negative_prompt_embeds`: "
+                       f"{negative_prompt_embeds}. Please make sure to only forward one of the two.")
+    if prompt is not None and self.tokenizer is None:
+      raise ValueError("text prompts need a tokenizer (tokenizer= / a `tokenizer/` directory next to the weights)")
+    # custom_sd.py:588-591
+    do_cfg = guidance_scale > 1.0 and not return_prompts_only
+    neg_texts = None
+    if text and do_cfg and negative_prompt_embeds is None and (prompt is not None or negative_prompt is not None):
+      neg_texts = self._negative_texts(prompt, negative_prompt, 1 if isinstance(prompt, str) else len(prompt or ()))
+    if return_prompts_only:      # :589-604: the prompt embeddings alone, no negative half, float32 for the caller's .cpu().numpy()
+      emb = self.encode_prompt_ids(self._prompt_ids(prompt)) if prompt is not None else prompt_embeds.to(torch.float32)
+      return emb.repeat_interleave(num_images_per_prompt, dim=0) if num_images_per_prompt != 1 else emb
+    if prompt is not None:
+      # the tower writes the bf16 context gill_sd_denoise reads: nothing visits the host between the two
+      prompt_embeds = self.encode_prompt_ids(self._prompt_ids(prompt), dtype=torch.bfloat16)
+      if neg_texts is not None:
+        # negative_prompt=None: "" for every prompt (:321-322) — identical rows, so one is encoded and shared by the batch
+        negative_prompt_embeds = self.encode_prompt_ids(self._tokenize([""] if negative_prompt is None else neg_texts),
+                                                        dtype=torch.bfloat16)
     if output_type is None:
       # the reference's default is "pil" (gill/custom_sd.py:491: `.images` is a list of PIL images); a handle built WITHOUT VAE
       # weights (UNet-only parity rigs) can only return latents

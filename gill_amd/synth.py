@@ -135,6 +135,52 @@ def clip_state_dict(cfg: ClipConfig, seed: int = 0) -> Dict[str, torch.Tensor]:
   return sd
 
 
+# ---------------------------------------------------------------------------------------------- CLIP text tower
+@dataclass
+class ClipTextConfig:
+  vocab_size: int = 49408
+  hidden_size: int = 768
+  num_layers: int = 12
+  num_heads: int = 12
+  intermediate_size: int = 3072
+  max_positions: int = 77
+  hidden_act: str = "quick_gelu"     # "quick_gelu" | "gelu"
+  use_attention_mask: bool = False   # text_encoder/config.json field custom_sd.py:300 tests; true is refused (no SD-1.5 / 2.1 sets it)
+
+  @staticmethod
+  def sd15():          # openai/clip-vit-large-patch14 text tower (runwayml/stable-diffusion-v1-5 text_encoder/config.json)
+    return ClipTextConfig()
+
+  @staticmethod
+  def sd21():          # the OpenCLIP ViT-H text tower as diffusers ships it for stable-diffusion-2-1 (23 layers, exact GELU)
+    return ClipTextConfig(hidden_size=1024, num_layers=23, num_heads=16, intermediate_size=4096, hidden_act="gelu")
+
+  @staticmethod
+  def tiny():          # head dim 64 (a supported attention width)
+    return ClipTextConfig(vocab_size=1000, hidden_size=128, num_layers=2, num_heads=2, intermediate_size=256)
+
+
+def clip_text_state_dict(cfg: ClipTextConfig, seed: int = 0) -> Dict[str, torch.Tensor]:
+  """transformers.CLIPTextModel parameters under the names of the published checkpoint files (`text_model.` prefix: the
+  text_encoder/model.safetensors of a Stable Diffusion directory)."""
+  sd: Dict[str, torch.Tensor] = {}
+  D, F = cfg.hidden_size, cfg.intermediate_size
+  tm = "text_model"
+  sd[f"{tm}.embeddings.token_embedding.weight"] = normal(f"{tm}.embeddings.token_embedding.weight", (cfg.vocab_size, D), seed, 0.5)
+  sd[f"{tm}.embeddings.position_embedding.weight"] = normal(f"{tm}.embeddings.position_embedding.weight", (cfg.max_positions, D),
+                                                            seed, 0.25)
+  for i in range(cfg.num_layers):
+    p = f"{tm}.encoder.layers.{i}"
+    for n in ("q_proj", "k_proj", "v_proj", "out_proj"):
+      _linear(sd, f"{p}.self_attn.{n}", D, D, seed)
+    _norm(sd, f"{p}.layer_norm1", D, seed)
+    _linear(sd, f"{p}.mlp.fc1", F, D, seed)
+    _linear(sd, f"{p}.mlp.fc2", D, F, seed)
+    _norm(sd, f"{p}.layer_norm2", D, seed)
+  _norm(sd, f"{tm}.final_layer_norm", D, seed)
+  return sd
+
+
 # ---------------------------------------------------------------------------------------------- GILLMapper
 @dataclass
 class MapperConfig:

@@ -151,6 +151,40 @@ void gill_clip_destroy(gill_clip* h);
 int gill_clip_forward(gill_clip* h, const float* pixel_values, int B, float* pooled_out, void* stream);
 
 /* ------------------------------------------------------------------------------------------
+ * Text prompts — the CLIP text tower of the Stable Diffusion pipeline (transformers CLIPTextModel, `self.text_encoder` of
+ * StableDiffusionPipeline: gill/custom_sd.py:305-309 and :353-357 read `text_encoder(input_ids)[0]`, i.e. last_hidden_state
+ * AFTER final_layer_norm; _encode_prompt as a whole is gill/custom_sd.py:224-373, and scripts/preprocess_sd_embeddings.py:71
+ * runs it over the captions the GILLMapper is trained to imitate).
+ * State-dict names are those of the published checkpoint files ("text_model.embeddings.token_embedding.weight",
+ * "text_model.embeddings.position_embedding.weight", "text_model.encoder.layers.0.self_attn.q_proj.weight",
+ * "text_model.final_layer_norm.weight", ...); other entries ("text_model.embeddings.position_ids") are ignored.
+ * ------------------------------------------------------------------------------------------ */
+#define GILL_CLIP_TEXT_ACT_QUICK_GELU 0 /* x * sigmoid(1.702 x): SD-1.x (OpenAI ViT-L/14 text tower) */
+#define GILL_CLIP_TEXT_ACT_GELU 1       /* exact (erf) GELU: SD-2.x (OpenCLIP ViT-H text tower as diffusers ships it) */
+typedef struct gill_clip_text_config {
+  int32_t vocab_size;         /* 49408 */
+  int32_t hidden_size;        /* 768 (SD-1.5) / 1024 (SD-2.x); head dim hidden_size / num_heads must be 48/64/80/128/160 */
+  int32_t num_layers;         /* 12 / 23 */
+  int32_t num_heads;          /* 12 / 16 */
+  int32_t intermediate_size;  /* 3072 / 4096 */
+  int32_t max_positions;      /* 77: rows of position_embedding */
+  int32_t hidden_act;         /* GILL_CLIP_TEXT_ACT_* */
+  int32_t max_batch;          /* workspace sizing */
+} gill_clip_text_config;
+typedef struct gill_clip_text gill_clip_text;
+
+int gill_clip_text_create(gill_clip_text** out, const gill_clip_text_config* cfg, const gill_tensor* weights, int n_weights);
+void gill_clip_text_destroy(gill_clip_text* h);
+
+/* text_encoder(input_ids)[0] (custom_sd.py:305-309): causal self-attention, no attention mask, LayerNorm eps 1e-5.
+ *   ids (B,T) int32 on the DEVICE, every id in [0, vocab_size) (the caller validates: ids come from a CPU tokenizer),
+ *   1 <= T <= max_positions, 1 <= B <= max_batch
+ *   -> out_bf16 (B,T,hidden) bf16 (what gill_sd_denoise takes as cond / uncond) and / or out_f32 (B,T,hidden) fp32; either may be
+ *   NULL, not both.  out_bf16 is the rounding of out_f32, written by the same pass.
+ * Enqueued on `stream` only: no host synchronisation and no blocking copy, so the call can be captured into a graph. */
+int gill_clip_text_forward(gill_clip_text* h, const int32_t* ids, int B, int T, void* out_bf16, float* out_f32, void* stream);
+
+/* ------------------------------------------------------------------------------------------
  * Stage 2 — GILLMapper = gill.layers.TextFcLayer(mode='gill_mapper').forward (layers.py:28-53).
  * State-dict names are TextFcLayer's ("fc.weight", "tfm.encoder.layers.0.self_attn.in_proj_weight",
  * "query_embs", "model.weight", ...).
