@@ -5,39 +5,24 @@
 //   out_proj, +res, LN2, fc1, quick_gelu | gelu, fc2, +res } -> final_layer_norm -> (B,T,D) bf16 and / or fp32.
 // fp32 residual stream, bf16 GEMM operands, fp32 accumulation (as clip.hip / opt.hip).  No attention mask: the reference passes
 // none (neither SD-1.5's nor SD-2.1's text_encoder config sets use_attention_mask), so padding positions attend causally like
-// any other.  Two kernels live here, the two ends of the tower; everything between them is a launch of ops.h.
+// any other.  Two kernels live here, the two ends of the tower; everything between them is the shared block of tfm.h.
 // Launches per forward: 1 + 7 L + 1 without split-K (86 at L = 12, 163 at L = 23); a GEMM that gemm_pick_splitk() splits
 // (few rows) adds its reducer.
-#include "ops.h"
-#include "engine_util.h"
-#include <string>
-#include <vector>
+#include "tfm.h"
 
 namespace {
-struct TextLayer {
-  bf16_t* wqkv = nullptr; float* bqkv = nullptr;   // [3D][D] rows: q | k | v
-  bf16_t* wo = nullptr; float* bo = nullptr;
-  bf16_t* w1 = nullptr; float* b1 = nullptr;
-  bf16_t* w2 = nullptr; float* b2 = nullptr;
-  float *ln1g = nullptr, *ln1b = nullptr, *ln2g = nullptr, *ln2b = nullptr;
-};
 constexpr int kFinalLnMaxOctets = 4;    // final LayerNorm keeps a row in registers: D <= 8 * 64 * 4 = 2048
 }  // namespace
 
 struct gill_clip_text {
   gill_clip_text_config cfg;
   DevPool pool;
-  int dp = 0, dpv = 0;
   float* tok = nullptr;       // [vocab][D] fp32: the rows enter the fp32 stream unrounded
   float* pos = nullptr;       // [max_positions][D]
   float *fing = nullptr, *finb = nullptr;
-  std::vector<TextLayer> layers;
-  // workspace
-  float* h = nullptr;         // [B*T][D]
-  bf16_t* nbuf = nullptr;     // [B*T][D]
-  bf16_t* ff = nullptr;       // [B*T][F]
-  bf16_t *q = nullptr, *k = nullptr, *vt = nullptr, *o = nullptr;
-  float* splitk_ws = nullptr; size_t splitk_ws_floats = 0;
+  std::vector<TfmLayer> layers;
+  Tfm tfm;
+  float* h = nullptr;         // [B*T][D] the fp32 stream
 };
 
 // h[b*T + t][:] = token_embedding[ids[b*T + t]][:] + position_embedding[t][:]       (CLIPTextEmbeddings.forward)
@@ -134,7 +119,6 @@ extern "C" int gill_clip_text_create(gill_clip_text** out, const gill_clip_text_
   GILL_REQUIRE(attn_padded_dim(hd) == hd, "CLIP text head dim must be one of 48/64/80/128/160");
   gill_clip_text* m = new gill_clip_text();
   m->cfg = *cfg;
-  m->dp = hd; m->dpv = round_up(hd, 32);
   WeightTable wt(weights, n_weights);
   hipStream_t s = nullptr;
   int rc = 0;
@@ -145,71 +129,23 @@ extern "C" int gill_clip_text_create(gill_clip_text** out, const gill_clip_text_
   if ((rc = load_f32(wt, m->pool, tm + "final_layer_norm.weight", D, &m->fing, s))) return fail(rc);
   if ((rc = load_f32(wt, m->pool, tm + "final_layer_norm.bias", D, &m->finb, s))) return fail(rc);
   m->layers.resize(cfg->num_layers);
-  for (int i = 0; i < cfg->num_layers; ++i) {
-    TextLayer& L = m->layers[i];
-    const std::string p = tm + "encoder.layers." + std::to_string(i) + ".";
-    if ((rc = m->pool.alloc(&L.wqkv, (size_t)3 * D * D, false))) return fail(rc);
-    if ((rc = m->pool.alloc(&L.bqkv, (size_t)3 * D, false))) return fail(rc);
-    const char* names[3] = {"q_proj", "k_proj", "v_proj"};
-    for (int j = 0; j < 3; ++j) {
-      const gill_tensor* t;
-      if ((rc = wt.get(p + "self_attn." + names[j] + ".weight", (int64_t)D * D, &t))) return fail(rc);
-      if ((rc = convert_to_bf16_launch(t->data, t->dtype, (int64_t)D * D, L.wqkv + (size_t)j * D * D, s))) return fail(rc);
-      if ((rc = wt.get(p + "self_attn." + names[j] + ".bias", D, &t))) return fail(rc);
-      if ((rc = convert_to_f32_launch(t->data, t->dtype, D, L.bqkv + (size_t)j * D, s))) return fail(rc);
-    }
-    if ((rc = load_bf16(wt, m->pool, p + "self_attn.out_proj.weight", (int64_t)D * D, &L.wo, s))) return fail(rc);
-    if ((rc = load_f32(wt, m->pool, p + "self_attn.out_proj.bias", D, &L.bo, s))) return fail(rc);
-    if ((rc = load_bf16(wt, m->pool, p + "mlp.fc1.weight", (int64_t)F * D, &L.w1, s))) return fail(rc);
-    if ((rc = load_f32(wt, m->pool, p + "mlp.fc1.bias", F, &L.b1, s))) return fail(rc);
-    if ((rc = load_bf16(wt, m->pool, p + "mlp.fc2.weight", (int64_t)D * F, &L.w2, s))) return fail(rc);
-    if ((rc = load_f32(wt, m->pool, p + "mlp.fc2.bias", D, &L.b2, s))) return fail(rc);
-    if ((rc = load_f32(wt, m->pool, p + "layer_norm1.weight", D, &L.ln1g, s))) return fail(rc);
-    if ((rc = load_f32(wt, m->pool, p + "layer_norm1.bias", D, &L.ln1b, s))) return fail(rc);
-    if ((rc = load_f32(wt, m->pool, p + "layer_norm2.weight", D, &L.ln2g, s))) return fail(rc);
-    if ((rc = load_f32(wt, m->pool, p + "layer_norm2.bias", D, &L.ln2b, s))) return fail(rc);
-  }
-  const size_t R = (size_t)cfg->max_batch * P;
-  const size_t Tpad = round_up(P, 32);
-  if ((rc = m->pool.alloc(&m->h, R * D))) return fail(rc);
-  if ((rc = m->pool.alloc(&m->nbuf, R * D))) return fail(rc);
-  if ((rc = m->pool.alloc(&m->ff, R * F))) return fail(rc);
-  if ((rc = m->pool.alloc(&m->q, (size_t)cfg->max_batch * H * Tpad * m->dp))) return fail(rc);
-  if ((rc = m->pool.alloc(&m->k, (size_t)cfg->max_batch * H * Tpad * m->dp))) return fail(rc);
-  if ((rc = m->pool.alloc(&m->vt, (size_t)cfg->max_batch * H * m->dpv * Tpad))) return fail(rc);
-  if ((rc = m->pool.alloc(&m->o, R * D))) return fail(rc);
-  // split-K partials: gemm_pick_splitk() splits only under-filled grids (< 384 tiles of 128 x 128, at most 16 ways aiming at 512
-  // workgroups), so splitk * M * N stays near 512 * 128 * 128 floats whatever max_batch is; a launch that would not fit runs unsplit
-  m->splitk_ws_floats = (size_t)16 * R * (size_t)(F > 3 * D ? F : 3 * D);
-  if (m->splitk_ws_floats > ((size_t)16 << 20)) m->splitk_ws_floats = (size_t)16 << 20;
-  if ((rc = m->pool.alloc(&m->splitk_ws, m->splitk_ws_floats, false))) return fail(rc);
+  const TfmNames names = {{"self_attn.q_proj.", "self_attn.k_proj.", "self_attn.v_proj."}, "self_attn.out_proj.", "mlp.fc1.", "mlp.fc2.",
+                          "layer_norm1.", "layer_norm2."};
+  // row-major weights, not the STREAM64 layout: kept as found
+  for (int i = 0; i < cfg->num_layers; ++i)
+    if ((rc = tfm_load_layer(wt, m->pool, tm + "encoder.layers." + std::to_string(i) + ".", names, D, F, false, &m->layers[i], s)))
+      return fail(rc);
+  if ((rc = m->pool.alloc(&m->h, (size_t)cfg->max_batch * P * D))) return fail(rc);
+  // fuse_ln stays off (a stand-alone LayerNorm at every seam): kept as found.  The split-K partials are capped at 16 Mi floats:
+  // gemm_pick_splitk() splits only under-filled grids (< 384 tiles of 128 x 128, at most 16 ways aiming at 512 workgroups), so
+  // splitk * M * N stays near 512 * 128 * 128 floats whatever max_batch is; that only this engine caps is kept as found
+  if ((rc = m->tfm.alloc(m->pool, cfg->max_batch, P, D, F, H, hd, round_up(hd, 32), (size_t)16 << 20))) return fail(rc);
   if (hipDeviceSynchronize() != hipSuccess) { gill_set_error("clip text create: device sync failed"); return fail(-1); }
   *out = m;
   return 0;
 }
 
 extern "C" void gill_clip_text_destroy(gill_clip_text* h) { delete h; }
-
-namespace {
-struct TextRun {
-  gill_clip_text* m;
-  hipStream_t s;
-  int splitk(int M, int N, int K, int act) const {
-    const int sk = gemm_pick_splitk(M, N, K, act);
-    return (size_t)sk * M * N > m->splitk_ws_floats ? 1 : sk;
-  }
-  int linear(const bf16_t* A, int M, const bf16_t* W, const float* b, int N, int K, const float* resid, int act, void* out,
-             bool out_f32) {
-    GemmArgs g;
-    g.M = M; g.N = N; g.K = K; g.K1 = K; g.A = A; g.lda = K; g.W = W; g.bias = b;
-    g.resid = resid; g.ldr = N; g.resid_f32 = 1;
-    g.act = act; g.out_mode = out_f32 ? OUT_F32 : OUT_BF16; g.C = out; g.ldc = N;
-    g.splitk = splitk(M, N, K, act);
-    g.ws = m->splitk_ws;
-    return gemm_launch(g, s);
-  }
-};
-}  // namespace
 
 extern "C" int gill_clip_text_forward(gill_clip_text* m, const int32_t* ids, int B, int T, void* out_bf16, float* out_f32,
                                       void* stream) {
@@ -219,37 +155,11 @@ extern "C" int gill_clip_text_forward(gill_clip_text* m, const int32_t* ids, int
   GILL_REQUIRE(T >= 1 && T <= m->cfg.max_positions, "sequence length exceeds the CLIP text handle's max_positions");
   hipStream_t s = (hipStream_t)stream;
   const gill_clip_text_config& c = m->cfg;
-  const int D = c.hidden_size, F = c.intermediate_size, R = B * T;
-  const int Tpad = round_up(T, 32);
+  const int D = c.hidden_size, R = B * T;
   const int act = c.hidden_act == GILL_CLIP_TEXT_ACT_GELU ? ACT_GELU : ACT_QUICK_GELU;
-  TextRun r{m, s};
   hipLaunchKernelGGL(clip_text_embed_kernel, dim3(cdiv(R, 4)), dim3(256), 0, s, ids, m->tok, m->pos, R, T, D, c.vocab_size, m->h);
   GILL_CHECK_HIP(hipGetLastError());
-  for (const TextLayer& L : m->layers) {
-    GILL_TRY(layernorm_launch(m->h, 1, L.ln1g, L.ln1b, m->nbuf, R, D, 1e-5f, s));
-    {
-      GemmArgs g;
-      g.M = R; g.N = 3 * D; g.K = D; g.K1 = D; g.A = m->nbuf; g.lda = D; g.W = L.wqkv; g.bias = L.bqkv;
-      g.out_mode = OUT_QKV; g.Cq = m->q; g.Ck = m->k; g.Cvt = m->vt;
-      g.heads = c.num_heads; g.dp = m->dp; g.dpv = m->dpv; g.ntok = T; g.ntok_pad_q = Tpad; g.ntok_pad_kv = Tpad;
-      g.seg_base = 0;
-      g.qscale = 1.4426950408889634f / sqrtf((float)m->dp);
-      g.splitk = r.splitk(R, 3 * D, D, 0);
-      g.ws = m->splitk_ws;
-      GILL_TRY(gemm_launch(g, s));
-    }
-    {
-      AttnArgs a;
-      a.Q = m->q; a.K = m->k; a.Vt = m->vt; a.O = m->o;
-      a.B = B; a.H = c.num_heads; a.nq = T; a.nkv = T; a.nq_pad = Tpad; a.nkv_pad = Tpad;
-      a.dp = m->dp; a.dpv = m->dpv; a.ldo = D; a.scale = 1.0f / sqrtf((float)m->dp); a.causal = 1;
-      GILL_TRY(attention_launch(a, s));
-    }
-    GILL_TRY(r.linear(m->o, R, L.wo, L.bo, D, D, m->h, ACT_NONE, m->h, true));
-    GILL_TRY(layernorm_launch(m->h, 1, L.ln2g, L.ln2b, m->nbuf, R, D, 1e-5f, s));
-    GILL_TRY(r.linear(m->nbuf, R, L.w1, L.b1, F, D, nullptr, act, m->ff, false));
-    GILL_TRY(r.linear(m->ff, R, L.w2, L.b2, D, F, m->h, ACT_NONE, m->h, true));
-  }
+  GILL_TRY((TfmRun{m->tfm, s}.layers(m->h, m->layers.data(), (int)m->layers.size(), B, T, act, true)));
   hipLaunchKernelGGL((clip_text_final_ln_kernel<kFinalLnMaxOctets>), dim3(cdiv(R, 4)), dim3(256), 0, s, m->h, m->fing, m->finb,
                      (bf16_t*)out_bf16, out_f32, R, D, 1e-5f);
   GILL_CHECK_HIP(hipGetLastError());

@@ -44,7 +44,7 @@ struct GemmArgs {
   // split-K (0/1 = off).  ws must hold splitk*M*N floats.
   int splitk = 1; float* ws = nullptr;
   int w_blk64 = 0;         // W is stored as [N / 64][K / 64][64][64] (convert_to_bf16_blk64_launch): the STREAM64 kernel up to GEMM_STREAM64_MAX_ROWS rows, the general tiles above
-  int partials_only = 0;   // split-K: write the fp32 partials and stop — the caller runs its own reducer (opt.hip: reduce + residual + LayerNorm)
+  int partials_only = 0;   // split-K: write the fp32 partials and stop — the caller runs its own reducer (tfm.hip: reduce + residual + LayerNorm)
   // Both kinds of fused statistics are FIXED-ORDER: a producer writes each partial sum exactly once (no atomics, nothing to
   // zero), the consumer adds the partials in index order, so two runs of the same launch sequence are bit-identical.
   // fused GroupNorm statistics of the output: gn_stats[(b * nslab + slab) * gn_groups + g][2] = {sum, sum of squares} of the

@@ -1,0 +1,65 @@
+// The pre-LayerNorm transformer block the OPT, CLIP vision, CLIP text and mapper engines share:
+//   h += out_proj(attn(q, k, v = qkv(LN1(h))))       q scaled by head_dim^-0.5
+//   h += fc2(act(fc1(LN2(h))))
+// fp32 residual stream, bf16 GEMM operands, fp32 accumulation; attention is the shared flash kernel.  One layer struct, one
+// weight loader, one workspace and one runner; an engine keeps what is particular to it (embeddings, caches, final norms) and
+// sets the switches of struct Tfm.  Nothing here allocates or builds strings per launch.
+#pragma once
+#include "engine_util.h"
+
+struct TfmLayer {
+  bf16_t* wqkv = nullptr; float* bqkv = nullptr;   // [3D][D] rows: q | k | v
+  bf16_t* wo = nullptr; float* bo = nullptr;
+  bf16_t* w1 = nullptr; float* b1 = nullptr;
+  bf16_t* w2 = nullptr; float* b2 = nullptr;
+  float *ln1g = nullptr, *ln1b = nullptr, *ln2g = nullptr, *ln2b = nullptr;
+  int blk_qkv = 0, blk_o = 0, blk_1 = 0, blk_2 = 0;   // matrix stored 64 x 64-blocked (gemm_stream64_weights: the STREAM64 layout)
+};
+
+// Tensor names under a layer's prefix, each up to and including the separator in front of "weight" / "bias".
+struct TfmNames {
+  const char* qkv[3];   // q, k, v projections; qkv[1] == nullptr: qkv[0] is one packed [3D][D] in_proj
+  const char *o, *fc1, *fc2, *ln1, *ln2;
+};
+// stream64: store the matrices gemm_stream64_weights() names in the STREAM64 layout (convert_to_bf16_blk64_launch)
+int tfm_load_layer(const WeightTable& wt, DevPool& pool, const std::string& prefix, const TfmNames& names, int D, int F, bool stream64,
+                   TfmLayer* L, hipStream_t s);
+
+// Geometry, per-engine switches and workspace of the block (the fp32 stream itself stays with the engine).
+struct Tfm {
+  int D = 0, F = 0, H = 0, dp = 0, dpv = 0;
+  bool fuse_ln = false;     // split-K out_proj / fc2 hand the LayerNorm that follows them to their reducer (opt_reduce_ln_kernel)
+  bool split_qkv = true;    // the QKV GEMM takes the split factor of gemm_pick_splitk*(); false: always 1
+  bf16_t* nbuf = nullptr;   // [rows][D] normalised stream: the operand of the next GEMM
+  bf16_t* ff = nullptr;     // [rows][F]
+  bf16_t *q = nullptr, *k = nullptr, *vt = nullptr, *o = nullptr;
+  float* splitk_ws = nullptr; size_t splitk_ws_floats = 0;
+  // buffers for max_batch sequences of up to max_tok tokens; ws_cap_floats != 0 caps the split-K partials
+  int alloc(DevPool& pool, int max_batch, int max_tok, int D, int F, int H, int dp, int dpv, size_t ws_cap_floats = 0);
+};
+
+// a K / Vt cache of one layer: K [B][H][pad][dp], Vt [B][H][dpv][pad]
+struct TfmKv { bf16_t* k = nullptr; bf16_t* vt = nullptr; int pad = 0; };
+
+struct TfmRun {
+  const Tfm& t;
+  hipStream_t s;
+  int splitk(int M, int N, int K, int act, int blk) const;
+  // y = act(A . W^T + b [+ resid_f32]); out fp32 or bf16.  ln_g / ln_b / ln_out: the LayerNorm that consumes the result (in-place
+  // residual GEMMs into the fp32 stream: out == resid).  With Tfm::fuse_ln a split-K launch hands it to the reducer
+  // (opt_reduce_ln_kernel); every other launch is followed by the stand-alone pass.
+  int linear(const bf16_t* A, int M, const bf16_t* W, int blk, const float* b, int N, int K, const float* resid, int act, void* out,
+             bool out_f32, const float* ln_g = nullptr, const float* ln_b = nullptr, bf16_t* ln_out = nullptr) const;
+  // scatter nseg segments of a projection into the head-major attention operands; seg_base: 0 = q(, k, v); 1 = k, v only
+  int qkv(const bf16_t* A, int B, int ntok, const bf16_t* W, const float* b, int nseg, int seg_base, int npad_q, int npad_kv,
+          bf16_t* K, bf16_t* Vt, int kv_tok_offset, int blk) const;
+  int attend(int B, int nq, int nkv, int npad_q, int npad_kv, const bf16_t* K, const bf16_t* Vt, bool causal) const;
+  // the two sub-blocks over the stream h (B * T rows); nbuf holds their LayerNorm of h on entry and, with next_g, that of next_g / next_b on exit.
+  // kv: the T rows are the tokens past .. past + T - 1 of each sequence; their K / Vt are appended to the cache and they attend to it
+  int self_attn(float* h, int B, int T, const TfmLayer& L, bool causal, const float* next_g, const float* next_b, const TfmKv* kv = nullptr,
+                int past = 0) const;
+  int ffn(float* h, int rows, const TfmLayer& L, int act, const float* next_g = nullptr, const float* next_b = nullptr) const;
+  // n layers: LN1 stand-alone for the first, every later LayerNorm rides on the GEMM in front of it (see linear).
+  // kv: one cache per layer holding `past` tokens (OPT's cached decode); nullptr: plain forward over T tokens
+  int layers(float* h, const TfmLayer* L, int n, int B, int T, int act, bool causal, const TfmKv* kv = nullptr, int past = 0) const;
+};
