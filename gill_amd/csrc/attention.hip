@@ -232,7 +232,9 @@ __global__ __launch_bounds__(ATT_THREADS, (DP <= 64 ? 4 : 2)) void attention_ker
       if (__any(grow)) {
         float delta;
         if (first) { m_run = (mx > -INFINITY) ? mx : 0.f; delta = m_run; }   // (a valid row always sees key 0)
-        else { delta = fmaxf(mx, 0.f); m_run += delta; }                    // fully masked row: mx = -inf -> 0
+        // a row that did not ask for the move keeps its max (delta 0: alpha = 1, every product below exact), so its bits do
+        // not depend on what the other rows of the wave see -- in a decode step they see keys this row has masked
+        else { delta = grow ? mx : 0.f; m_run += delta; }
         if (!first) {
           const float alpha = __builtin_amdgcn_exp2f(-delta);
           l_run *= alpha;

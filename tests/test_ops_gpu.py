@@ -331,6 +331,74 @@ def test_attention_softmax_spike(cuda):
   assert _report("attn spike", out, ref) < 2e-2
 
 
+def _decode_shapes():
+  from kv_cache_util import DECODE_SHAPES
+  return DECODE_SHAPES
+
+
+@pytest.mark.parametrize("B,H,nq,nkv,d", _decode_shapes())
+def test_attention_causal_decode_offset(cuda, B, H, nq, nkv, d):
+  """causal=True with nq < nkv, as a KV-cached decode step runs it: nq new rows (1, an 8-token [IMG] block, or a late prefill piece)
+  against nkv = past + nq keys, query i attending kv <= i + (nkv - nq).  attention.hip's per-tile bound (kv_end_blk), per-wave bound
+  (wave_kv_end), need_mask and qidx = qrow + coff all depend on that offset.  The bar of test_attention, per query row, so that one
+  wrong row cannot hide under another row's maximum.  Operands (kv_cache_util.decode_attn_inputs): a peaked softmax in which the
+  diagonal key matters, for which tests/test_kv_cache_host.py shows that a hidden newest key, an offset off by one, a visible
+  stale key, K/V of the wrong batch row or a shifted V all fail this very check."""
+  from gill_amd import ops
+  from kv_cache_util import ATTN_BAR, decode_attn_inputs, report_rows
+  q, k, v = decode_attn_inputs(B, H, nq, nkv, d, seed=40)
+  scale = d ** -0.5
+  ref = _attn_ref(q, k, v, H, scale, True)
+  out = ops.attention(_bf(q).to(cuda), _bf(k).to(cuda), _bf(v).to(cuda), H, scale, True)
+  assert torch.isfinite(out.float()).all()
+  assert report_rows(f"attn decode B{B} H{H} {nq}x{nkv} d{d}", out, ref) < ATTN_BAR
+  assert _report(f"attn decode B{B} H{H} {nq}x{nkv} d{d} (whole tensor)", out, ref) < 2e-2
+
+
+@pytest.mark.parametrize("H,nq,nkv,d", [(32, 1, 129, 128), (12, 8, 71, 64), (12, 8, 136, 64)])
+def test_attention_causal_decode_spike_on_newest_key(cuda, H, nq, nkv, d):
+  """In the style of test_attention_softmax_spike: the key the step has just appended (index nkv - 1) is aligned with the last query, so
+  it dominates that row's softmax -- from the last key tile, after the running max has settled on earlier tiles.  A step that did
+  not see its newest key would return a different row altogether."""
+  from gill_amd import ops
+  from kv_cache_util import ATTN_BAR, report_rows
+  B = 2
+  q, k, v = _rnd((B, nq, H * d), 61), _rnd((B, nkv, H * d), 62), _rnd((B, nkv, H * d), 63)
+  k[:, nkv - 1] = q[:, nq - 1] * 4.0
+  q, k, v = _bf(q), _bf(k), _bf(v)
+  ref = _attn_ref(q, k, v, H, d ** -0.5, True)
+  blind = _attn_ref(q[:, -1:], k[:, :-1], v[:, :-1], H, d ** -0.5, False)
+  assert _report("newest key matters to the last row (oracle with vs without it)", blind, ref[:, -1:]) > 10 * ATTN_BAR
+  out = ops.attention(q.to(cuda), k.to(cuda), v.to(cuda), H, d ** -0.5, True)
+  assert report_rows(f"attn decode spike on the newest key H{H} {nq}x{nkv} d{d}", out, ref) < ATTN_BAR
+
+
+@pytest.mark.parametrize("H,nq,nkv,d,row", [(32, 8, 72, 128, 3), (12, 8, 65, 64, 0), (12, 33, 97, 64, 30), (12, 130, 300, 64, 127)])
+def test_attention_causal_decode_first_masked_key_has_no_effect(cuda, H, nq, nkv, d, row):
+  """The first masked key of query `row` (index qidx + 1, present in K: the next token of the same step) is aligned with that query:
+  seen, it would dominate the row.  It must have exactly no effect on rows 0 .. row: they are bit-identical to a run in which that
+  key's K and V rows hold other finite values (the later rows, which do see the key, must differ), and they meet the oracle.
+  (The 33 x 97 case caught attention.hip moving the running max of every row of a wave as soon as one row asked for it: rows 0 .. 30
+  share their wave with row 31, which sees the key, so their rounding followed a key they have masked.)"""
+  from gill_amd import ops
+  from kv_cache_util import ATTN_BAR, report_rows
+  B = 2
+  q, k, v = _rnd((B, nq, H * d), 64), _rnd((B, nkv, H * d), 65), _rnd((B, nkv, H * d), 66)
+  masked = row + (nkv - nq) + 1
+  k[:, masked] = q[:, row] * 4.0
+  q, k, v = _bf(q), _bf(k), _bf(v)
+  k2, v2 = k.clone(), v.clone()
+  k2[:, masked], v2[:, masked] = _bf(_rnd((B, H * d), 67) * 3.0), _bf(_rnd((B, H * d), 68) * 50.0)
+  ref = _attn_ref(q, k, v, H, d ** -0.5, True)
+  seen = _attn_ref(q[:, row:row + 1], k[:, :masked + 1], v[:, :masked + 1], H, d ** -0.5, False)
+  assert _report("the masked key would matter (oracle, seen vs masked)", seen, ref[:, row:row + 1]) > 10 * ATTN_BAR
+  out = ops.attention(q.to(cuda), k.to(cuda), v.to(cuda), H, d ** -0.5, True)
+  out2 = ops.attention(q.to(cuda), k2.to(cuda), v2.to(cuda), H, d ** -0.5, True)
+  assert torch.equal(out[:, :row + 1], out2[:, :row + 1])
+  assert not torch.equal(out[:, row + 1:], out2[:, row + 1:])
+  assert report_rows(f"attn decode, first masked key aligned H{H} {nq}x{nkv} d{d}", out, ref) < ATTN_BAR
+
+
 @pytest.mark.parametrize("mag", [1.0, 64.0, 4096.0])
 def test_attention_d40_large_scores(cuda, mag):
   """d = 40 (the QF3 / LDS-DMA kernel): scores far outside bf16's integer range, and a running max that jumps in a late tile.
