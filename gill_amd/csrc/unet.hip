@@ -18,7 +18,7 @@
 // (they depend only on the prompt embedding) and the whole time-embedding MLP + the 22 resnet
 // time projections for every timestep (one batched GEMM chain -> a [steps][sum Cout] table that the
 // conv epilogues add as a per-channel row vector).
-#include "engine_util.h"
+#include "convnet.h"
 #include <math.h>
 #include <stdlib.h>
 #include <map>
@@ -27,22 +27,11 @@
 
 namespace {
 
-struct ConvW {
-  bf16_t* w = nullptr; float* b = nullptr; int cin = 0, cout = 0; int chunked = 0; /* K order: GemmArgs::k_chunked */ int ups4 = 0; /* w = the 4-tap parity-class form (GemmArgs::ups == 2) */
-  // gill_unet_config.fp8_convs: e4m3 weights [cout][kpad] in conv_fp8.hip's K order + per-output-channel de-quantisation scale
-  unsigned char* w8 = nullptr; float* cs = nullptr; int kpad = 0;
-};
 struct LinW { bf16_t* w = nullptr; float* b = nullptr; int out = 0, in = 0; };
-struct NormW { float* g = nullptr; float* b = nullptr; int c = 0; };
 
-struct ResnetW {
-  NormW n1, n2;
-  ConvW c1, c2;
-  bool has_sc = false;
-  LinW sc;
-  // conv2 with the 1x1 conv_shortcut fused as extra K channels: weights [cout][9*cout + cin], bias b2 + b_sc
-  bf16_t* c2f_w = nullptr; float* c2f_b = nullptr;
-  int cin = 0, cout = 0, temb_off = 0;
+struct ResnetW : ResW {
+  LinW sc;             // conv_shortcut as a GEMM of its own (fp8 mode)
+  int temb_off = 0;    // this block's columns of the time-embedding table
 };
 
 struct XfW {  // Transformer2DModel with one BasicTransformerBlock
@@ -68,28 +57,8 @@ struct XfW {  // Transformer2DModel with one BasicTransformerBlock
   bf16_t* wfo = nullptr; float* bfo = nullptr;   // ff2 and proj_out as one map: [C][4C + C] = [Wp W2 | Wp], bias Wp b2 + bp
 };
 
-// stats: optional slot [Bx][H*W/64][C/sbin][2] that the PRODUCING GEMM epilogue fills with this tensor's per-slab GroupNorm
-// partial sums (GemmArgs::gn_stats: written once each, added in slab order by the consumer)
-// sbin: channels per statistics bin (C/64: finer than a group, so the sums also serve the wider groups of a skip concat)
-// nslab: partials per (sample, bin) the producer actually wrote (set when the producing GEMM is launched)
-struct Tensor { bf16_t* p = nullptr; int H = 0, W = 0, C = 0; float* stats = nullptr; int sbin = 0; int nslab = 1; };
 // row sums feeding a folded LayerNorm: [planes][rows][2], planes fixed by the producing GEMM's tiling (gemm_row_planes)
 struct RowStats { float* p = nullptr; int planes = 1; };
-
-struct Arena {
-  unsigned char* base = nullptr;
-  size_t cap = 0, off = 0, high = 0;
-  bool dry = false;
-  void* alloc(size_t bytes) {
-    bytes = (bytes + 255) & ~(size_t)255;
-    void* p = dry ? (void*)(uintptr_t)(0x1000 + off) : (void*)(base + off);
-    off += bytes;
-    if (off > high) high = off;
-    return p;
-  }
-  size_t mark() const { return off; }
-  void release(size_t m) { off = m; }
-};
 
 }  // namespace
 
@@ -101,7 +70,7 @@ struct GraphKey {     // (the guidance scale is a device-side scalar, not part o
   }
 };
 
-struct gill_unet {
+struct gill_unet : ConvWorkspace {
   gill_unet_config cfg;
   DevPool pool;
   // weights
@@ -117,14 +86,9 @@ struct gill_unet {
   XfW mid_xf;
   int n_xf = 0;
   int temb_dim = 0;
-  // workspace
-  Arena arena;
-  unsigned char* arena_mem = nullptr;
-  float* gn_stats = nullptr;      // per-forward pool of GroupNorm partial-sum slots (bump-allocated; the dry run sizes it)
-  size_t gn_floats = 0, gn_next = 0;
+  // workspace (+ ConvWorkspace)
   float* ln_stats = nullptr;      // per-forward pool of the row-sum planes feeding the folded LayerNorms
   size_t ln_floats = 0, ln_next = 0;
-  float* splitk_ws = nullptr; size_t splitk_ws_floats = 0;
   // COOP arrival counters (GemmArgs::coop_ctr): one slot range per GEMM launch of a forward, bump-allocated in launch order (the dry run sizes the
   // pool), all zeroed by the forward's first kernel (im2col_nchw_launch)
   unsigned* coop_ctr = nullptr; size_t coop_n = 0, coop_next = 0;
@@ -162,11 +126,6 @@ struct gill_unet {
     for (auto& kv : graphs) (void)hipGraphExecDestroy(kv.second);
   }
 };
-
-__global__ void vec_add_f32_kernel(const float* a, const float* b, int n, float* out) {
-  const int i = blockIdx.x * blockDim.x + threadIdx.x;
-  if (i < n) out[i] = a[i] + b[i];
-}
 
 // dst[r][h*dp + dd] = src[r][h*d + dd] (dd < d), zero elsewhere.  dst pre-zeroed.
 __global__ __launch_bounds__(256) void pad_head_cols_kernel(const void* src, int dtype, int rows, int H, int d, int dp,
@@ -342,36 +301,10 @@ struct Loader {
   DevPool& pool;
   hipStream_t s;
   int ctx_len = 0;
-  int norm(const std::string& p, int c, NormW* n) {
-    n->c = c;
-    GILL_TRY(load_f32(wt, pool, p + ".weight", c, &n->g, s));
-    return load_f32(wt, pool, p + ".bias", c, &n->b, s);
-  }
-  // hw: pixels per sample of the conv's INPUT (decides the K order, see GemmArgs::k_chunked)
-  // ups4: the conv follows a nearest-2x upsample — store the four pre-summed 2x2-tap kernels instead (gemm.hip "UPS4";
-  // GILL_CONV_UPS4 = 0 keeps the 9-tap gather over the upsampled grid)
+  int norm(const std::string& p, int c, NormW* n) { return load_norm(wt, pool, s, p, c, n); }
+  // hw: pixels per sample of the conv's INPUT (decides the K order, see load_conv3)
   int conv3(const std::string& p, int cin, int cout, int hw, ConvW* c, bool f8 = false, bool ups4 = false) {
-    c->cin = cin; c->cout = cout; c->chunked = conv_k_chunked(hw, cin, cout) ? 1 : 0;
-    const gill_tensor* t;
-    GILL_TRY(wt.get(p + ".weight", (int64_t)cout * cin * 9, &t));
-    static const int ups4_on = [] { const char* v = getenv("GILL_CONV_UPS4"); return v ? atoi(v) : 1; }();
-    if (ups4 && ups4_on && !f8) {
-      c->ups4 = 1; c->chunked = 0;
-      GILL_TRY(pool.alloc(&c->w, (size_t)16 * cout * cin, false));
-      GILL_TRY(conv_weight_relayout_ups4_launch(t->data, t->dtype, cout, cin, c->w, s));
-      return load_f32(wt, pool, p + ".bias", cout, &c->b, s);
-    }
-    if (f8) {
-      c->kpad = conv_fp8_kpad(cin);
-      GILL_TRY(pool.alloc(&c->w8, (size_t)cout * c->kpad, false));
-      GILL_TRY(pool.alloc(&c->cs, (size_t)cout, false));
-      GILL_TRY(conv_weight_quant_fp8_launch(t->data, t->dtype, cout, cin, F8_ACT_SCALE, c->w8, c->cs, s));
-      return load_f32(wt, pool, p + ".bias", cout, &c->b, s);
-    }
-    GILL_TRY(pool.alloc(&c->w, (size_t)cout * cin * 9, false));
-    if (c->chunked) GILL_TRY(conv_weight_relayout_chunked_launch(t->data, t->dtype, cout, cin, c->w, s));
-    else GILL_TRY(conv_weight_relayout_launch(t->data, t->dtype, cout, cin, c->w, s));
-    return load_f32(wt, pool, p + ".bias", cout, &c->b, s);
+    return load_conv3(wt, pool, s, p, cin, cout, hw, c, f8, ups4);
   }
   int lin(const std::string& p, int out, int in, LinW* l, bool bias = true) {
     l->out = out; l->in = in;
@@ -397,21 +330,8 @@ struct Loader {
     GILL_TRY(conv3(p + ".conv2", cout, cout, hw, &r->c2, f8));
     r->has_sc = (cin != cout);
     if (r->has_sc) GILL_TRY(lin(p + ".conv_shortcut", cout, cin, &r->sc));
-    if (r->has_sc && !f8) {   // (fp8 mode: the 1x1 shortcut stays a bf16 GEMM of its own whose output is conv2's residual)
-      // fused weight rows: [conv2 taps (9*cout) | shortcut (cin)]
-      const int kf = 9 * cout + cin;
-      std::vector<int32_t> ident(cout);
-      for (int i = 0; i < cout; ++i) ident[i] = i;
-      int32_t* idx;
-      GILL_TRY(pool.alloc(&idx, (size_t)cout, false));
-      GILL_CHECK_HIP(hipMemcpy(idx, ident.data(), sizeof(int32_t) * cout, hipMemcpyHostToDevice));
-      GILL_TRY(pool.alloc(&r->c2f_w, (size_t)cout * kf, false));
-      GILL_TRY(scatter_rows_bf16_launch(r->c2.w, cout, 9 * cout, idx, r->c2f_w, kf, s));
-      GILL_TRY(scatter_rows_bf16_launch(r->sc.w, cout, cin, idx, r->c2f_w + 9 * cout, kf, s));
-      GILL_TRY(pool.alloc(&r->c2f_b, (size_t)cout, false));
-      hipLaunchKernelGGL(vec_add_f32_kernel, dim3(cdiv(cout, 256)), dim3(256), 0, s, r->c2.b, r->sc.b, cout, r->c2f_b);
-      GILL_CHECK_HIP(hipGetLastError());
-    }
+    // (fp8 mode: the 1x1 shortcut stays a bf16 GEMM of its own whose output is conv2's residual)
+    if (r->has_sc && !f8) GILL_TRY(fuse_shortcut_into_conv2(pool, s, r->sc.w, r->sc.b, r));
     // time_emb_proj rows go into the shared [sum Cout][temb_dim] matrix
     r->temb_off = *temb_off;
     const gill_tensor* t;
@@ -566,30 +486,9 @@ extern "C" int gill_unet_create(gill_unet** out, const gill_unet_config* cfg, co
   if ((rc = m->pool.alloc(&m->temb_proj_b, (size_t)temb_total, false))) return fail(rc);
   int temb_off = 0;
 
-  // conv_in / conv_out (direct kernels, [Cout][9][Cin] layout as well)
-  {
-    const gill_tensor* t;
-    GILL_REQUIRE(cfg->in_channels * 9 <= 64, "conv_in: in_channels * 9 must fit one 64-wide K step");
-    if ((rc = wt.get("conv_in.weight", (int64_t)ch[0] * cfg->in_channels * 9, &t))) return fail(rc);
-    {
-      // conv_in runs as im2col (K = 36 zero-padded to 64) + the MFMA GEMM: weights [Cout][tap*Cin + c] padded to [Cout][64]
-      bf16_t* tmp; int32_t* idx;
-      const int kk = cfg->in_channels * 9;
-      if ((rc = m->pool.alloc(&tmp, (size_t)ch[0] * kk, false))) return fail(rc);
-      if ((rc = conv_weight_relayout_launch(t->data, t->dtype, ch[0], cfg->in_channels, tmp, s))) return fail(rc);
-      if ((rc = m->pool.alloc(&m->conv_in_w, (size_t)ch[0] * 64, true))) return fail(rc);
-      std::vector<int32_t> rows(ch[0]);
-      for (int i = 0; i < ch[0]; ++i) rows[i] = i;
-      if ((rc = m->pool.alloc(&idx, (size_t)ch[0], false))) return fail(rc);
-      if (hipMemcpy(idx, rows.data(), sizeof(int32_t) * ch[0], hipMemcpyHostToDevice) != hipSuccess) return fail(-1);
-      if ((rc = scatter_rows_bf16_launch(tmp, ch[0], kk, idx, m->conv_in_w, 64, s))) return fail(rc);
-    }
-    if ((rc = load_f32(wt, m->pool, "conv_in.bias", ch[0], &m->conv_in_b, s))) return fail(rc);
-    if ((rc = wt.get("conv_out.weight", (int64_t)cfg->out_channels * ch[0] * 9, &t))) return fail(rc);
-    if ((rc = m->pool.alloc(&m->conv_out_w, (size_t)cfg->out_channels * ch[0] * 9, false))) return fail(rc);
-    if ((rc = conv_weight_relayout_launch(t->data, t->dtype, cfg->out_channels, ch[0], m->conv_out_w, s))) return fail(rc);
-    if ((rc = load_f32(wt, m->pool, "conv_out.bias", cfg->out_channels, &m->conv_out_b, s))) return fail(rc);
-  }
+  // conv_in runs as im2col (K = 36 zero-padded to 64) + the MFMA GEMM, conv_out as a direct kernel
+  if ((rc = load_conv_in_im2col(wt, m->pool, s, "conv_in", cfg->in_channels, ch[0], &m->conv_in_w, &m->conv_in_b))) return fail(rc);
+  if ((rc = load_conv_out(wt, m->pool, s, "conv_out", ch[0], cfg->out_channels, &m->conv_out_w, &m->conv_out_b))) return fail(rc);
   if ((rc = L.norm("conv_norm_out", ch[0], &m->norm_out))) return fail(rc);
   if ((rc = L.lin("time_embedding.linear_1", temb_dim, ch[0], &m->te1))) return fail(rc);
   if ((rc = L.lin("time_embedding.linear_2", temb_dim, temb_dim, &m->te2))) return fail(rc);
@@ -655,13 +554,12 @@ extern "C" void gill_unet_destroy(gill_unet* h) { delete h; }
 // ------------------------------------------------------------------------------------------------------------------
 namespace {
 
-struct UNetRun {
+struct UNetRun : ConvRun {
   gill_unet* m;
-  hipStream_t s;
-  int Bx;
   const float* temb_rows;   // row for sample 0
   int temb_bstride;         // 0: every sample uses the same row
-  bool dry;
+  UNetRun(gill_unet* m, hipStream_t s, int Bx, const float* temb_rows, int temb_bstride, bool dry)
+      : ConvRun{m, m->cfg.norm_num_groups, s, Bx, dry}, m(m), temb_rows(temb_rows), temb_bstride(temb_bstride) {}
   // classifier-free-guidance pair: samples b and b + Bx/2 carry the same latents and timestep and differ only in the prompt,
   // so everything before the first cross-attention runs once on the first half (gill_sd_denoise sets this)
   bool cfg_pair = false;
@@ -673,38 +571,22 @@ struct UNetRun {
     fprintf(stderr, "[unet] ok: %s %d %d %d\n", what, a, b, c);
     return 0;
   }
-  float* stats_slot(size_t floats) {   // next slot of the per-forward GroupNorm partial-sum pool (the dry run sizes it)
-    float* p = dry ? (float*)(uintptr_t)16 : m->gn_stats + m->gn_next;
-    m->gn_next += (floats + 3) & ~(size_t)3;
-    return p;
-  }
   RowStats ln_slot(int rows, int C) {   // row-sum planes of a [rows][C] residual stream (sized for any tiling of C columns)
     RowStats r;
     r.p = dry ? (float*)(uintptr_t)16 : m->ln_stats + m->ln_next;
     m->ln_next += (size_t)rows * 2 * GEMM_MAX_ROW_PLANES(C);
     return r;
   }
+  // want_stats: the producer files this tensor's GroupNorm partial sums, in bins of C / 64 channels (finer than a group, so the sums also
+  // serve the wider groups of a skip concat) where there are at least two of them, else per group
   Tensor talloc(int H, int W, int C, bool want_stats = false) {
-    Tensor t; t.H = H; t.W = W; t.C = C;
-    t.p = (bf16_t*)m->arena.alloc(sizeof(bf16_t) * (size_t)Bx * H * W * C);
-    if (want_stats && (H * W) % GN_SLAB_ROWS == 0 && C % m->cfg.norm_num_groups == 0) {
-      const int sbin = (C % 64 == 0 && C / 64 >= 2) ? C / 64 : C / m->cfg.norm_num_groups;
-      if (gemm_fused_gn_ok(C, sbin)) {
-        t.sbin = sbin;
-        t.stats = stats_slot((size_t)Bx * (H * W / GN_SLAB_ROWS_MIN) * (C / sbin) * 2);
-      }
-    }
-    return t;
+    if (!want_stats || C % groups != 0) return tensor(H, W, C);
+    return tensor(H, W, C, (C % 64 == 0 && C / 64 >= 2) ? C / 64 : C / groups);
   }
   Tensor talloc8(int H, int W, int C) {   // fp8 activation tensor (one byte per element)
     Tensor t; t.H = H; t.W = W; t.C = C;
     t.p = (bf16_t*)m->arena.alloc((size_t)Bx * H * W * C);
     return t;
-  }
-  void fuse_stats(GemmArgs& g, const Tensor& y) {
-    if (!y.stats) return;
-    g.gn_stats = y.stats; g.gn_groups = y.C / y.sbin; g.gn_cg = y.sbin;
-    g.rows_per_batch = y.H * y.W;
   }
   int pick_sk(GemmArgs& g, bool generic = false) {
     g.splitk = gemm_pick_splitk(g.M, g.N, g.K, g.act, !g.conv, generic);
@@ -718,6 +600,32 @@ struct UNetRun {
   // ss: (optional) the consumer wants the per-(sample, channel) scale | shift table [Bx][2][C] instead of a normalised copy (the level-0 transformer
   // blocks: lnproj.hip applies it to the rows it loads) — only the in-kernel finish (COOP) writes it; y is then unused.
   struct FusedNorm { const NormW* n; float eps; int silu; Tensor y; bool raw_needed; bool done; float* ss = nullptr; };
+  // One such offer on its way from the producing block to the consuming one (forward() keeps a single one in flight): offer() names the
+  // consumer's GroupNorm, the producer sets `done` if it ran it, take() hands the result to the consumer — once: a second take() finds nothing.
+  // The normalised copy (or, table = true, the scale | shift table) is allocated whether or not the offer is taken: same arena layout in the
+  // dry run and in every real run.
+  struct Handoff {
+    UNetRun& r;
+    FusedNorm fn{nullptr, 0.f, 0, Tensor(), true, false};
+    struct Taken {   // by value: the next offer() overwrites fn while the consumer still reads what it took
+      Tensor y; bool has_y = false; const float* ss = nullptr;
+      const Tensor* copy() const { return has_y ? &y : nullptr; }
+    };
+    FusedNorm* offer(const NormW& n, float eps, int silu, int H, int W, int C, bool table = false) {
+      Tensor y; y.H = H; y.W = W; y.C = C;
+      if (!table) y = r.talloc(H, W, C);
+      fn = FusedNorm{&n, eps, silu, y, true, false};
+      if (table) fn.ss = (float*)r.m->arena.alloc(sizeof(float) * (size_t)r.Bx * 2 * C);
+      return &fn;
+    }
+    Taken take() {
+      Taken t;
+      if (fn.done && fn.ss) t.ss = fn.ss;
+      else if (fn.done) { t.y = fn.y; t.has_y = true; }
+      fn.done = false;
+      return t;
+    }
+  };
   int gemm(GemmArgs& g, RowStats* rs = nullptr, Tensor* ys = nullptr, FusedNorm* fn = nullptr) {
     // COOP counters of this launch: the same slot range in the dry run and in every real run (whether or not the launch ends up using them)
     unsigned* ctr = dry ? nullptr : m->coop_ctr + m->coop_next;
@@ -752,32 +660,11 @@ struct UNetRun {
     GILL_TRY(gemm_launch(g, s));
     return dbg_sync(g.conv ? "conv" : (g.act == ACT_GEGLU ? "geglu" : (g.out_mode == OUT_QKV ? "qkv" : (g.out_mode == OUT_SOFTMAX80 ? "scores+softmax" : "gemm"))), g.M, g.N, g.K);
   }
-  // y8_scale > 0: y holds fp8(y8_scale * value) instead of bf16 (same shape; the A operand of conv8())
-  // ss_out: write the per-(sample, channel) scale / shift table instead of normalising (single-source inputs whose producer filed the
-  // statistics; *folded says whether that was possible — if not, y is normalised as usual)
+  // ConvRun::gnorm, named on stderr under GILL_DEBUG_SYNC
   int gnorm(const Tensor& x1, const Tensor* x2, const NormW& n, float eps, int silu, const Tensor& y, float y8_scale = 0.f,
             float* ss_out = nullptr, bool* folded = nullptr) {
-    // single-source input whose producer already accumulated the sums: no statistics pass
-    const int C = x1.C + (x2 ? x2->C : 0);
-    const bool ready = x1.stats != nullptr && (x2 == nullptr || x2->stats != nullptr) &&
-                       groupnorm_bins_align(C / m->cfg.norm_num_groups, x1.C, x1.sbin, x2 ? x2->sbin : 0);
-    const int HW = x1.H * x1.W;
-    float* stats = ready ? nullptr : stats_slot(groupnorm_stats_floats(Bx, HW, m->cfg.norm_num_groups));
-    // out-of-place totals for producers that wrote more than 64 partials per bin (SD-2.1-768: 96x96 maps); a skip tensor's
-    // partials are read again by the up block's concatenated norm1 and must stay as their producer wrote them
-    float* tot = ready ? stats_slot(groupnorm_totals_floats(Bx, x1.C / x1.sbin, x2 ? x2->C / x2->sbin : 0)) : nullptr;
-    if (dry) return 0;
-    GILL_REQUIRE(m->gn_next <= m->gn_floats, "internal: GroupNorm stats pool exhausted");
-    GILL_TRY(dbg_sync("before groupnorm", x1.C, x2 ? x2->C : 0, HW));
-    if (ready) {
-      const bool fold = ss_out != nullptr && x2 == nullptr;
-      if (folded) *folded = fold;
-      return groupnorm_apply_launch(x1.p, x1.C, x2 ? x2->p : nullptr, x2 ? x2->C : 0, Bx, HW, m->cfg.norm_num_groups,
-                                    n.g, n.b, eps, silu, y.p, x1.stats, x1.sbin, x1.C, x1.nslab,
-                                    x2 ? x2->stats : nullptr, x2 ? x2->sbin : 0, x2 ? x2->nslab : 0, s, y8_scale, tot, fold ? ss_out : nullptr);
-    }
-    return groupnorm_launch(x1.p, x1.C, x2 ? x2->p : nullptr, x2 ? x2->C : 0, Bx, HW, m->cfg.norm_num_groups, n.g,
-                            n.b, eps, silu, y.p, stats, s, y8_scale);
+    GILL_TRY(dbg_sync("before groupnorm", x1.C, x2 ? x2->C : 0, x1.H * x1.W));
+    return ConvRun::gnorm(x1, x2, n, eps, silu, y, y8_scale, ss_out, folded);
   }
   // 3x3 conv (pad 1, stride 1) of an fp8 activation tensor x8 (gnorm(..., F8_ACT_SCALE)) with fp8 weights:
   // y = conv + bias + rowvec + resid (resid may alias y.p), GroupNorm partials of y fused like conv()
@@ -807,16 +694,7 @@ struct UNetRun {
   // 3x3 conv (pad 1) over x1 (++ x2): stride 1|2, optional fused nearest-2x upsample
   int conv(const Tensor& x1, const Tensor* x2, const ConvW& w, int stride, int ups, const float* rowvec, int rv_bstride,
            const bf16_t* resid, Tensor& y, FusedNorm* fn = nullptr) {
-    GemmArgs g;
-    g.conv = 1; g.IH = x1.H; g.IW = x1.W; g.OH = y.H; g.OW = y.W; g.Cin = w.cin; g.stride = stride; g.ups = ups;
-    g.M = Bx * y.H * y.W; g.N = w.cout; g.K = 9 * w.cin;
-    g.A = x1.p; g.A2 = x2 ? x2->p : nullptr; g.K1 = x1.C;
-    g.W = w.w; g.bias = w.b; g.k_chunked = w.chunked;
-    if (ups && w.ups4) { g.ups = 2; g.K = 4 * w.cin; }
-    g.rowvec = rowvec; g.rows_per_batch = y.H * y.W; g.rowvec_bstride = rv_bstride;
-    g.resid = resid; g.ldr = w.cout;
-    g.C = y.p; g.ldc = w.cout;
-    fuse_stats(g, y);
+    GemmArgs g = conv_args(x1, x2, w, stride, ups, rowvec, rv_bstride, resid, y);
     return gemm(g, nullptr, &y, fn);
   }
   int linear(const bf16_t* A, int lda, const bf16_t* A2, int lda2, int K1, int M, const bf16_t* W, const float* b, int N,
@@ -865,17 +743,7 @@ struct UNetRun {
     GILL_TRY(conv(n1, nullptr, w.c1, 1, 0, temb_rows ? temb_rows + w.temb_off : nullptr, temb_bstride, nullptr, h, &f2));
     if (!f2.done) GILL_TRY(gnorm(h, nullptr, w.n2, 1e-5f, 1, n2));
     if (w.has_sc) {
-      // out = conv2(n2) + conv_shortcut(x1 ++ x2): ONE implicit GEMM whose K runs over the 9 taps of n2 and then over
-      // the raw input channels (no separate 1x1 GEMM, no shortcut tensor written and re-read as a residual)
-      GemmArgs g;
-      g.conv = 1; g.IH = H; g.IW = Wd; g.OH = H; g.OW = Wd; g.Cin = w.cout; g.stride = 1; g.ups = 0;
-      g.M = Bx * H * Wd; g.N = w.cout; g.K = 9 * w.cout + w.cin;
-      g.A = n2.p; g.K1 = w.cout;
-      g.X1 = x1.p; g.X2 = x2 ? x2->p : nullptr; g.KX = w.cin; g.KX1 = x1.C;
-      g.W = w.c2f_w; g.bias = w.c2f_b; g.k_chunked = w.c2.chunked;
-      g.rows_per_batch = H * Wd;
-      g.C = out->p; g.ldc = w.cout;
-      fuse_stats(g, *out);
+      GemmArgs g = conv2_shortcut_args(n2, x1, x2, w, *out);
       GILL_TRY(gemm(g, nullptr, out, next));
     } else {
       GILL_TRY(conv(n2, nullptr, w.c2, 1, 0, nullptr, 0, x1.p, *out, next));
@@ -1073,20 +941,10 @@ struct UNetRun {
     skips.push_back(x);
     // Where a block's last GEMM is a split-K launch (levels 2-3 at the 8-sample batch) and the next consumer's first op is a
     // single-source GroupNorm, that norm is offered to the producer's reducer (FusedNorm): `pn` carries the normalised copy forward.
-    // The copy is allocated whether or not the offer is taken (same arena layout in the dry run and in every real run).
     // Round 6: the same offer goes to non-split producers too — the 3x3 convolutions of levels 0-1 finish the norm in their own epilogue
     // (gemm.hip "COOP": the workgroups of a sample wait for each other's partials) — as a normalised copy, or (table) as the scale | shift table
     // the level-0 projection kernel applies on load.
-    FusedNorm pn{nullptr, 0.f, 0, Tensor(), true, false};
-    auto offer = [&](const NormW& n, float eps, int silu, int H, int W, int C, bool table = false) -> FusedNorm* {
-      Tensor y; y.H = H; y.W = W; y.C = C;
-      if (!table) y = talloc(H, W, C);
-      pn = FusedNorm{&n, eps, silu, y, true, false};
-      if (table) pn.ss = (float*)m->arena.alloc(sizeof(float) * (size_t)Bx * 2 * C);
-      return &pn;
-    };
-    auto taken = [&]() -> const Tensor* { return (pn.done && !pn.ss) ? &pn.y : nullptr; };
-    auto taken_ss = [&]() -> const float* { return (pn.done && pn.ss) ? pn.ss : nullptr; };
+    Handoff pn{*this};
     for (int i = 0; i < 4; ++i) {
       for (int j = 0; j < 2; ++j) {
         Tensor y;
@@ -1094,66 +952,50 @@ struct UNetRun {
         // both halves of the batch -> run them on the first half only (xf() widens back to the full batch)
         const bool share = cfg_pair && i == 0 && j == 0 && Bx % 2 == 0 && temb_bstride == 0;
         if (share) Bx /= 2;
-        const Tensor* pre = taken();
-        Tensor pre_t; if (pre) { pre_t = *pre; pre = &pre_t; }
-        pn.done = false;
+        const Handoff::Taken pre = pn.take();
         // this resnet's consumer: the transformer block's GroupNorm (i < 3), else the next resnet's / the mid block's norm1
         FusedNorm* nx = nullptr;
-        if (i < 3) nx = offer(m->down_xf[i][j].gn, 1e-6f, 0, x.H, x.W, ch[i], xf_wants_table(m->down_xf[i][j], x.H * x.W, share));
-        else nx = offer(j == 0 ? m->down_res[3][1].n1 : m->mid_res[0].n1, 1e-5f, 1, x.H, x.W, ch[i]);
-        GILL_TRY(resnet(x, nullptr, m->down_res[i][j], &y, true, pre, nx));
+        if (i < 3) nx = pn.offer(m->down_xf[i][j].gn, 1e-6f, 0, x.H, x.W, ch[i], xf_wants_table(m->down_xf[i][j], x.H * x.W, share));
+        else nx = pn.offer(j == 0 ? m->down_res[3][1].n1 : m->mid_res[0].n1, 1e-5f, 1, x.H, x.W, ch[i]);
+        GILL_TRY(resnet(x, nullptr, m->down_res[i][j], &y, true, pre.copy(), nx));
         x = y;
         // next consumer: resnet norm1 (j == 0) / the downsample conv or the mid block's norm1 (j == 1)
         if (i < 3) {
-          const Tensor* pre2 = taken();
-          Tensor pre2_t; if (pre2) { pre2_t = *pre2; pre2 = &pre2_t; }
-          const float* pre2_ss = taken_ss();
-          pn.done = false;
-          FusedNorm* nx2 = (i >= 2 && j == 0) ? offer(m->down_res[i][1].n1, 1e-5f, 1, x.H, x.W, ch[i]) : nullptr;
-          Tensor z; GILL_TRY(xf(x, m->down_xf[i][j], &z, true, share, pre2, nx2, pre2_ss)); x = z;   // next GroupNorm and / or a skip
+          const Handoff::Taken pre2 = pn.take();
+          FusedNorm* nx2 = (i >= 2 && j == 0) ? pn.offer(m->down_res[i][1].n1, 1e-5f, 1, x.H, x.W, ch[i]) : nullptr;
+          Tensor z; GILL_TRY(xf(x, m->down_xf[i][j], &z, true, share, pre2.copy(), nx2, pre2.ss)); x = z;   // next GroupNorm and / or a skip
         }
         skips.push_back(x);
       }
       if (i < 3) {
         Tensor y = talloc(x.H / 2, x.W / 2, ch[i], true);
-        pn.done = false;
-        FusedNorm* nx = offer(m->down_res[i + 1][0].n1, 1e-5f, 1, y.H, y.W, ch[i]);
+        FusedNorm* nx = pn.offer(m->down_res[i + 1][0].n1, 1e-5f, 1, y.H, y.W, ch[i]);
         GILL_TRY(conv(x, nullptr, m->down_ds[i], 2, 0, nullptr, 0, nullptr, y, nx));
         x = y;
         skips.push_back(x);
       }
     }
     {
-      const Tensor* pre = taken();
-      Tensor pre_t; if (pre) { pre_t = *pre; pre = &pre_t; }
-      pn.done = false;
-      FusedNorm* nx = offer(m->mid_xf.gn, 1e-6f, 0, x.H, x.W, ch[3]);
-      Tensor y; GILL_TRY(resnet(x, nullptr, m->mid_res[0], &y, true, pre, nx)); x = y;
-      const Tensor* pre2 = taken();
-      Tensor pre2_t; if (pre2) { pre2_t = *pre2; pre2 = &pre2_t; }
-      pn.done = false;
-      FusedNorm* nx2 = offer(m->mid_res[1].n1, 1e-5f, 1, x.H, x.W, ch[3]);
-      Tensor z; GILL_TRY(xf(x, m->mid_xf, &z, true, false, pre2, nx2)); x = z;
-      const Tensor* pre3 = taken();
-      Tensor pre3_t; if (pre3) { pre3_t = *pre3; pre3 = &pre3_t; }
-      pn.done = false;
-      Tensor u; GILL_TRY(resnet(x, nullptr, m->mid_res[1], &u, true, pre3, nullptr)); x = u;   // -> two-source norm1 of up block 0
+      const Handoff::Taken pre = pn.take();
+      FusedNorm* nx = pn.offer(m->mid_xf.gn, 1e-6f, 0, x.H, x.W, ch[3]);
+      Tensor y; GILL_TRY(resnet(x, nullptr, m->mid_res[0], &y, true, pre.copy(), nx)); x = y;
+      const Handoff::Taken pre2 = pn.take();
+      FusedNorm* nx2 = pn.offer(m->mid_res[1].n1, 1e-5f, 1, x.H, x.W, ch[3]);
+      Tensor z; GILL_TRY(xf(x, m->mid_xf, &z, true, false, pre2.copy(), nx2)); x = z;
+      const Handoff::Taken pre3 = pn.take();
+      Tensor u; GILL_TRY(resnet(x, nullptr, m->mid_res[1], &u, true, pre3.copy(), nullptr)); x = u;   // -> two-source norm1 of up block 0
     }
     for (int i = 0; i < 4; ++i) {
       for (int j = 0; j < 3; ++j) {
         Tensor skip = skips.back(); skips.pop_back();
         Tensor y;
-        pn.done = false;
         // (norm1 of an up-block resnet is two-source: never offered; its conv2 feeds the transformer block's GroupNorm)
-        FusedNorm* nx = (i >= 1) ? offer(m->up_xf[i][j].gn, 1e-6f, 0, x.H, x.W, ch[3 - i], xf_wants_table(m->up_xf[i][j], x.H * x.W, false)) : nullptr;
+        FusedNorm* nx = (i >= 1) ? pn.offer(m->up_xf[i][j].gn, 1e-6f, 0, x.H, x.W, ch[3 - i], xf_wants_table(m->up_xf[i][j], x.H * x.W, false)) : nullptr;
         GILL_TRY(resnet(x, &skip, m->up_res[i][j], &y, true, nullptr, nx));
         x = y;
         if (i > 0) {
-          const Tensor* pre = taken();
-          Tensor pre_t; if (pre) { pre_t = *pre; pre = &pre_t; }
-          const float* pre_ss = taken_ss();
-          pn.done = false;
-          Tensor z; GILL_TRY(xf(x, m->up_xf[i][j], &z, true, false, pre, nullptr, pre_ss)); x = z;
+          const Handoff::Taken pre = pn.take();
+          Tensor z; GILL_TRY(xf(x, m->up_xf[i][j], &z, true, false, pre.copy(), nullptr, pre.ss)); x = z;
         }
       }
       if (i < 3) {
