@@ -1556,3 +1556,99 @@ extern "C" int gill_op_cross_attention_folded(const void* t, const float* ln_g, 
   GILL_CHECK_HIP(hipStreamSynchronize(s));
   return 0;
 }
+
+// ------------------------------------------------------------------------------------------------------------------
+// Operator-level entries for the folded-LayerNorm chain of UNet levels 1-3 (xf() above): the GEMM that writes the residual stream and files
+// its row-sum planes (GemmArgs::row_stats), and the GEMM that reads them back (GemmArgs::ln_stats) in its GEGLU / QKV epilogue or its split-K
+// reducer.  Both build their GemmArgs as UNetRun::linear() / xf() do and synchronise.  For tests/test_ln_gemm_gpu.py and tools.
+// splitk: 0 = the engine's heuristic (UNetRun::pick_sk), 1 = unsplit, n > 1 = forced.
+static int op_ln_splitk(GemmArgs& g, int splitk, DevBuf& ws) {
+  g.splitk = splitk > 0 ? splitk : gemm_pick_splitk(g.M, g.N, g.K, g.act, true, false);
+  if (g.splitk > 1) {
+    GILL_TRY(ws.alloc(sizeof(float) * (size_t)g.splitk * g.M * g.N));
+    g.ws = (float*)ws.p;
+  }
+  return 0;
+}
+// Producer.  T [M][N] bf16 = (A [M][K1] ++ A2 [M][K - K1]) . W [N][K]^T + bias + resid (resid may alias T: attn1 / attn2.to_out run in place),
+// planes [*nplanes][M][2] fp32 = {sum, sum of squares} of the stored row m over the columns of each plane; *nplanes = gemm_row_planes() of the
+// launch (an error when it exceeds planes_cap, the planes the caller's buffer holds).
+extern "C" int gill_op_linear_rowstats(const void* A, const void* A2, int K1, const void* W, const float* bias, const void* resid, void* T,
+                                       float* planes, int planes_cap, int* nplanes, int M, int N, int K, int splitk, void* stream) {
+  hipStream_t s = (hipStream_t)stream;
+  GILL_REQUIRE(A && W && T && planes && nplanes && M > 0 && N > 0 && K > 0, "linear_rowstats: null argument");
+  GILL_REQUIRE((A2 != nullptr) == (K1 < K) && K1 > 0 && K1 <= K, "linear_rowstats: A2 if and only if K1 < K");
+  DevBuf ws;
+  GemmArgs g;
+  g.M = M; g.N = N; g.K = K; g.K1 = K1; g.A = (const bf16_t*)A; g.lda = K1; g.A2 = (const bf16_t*)A2; g.lda2 = K - K1;
+  g.W = (const bf16_t*)W; g.bias = bias; g.resid = resid; g.ldr = N; g.act = ACT_NONE; g.C = T; g.ldc = N;
+  GILL_TRY(op_ln_splitk(g, splitk, ws));
+  g.row_stats = planes;
+  *nplanes = gemm_row_planes(g);
+  GILL_REQUIRE(*nplanes <= planes_cap, "linear_rowstats: the planes buffer is too small for this launch");
+  const int rep = [] { const char* e = getenv("GILL_OP_REPEAT"); const int v = e ? atoi(e) : 1; return v > 0 ? v : 1; }();
+  for (int r = 0; r < (resid == T ? 1 : rep); ++r) GILL_TRY(gemm_launch(g, s));      // (in place: a second launch would add the residual twice)
+  GILL_CHECK_HIP(hipStreamSynchronize(s));
+  return 0;
+}
+
+// dst[h * dp + dd] = src[h * d + dd] (a projection bias padded like the weight rows).  dst pre-zeroed.
+__global__ __launch_bounds__(256) void pad_head_vec_kernel(const float* __restrict__ src, int H, int d, int dp, float* __restrict__ dst) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i < H * d) dst[(i / d) * dp + i % d] = src[i];
+}
+// Consumer.  LN(T; ln_g, ln_b) W^T + b on T [M][C] bf16 and the caller's row-sum planes [P][R][2] (R = ln_rows, or M when ln_rows == 0; rows
+// m >= R read the sums of row m - R), W / b in diffusers layout, folded by ln_fold_rows_launch as the loader folds them.
+//   mode 0 (GEGLU): W [2 inner][C] = [value rows | gate rows], b [2 inner] -> out [M][inner] bf16 = value * gelu(gate).
+//   mode 1 (QKV):   W [nseg C][C] = to_q (| to_k | to_v), nseg = 1 | 3, heads * d == C, b [nseg C] or null, M = B * ntok ->
+//                   q, k [B][heads][ntok_pad][dp], vt [B][heads][dpv][ntok_pad] (dp = attn_padded_dim(d), dpv = dp rounded up to 32, ntok_pad = ntok
+//                   rounded up to 32, q scaled by log2(e) / sqrt(d), row dp of vt = 1 where dpv > dp): what xf() passes.  k, vt unused for nseg = 1.
+extern "C" int gill_op_ln_gemm(int mode, const void* T, const float* planes, int P, int ln_rows, const float* ln_g, const float* ln_b, const void* W,
+                               const float* b, void* out, void* q, void* k, void* vt, int M, int C, int inner, int nseg, int heads, int d, int ntok,
+                               int splitk, void* stream) {
+  hipStream_t s = (hipStream_t)stream;
+  GILL_REQUIRE(mode == 0 || mode == 1, "ln_gemm: mode must be 0 (GEGLU) or 1 (QKV)");
+  GILL_REQUIRE(T && planes && ln_g && ln_b && W && M > 0 && C > 0 && P >= 1, "ln_gemm: null argument");
+  GILL_REQUIRE(ln_rows >= 0 && ln_rows <= M && (ln_rows == 0 || 2 * ln_rows >= M), "ln_gemm: ln_rows must cover at least half the rows");
+  DevBuf idx, wf, cs, cb, ws;
+  GemmArgs g;
+  g.M = M; g.K = C; g.K1 = C; g.A = (const bf16_t*)T; g.lda = C;
+  g.ln_stats = planes; g.ln_planes = P; g.ln_rows = ln_rows;
+  if (mode == 0) {
+    GILL_REQUIRE(out && b && inner > 0 && inner % 64 == 0, "ln_gemm (GEGLU): output / bias missing, or inner not a multiple of 64");
+    const int N = 2 * inner;
+    std::vector<int32_t> map = geglu_row_permutation(inner);
+    GILL_TRY(idx.alloc(sizeof(int32_t) * map.size()));
+    GILL_CHECK_HIP(hipMemcpyAsync(idx.p, map.data(), sizeof(int32_t) * map.size(), hipMemcpyHostToDevice, s));
+    GILL_TRY(wf.alloc(sizeof(bf16_t) * (size_t)N * C)); GILL_TRY(cb.alloc(sizeof(float) * N)); GILL_TRY(cs.alloc(sizeof(float) * N));
+    GILL_TRY(scatter_rows_bf16_launch((const bf16_t*)W, N, C, (const int32_t*)idx.p, (bf16_t*)wf.p, C, s));
+    GILL_TRY(permute_f32_launch(b, (const int32_t*)idx.p, N, (float*)cb.p, s));
+    GILL_TRY(ln_fold_rows_launch((bf16_t*)wf.p, N, C, ln_g, ln_b, (float*)cs.p, (float*)cb.p, s));
+    g.N = N; g.act = ACT_GEGLU; g.C = out; g.ldc = inner;
+  } else {
+    GILL_REQUIRE((nseg == 1 || nseg == 3) && heads > 0 && d > 0 && heads * d == C && ntok > 0 && M % ntok == 0,
+                 "ln_gemm (QKV): nseg 1 or 3, heads * d == C, M a multiple of ntok");
+    GILL_REQUIRE(q && (nseg == 1 || (k && vt)), "ln_gemm (QKV): output missing");
+    const int dp = attn_padded_dim(d);
+    GILL_REQUIRE(dp > 0, "ln_gemm (QKV): unsupported head dim");
+    const int dpv = round_up(dp, 32), hdp = heads * dp, N = nseg * hdp, ntok_pad = round_up(ntok, 32);
+    GILL_TRY(wf.alloc_zero(sizeof(bf16_t) * (size_t)N * C, s));
+    GILL_TRY(cs.alloc_zero(sizeof(float) * N, s)); GILL_TRY(cb.alloc_zero(sizeof(float) * N, s));
+    for (int sg = 0; sg < nseg; ++sg) {
+      hipLaunchKernelGGL(pad_head_rows_kernel, dim3(1024), dim3(256), 0, s, (const void*)((const bf16_t*)W + (size_t)sg * C * C), 0, heads, d, dp, C,
+                         (bf16_t*)wf.p + (size_t)sg * hdp * C);
+      if (b) hipLaunchKernelGGL(pad_head_vec_kernel, dim3(cdiv(C, 256)), dim3(256), 0, s, b + (size_t)sg * C, heads, d, dp, (float*)cb.p + (size_t)sg * hdp);
+    }
+    GILL_CHECK_HIP(hipGetLastError());
+    GILL_TRY(ln_fold_rows_launch((bf16_t*)wf.p, N, C, ln_g, ln_b, (float*)cs.p, (float*)cb.p, s));
+    g.N = N; g.out_mode = OUT_QKV; g.Cq = (bf16_t*)q; g.Ck = (bf16_t*)k; g.Cvt = (bf16_t*)vt; g.heads = heads; g.dp = dp; g.dpv = dpv;
+    g.ntok = ntok; g.ntok_pad_q = ntok_pad; g.ntok_pad_kv = ntok_pad; g.seg_base = 0;
+    g.qscale = 1.4426950408889634f / sqrtf((float)d);
+  }
+  g.W = (const bf16_t*)wf.p; g.ln_colsum = (const float*)cs.p; g.bias = (const float*)cb.p;
+  GILL_TRY(op_ln_splitk(g, splitk, ws));
+  const int rep = [] { const char* e = getenv("GILL_OP_REPEAT"); const int v = e ? atoi(e) : 1; return v > 0 ? v : 1; }();
+  for (int r = 0; r < rep; ++r) GILL_TRY(gemm_launch(g, s));
+  GILL_CHECK_HIP(hipStreamSynchronize(s));
+  return 0;
+}

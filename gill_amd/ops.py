@@ -5,6 +5,7 @@ themselves (gill_amd.models / layers / sd) call the stage-level entry points, no
 """
 from __future__ import annotations
 
+import ctypes
 from typing import Optional
 
 import torch
@@ -261,3 +262,87 @@ def cross_attention_folded(t: torch.Tensor, ln_g: torch.Tensor, ln_b: torch.Tens
   N.check(N.lib().gill_op_cross_attention_folded(N.ptr(t), N.ptr(ln_g), N.ptr(ln_b), N.ptr(wq), N.ptr(wk), N.ptr(wv), N.ptr(wo), N.ptr(bo),
                                                  N.ptr(ctx), N.ptr(out), N.ptr(P), B, HW, C, heads, ctx.shape[1], E, N.current_stream()))
   return out, P
+
+
+def padded_head_dim(d: int) -> int:
+  """csrc/ops.h attn_padded_dim()."""
+  for dp in (48, 64, 80, 128, 160):
+    if d <= dp:
+      return dp
+  raise ValueError(f"unsupported head dim {d}")
+
+
+ROWSTATS_GUARD_ROWS = 64
+
+
+def linear_rowstats(a: torch.Tensor, w: torch.Tensor, bias: Optional[torch.Tensor] = None, resid: Optional[torch.Tensor] = None,
+                    a2: Optional[torch.Tensor] = None, splitk: int = 0, inplace: bool = False):
+  """The GEMM that writes the residual stream at UNet levels 1-3 and files its LayerNorm row sums (include/gill_amd.h gill_op_linear_rowstats):
+  t = [a | a2] @ w.T + bias + resid; a (M,K1), a2 (M,K-K1), w (N,K) bf16.  inplace: the residual is read from the output buffer itself, as the engine's
+  attn1 / attn2.to_out run.  Returns (t (M,N) bf16, planes (P,M,2) fp32, P = the launcher's plane count, guard): t and planes are NaN-prefilled (not t
+  when inplace), and guard = (the ROWSTATS_GUARD_ROWS rows after t, the plane after the last one), which must still be all NaN afterwards."""
+  a, w = _bf(a), _bf(w)
+  M, K1 = a.shape
+  Nn, K = w.shape
+  if a2 is not None:
+    a2 = _bf(a2)
+    assert a2.shape == (M, K - K1)
+  nan = float("nan")
+  tbuf = torch.full((M + ROWSTATS_GUARD_ROWS, Nn), nan, device=a.device, dtype=torch.bfloat16)
+  if resid is not None:
+    resid = _bf(resid)
+    if inplace:
+      tbuf[:M] = resid
+      resid = tbuf
+  cap = max((Nn + 63) // 64, 2 * ((Nn + 127) // 128))        # csrc/ops.h GEMM_MAX_ROW_PLANES
+  planes = torch.full((cap + 1, M, 2), nan, device=a.device, dtype=torch.float32)
+  if bias is not None:
+    bias = bias.float().contiguous()
+  npl = ctypes.c_int(0)
+  N.check(N.lib().gill_op_linear_rowstats(N.ptr(a), N.ptr(a2), K1, N.ptr(w), N.ptr(bias), N.ptr(resid), N.ptr(tbuf), N.ptr(planes), cap,
+                                          ctypes.byref(npl), M, Nn, K, splitk, N.current_stream()))
+  P = npl.value
+  return tbuf[:M], planes[:P], (tbuf[M:], planes[P:])
+
+
+def ln_gemm_geglu(t: torch.Tensor, planes: torch.Tensor, ln_g: torch.Tensor, ln_b: torch.Tensor, w: torch.Tensor, bias: torch.Tensor,
+                  ln_rows: int = 0, splitk: int = 1) -> torch.Tensor:
+  """diffusers GEGLU of LayerNorm(t) as UNet levels 1-3 run it (include/gill_amd.h gill_op_ln_gemm, mode 0): the LayerNorm folded into the weights,
+  mean / rstd from the row-sum planes (P, R, 2) fp32 (R = ln_rows or M; rows >= R wrap onto row - R).  t (M,C) bf16, w (2 inner, C) bf16 in diffusers
+  order, bias (2 inner).  Returns (M, inner) bf16, NaN-prefilled."""
+  t, w = _bf(t), _bf(w)
+  M, Cc = t.shape
+  inner = w.shape[0] // 2
+  planes = planes.float().contiguous()
+  assert planes.is_cuda and planes.shape[1:] == (ln_rows or M, 2)
+  f = lambda x: x.float().contiguous()   # noqa: E731
+  ln_g, ln_b, bias = f(ln_g), f(ln_b), f(bias)
+  out = torch.full((M, inner), float("nan"), device=t.device, dtype=torch.bfloat16)
+  N.check(N.lib().gill_op_ln_gemm(0, N.ptr(t), N.ptr(planes), planes.shape[0], ln_rows, N.ptr(ln_g), N.ptr(ln_b), N.ptr(w), N.ptr(bias), N.ptr(out),
+                                  None, None, None, M, Cc, inner, 0, 0, 0, 0, splitk, N.current_stream()))
+  return out
+
+
+def ln_gemm_qkv(t: torch.Tensor, planes: torch.Tensor, ln_g: torch.Tensor, ln_b: torch.Tensor, w: torch.Tensor, bias: Optional[torch.Tensor],
+                heads: int, ntok: int, ln_rows: int = 0, splitk: int = 1):
+  """to_q [| to_k | to_v] of LayerNorm(t) scattered head-major, as UNet levels 1-3 run it (gill_op_ln_gemm, mode 1): t (B * ntok, C) bf16, planes as
+  in ln_gemm_geglu, w (nseg C, C) bf16 with nseg = 1 | 3, bias (nseg C) or None.  Returns (q, k, vt): q, k (B, heads, ntok_pad, dp) with q pre-scaled
+  by log2(e) / sqrt(d), vt (B, heads, dpv, ntok_pad) with row dp = 1 where dpv > dp; k, vt None when nseg == 1.  All NaN-prefilled."""
+  t, w = _bf(t), _bf(w)
+  M, Cc = t.shape
+  nseg = w.shape[0] // Cc
+  d = Cc // heads
+  dp = padded_head_dim(d)
+  dpv, ntok_pad, B = (dp + 31) // 32 * 32, (ntok + 31) // 32 * 32, M // ntok
+  planes = planes.float().contiguous()
+  assert planes.is_cuda and planes.shape[1:] == (ln_rows or M, 2)
+  f = lambda x: x.float().contiguous()   # noqa: E731
+  ln_g, ln_b = f(ln_g), f(ln_b)
+  bias = None if bias is None else f(bias)
+  nan = float("nan")
+  q = torch.full((B, heads, ntok_pad, dp), nan, device=t.device, dtype=torch.bfloat16)
+  k = torch.full_like(q, nan) if nseg == 3 else None
+  vt = torch.full((B, heads, dpv, ntok_pad), nan, device=t.device, dtype=torch.bfloat16) if nseg == 3 else None
+  N.check(N.lib().gill_op_ln_gemm(1, N.ptr(t), N.ptr(planes), planes.shape[0], ln_rows, N.ptr(ln_g), N.ptr(ln_b), N.ptr(w), N.ptr(bias), None,
+                                  N.ptr(q), N.ptr(k), N.ptr(vt), M, Cc, 0, nseg, heads, d, ntok, splitk, N.current_stream()))
+  return q, k, vt

@@ -374,6 +374,25 @@ int gill_op_cross_attention_folded(const void* t_bf16, const float* ln_g, const 
                                    const void* Wv_bf16, const void* Wo_bf16, const float* bo, const void* ctx_bf16, void* out_bf16,
                                    void* P_bf16, int B, int HW, int C, int H, int ctx_len, int E, void* stream);
 
+/* The folded-LayerNorm chain of UNet levels 1-3 (csrc/unet.hip xf(): norm1 / norm2 / norm3 never run as kernels), one GEMM each.
+ * Producer: T (M, N) bf16 = [A (M, K1) | A2 (M, K - K1)] . W (N, K)^T + bias + resid (resid may be T itself), as the engine's linear() launches
+ * it with GemmArgs::row_stats set; planes ([*nplanes][M][2] fp32, room for planes_cap planes) = {sum, sum of squares} of every stored row over the
+ * columns of each plane, *nplanes = what gemm_row_planes() reports for the launch.  A2 null when K1 == K.  splitk: 0 = the engine's heuristic,
+ * 1 = unsplit (planes from the GEMM epilogue), n > 1 = forced (planes from the split-K reducer).  Synchronises. */
+int gill_op_linear_rowstats(const void* A_bf16, const void* A2_bf16, int K1, const void* W_bf16, const float* bias, const void* resid_bf16,
+                            void* T_bf16, float* planes, int planes_cap, int* nplanes, int M, int N, int K, int splitk, void* stream);
+/* Consumer: LayerNorm(T; ln_g, ln_b) W^T + b from T (M, C) bf16 and row-sum planes ([P][R][2] fp32, R = ln_rows or M when ln_rows == 0; rows
+ * m >= R use the sums of row m - R: the shared classifier-free-guidance prefix), never normalising T: W / b (diffusers layout) are folded with
+ * the LayerNorm gain / bias as the engine's loader folds them.  mode 0: GEGLU, W (2 inner, C) = [value rows | gate rows], b (2 inner) ->
+ * out (M, inner) bf16.  mode 1: W (nseg C, C) = to_q [| to_k | to_v], nseg 1 | 3, heads * d == C, b (nseg C) or NULL, M = B * ntok -> q, k
+ * [B][heads][ntok_pad][dp], vt [B][heads][dpv][ntok_pad] in the attention kernels' layout (dp = padded head dim, dpv = dp rounded up to 32,
+ * ntok_pad = ntok rounded up to 32, q pre-scaled by log2(e) / sqrt(d), vt row dp = 1 where dpv > dp); k, vt unused when nseg == 1.
+ * splitk as above (GEGLU cannot split).  Replaces norm1 + attn1.to_q/k/v, norm2 + attn2.to_q, norm3 + ff.net.0 of diffusers'
+ * BasicTransformerBlock inside gill_unet_forward (reference call site: gill/custom_sd.py:633-638).  Synchronises. */
+int gill_op_ln_gemm(int mode, const void* T_bf16, const float* planes, int P, int ln_rows, const float* ln_g, const float* ln_b, const void* W_bf16,
+                    const float* b, void* out_bf16, void* q_bf16, void* k_bf16, void* vt_bf16, int M, int C, int inner, int nseg, int heads, int d,
+                    int ntok, int splitk, void* stream);
+
 /* fp8 (OCP e4m3) 3x3 convolution on CDNA4's v_mfma_scale_f32_16x16x128_f8f6f4 — BASELINE.json configs[4]; no reference
  * counterpart (the reference runs SD in fp16, gill/models.py:550-551).  x (B,H,W,Cin) bf16 NHWC, w (Cout,Cin,3,3) fp32,
  * optional bias (Cout) fp32 and residual (B,H,W,Cout) bf16 -> y (B,H,W,Cout) bf16.  Operands are quantised inside
