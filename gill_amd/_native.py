@@ -65,6 +65,13 @@ class gill_vae_config(C.Structure):
               ("scaling_factor", C.c_float), ("max_batch", C.c_int32)]
 
 
+class gill_sd_sampler(C.Structure):
+  _fields_ = [("kind", C.c_int32), ("steps_offset", C.c_int32), ("set_alpha_to_one", C.c_int32), ("eta", C.c_float)]
+
+
+SD_ROW_DOUBLES = 12     # GILL_SD_ROW_DOUBLES: [mode, slot_new, s1, s2, s3, in_scale, p_x, p_e, c_x, c_0, c_1, c_n]
+
+
 # every symbol include/gill_amd.h declares: (restype, argtypes)
 _vp, _i, _f = C.c_void_p, C.c_int, C.c_float
 SYMBOLS: Dict[str, Tuple[object, List[object]]] = {
@@ -99,6 +106,9 @@ SYMBOLS: Dict[str, Tuple[object, List[object]]] = {
   "gill_vae_decode": (_i, [_vp, _vp, _i, _vp, _vp, _vp]),
   "gill_op_conv3x3_fp8": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp]),
   "gill_pndm_schedule": (_i, [_i, C.POINTER(C.c_int32), C.POINTER(C.c_double)]),
+  "gill_sd_denoise_ex": (_i, [_vp, _vp, _vp, _vp, _i, _vp, _i, _i, _f, _vp, _vp, _vp]),
+  "gill_sd_schedule": (_i, [_vp, _i, _i, C.POINTER(C.c_float), C.POINTER(C.c_double), C.POINTER(C.c_double)]),
+  "gill_op_sd_sampler_run": (_i, [_vp, _i, _i, _f, _vp, _vp, _vp, _i, C.c_int64, _vp, _vp, _vp]),
   "gill_coop_timeouts": (_i, []),
   "gill_op_gemm": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _f, _i, _i, _i, _vp]),
   "gill_op_geglu": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _vp]),

@@ -434,9 +434,11 @@ __global__ __launch_bounds__(256) void sd_stage_kernel(const SdLoopArgs a) {
   const int64_t total = (int64_t)a.B * a.n;
   const int64_t stride = (int64_t)gridDim.x * blockDim.x;
   const int64_t t0 = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  const float in_scale = a.srows ? a.srows[step].in_scale : 1.f;   // scale_model_input (custom_sd.py:630-631): the identity for PNDM
   for (int64_t i = t0; i < total; i += stride) {
-    const float v = a.lat[i];
-    a.lat2[i] = v;                    // scale_model_input is the identity for PNDM (custom_sd.py:630-631)
+    float v = a.lat[i];
+    if (a.srows) v *= in_scale;
+    a.lat2[i] = v;
     if (a.cfg) a.lat2[total + i] = v;
   }
   const float* row = a.temb_table + (size_t)step * a.temb_total;
@@ -491,6 +493,46 @@ __global__ __launch_bounds__(256) void plms_step_kernel(const SdLoopArgs a) {
 }
 int plms_step_launch(const SdLoopArgs& a, hipStream_t s) {
   hipLaunchKernelGGL(plms_step_kernel, dim3(grid_for((int64_t)a.B * a.n)), dim3(256), 0, s, a);
+  GILL_CHECK_HIP(hipGetLastError());
+  return 0;
+}
+
+__global__ __launch_bounds__(256) void sampler_step_kernel(const SdLoopArgs a) {
+  kernarg_warm<sizeof(SdLoopArgs)>();
+  const int step = a.ctr[1];          // written by this step's stage kernel; nobody writes it while this kernel runs
+  const SamplerRow r = a.srows[step];
+  const int64_t total = (int64_t)a.B * a.n;
+  const float guidance = a.cfg ? a.guidance[0] : 0.f;
+  const float* z = r.c_n != 0.f ? a.noise[0] + (size_t)step * total : nullptr;   // the table's address is read only by rows that use it
+  float* ring = a.ets;
+  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (int64_t)gridDim.x * blockDim.x) {
+    float e = a.eps[i];
+    if (a.cfg) {
+      const float ec = a.eps[total + i];
+      e = e + guidance * (ec - e);
+    }
+    const float x = a.lat[i];
+    const float m = r.p_x * x + r.p_e * e;
+    if (r.slot_new >= 0) ring[(size_t)r.slot_new * total + i] = m;
+    float y = r.c_x * x + r.c_0 * m;
+    if (r.c_1 != 0.f) y += r.c_1 * ring[(size_t)r.s1 * total + i];
+    if (z) y += r.c_n * z[i];
+    a.lat[i] = y;
+  }
+  if (blockIdx.x == 0 && threadIdx.x == 0) a.ctr[0] = step + 1;   // read only by the next step's stage kernel
+}
+int sampler_step_launch(const SdLoopArgs& a, hipStream_t s) {
+  GILL_REQUIRE(a.srows && a.noise, "sampler step: rows and noise slot required");
+  hipLaunchKernelGGL(sampler_step_kernel, dim3(grid_for((int64_t)a.B * a.n)), dim3(256), 0, s, a);
+  GILL_CHECK_HIP(hipGetLastError());
+  return 0;
+}
+
+__global__ __launch_bounds__(256) void scale_f32_kernel(const float* __restrict__ src, float scale, int64_t n, float* __restrict__ dst) {
+  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) dst[i] = scale * src[i];
+}
+int scale_f32_launch(const float* src, float scale, int64_t n, float* dst, hipStream_t s) {
+  hipLaunchKernelGGL(scale_f32_kernel, dim3(grid_for(n)), dim3(256), 0, s, src, scale, n, dst);
   GILL_CHECK_HIP(hipGetLastError());
   return 0;
 }

@@ -301,8 +301,21 @@ struct PlmsRow {
   int s1, s2, s3;        // ring slots of ets[-2], ets[-3], ets[-4] where needed (ets[-1] = new / slot of last)
   float sample_coeff, eps_coeff;   // x_prev = sample_coeff * sample - eps_coeff * eps'
 };
+// The same for every sampler that is a linear update in (sample, model output, one step of history, noise): DDIM, DPM-Solver++(2M), Euler,
+// Euler ancestral (unet.hip builds the rows in double and rounds them to fp32 once).  With e the guided model output and x the latents:
+//   m = p_x * x + p_e * e ;  if slot_new >= 0: ring[slot_new] = m ;  x_next = c_x * x + c_0 * m + c_1 * ring[s1] + c_n * z[step]
+// ring[s1] is read only where c_1 != 0 and the noise only where c_n != 0.  in_scale is scale_model_input, applied by the stage kernel.
+struct SamplerRow {
+  int slot_new, s1;
+  float in_scale;
+  float p_x, p_e;
+  float c_x, c_0, c_1, c_n;
+};
 struct SdLoopArgs {
-  const PlmsRow* rows;   // [ncalls] on device
+  const PlmsRow* rows;   // [ncalls] on device (PNDM loops)
+  const SamplerRow* srows = nullptr;        // [ncalls] on device (every other sampler; nullptr in a PNDM loop)
+  const float* const* noise = nullptr;      // device slot holding the [ncalls][B][n] noise table's address (or null): not a kernel argument, so
+                                            // one captured step serves every call's table
   int* ctr;              // ctr[0]: next step (written by the PLMS kernel only), ctr[1]: current step (written by the stage kernel only)
   const float* temb_table; int temb_total;   // [ncalls][temb_total] -> temb_cur
   float* temb_cur;
@@ -324,6 +337,10 @@ int dup_pair_launch(void* a, const void* b, void* b2, size_t bytes, hipStream_t 
 int sd_stage_launch(const SdLoopArgs& a, hipStream_t s);
 // last kernel of a step: CFG combine + PLMS update of the latents (custom_sd.py:641-646), then step counter + 1
 int plms_step_launch(const SdLoopArgs& a, hipStream_t s);
+// the same for a SamplerRow loop (a.srows)
+int sampler_step_launch(const SdLoopArgs& a, hipStream_t s);
+// dst = scale * src over n floats (latents * init_noise_sigma, custom_sd.py:472)
+int scale_f32_launch(const float* src, float scale, int64_t n, float* dst, hipStream_t s);
 
 // weight re-layout helpers (run once at engine creation)
 int conv_weight_relayout_launch(const void* w, int dtype, int Cout, int Cin, bf16_t* out /*[Cout][9][Cin]*/, hipStream_t s);   // conv_in / conv_out

@@ -62,11 +62,13 @@ struct RowStats { float* p = nullptr; int planes = 1; };
 
 }  // namespace
 
-struct GraphKey {     // (the guidance scale is a device-side scalar, not part of the captured step)
+struct GraphKey {     // (the guidance scale and the noise table's address are device-side scalars, not part of the captured step)
   int Bx, cfg;
+  int linear;         // which step kernel the step ends with: 0 plms_step_kernel, 1 sampler_step_kernel (and the stage kernel's row table)
   bool operator<(const GraphKey& o) const {
     if (Bx != o.Bx) return Bx < o.Bx;
-    return cfg < o.cfg;
+    if (cfg != o.cfg) return cfg < o.cfg;
+    return linear < o.linear;
   }
 };
 
@@ -113,6 +115,8 @@ struct gill_unet : ConvWorkspace {
   bf16_t* ctx_full = nullptr;   // [2B][77][768]
   float* temb_cur = nullptr;    // [temb_total]: time-embedding row of the step being replayed
   PlmsRow* plms_rows = nullptr; // [temb_rows_cap]: per-step PLMS coefficients of the running loop
+  SamplerRow* sampler_rows = nullptr;   // [temb_rows_cap]: the same for the linear samplers (SdLoopArgs::srows)
+  const float** noise_slot = nullptr;   // [1]: address of the running loop's noise table (SdLoopArgs::noise)
   int* step_ctr = nullptr;      // [2]: next / current step of the running loop (SdLoopArgs::ctr)
   float* guidance_dev = nullptr; // [1]: guidance scale of the running loop (SdLoopArgs::guidance)
   // hipGraph of one UNet forward per UNet batch size (captured after the first eager forward of that size)
@@ -1086,6 +1090,8 @@ static int unet_plan_and_alloc(gill_unet* m) {
   GILL_TRY(m->pool.alloc(&m->ctx_full, (size_t)Bx * c.ctx_len * c.cross_attention_dim));
   GILL_TRY(m->pool.alloc(&m->temb_cur, (size_t)m->temb_total));
   GILL_TRY(m->pool.alloc(&m->plms_rows, (size_t)m->temb_rows_cap));
+  GILL_TRY(m->pool.alloc(&m->sampler_rows, (size_t)m->temb_rows_cap));
+  GILL_TRY(m->pool.alloc(&m->noise_slot, (size_t)1));
   GILL_TRY(m->pool.alloc(&m->step_ctr, (size_t)2));
   GILL_TRY(m->pool.alloc(&m->guidance_dev, (size_t)4));
   { const char* e = getenv("GILL_NO_GRAPH"); m->use_graph = !(e && e[0] == '1'); }
@@ -1193,10 +1199,10 @@ static void pndm_alphas_cumprod(std::vector<float>& ac) {
     ac[i] = prod;
   }
 }
-static void pndm_timesteps(int num_steps, std::vector<int>& ts, int* ratio_out) {
+static void pndm_timesteps(int num_steps, std::vector<int>& ts, int* ratio_out, int steps_offset = 1) {
   const int ratio = 1000 / num_steps;
   std::vector<int> base(num_steps);
-  for (int i = 0; i < num_steps; ++i) base[i] = i * ratio + 1;   // steps_offset = 1
+  for (int i = 0; i < num_steps; ++i) base[i] = i * ratio + steps_offset;   // (1 for SD)
   // plms_timesteps = concat(base[:-1], base[-2:-1], base[-1:])[::-1]
   std::vector<int> seq(base.begin(), base.end() - 1);
   if (num_steps >= 2) seq.push_back(base[num_steps - 2]);
@@ -1217,25 +1223,213 @@ extern "C" int gill_pndm_schedule(int num_steps, int32_t* timesteps_out, double*
   return (int)ts.size();
 }
 
-static int sd_denoise_on(gill_unet* m, const void* cond_bf16, const void* uncond_bf16, int n_uncond, const float* latents0, int B,
-                         int num_steps, float guidance, float* latents_out, hipStream_t s);
+// the PLMS schedule of every call (host arithmetic in double, like the scheduler's numpy/torch-CPU tables)
+static void pndm_rows(const std::vector<int>& ts, int ratio, const std::vector<float>& ac, bool v_prediction, bool set_alpha_to_one,
+                      std::vector<PlmsRow>& rows) {
+  const int ncalls = (int)ts.size();
+  rows.resize(ncalls);
+  int counter = 0, n_ets = 0, last = -1;
+  for (int i = 0; i < ncalls; ++i) {
+    int t = ts[i];
+    int prev_t = t - ratio;
+    PlmsRow& a = rows[i];
+    a.slot_new = -1; a.s1 = a.s2 = a.s3 = 0;
+    if (counter != 1) {
+      a.slot_new = (last + 1) & 3;
+      a.s1 = last & 3; a.s2 = (last + 3) & 3; a.s3 = (last + 2) & 3;
+      last = a.slot_new;
+      if (n_ets < 4) ++n_ets;
+    } else {
+      prev_t = t; t = t + ratio;
+      a.s1 = last & 3;
+    }
+    if (n_ets == 1 && counter == 0) a.mode = 0;
+    else if (n_ets == 1 && counter == 1) a.mode = 1;
+    else if (n_ets == 2) a.mode = 2;
+    else if (n_ets == 3) a.mode = 3;
+    else a.mode = 4;
+    // _get_prev_sample
+    const double at = ac[t];
+    const double ap = prev_t >= 0 ? (double)ac[prev_t] : (set_alpha_to_one ? 1.0 : (double)ac[0]);   // (False for SD)
+    const double bt = 1.0 - at, bp = 1.0 - ap;
+    const double sample_coeff = sqrt(ap / at);
+    const double denom = at * sqrt(bp) + sqrt(at * bt * ap);
+    double sc = sample_coeff, ec = (ap - at) / denom;
+    if (v_prediction) {   // the model output is v: eps' = sqrt(a_t) v + sqrt(1 - a_t) sample, folded into the two coefficients
+      sc -= ec * sqrt(bt);
+      ec *= sqrt(at);
+    }
+    a.sample_coeff = (float)sc;
+    a.eps_coeff = (float)ec;
+    ++counter;
+  }
+}
 
-extern "C" int gill_sd_denoise(gill_unet* m, const void* cond_bf16, const void* uncond_bf16, int n_uncond, const float* latents0,
-                               int B, int num_steps, float guidance, float* latents_out, void* stream) {
-  GILL_REQUIRE(m && cond_bf16 && latents0 && latents_out, "null argument");
+// ------------------------------------------------------------------------------------------------------------------
+// The linear samplers (diffusers 0.17.1 as configured for SD: scaled_linear betas, no clipping / thresholding / Karras sigmas).  Every table is
+// built in double from the fp32 alphas_cumprod above and rounded to fp32 once, into SamplerRow.
+enum { SD_PNDM = 0, SD_DDIM = 1, SD_DPMPP_2M = 2, SD_EULER = 3, SD_EULER_A = 4 };
+
+// np.linspace(0, 999, num): arange(num) * step, the last element set to the end point
+static void linspace_999(int num, std::vector<double>& v) {
+  v.resize(num);
+  const double step = num > 1 ? 999.0 / (double)(num - 1) : 0.0;
+  for (int i = 0; i < num; ++i) v[i] = (double)i * step;
+  if (num > 1) v[num - 1] = 999.0;
+}
+
+struct SdSchedule {
+  int kind = 0;
+  std::vector<float> timesteps;       // one per UNet call, as the time embedding sees them
+  double init_noise_sigma = 1.0;
+  std::vector<PlmsRow> plms;          // kind 0
+  std::vector<SamplerRow> rows;       // every other kind
+  bool needs_noise = false;           // some row has c_n != 0
+};
+
+static int sd_schedule(const gill_sd_sampler* sp, bool vpred, int num_steps, SdSchedule& out) {
+  GILL_REQUIRE(sp != nullptr, "null sampler");
+  GILL_REQUIRE(sp->kind >= SD_PNDM && sp->kind <= SD_EULER_A, "unknown sampler kind (0 pndm, 1 ddim, 2 dpmsolver++, 3 euler, 4 euler_ancestral)");
+  out.kind = sp->kind;
+  std::vector<float> ac; pndm_alphas_cumprod(ac);
+  const int T = 1000;
+  if (sp->kind == SD_PNDM) {
+    GILL_REQUIRE(num_steps >= 2 && num_steps <= 1000, "num_steps out of range");
+    GILL_REQUIRE(sp->steps_offset >= 0, "pndm: steps_offset must be >= 0");
+    GILL_REQUIRE((num_steps - 1) * (T / num_steps) + sp->steps_offset < T, "pndm: num_steps and steps_offset put a timestep past the training range");
+    std::vector<int> ts; int ratio;
+    pndm_timesteps(num_steps, ts, &ratio, sp->steps_offset);
+    pndm_rows(ts, ratio, ac, vpred, sp->set_alpha_to_one != 0, out.plms);
+    out.timesteps.resize(ts.size());
+    for (size_t i = 0; i < ts.size(); ++i) out.timesteps[i] = (float)ts[i];
+    return 0;
+  }
+  GILL_REQUIRE(num_steps >= 1 && num_steps <= 1000, "num_steps out of range");
+  const int N = num_steps;
+  out.rows.assign(N, SamplerRow{-1, 0, 1.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f});
+  out.timesteps.resize(N);
+  auto put = [&](int i, int slot_new, int s1, double in_scale, double p_x, double p_e, double c_x, double c_0, double c_1, double c_n) {
+    out.rows[i] = SamplerRow{slot_new, s1, (float)in_scale, (float)p_x, (float)p_e, (float)c_x, (float)c_0, (float)c_1, (float)c_n};
+  };
+  if (sp->kind == SD_DDIM) {
+    GILL_REQUIRE(sp->eta >= 0.f, "ddim: eta must be >= 0");     // (a NaN fails this too)
+    GILL_REQUIRE(sp->steps_offset >= 0, "ddim: steps_offset must be >= 0");
+    const int r = T / N;
+    GILL_REQUIRE((N - 1) * r + sp->steps_offset < T, "ddim: num_steps and steps_offset put a timestep past the training range");
+    for (int i = 0; i < N; ++i) {
+      const int t = (N - 1 - i) * r + sp->steps_offset, prev = t - r;
+      const double at = ac[t], ap = prev >= 0 ? (double)ac[prev] : (sp->set_alpha_to_one ? 1.0 : (double)ac[0]);
+      const double sd = (double)sp->eta * sqrt((1.0 - ap) / (1.0 - at)) * sqrt(1.0 - at / ap);
+      const double dir = sqrt(1.0 - ap - sd * sd);
+      // m = eps;  x0 = (x - sqrt(1 - a_t) eps) / sqrt(a_t);  x_prev = sqrt(a_p) x0 + dir eps + sd z
+      put(i, -1, 0, 1.0, vpred ? sqrt(1.0 - at) : 0.0, vpred ? sqrt(at) : 1.0, sqrt(ap / at), dir - sqrt(ap) * sqrt(1.0 - at) / sqrt(at), 0.0, sd);
+      out.timesteps[i] = (float)t;
+    }
+  } else if (sp->kind == SD_DPMPP_2M) {
+    GILL_REQUIRE(N <= 999, "dpmsolver++: num_steps above 999 repeats a timestep");
+    std::vector<double> ls; linspace_999(N + 1, ls);
+    std::vector<int> ts(N + 1);       // ts[N] = 0: the target of the last call
+    for (int i = 0; i < N; ++i) ts[i] = (int)rint(ls[N - i]);     // np.round: half to even
+    ts[N] = 0;
+    auto alpha = [&](int t) { return sqrt((double)ac[t]); };
+    auto sigma = [&](int t) { return sqrt(1.0 - (double)ac[t]); };
+    auto lambda = [&](int t) { return log(alpha(t)) - log(sigma(t)); };
+    for (int i = 0; i < N; ++i) {
+      const int s0 = ts[i], t = ts[i + 1];
+      const double h = lambda(t) - lambda(s0), E = exp(-h) - 1.0;
+      const double p_x = vpred ? alpha(s0) : 1.0 / alpha(s0), p_e = vpred ? -sigma(s0) : -sigma(s0) / alpha(s0);   // m = x0
+      const bool first_order = i == 0 || (i == N - 1 && N < 15);    // lower_order_final
+      double c_0 = -alpha(t) * E, c_1 = 0.0;
+      if (!first_order) {
+        const double r0 = (lambda(s0) - lambda(ts[i - 1])) / h;
+        c_0 = -alpha(t) * E * (1.0 + 0.5 / r0);       // D1 = (m0 - m1) / r0
+        c_1 = 0.5 * alpha(t) * E / r0;
+      }
+      put(i, i & 1, (i + 1) & 1, 1.0, p_x, p_e, sigma(t) / sigma(s0), c_0, c_1, 0.0);
+      out.timesteps[i] = (float)s0;
+    }
+  } else {   // Euler, Euler ancestral
+    std::vector<double> ls; linspace_999(N, ls);
+    std::vector<double> sg(N + 1);
+    double smax = 0.0;
+    for (int i = 0; i < N; ++i) {
+      const double t = ls[N - 1 - i];
+      int j = (int)floor(t); if (j > T - 2) j = T - 2;
+      const double f0 = sqrt((1.0 - (double)ac[j]) / (double)ac[j]), f1 = sqrt((1.0 - (double)ac[j + 1]) / (double)ac[j + 1]);
+      sg[i] = (f1 - f0) * (t - (double)j) + f0;      // np.interp
+      if (sg[i] > smax) smax = sg[i];
+      out.timesteps[i] = (float)t;
+    }
+    sg[N] = 0.0;
+    out.init_noise_sigma = smax;
+    for (int i = 0; i < N; ++i) {
+      const double s = sg[i], to = sg[i + 1], q = s * s + 1.0;
+      // m = eps;  v-prediction: x0 = x / (s^2 + 1) - v s / sqrt(s^2 + 1), eps = (x - x0) / s
+      const double p_x = vpred ? s / q : 0.0, p_e = vpred ? 1.0 / sqrt(q) : 1.0;
+      if (sp->kind == SD_EULER) put(i, -1, 0, 1.0 / sqrt(q), p_x, p_e, 1.0, to - s, 0.0, 0.0);
+      else {
+        const double up = sqrt(to * to * (s * s - to * to) / (s * s)), down = sqrt(to * to - up * up);
+        put(i, -1, 0, 1.0 / sqrt(q), p_x, p_e, 1.0, down - s, 0.0, up);
+      }
+    }
+  }
+  for (const SamplerRow& r : out.rows) {
+    const float v[7] = {r.in_scale, r.p_x, r.p_e, r.c_x, r.c_0, r.c_1, r.c_n};
+    for (float f : v) GILL_REQUIRE(std::isfinite(f), "sampler table: a coefficient is not finite for these arguments");
+    if (r.c_n != 0.f) out.needs_noise = true;
+  }
+  return 0;
+}
+
+extern "C" int gill_sd_schedule(const gill_sd_sampler* sampler, int v_prediction, int num_steps, float* timesteps_out,
+                                double* init_noise_sigma_out, double* rows_out) {
+  SdSchedule sc;
+  GILL_TRY(sd_schedule(sampler, v_prediction != 0, num_steps, sc));
+  const int ncalls = (int)sc.timesteps.size();
+  if (timesteps_out) for (int i = 0; i < ncalls; ++i) timesteps_out[i] = sc.timesteps[i];
+  if (init_noise_sigma_out) *init_noise_sigma_out = sc.init_noise_sigma;
+  if (rows_out) {
+    for (int i = 0; i < ncalls; ++i) {
+      double* o = rows_out + (size_t)i * GILL_SD_ROW_DOUBLES;
+      for (int k = 0; k < GILL_SD_ROW_DOUBLES; ++k) o[k] = 0.0;
+      if (sc.kind == SD_PNDM) {
+        const PlmsRow& r = sc.plms[i];
+        o[0] = r.mode; o[1] = r.slot_new; o[2] = r.s1; o[3] = r.s2; o[4] = r.s3;
+        o[5] = 1.0; o[7] = 1.0; o[8] = r.sample_coeff; o[9] = -(double)r.eps_coeff;
+      } else {
+        const SamplerRow& r = sc.rows[i];
+        o[0] = -1.0; o[1] = r.slot_new; o[2] = r.s1;
+        o[5] = r.in_scale; o[6] = r.p_x; o[7] = r.p_e; o[8] = r.c_x; o[9] = r.c_0; o[10] = r.c_1; o[11] = r.c_n;
+      }
+    }
+  }
+  return ncalls;
+}
+
+static int sd_denoise_on(gill_unet* m, const gill_sd_sampler* sampler, const void* cond_bf16, const void* uncond_bf16, int n_uncond,
+                         const float* latents0, int B, int num_steps, float guidance, float* latents_out, const float* noise, hipStream_t s);
+
+extern "C" int gill_sd_denoise_ex(gill_unet* m, const gill_sd_sampler* sampler, const void* cond_bf16, const void* uncond_bf16, int n_uncond,
+                                  const float* latents0, int B, int num_steps, float guidance, float* latents_out, const float* noise,
+                                  void* stream) {
+  GILL_REQUIRE(m && sampler && cond_bf16 && latents0 && latents_out, "null argument");
   GILL_REQUIRE(guidance <= 1.0f || uncond_bf16 == nullptr || n_uncond == 1 || n_uncond == B,
                "negative embeddings: batch must be 1 or B");
   GILL_TRY(unet_coop_check());
   hipStream_t caller = (hipStream_t)stream;
   GILL_TRY(m->fence.enter(caller));
-  const int rc = sd_denoise_on(m, cond_bf16, uncond_bf16, n_uncond, latents0, B, num_steps, guidance, latents_out, m->fence.stream);
+  const int rc = sd_denoise_on(m, sampler, cond_bf16, uncond_bf16, n_uncond, latents0, B, num_steps, guidance, latents_out, noise, m->fence.stream);
   GILL_TRY(m->fence.leave(caller));
   return rc;
 }
+extern "C" int gill_sd_denoise(gill_unet* m, const void* cond_bf16, const void* uncond_bf16, int n_uncond, const float* latents0,
+                               int B, int num_steps, float guidance, float* latents_out, void* stream) {
+  const gill_sd_sampler pndm = {SD_PNDM, 1, 0, 0.f};
+  return gill_sd_denoise_ex(m, &pndm, cond_bf16, uncond_bf16, n_uncond, latents0, B, num_steps, guidance, latents_out, nullptr, stream);
+}
 
-static int sd_denoise_on(gill_unet* m, const void* cond_bf16, const void* uncond_bf16, int n_uncond, const float* latents0, int B,
-                         int num_steps, float guidance, float* latents_out, hipStream_t s) {
-  GILL_REQUIRE(num_steps >= 2 && num_steps <= 1000, "num_steps out of range");
+static int sd_denoise_on(gill_unet* m, const gill_sd_sampler* sampler, const void* cond_bf16, const void* uncond_bf16, int n_uncond,
+                         const float* latents0, int B, int num_steps, float guidance, float* latents_out, const float* noise, hipStream_t s) {
   const bool cfg = guidance > 1.0f;     // do_classifier_free_guidance (custom_sd.py:588)
   const int Bx = cfg ? 2 * B : B;
   GILL_REQUIRE(B >= 1 && Bx <= m->cfg.max_batch, "batch exceeds the UNet handle's max_batch");
@@ -1245,58 +1439,22 @@ static int sd_denoise_on(gill_unet* m, const void* cond_bf16, const void* uncond
   const int64_t n_lat = (int64_t)c.in_channels * L * L;
   const size_t ctx_elems = (size_t)c.ctx_len * c.cross_attention_dim;
 
-  std::vector<int> ts; int ratio;
-  pndm_timesteps(num_steps, ts, &ratio);
-  std::vector<float> ac; pndm_alphas_cumprod(ac);
-  const int ncalls = (int)ts.size();
+  SdSchedule sched;
+  GILL_TRY(sd_schedule(sampler, c.v_prediction != 0, num_steps, sched));
+  const bool linear = sched.kind != SD_PNDM;
+  const int ncalls = (int)sched.timesteps.size();
   GILL_REQUIRE(ncalls <= m->temb_rows_cap, "too many steps for the time-embedding scratch");
+  GILL_REQUIRE(!sched.needs_noise || noise != nullptr, "this sampler draws noise in its steps: a [ncalls][B][n] noise table is required");
 
-  // the PLMS schedule of every call (host arithmetic in double, like the scheduler's numpy/torch-CPU tables)
-  std::vector<PlmsRow> rows(ncalls);
-  {
-    int counter = 0, n_ets = 0, last = -1;
-    for (int i = 0; i < ncalls; ++i) {
-      int t = ts[i];
-      int prev_t = t - ratio;
-      PlmsRow& a = rows[i];
-      a.slot_new = -1; a.s1 = a.s2 = a.s3 = 0;
-      if (counter != 1) {
-        a.slot_new = (last + 1) & 3;
-        a.s1 = last & 3; a.s2 = (last + 3) & 3; a.s3 = (last + 2) & 3;
-        last = a.slot_new;
-        if (n_ets < 4) ++n_ets;
-      } else {
-        prev_t = t; t = t + ratio;
-        a.s1 = last & 3;
-      }
-      if (n_ets == 1 && counter == 0) a.mode = 0;
-      else if (n_ets == 1 && counter == 1) a.mode = 1;
-      else if (n_ets == 2) a.mode = 2;
-      else if (n_ets == 3) a.mode = 3;
-      else a.mode = 4;
-      // _get_prev_sample
-      const double at = ac[t];
-      const double ap = prev_t >= 0 ? (double)ac[prev_t] : (double)ac[0];   // set_alpha_to_one = False
-      const double bt = 1.0 - at, bp = 1.0 - ap;
-      const double sample_coeff = sqrt(ap / at);
-      const double denom = at * sqrt(bp) + sqrt(at * bt * ap);
-      double sc = sample_coeff, ec = (ap - at) / denom;
-      if (c.v_prediction) {   // the model output is v: eps' = sqrt(a_t) v + sqrt(1 - a_t) sample, folded into the two coefficients
-        sc -= ec * sqrt(bt);
-        ec *= sqrt(at);
-      }
-      a.sample_coeff = (float)sc;
-      a.eps_coeff = (float)ec;
-      ++counter;
-    }
-  }
-  GILL_CHECK_HIP(hipMemcpyAsync(m->plms_rows, rows.data(), sizeof(PlmsRow) * ncalls, hipMemcpyHostToDevice, s));
+  if (linear) {
+    GILL_CHECK_HIP(hipMemcpyAsync(m->sampler_rows, sched.rows.data(), sizeof(SamplerRow) * ncalls, hipMemcpyHostToDevice, s));
+    GILL_CHECK_HIP(hipMemcpyAsync(m->noise_slot, &noise, sizeof(noise), hipMemcpyHostToDevice, s));   // (synchronised below)
+  } else
+  GILL_CHECK_HIP(hipMemcpyAsync(m->plms_rows, sched.plms.data(), sizeof(PlmsRow) * ncalls, hipMemcpyHostToDevice, s));
   GILL_CHECK_HIP(hipMemsetAsync(m->step_ctr, 0, sizeof(int) * 2, s));
   GILL_CHECK_HIP(hipMemcpyAsync(m->guidance_dev, &guidance, sizeof(float), hipMemcpyHostToDevice, s));   // (synchronised below)
   // hoisted: time-embedding table for every call (its stream sync also covers the host `rows` buffer), prompt K/V caches
-  std::vector<float> tf(ncalls);
-  for (int i = 0; i < ncalls; ++i) tf[i] = (float)ts[i];
-  GILL_TRY(unet_time_table(m, tf.data(), ncalls, s));
+  GILL_TRY(unet_time_table(m, sched.timesteps.data(), ncalls, s));
   // prompt_embeds = cat([negative_prompt_embeds.repeat(B), prompt_embeds])  (custom_sd.py:365-371)
   if (cfg) {
     for (int b = 0; b < B; ++b)
@@ -1309,7 +1467,7 @@ static int sd_denoise_on(gill_unet* m, const void* cond_bf16, const void* uncond
     GILL_CHECK_HIP(hipMemcpyAsync(m->ctx_full, cond_bf16, sizeof(bf16_t) * ctx_elems * B, hipMemcpyDeviceToDevice, s));
   }
   GILL_TRY(unet_ctx_cache(m, m->ctx_full, Bx, s));
-  GILL_CHECK_HIP(hipMemcpyAsync(m->lat, latents0, sizeof(float) * n_lat * B, hipMemcpyDeviceToDevice, s));
+  GILL_TRY(scale_f32_launch(latents0, (float)sched.init_noise_sigma, n_lat * B, m->lat, s));    // custom_sd.py:472
 
   // One loop step = stage kernel (latents -> UNet input, time-embedding row of the device-side step counter) + UNet forward
   // (~390 launches at ~10+ us of host time each: at small batch the GPU outruns the host) + CFG/PLMS kernel (reads its
@@ -1319,14 +1477,15 @@ static int sd_denoise_on(gill_unet* m, const void* cond_bf16, const void* uncond
   la.rows = m->plms_rows; la.ctr = m->step_ctr; la.temb_table = m->temb_table; la.temb_total = m->temb_total;
   la.temb_cur = m->temb_cur; la.eps = m->eps; la.lat = m->lat; la.lat2 = m->lat2; la.cur_sample = m->cur_sample; la.ets = m->ets;
   la.B = B; la.n = n_lat; la.guidance = m->guidance_dev; la.cfg = cfg ? 1 : 0;
-  // the graph bakes in B and the CFG flag besides the buffer addresses
-  const GraphKey gkey{Bx, cfg ? 1 : 0};
+  if (linear) { la.srows = m->sampler_rows; la.noise = m->noise_slot; }
+  // the graph bakes in B, the CFG flag and the step's two loop kernels (with their row table) besides the buffer addresses
+  const GraphKey gkey{Bx, cfg ? 1 : 0, linear ? 1 : 0};
   auto one_step = [&](hipStream_t st) -> int {
     GILL_TRY(sd_stage_launch(la, st));
     UNetRun r{m, st, Bx, m->temb_cur, 0, false};
     r.cfg_pair = cfg;
     GILL_TRY(r.forward(m->lat2, m->eps));
-    return plms_step_launch(la, st);
+    return linear ? sampler_step_launch(la, st) : plms_step_launch(la, st);
   };
   for (int i = 0; i < ncalls; ++i) {
     auto git = m->graphs.find(gkey);
@@ -1353,6 +1512,49 @@ static int sd_denoise_on(gill_unet* m, const void* cond_bf16, const void* uncond
     }
   }
   GILL_CHECK_HIP(hipMemcpyAsync(latents_out, m->lat, sizeof(float) * n_lat * B, hipMemcpyDeviceToDevice, s));
+  return 0;
+}
+
+// ------------------------------------------------------------------------------------------------------------------
+// Operator-level entry for the loop's sampler arithmetic: the schedule, the stage and step kernels and the device-side step counter exactly as
+// sd_denoise_on drives them, the UNet replaced by the caller's model outputs.  For tests/test_samplers_gpu.py; synchronises.
+extern "C" int gill_op_sd_sampler_run(const gill_sd_sampler* sampler, int v_prediction, int num_steps, float guidance, const float* latents0,
+                                      const float* model_out, const float* noise, int B, int64_t n, float* lat_out, float* unet_in_out,
+                                      void* stream) {
+  hipStream_t s = (hipStream_t)stream;
+  GILL_REQUIRE(sampler && latents0 && model_out && lat_out && unet_in_out, "null argument");
+  GILL_REQUIRE(B >= 1 && n >= 1 && (int64_t)B * n <= ((int64_t)1 << 28), "B, n out of range");
+  SdSchedule sched;
+  GILL_TRY(sd_schedule(sampler, v_prediction != 0, num_steps, sched));
+  GILL_REQUIRE(!sched.needs_noise || noise != nullptr, "this sampler draws noise in its steps: a [ncalls][B][n] noise table is required");
+  const bool linear = sched.kind != SD_PNDM, cfg = guidance > 1.0f;
+  const int ncalls = (int)sched.timesteps.size(), Bx = cfg ? 2 * B : B;
+  const size_t total = (size_t)B * n;
+  DevBuf rows, ctr, gd, slot, lat, lat2, saved, ring;
+  GILL_TRY(rows.alloc(linear ? sizeof(SamplerRow) * ncalls : sizeof(PlmsRow) * ncalls));
+  GILL_CHECK_HIP(hipMemcpyAsync(rows.p, linear ? (const void*)sched.rows.data() : (const void*)sched.plms.data(), rows.bytes, hipMemcpyHostToDevice, s));
+  GILL_TRY(ctr.alloc_zero(sizeof(int) * 2, s));
+  GILL_TRY(gd.alloc(sizeof(float)));
+  GILL_CHECK_HIP(hipMemcpyAsync(gd.p, &guidance, sizeof(float), hipMemcpyHostToDevice, s));
+  GILL_TRY(slot.alloc(sizeof(noise)));
+  GILL_CHECK_HIP(hipMemcpyAsync(slot.p, &noise, sizeof(noise), hipMemcpyHostToDevice, s));
+  GILL_TRY(lat.alloc(sizeof(float) * total)); GILL_TRY(lat2.alloc(sizeof(float) * total * 2));
+  GILL_TRY(saved.alloc(sizeof(float) * total)); GILL_TRY(ring.alloc(sizeof(float) * total * 4));
+  GILL_CHECK_HIP(hipStreamSynchronize(s));     // the host-side sources above are locals
+  GILL_TRY(scale_f32_launch(latents0, (float)sched.init_noise_sigma, (int64_t)total, (float*)lat.p, s));
+  SdLoopArgs la;
+  la.rows = linear ? nullptr : (const PlmsRow*)rows.p; la.ctr = (int*)ctr.p; la.temb_table = nullptr; la.temb_total = 0; la.temb_cur = nullptr;
+  la.lat = (float*)lat.p; la.lat2 = (float*)lat2.p; la.cur_sample = (float*)saved.p; la.ets = (float*)ring.p;
+  la.B = B; la.n = n; la.guidance = (const float*)gd.p; la.cfg = cfg ? 1 : 0;
+  if (linear) { la.srows = (const SamplerRow*)rows.p; la.noise = (const float* const*)slot.p; }
+  for (int i = 0; i < ncalls; ++i) {
+    GILL_TRY(sd_stage_launch(la, s));
+    GILL_CHECK_HIP(hipMemcpyAsync(unet_in_out + (size_t)i * total, lat2.p, sizeof(float) * total, hipMemcpyDeviceToDevice, s));
+    la.eps = model_out + (size_t)i * Bx * n;
+    GILL_TRY(linear ? sampler_step_launch(la, s) : plms_step_launch(la, s));
+    GILL_CHECK_HIP(hipMemcpyAsync(lat_out + (size_t)i * total, lat.p, sizeof(float) * total, hipMemcpyDeviceToDevice, s));
+  }
+  GILL_CHECK_HIP(hipStreamSynchronize(s));
   return 0;
 }
 

@@ -840,8 +840,9 @@ class GILL(nn.Module):
   @torch.no_grad()
   def generate_images(self, prompts, num_inference_steps: int = 50, guidance_scale: float = 7.5,
                       latents: Optional[Tensor] = None, seed: int = 1337, return_latents: bool = True,
-                      return_embeddings: bool = False, distributed: bool = True, decode: bool = False):
-    """Batched text -> image latents.  `prompts` is a list of strings (tokenized here) or an int64 tensor
+                      return_embeddings: bool = False, distributed: bool = True, decode: bool = False, scheduler=None):
+    """Batched text -> image latents.  scheduler: the sampler of this call (GillSDPipeline.__call__), None = the pipeline's own; a stochastic
+    one draws its step noise from a CPU generator seeded with `seed` and the chunk's first prompt index.  `prompts` is a list of strings (tokenized here) or an int64 tensor
     (B,T) of prompt token ids WITHOUT the [IMG] tokens (right-padded with pad_token_id).  Per prompt this equals the
     'gen' branch of generate_for_images_and_texts([p], num_words=2, gen_scale_factor=1e5): the 8 [IMG] ids are
     appended, one OPT pass yields their hidden states (models.py:384), the GILLMapper maps them to the (77,768)
@@ -889,7 +890,8 @@ class GILL(nn.Module):
         outs = []
         for i in range(0, B, 8):                                    # gen_max_bs = 8 (models.py:726)
           outs.append(self.sd_pipe(prompt_embeds=embs[i:i + 8], latents=lat0[i:i + 8], guidance_scale=guidance_scale,
-                                   num_inference_steps=num_inference_steps, output_type="latent").images)
+                                   num_inference_steps=num_inference_steps, output_type="latent", scheduler=scheduler,
+                                   generator=torch.Generator().manual_seed(seed + 1 + lo + i)).images)
         local = torch.cat(outs, 0)
     images = None
     if decode:

@@ -346,3 +346,27 @@ def ln_gemm_qkv(t: torch.Tensor, planes: torch.Tensor, ln_g: torch.Tensor, ln_b:
   N.check(N.lib().gill_op_ln_gemm(1, N.ptr(t), N.ptr(planes), planes.shape[0], ln_rows, N.ptr(ln_g), N.ptr(ln_b), N.ptr(w), N.ptr(bias), None,
                                   N.ptr(q), N.ptr(k), N.ptr(vt), M, Cc, 0, nseg, heads, d, ntok, splitk, N.current_stream()))
   return q, k, vt
+
+
+def sd_sampler_run(sampler, v_prediction: bool, num_steps: int, guidance: float, latents0: torch.Tensor, model_out: torch.Tensor,
+                   noise: Optional[torch.Tensor] = None, eta: float = 0.0):
+  """The denoise loop's schedule, stage kernel, step kernel and device step counter with the UNet replaced by `model_out`
+  (gill_op_sd_sampler_run).  sampler: kind string or gill_amd.sd.SamplerConfig; latents0 (B,n) fp32, model_out (ncalls,Bx,n) fp32 with
+  Bx = 2B when guidance > 1, noise (ncalls,B,n) fp32 or None -> (latents after every call, UNet input of every call), each (ncalls,B,n)."""
+  import ctypes as C
+  from .sd import as_sampler_config
+  sp = as_sampler_config(sampler).native(eta)
+  B, n = latents0.shape
+  ncalls = N.lib().gill_sd_schedule(C.byref(sp), int(bool(v_prediction)), int(num_steps), None, None, None)
+  if ncalls < 0:
+    N.check(ncalls)
+  Bx = 2 * B if guidance > 1.0 else B
+  if tuple(model_out.shape) != (ncalls, Bx, n) or (noise is not None and tuple(noise.shape) != (ncalls, B, n)):
+    raise ValueError(f"model_out must be {(ncalls, Bx, n)} and noise {(ncalls, B, n)}")
+  lat0, mo = latents0.float().contiguous(), model_out.float().contiguous()
+  z = None if noise is None else noise.float().contiguous()
+  lat = torch.empty((ncalls, B, n), device=lat0.device, dtype=torch.float32)
+  uin = torch.empty_like(lat)
+  N.check(N.lib().gill_op_sd_sampler_run(C.byref(sp), int(bool(v_prediction)), int(num_steps), float(guidance), N.ptr(lat0), N.ptr(mo),
+                                         None if z is None else N.ptr(z), B, n, N.ptr(lat), N.ptr(uin), N.current_stream()))
+  return lat, uin

@@ -6,7 +6,8 @@ The reference builds `StableDiffusionPipeline.from_pretrained("runwayml/stable-d
 (gill/models.py:730-731); the loop it runs is restated in-tree at gill/custom_sd.py:567-651.
 `GillSDPipeline` keeps that call signature (prompt / negative_prompt / prompt_embeds / negative_prompt_embeds / latents /
 generator / guidance_scale / num_inference_steps / num_images_per_prompt / output_type / return_prompts_only) and runs the UNet +
-PNDM loop in libgill_amd (gill_sd_denoise: csrc/unet.hip).
+denoise loop in libgill_amd (gill_sd_denoise_ex: csrc/unet.hip) under the pipeline's `scheduler`: PNDM (the default, and what
+SD-1.5's scheduler_config.json names), DDIM, DPM-Solver++(2M), Euler or Euler ancestral.
 
 Text prompts (`prompt=`, `negative_prompt=`: _encode_prompt, gill/custom_sd.py:224-373) run through the CLIP text tower in libgill_amd
 (gill_clip_text_forward: csrc/cliptext.hip) when the pipeline was built with text-encoder weights (`text_state=` / a model directory
@@ -24,7 +25,8 @@ from __future__ import annotations
 import ctypes as C
 import json
 import os
-from dataclasses import dataclass
+import warnings
+from dataclasses import dataclass, replace
 from typing import Dict, List, Optional, Union
 
 import torch
@@ -39,16 +41,92 @@ class PipelineOutput:
   nsfw_content_detected: Optional[List[bool]] = None
 
 
+SAMPLER_KINDS = ("pndm", "ddim", "dpmsolver++", "euler", "euler_ancestral")      # gill_sd_sampler.kind, in order
+_SCHEDULER_CLASSES = {"PNDMScheduler": "pndm", "DDIMScheduler": "ddim", "DPMSolverMultistepScheduler": "dpmsolver++",
+                      "EulerDiscreteScheduler": "euler", "EulerAncestralDiscreteScheduler": "euler_ancestral"}
+
+
+@dataclass
+class SamplerConfig:
+  """Which scheduler the denoise loop runs (the tables are built in libgill_amd: gill_sd_schedule).  steps_offset / set_alpha_to_one are
+  PNDM's and DDIM's; `eta` is not here: it is the pipeline call's argument and reaches DDIM only (custom_sd.py:395-403)."""
+  kind: str = "pndm"
+  steps_offset: int = 1
+  set_alpha_to_one: bool = False
+
+  def __post_init__(self):
+    if self.kind not in SAMPLER_KINDS:
+      raise ValueError(f"unknown scheduler {self.kind!r}: one of {', '.join(SAMPLER_KINDS)}")
+
+  def native(self, eta: float = 0.0) -> "N.gill_sd_sampler":
+    return N.gill_sd_sampler(kind=SAMPLER_KINDS.index(self.kind), steps_offset=int(self.steps_offset),
+                             set_alpha_to_one=int(bool(self.set_alpha_to_one)), eta=float(eta) if self.kind == "ddim" else 0.0)
+
+  def schedule(self, num_steps: int, v_prediction: bool = False, eta: float = 0.0):
+    """(timesteps [ncalls] float32, init_noise_sigma, rows [ncalls][12] float64 in the layout of include/gill_amd.h) — host only."""
+    cap = int(num_steps) + 1 if num_steps >= 1 else 1
+    ts, sig, rows = (C.c_float * cap)(), C.c_double(), (C.c_double * (cap * N.SD_ROW_DOUBLES))()
+    sp = self.native(eta)
+    n = N.lib().gill_sd_schedule(C.byref(sp), int(bool(v_prediction)), int(num_steps), ts, C.byref(sig), rows)
+    if n < 0:
+      N.check(n)
+    return (torch.tensor(list(ts)[:n], dtype=torch.float32), float(sig.value),
+            torch.tensor(list(rows)[:n * N.SD_ROW_DOUBLES], dtype=torch.float64).reshape(n, N.SD_ROW_DOUBLES))
+
+
+def as_sampler_config(scheduler: Union[None, str, SamplerConfig]) -> SamplerConfig:
+  if scheduler is None:
+    return SamplerConfig()
+  if isinstance(scheduler, SamplerConfig):
+    return replace(scheduler)
+  if isinstance(scheduler, str):
+    return SamplerConfig(kind=_SCHEDULER_CLASSES.get(scheduler, scheduler))
+  raise TypeError(f"scheduler must be a kind string or a SamplerConfig, got {type(scheduler)}")
+
+
+def parse_scheduler_config(model_dir: str, scheduler: Union[None, str, SamplerConfig] = None):
+  """`scheduler/scheduler_config.json` of a diffusers directory -> (SamplerConfig, prediction_type); needs no weights.  An absent file or
+  class name means PNDM; a scheduler class this build does not have warns and runs PNDM; `scheduler=` overrides the file's class (and, given
+  as a SamplerConfig, its fields).  A configuration the tables are not built for raises instead of running something else."""
+  c = {}
+  spath = os.path.join(model_dir, "scheduler", "scheduler_config.json")
+  if os.path.exists(spath):
+    with open(spath) as f:
+      c = json.load(f)
+  pred = c.get("prediction_type", "epsilon")
+  if c.get("beta_schedule", "scaled_linear") != "scaled_linear":
+    raise ValueError(f"{spath}: beta_schedule {c['beta_schedule']!r} is not built (only 'scaled_linear')")
+  if isinstance(scheduler, SamplerConfig):
+    return replace(scheduler), pred
+  name = c.get("_class_name", "PNDMScheduler")
+  if scheduler is not None:
+    kind = as_sampler_config(scheduler).kind
+  elif name in _SCHEDULER_CLASSES:
+    kind = _SCHEDULER_CLASSES[name]
+  else:
+    warnings.warn(f"{spath}: scheduler class {name} is not built into this pipeline; running PNDMScheduler instead "
+                  f"(available: {', '.join(_SCHEDULER_CLASSES)})")
+    kind = "pndm"
+  if kind == "dpmsolver++" and name == "DPMSolverMultistepScheduler":
+    if c.get("algorithm_type", "dpmsolver++") != "dpmsolver++" or c.get("solver_order", 2) != 2:
+      raise ValueError(f"{spath}: only algorithm_type 'dpmsolver++' with solver_order 2 is built, got "
+                       f"{c.get('algorithm_type')!r} / {c.get('solver_order')!r}")
+  # (a file that leaves these two out gets SD's values, as every directory did before the file was read for them)
+  return SamplerConfig(kind=kind, steps_offset=int(c.get("steps_offset", 1)), set_alpha_to_one=bool(c.get("set_alpha_to_one", False))), pred
+
+
 class GillSDPipeline:
   def __init__(self, unet_state: Dict[str, torch.Tensor], cfg: UNetConfig, uncond_embeds: Optional[torch.Tensor],
                device: Union[str, torch.device] = "cuda", max_batch: int = 16,
                vae_state: Optional[Dict[str, torch.Tensor]] = None, vae_cfg: Optional[VAEConfig] = None,
                text_state: Optional[Dict[str, torch.Tensor]] = None, text_cfg: Optional[ClipTextConfig] = None, tokenizer=None,
-               text_max_batch: Optional[int] = None):
-    """text_state / text_cfg: the CLIP text tower (state-dict names of the published text_encoder files, `text_model.` prefix);
+               text_max_batch: Optional[int] = None, scheduler: Union[None, str, SamplerConfig] = None):
+    """scheduler: a kind string ("pndm", "ddim", "dpmsolver++", "euler", "euler_ancestral", or the diffusers class name) or a SamplerConfig;
+    None is PNDM.  text_state / text_cfg: the CLIP text tower (state-dict names of the published text_encoder files, `text_model.` prefix);
     tokenizer: a Hugging Face style tokenizer object (CLIPTokenizer).  Without text_state nothing is allocated for text and
     `prompt=` raises.  uncond_embeds may be None only when text_state and tokenizer are given: it is then the native encoding of ""."""
     self.cfg = cfg
+    self.scheduler = as_sampler_config(scheduler)
     self.truncate_side = "right"        # custom_sd.py:90, :169 ('left': keep the tail of an over-long prompt)
     self.tokenizer = tokenizer
     self.text_encoder = None
@@ -92,6 +170,11 @@ class GillSDPipeline:
     if vae_state is not None:
       self.load_vae(vae_state, vae_cfg or VAEConfig(latent_size=cfg.sample_size))
 
+  def set_scheduler(self, scheduler: Union[None, str, SamplerConfig]) -> "GillSDPipeline":
+    """Swap the sampler of later calls (the handle keeps one captured step per step kernel: nothing is rebuilt)."""
+    self.scheduler = as_sampler_config(scheduler)
+    return self
+
   def load_vae(self, vae_state: Dict[str, torch.Tensor], vae_cfg: VAEConfig) -> None:
     """AutoencoderKL decoder half (state-dict keys post_quant_conv.* / decoder.*) -> gill_vae handle."""
     v = N.gill_vae_config(latent_channels=vae_cfg.latent_channels, out_channels=vae_cfg.out_channels,
@@ -130,8 +213,9 @@ class GillSDPipeline:
   # ---- construction from a local diffusers directory (no diffusers import: safetensors + json only)
   @classmethod
   def from_pretrained(cls, model_dir: str, uncond_embeds: Optional[torch.Tensor] = None, device="cuda", max_batch: int = 16,
-                      tokenizer=None, text_max_batch: Optional[int] = None, **_ignored):
-    """When `text_encoder/model.safetensors` and its `config.json` exist they are loaded into the native text tower, with the
+                      tokenizer=None, text_max_batch: Optional[int] = None, scheduler: Union[None, str, SamplerConfig] = None, **_ignored):
+    """The sampler comes from `scheduler/scheduler_config.json` (parse_scheduler_config) unless `scheduler=` names one.
+    When `text_encoder/model.safetensors` and its `config.json` exist they are loaded into the native text tower, with the
     tokenizer from `tokenizer=` or `tokenizer/` (transformers.CLIPTokenizer: plumbing).  The default negative embedding comes from,
     in this order: `uncond_embeds=`; `uncond_embeds.safetensors`; the native tower on ""; the transformers host forward, only when
     there are no text-encoder weights the native tower can load.  The third arm replaces what used to be that host computation
@@ -141,11 +225,7 @@ class GillSDPipeline:
       c = json.load(f)
     ahd = c["attention_head_dim"]     # diffusers quirk: this field holds the head COUNT(s)
     heads = ahd if isinstance(ahd, int) else ahd[0]
-    pred = "epsilon"
-    spath = os.path.join(model_dir, "scheduler", "scheduler_config.json")
-    if os.path.exists(spath):
-      with open(spath) as f:
-        pred = json.load(f).get("prediction_type", "epsilon")
+    sampler, pred = parse_scheduler_config(model_dir, scheduler)
     cfg = UNetConfig(in_channels=c["in_channels"], out_channels=c["out_channels"],
                      block_out_channels=tuple(c["block_out_channels"]), layers_per_block=c["layers_per_block"],
                      cross_attention_dim=c["cross_attention_dim"], num_heads=heads,
@@ -192,7 +272,7 @@ class GillSDPipeline:
                           norm_num_groups=vc["norm_num_groups"], latent_size=cfg.sample_size)   # scaling 0.18215: custom_sd.py:387
       vae_sd = load_file(os.path.join(vdir, "diffusion_pytorch_model.safetensors"))
     pipe = cls(sd, cfg, uncond_embeds, device, max_batch, vae_state=vae_sd, vae_cfg=vae_cfg, text_state=text_sd, text_cfg=text_cfg,
-               tokenizer=tokenizer, text_max_batch=text_max_batch)    # uncond_embeds None here: the native tower encodes ""
+               tokenizer=tokenizer, text_max_batch=text_max_batch, scheduler=sampler)    # uncond_embeds None here: the native tower encodes ""
     sdir = os.path.join(model_dir, "safety_checker")
     if os.path.exists(os.path.join(sdir, "model.safetensors")):     # the reference's from_pretrained loads it by default
       from .safety import GillSafetyChecker
@@ -236,8 +316,8 @@ class GillSDPipeline:
     return out
 
   def prepare_latents(self, batch_size: int, generator=None, latents: Optional[torch.Tensor] = None) -> torch.Tensor:
-    """custom_sd.py:458-473.  Latents are drawn on the CPU generator (cuRAND Philox streams of the reference
-    notebooks are not reproducible off-NVIDIA); init_noise_sigma == 1 for PNDM."""
+    """custom_sd.py:458-472.  Latents are drawn on the CPU generator (cuRAND Philox streams of the reference
+    notebooks are not reproducible off-NVIDIA); the multiplication by init_noise_sigma (:472) is gill_sd_denoise_ex's first kernel."""
     L = self.cfg.sample_size
     shape = (batch_size, self.cfg.in_channels, L, L)
     if isinstance(generator, list) and len(generator) != batch_size:
@@ -251,6 +331,21 @@ class GillSDPipeline:
         gdev = generator.device if generator is not None else torch.device("cpu")
         latents = torch.randn(shape, generator=generator, device=gdev, dtype=torch.float32)
     return latents.to(self.device, torch.float32).contiguous()
+
+  def _step_noise(self, ncalls: int, batch_size: int, generator=None) -> torch.Tensor:
+    """The variance noise of a stochastic sampler: one randn per UNet call, in call order, from the generator(s) the latents came from
+    (so: after them), as the schedulers' step() draws it; uploaded once."""
+    L = self.cfg.sample_size
+    one = (self.cfg.in_channels, L, L)
+    calls = []
+    for _ in range(ncalls):
+      if isinstance(generator, list):
+        calls.append(torch.cat([torch.randn((1,) + one, generator=g, device=g.device if g is not None else "cpu", dtype=torch.float32).cpu()
+                                for g in generator], 0))
+      else:
+        gdev = generator.device if generator is not None else torch.device("cpu")
+        calls.append(torch.randn((batch_size,) + one, generator=generator, device=gdev, dtype=torch.float32).cpu())
+    return torch.stack(calls, 0).to(self.device).contiguous()
 
   # ---- text prompts (custom_sd.py:224-373)
   def encode_prompt_ids(self, ids: torch.Tensor, dtype: torch.dtype = torch.float32) -> torch.Tensor:
@@ -294,7 +389,8 @@ class GillSDPipeline:
                negative_prompt=None, num_images_per_prompt: int = 1, eta: float = 0.0, generator=None,
                latents: Optional[torch.Tensor] = None, prompt_embeds: Optional[torch.Tensor] = None,
                negative_prompt_embeds: Optional[torch.Tensor] = None, output_type: Optional[str] = None, return_dict: bool = True,
-               return_prompts_only: bool = False, **_ignored):
+               return_prompts_only: bool = False, scheduler: Union[None, str, SamplerConfig] = None, **_ignored):
+    """scheduler: this call's sampler instead of `self.scheduler`.  eta reaches DDIM only (custom_sd.py:395-403)."""
     text = getattr(self, "text_encoder", None) is not None
     if prompt is not None and not text:
       raise ValueError("GillSDPipeline is driven by prompt_embeds (gill/models.py:730); text prompts need the CLIP text "
@@ -353,11 +449,16 @@ class GillSDPipeline:
       if uncond.shape[0] not in (1, B) or tuple(uncond.shape[1:]) != tuple(cond.shape[1:]):
         raise ValueError(f"`negative_prompt_embeds` must have the shape of `prompt_embeds` (or batch 1): got "
                          f"{tuple(negative_prompt_embeds.shape)} for prompt_embeds {tuple(prompt_embeds.shape)}")
+    sampler = self.scheduler if scheduler is None else as_sampler_config(scheduler)
+    _, _, rows = sampler.schedule(int(num_inference_steps), self.cfg.prediction_type == "v_prediction", eta)   # (raises on bad arguments)
     lat0 = self.prepare_latents(B, generator, latents)
+    noise = self._step_noise(rows.shape[0], B, generator) if bool((rows[:, 11] != 0).any()) else None
     out = torch.empty_like(lat0)
+    sp = sampler.native(eta)
     with torch.cuda.device(self.device):
-      N.check(N.lib().gill_sd_denoise(self._h, N.ptr(cond), N.ptr(uncond), int(uncond.shape[0]), N.ptr(lat0), B,
-                                      int(num_inference_steps), float(guidance_scale), N.ptr(out), N.current_stream()))
+      N.check(N.lib().gill_sd_denoise_ex(self._h, C.byref(sp), N.ptr(cond), N.ptr(uncond), int(uncond.shape[0]), N.ptr(lat0), B,
+                                         int(num_inference_steps), float(guidance_scale), N.ptr(out),
+                                         None if noise is None else N.ptr(noise), N.current_stream()))
     has_nsfw = None
     if output_type in ("pil", "np"):      # custom_sd.py:654-661: decode_latents -> run_safety_checker -> numpy_to_pil
       from PIL import Image

@@ -254,6 +254,38 @@ int gill_unet_forward(gill_unet* h, const float* sample, const float* timesteps_
 int gill_sd_denoise(gill_unet* h, const void* cond_bf16, const void* uncond_bf16, int n_uncond, const float* latents0, int B,
                     int num_steps, float guidance, float* latents_out, void* stream);
 
+/* The same loop under another sampler (the reference's pipeline is written against KarrasDiffusionSchedulers, custom_sd.py:86).  Tables follow
+ * diffusers 0.17.1 with scaled_linear betas 0.00085..0.012 over 1000 train steps; DPM-Solver++ is (2M): solver_order 2, midpoint,
+ * lower_order_final, no thresholding, no Karras sigmas; Euler has s_churn 0. */
+typedef struct {
+  int32_t kind;             /* 0 pndm, 1 ddim, 2 dpmsolver++ (2M), 3 euler, 4 euler_ancestral */
+  int32_t steps_offset;     /* pndm / ddim; 1 for SD */
+  int32_t set_alpha_to_one; /* pndm / ddim; 0 for SD */
+  float eta;                /* ddim */
+} gill_sd_sampler;
+
+/* gill_sd_denoise with a sampler; kind 0 (steps_offset 1, set_alpha_to_one 0) is gill_sd_denoise itself, bit for bit.  The sampler multiplies
+ * latents0 by its init_noise_sigma itself (custom_sd.py:472): pass the unit-variance draw.  num_steps >= 1 (pndm: >= 2) UNet calls
+ * (pndm: num_steps + 1).  noise: (ncalls,B,4,L,L) fp32 on the device, unit variance, row i read by call i — required when a row of the table has
+ * c_n != 0 (ddim with eta > 0, euler_ancestral), otherwise never read and may be NULL.  v-prediction comes from the handle's configuration. */
+int gill_sd_denoise_ex(gill_unet* h, const gill_sd_sampler* sampler, const void* cond_bf16, const void* uncond_bf16, int n_uncond,
+                       const float* latents0, int B, int num_steps, float guidance, float* latents_out, const float* noise, void* stream);
+
+/* The tables gill_sd_denoise_ex runs on, for tests and callers that must know the number of calls (host arrays, no GPU needed).  Returns the
+ * number of UNet calls (<= num_steps + 1), negative on invalid arguments.  Every output may be NULL.  timesteps_out: one float per call (Euler's are
+ * fractional).  rows_out: GILL_SD_ROW_DOUBLES doubles per call, the fp32 values the device reads, widened:
+ *   [0] mode  [1] slot_new  [2] s1  [3] s2  [4] s3  [5] in_scale  [6] p_x  [7] p_e  [8] c_x  [9] c_0  [10] c_1  [11] c_n
+ * With e the guided model output, x the latents and ring[] the stored history:
+ *   mode -1 (every kind but pndm):  m = p_x x + p_e e;  if slot_new >= 0: ring[slot_new] = m;
+ *                                   x_next = c_x x + c_0 m + c_1 ring[s1] + c_n noise[call]      (the UNet sees in_scale * x)
+ *   mode 0..4 (pndm; v-prediction is folded into c_x, c_0):  x_next = c_x x' + c_0 e'  with
+ *     0: e' = e, x' = x, saved = x, ring[slot_new] = e          1: e' = (e + ring[s1]) / 2, x' = saved
+ *     2..4: ring[slot_new] = e, then e' = (3 e - ring[s1]) / 2;  (23 e - 16 ring[s1] + 5 ring[s2]) / 12;
+ *           (55 e - 59 ring[s1] + 37 ring[s2] - 9 ring[s3]) / 24;  x' = x */
+#define GILL_SD_ROW_DOUBLES 12
+int gill_sd_schedule(const gill_sd_sampler* sampler, int v_prediction, int num_steps, float* timesteps_out, double* init_noise_sigma_out,
+                     double* rows_out);
+
 /* ------------------------------------------------------------------------------------------
  * Stage 3b — VAE decode of the final latents.  Replaces StableDiffusionPipeline.decode_latents
  * (gill/custom_sd.py:385-392: latents / 0.18215 -> vae.decode -> (x/2+0.5).clamp(0,1)) and the uint8 conversion
@@ -399,6 +431,13 @@ int gill_op_ln_gemm(int mode, const void* T_bf16, const float* planes, int P, in
  * (activations x 8 per tensor, weights per output channel).  splitk 0 = heuristic. */
 int gill_op_conv3x3_fp8(const void* x_bf16, const float* w_oihw, const float* bias, const void* resid_bf16, void* y_bf16,
                         int B, int H, int W, int Cin, int Cout, int splitk, void* stream);
+
+/* The denoise loop's own kernels under a teacher: gill_sd_denoise_ex's table, stage kernel, step kernel and device step counter, with the UNet
+ * replaced by "read this call's model output".  latents0 (B,n) fp32 (any n), model_out (ncalls,Bx,n) fp32 with Bx = 2B (uncond rows, then cond
+ * rows) when guidance > 1, else B; noise (ncalls,B,n) fp32 or NULL as for gill_sd_denoise_ex -> lat_out (ncalls,B,n): the latents after every
+ * call, unet_in_out (ncalls,B,n): the scaled UNet input of every call.  ncalls = gill_sd_schedule(...).  Synchronises. */
+int gill_op_sd_sampler_run(const gill_sd_sampler* sampler, int v_prediction, int num_steps, float guidance, const float* latents0,
+                           const float* model_out, const float* noise, int B, int64_t n, float* lat_out, float* unet_in_out, void* stream);
 
 #ifdef __cplusplus
 }
