@@ -196,6 +196,24 @@ extern "C" int gill_op_conv3x3_gn(const void* x, const float* w_oihw, const floa
   return 0;
 }
 
+// ResnetBlock2D's conv2 with the 1x1 conv_shortcut fused as extra K channels: wf rows = [the 9 Cin conv taps of wr (its K order) | the CS shortcut channels
+// of w_sc (fp32, rounded to bf16)], as the engines' fuse_shortcut_into_conv2() builds them.  Synchronises.
+static int op_fuse_shortcut_rows(const bf16_t* wr, int k9, const float* w_sc, int CS, int Cout, DevBuf& wf, hipStream_t s) {
+  const int kf = k9 + CS;
+  DevBuf wsb, idx;
+  GILL_TRY(wsb.alloc(sizeof(bf16_t) * (size_t)Cout * CS));
+  GILL_TRY(wf.alloc(sizeof(bf16_t) * (size_t)Cout * kf));
+  GILL_TRY(idx.alloc(sizeof(int32_t) * (size_t)Cout));
+  GILL_TRY(convert_to_bf16_launch(w_sc, GILL_DTYPE_F32, (int64_t)Cout * CS, (bf16_t*)wsb.p, s));
+  std::vector<int32_t> ident(Cout);
+  for (int i = 0; i < Cout; ++i) ident[i] = i;
+  GILL_CHECK_HIP(hipMemcpyAsync(idx.p, ident.data(), sizeof(int32_t) * Cout, hipMemcpyHostToDevice, s));
+  GILL_TRY(scatter_rows_bf16_launch(wr, Cout, k9, (const int32_t*)idx.p, (bf16_t*)wf.p, kf, s));
+  GILL_TRY(scatter_rows_bf16_launch((const bf16_t*)wsb.p, Cout, CS, (const int32_t*)idx.p, (bf16_t*)wf.p + k9, kf, s));
+  GILL_CHECK_HIP(hipStreamSynchronize(s));     // (the staging buffers leave scope)
+  return 0;
+}
+
 // ResnetBlock2D's conv2 with the 1x1 conv_shortcut of the raw block input fused as extra K channels (the engine's c2f weights):
 // y = conv3x3(x1 ++ x2) + bias + conv1x1(xs1 ++ xs2), one implicit GEMM with K = 9 (C1 + C2) + CS1 + CS2.  For the operator tests.
 extern "C" int gill_op_conv3x3_shortcut(const void* x1, int C1, const void* x2, int C2, const float* w_oihw, const float* bias,
@@ -204,20 +222,12 @@ extern "C" int gill_op_conv3x3_shortcut(const void* x1, int C1, const void* x2, 
   hipStream_t s = (hipStream_t)stream;
   const int Cin = C1 + C2, CS = CS1 + CS2, kf = 9 * Cin + CS;
   GILL_REQUIRE(x1 && w_oihw && xs1 && w_sc && y && CS % 64 == 0 && CS1 % 64 == 0, "bad argument");
-  DevBuf wr, wsb, wf, idx, ws;
+  DevBuf wr, wf, ws;
   GILL_TRY(wr.alloc(sizeof(bf16_t) * (size_t)Cout * 9 * Cin));
-  GILL_TRY(wsb.alloc(sizeof(bf16_t) * (size_t)Cout * CS));
-  GILL_TRY(wf.alloc(sizeof(bf16_t) * (size_t)Cout * kf));
-  GILL_TRY(idx.alloc(sizeof(int32_t) * (size_t)Cout));
   const int chunked = conv_k_chunked(IH * IW, Cin, Cout) ? 1 : 0;
   if (chunked) GILL_TRY(conv_weight_relayout_chunked_launch(w_oihw, GILL_DTYPE_F32, Cout, Cin, (bf16_t*)wr.p, s));
   else GILL_TRY(conv_weight_relayout_launch(w_oihw, GILL_DTYPE_F32, Cout, Cin, (bf16_t*)wr.p, s));
-  GILL_TRY(convert_to_bf16_launch(w_sc, GILL_DTYPE_F32, (int64_t)Cout * CS, (bf16_t*)wsb.p, s));
-  std::vector<int32_t> ident(Cout);
-  for (int i = 0; i < Cout; ++i) ident[i] = i;
-  GILL_CHECK_HIP(hipMemcpyAsync(idx.p, ident.data(), sizeof(int32_t) * Cout, hipMemcpyHostToDevice, s));
-  GILL_TRY(scatter_rows_bf16_launch((const bf16_t*)wr.p, Cout, 9 * Cin, (const int32_t*)idx.p, (bf16_t*)wf.p, kf, s));
-  GILL_TRY(scatter_rows_bf16_launch((const bf16_t*)wsb.p, Cout, CS, (const int32_t*)idx.p, (bf16_t*)wf.p + 9 * Cin, kf, s));
+  GILL_TRY(op_fuse_shortcut_rows((const bf16_t*)wr.p, 9 * Cin, w_sc, CS, Cout, wf, s));
   GemmArgs g;
   g.conv = 1; g.IH = IH; g.IW = IW; g.OH = IH; g.OW = IW; g.Cin = Cin; g.stride = 1; g.ups = 0;
   g.M = B * IH * IW; g.N = Cout; g.K = kf;
@@ -309,6 +319,89 @@ extern "C" int gill_op_conv3x3_fp8(const void* x_bf16, const float* w_oihw, cons
     a.bias = bias; a.resid = (const bf16_t*)resid_bf16;
     for (int r = 0; r < op_repeat(); ++r) GILL_TRY(conv3x3_fp8_launch(a, s));
   }
+  GILL_CHECK_HIP(hipStreamSynchronize(s));
+  return 0;
+}
+
+// ---- fused GroupNorm statistics on their own (tests/test_gn_stats_gpu.py): the producers' raw partials, and the consumer on caller-made partials.
+// Launches `g` with GemmArgs::gn_stats set the way ConvRun::fuse_stats() sets it (bins of `bin` channels, rows_per_batch = output rows per sample),
+// forced `splitk` ways (<= 1: unsplit), and reports the slab geometry the launcher used.
+static int op_gn_producer_launch(GemmArgs& g, int rows_per_batch, float* stats, int bin, int splitk, int* slab_rows, int* nslab, DevBuf& ws, hipStream_t s) {
+  GILL_REQUIRE(stats && slab_rows && nslab && bin > 0 && g.N % bin == 0, "gn_stats producer: bad argument");
+  GILL_REQUIRE(gemm_fused_gn_ok(g.N, bin) && rows_per_batch % GN_SLAB_ROWS == 0, "gn_stats producer: no fused statistics for this width / bin / map size");
+  g.gn_stats = stats; g.gn_groups = g.N / bin; g.gn_cg = bin;
+  g.rows_per_batch = rows_per_batch;
+  g.splitk = splitk > 1 ? splitk : 1;
+  if (g.splitk > 1) {
+    GILL_TRY(ws.alloc(sizeof(float) * (size_t)g.splitk * g.M * g.N));
+    g.ws = (float*)ws.p;
+  }
+  *slab_rows = gemm_gn_slab_rows(g);
+  *nslab = rows_per_batch / *slab_rows;
+  for (int r = 0; r < op_repeat(); ++r) GILL_TRY(gemm_launch(g, s));
+  GILL_CHECK_HIP(hipStreamSynchronize(s));
+  return 0;
+}
+
+extern "C" int gill_op_conv3x3_gn_stats(const void* x1, int C1, const void* x2, int C2, const float* w_oihw, const float* bias, const float* rowvec,
+                                        const void* resid, const void* xs1, int CS1, const void* xs2, int CS2, const float* w_sc, void* y,
+                                        float* gn_stats, int bin, int B, int IH, int IW, int Cout, int ups, int splitk, int* slab_rows, int* nslab,
+                                        void* stream) {
+  hipStream_t s = (hipStream_t)stream;
+  const int Cin = C1 + C2, CS = xs1 ? CS1 + CS2 : 0, k9 = 9 * Cin, kf = k9 + CS;
+  GILL_REQUIRE(x1 && w_oihw && y && Cin > 0, "bad argument");
+  GILL_REQUIRE(!ups || (!rowvec && !resid && !xs1), "conv3x3_gn_stats: the four-tap upsample form takes no row vector, residual or shortcut segment");
+  GILL_REQUIRE(!xs1 || (w_sc && CS % 64 == 0 && CS1 % 64 == 0 && !rowvec && !resid), "conv3x3_gn_stats: bad shortcut segment");
+  DevBuf wr, wf, ws;
+  GILL_TRY(wr.alloc(sizeof(bf16_t) * (size_t)Cout * 16 * Cin));     // 9 taps, or 4 classes x 4 taps
+  const int chunked = (!ups && conv_k_chunked(IH * IW, Cin, Cout)) ? 1 : 0;
+  if (ups) GILL_TRY(conv_weight_relayout_ups4_launch(w_oihw, GILL_DTYPE_F32, Cout, Cin, (bf16_t*)wr.p, s));
+  else if (chunked) GILL_TRY(conv_weight_relayout_chunked_launch(w_oihw, GILL_DTYPE_F32, Cout, Cin, (bf16_t*)wr.p, s));
+  else GILL_TRY(conv_weight_relayout_launch(w_oihw, GILL_DTYPE_F32, Cout, Cin, (bf16_t*)wr.p, s));
+  const bf16_t* wk = (const bf16_t*)wr.p;
+  if (CS) {
+    GILL_TRY(op_fuse_shortcut_rows((const bf16_t*)wr.p, k9, w_sc, CS, Cout, wf, s));
+    wk = (const bf16_t*)wf.p;
+  }
+  GemmArgs g;
+  g.conv = 1; g.IH = IH; g.IW = IW; g.Cin = Cin; g.stride = 1; g.ups = ups ? 2 : 0;
+  g.OH = ups ? 2 * IH : IH; g.OW = ups ? 2 * IW : IW;
+  g.M = B * g.OH * g.OW; g.N = Cout; g.K = ups ? 4 * Cin : kf;
+  g.A = (const bf16_t*)x1; g.A2 = (const bf16_t*)x2; g.K1 = C1;
+  g.X1 = (const bf16_t*)xs1; g.X2 = (const bf16_t*)xs2; g.KX = CS; g.KX1 = CS ? CS1 : 0;
+  g.W = wk; g.k_chunked = chunked; g.bias = bias;
+  g.rowvec = rowvec; g.rowvec_bstride = Cout;
+  g.resid = resid; g.ldr = Cout;
+  g.C = y; g.ldc = Cout;
+  return op_gn_producer_launch(g, g.OH * g.OW, gn_stats, bin, splitk, slab_rows, nslab, ws, s);
+}
+
+extern "C" int gill_op_gemm_gn_stats(const void* A, const void* W, const float* bias, const void* resid, void* C, float* gn_stats, int bin, int M, int N,
+                                     int K, int rows_per_batch, int splitk, int* slab_rows, int* nslab, void* stream) {
+  hipStream_t s = (hipStream_t)stream;
+  GILL_REQUIRE(A && W && C && rows_per_batch > 0 && M % rows_per_batch == 0, "bad argument");
+  DevBuf ws;
+  GemmArgs g;
+  g.M = M; g.N = N; g.K = K; g.K1 = K;
+  g.A = (const bf16_t*)A; g.lda = K;
+  g.W = (const bf16_t*)W; g.bias = bias;
+  g.resid = resid; g.ldr = N;
+  g.C = C; g.ldc = N;
+  return op_gn_producer_launch(g, rows_per_batch, gn_stats, bin, splitk, slab_rows, nslab, ws, s);
+}
+
+extern "C" int gill_op_groupnorm_from_stats(const void* x1, int C1, const void* x2, int C2, int B, int HW, int groups, const float* gamma,
+                                            const float* beta, float eps, int silu, const float* stats1, int bin1, int nslab1,
+                                            const float* stats2, int bin2, int nslab2, void* y, float* ss_out, void* stream) {
+  hipStream_t s = (hipStream_t)stream;
+  GILL_REQUIRE(x1 && gamma && beta && stats1 && (y || ss_out) && C1 > 0 && C2 >= 0 && bin1 > 0 && C1 % bin1 == 0, "bad argument");
+  GILL_REQUIRE((C2 == 0) == (stats2 == nullptr) && (C2 == 0 || (x2 && bin2 > 0 && C2 % bin2 == 0)), "groupnorm_from_stats: second source and its statistics come together");
+  GILL_REQUIRE(ss_out == nullptr || C2 == 0, "groupnorm_from_stats: the scale | shift table is for single-source inputs");
+  DevBuf tot;      // always passed, as ConvRun::gnorm() does
+  GILL_TRY(tot.alloc(sizeof(float) * groupnorm_totals_floats(B, C1 / bin1, C2 ? C2 / bin2 : 0)));
+  for (int r = 0; r < op_repeat(); ++r)
+    GILL_TRY(groupnorm_apply_launch((const bf16_t*)x1, C1, (const bf16_t*)x2, C2, B, HW, groups, gamma, beta, eps, silu, (bf16_t*)y, stats1, bin1, C1,
+                                    nslab1, stats2, C2 ? bin2 : 0, C2 ? nslab2 : 0, s, 0.f, (float*)tot.p, ss_out));
   GILL_CHECK_HIP(hipStreamSynchronize(s));
   return 0;
 }

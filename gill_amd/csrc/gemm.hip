@@ -198,11 +198,12 @@ __device__ __forceinline__ void splitk_finish_unit(const GemmArgs& p, const int 
   }
   add.x += rv.x; add.y += rv.y; add.z += rv.z; add.w += rv.w;
   if (poison) add.x = add.y = add.z = add.w = __builtin_nanf("");
-  // STATISTICS SOURCE: every FUSED producer of GroupNorm statistics in this file — the in-kernel epilogue (gs / gq), the plain reducer
-  // (store4()'s `fin`) and this unit — sums the fp32 values BEFORE their rounding to bf16, and every consumer normalises the ROUNDED tensor (below:
-  // raw[r], what a stand-alone apply pass would read).  The fused and unfused forms of one layer therefore see the same statistics source and differ
-  // only in the (fixed) order of the fp32 additions, which is why the fused and unfused forms are held to closeness, not equality.  Only the stand-alone
-  // statistics kernel of two-source (skip-concat) inputs reads rounded values — it has nothing else.  Variance: E[x^2] - E[x]^2 in fp32 over a
+  // STATISTICS SOURCE.  The producers that file RAW partials for a later GroupNorm-apply launch — the in-kernel epilogue (gs / gq) and the plain reducer
+  // (store4()'s `fin`) — sum the values AS STORED, i.e. after their rounding to bf16: their partials are the sums of the tensor the consumer reads
+  // (tests/test_gn_stats_gpu.py holds them to that within fp32 summation error).  This unit, which normalises in the same breath, sums the fp32 values
+  // BEFORE their rounding and normalises the ROUNDED tensor (below: raw[r], what a stand-alone apply pass would read); its one-slab
+  // partials for a later two-source consumer are those same sums.  The fused and unfused forms of one layer differ by that rounding noise (~1e-4 of a
+  // sum) and by the (fixed) order of the fp32 additions, which is why they are held to closeness, not equality.  Variance: E[x^2] - E[x]^2 in fp32 over a
   // (sample, group) slab of <= 256 x 80 values of O(1): cancellation costs ~1e-6 relative at |mean| ~ sigma, far below the bf16 output step.
 #pragma unroll
   for (int r = 0; r < RPT; ++r) {
@@ -1276,11 +1277,16 @@ __device__ __forceinline__ void gemm_tile(const GemmDev& d, const GemmTileCtx cx
           for (int e = 0; e < 8; ++e) v[e] = apply_act(v[e], p.act);
         }
         const bool st = mok[i] && nok;
+        float vs[8];      // what the GroupNorm partials add up: the values as stored (rounded, where the output is bf16)
+#pragma unroll
+        for (int e = 0; e < 8; ++e) vs[e] = v[e];
         if (F32_PATHS && p.out_mode == OUT_F32) {
           if (st) *reinterpret_cast<float4*>((float*)p.C + crow[i] + n) = make_float4(v[0], v[1], v[2], v[3]);
           if (st && hi) *reinterpret_cast<float4*>((float*)p.C + crow[i] + n + 4) = make_float4(v[4], v[5], v[6], v[7]);
         } else {
           uint4 o; o.x = pack_bf2(v[0], v[1]); o.y = pack_bf2(v[2], v[3]); o.z = pack_bf2(v[4], v[5]); o.w = pack_bf2(v[6], v[7]);
+          vs[0] = __uint_as_float(o.x << 16); vs[1] = __uint_as_float(o.x & 0xffff0000u); vs[2] = __uint_as_float(o.y << 16); vs[3] = __uint_as_float(o.y & 0xffff0000u);
+          vs[4] = __uint_as_float(o.z << 16); vs[5] = __uint_as_float(o.z & 0xffff0000u); vs[6] = __uint_as_float(o.w << 16); vs[7] = __uint_as_float(o.w & 0xffff0000u);
           const bool stc = st && EPI != 6;     // (COOP: the raw tensor — where somebody else reads it — is stored AFTER the arrival, see below)
           if (stc && hi) *reinterpret_cast<uint4*>((bf16_t*)p.C + crow[i] + n) = o;
           else if (stc) *reinterpret_cast<uint2*>((bf16_t*)p.C + crow[i] + n) = make_uint2(o.x, o.y);
@@ -1303,7 +1309,7 @@ __device__ __forceinline__ void gemm_tile(const GemmDev& d, const GemmTileCtx cx
         }
 #pragma unroll
         for (int e = 0; e < 8; ++e) {       // (rows beyond M hold the clamped row's values: they must not reach the statistics)
-          const float ve = mok[i] ? v[e] : 0.f;
+          const float ve = mok[i] ? vs[e] : 0.f;
           gs[e] += ve; gq[e] += ve * ve;
         }
       }
@@ -1542,9 +1548,11 @@ __global__ __launch_bounds__(4 * W) void gemm_splitk_reduce_kernel(const GemmArg
       float fin[4];
       store4(p, m, n, s[r].x, s[r].y, s[r].z, s[r].w, fin);
 #pragma unroll
-      for (int e = 0; e < 4; ++e) { gs[e] += fin[e]; gq[e] += fin[e] * fin[e]; }
-#pragma unroll
-      for (int e = 0; e < 4; ++e) { const float q = bf2f(f2bf(fin[e])); rsum[r] += q; rsq[r] += q * q; }
+      for (int e = 0; e < 4; ++e) {      // both kinds of statistics are those of the STORED values (the fp32 output: as they are)
+        const float q = bf2f(f2bf(fin[e])), g = (p.out_mode == OUT_F32) ? fin[e] : q;
+        gs[e] += g; gq[e] += g * g;
+        rsum[r] += q; rsq[r] += q * q;
+      }
     }
   }
   if (p.row_stats) {

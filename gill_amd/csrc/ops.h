@@ -48,9 +48,12 @@ struct GemmArgs {
   // Both kinds of fused statistics are FIXED-ORDER: a producer writes each partial sum exactly once (no atomics, nothing to
   // zero), the consumer adds the partials in index order, so two runs of the same launch sequence are bit-identical.
   // fused GroupNorm statistics of the output: gn_stats[(b * nslab + slab) * gn_groups + g][2] = {sum, sum of squares} of the
-  // gn_cg channels of bin g over the output rows of slab `slab` of sample b = m / rows_per_batch; rows per slab =
+  // STORED (bf16-rounded) values of the gn_cg channels of bin g over the output rows of slab `slab` of sample b = m / rows_per_batch; rows per slab =
   // gemm_gn_slab_rows() (64, or 16 when a split-K reducer with small blocks produces them), nslab = rows_per_batch / that
   // (row-major epilogue only; the tile width must be a multiple of gn_cg: gemm_fused_gn_ok())
+  // Statistics source: the in-kernel epilogue and the plain split-K reducer sum the values as stored.  Two producers of this layout still sum the fp32
+  // values BEFORE their rounding to bf16 (~1e-4 of a sum away): the fused-norm reducer / in-kernel split-K finish (gemm.hip splitk_finish_unit, one slab
+  // per sample) and the fp8 convolution's epilogue (conv_fp8.hip); a two-source consumer may therefore read one block of each kind.
   float* gn_stats = nullptr; int gn_groups = 0; int gn_cg = 0;
   // LayerNorm folded into the NEXT GEMM: LN(x) W^T + b = rstd (x (g*W)^T - mean * colsum(g*W)) + (beta W^T + b).
   //  producer: row_stats[(plane * M + m)][2] = {sum, sum of squares} of the bf16-rounded outputs of row m in the columns of

@@ -181,6 +181,84 @@ def groupnorm(x1: torch.Tensor, gamma: torch.Tensor, beta: torch.Tensor, groups:
   return y
 
 
+GN_SLAB_ROWS_MIN = 16      # csrc/ops.h: statistics buffers are sized for 16-row slabs, the smallest any producer files
+
+
+def _gn_stats_buffer(B: int, rows: int, nbins: int, device) -> torch.Tensor:
+  return torch.full((B * (rows // GN_SLAB_ROWS_MIN) * nbins * 2,), float("nan"), device=device, dtype=torch.float32)
+
+
+def conv3x3_gn_stats(x1: torch.Tensor, w_oihw: torch.Tensor, bin: int, bias: Optional[torch.Tensor] = None, x2: Optional[torch.Tensor] = None,
+                     rowvec: Optional[torch.Tensor] = None, resid: Optional[torch.Tensor] = None, xs1: Optional[torch.Tensor] = None,
+                     w_sc: Optional[torch.Tensor] = None, xs2: Optional[torch.Tensor] = None, upsample: bool = False, splitk: int = 1):
+  """3x3 / pad 1 / stride 1 convolution launched with fused GroupNorm statistics in bins of `bin` channels (include/gill_amd.h
+  gill_op_conv3x3_gn_stats; xs1 / w_sc [/ xs2]: the fused 1x1 shortcut segment; upsample: the four-tap form).  Returns (y (B,OH,OW,Cout) bf16,
+  the whole raw partial buffer (flat fp32, sized for 16-row slabs), slab_rows, nslab): y and the buffer NaN-prefilled; the launcher wrote
+  buffer[:B * nslab * (Cout // bin) * 2] as [B][nslab][Cout // bin][2]."""
+  x1 = _bf(x1)
+  B, IH, IW, C1 = x1.shape
+  x2 = None if x2 is None else _bf(x2)
+  xs1 = None if xs1 is None else _bf(xs1)
+  xs2 = None if xs2 is None else _bf(xs2)
+  C2 = 0 if x2 is None else x2.shape[-1]
+  CS1 = 0 if xs1 is None else xs1.shape[-1]
+  CS2 = 0 if xs2 is None else xs2.shape[-1]
+  f = lambda t: None if t is None else t.float().contiguous()   # noqa: E731
+  w, wsc, bias, rowvec = f(w_oihw), f(w_sc), f(bias), f(rowvec)
+  Cout = w.shape[0]
+  assert w.shape[1] == C1 + C2 and (wsc is None or tuple(wsc.shape) == (Cout, CS1 + CS2))
+  resid = None if resid is None else _bf(resid)
+  OH, OW = (2 * IH, 2 * IW) if upsample else (IH, IW)
+  y = torch.full((B, OH, OW, Cout), float("nan"), device=x1.device, dtype=torch.bfloat16)
+  stats = _gn_stats_buffer(B, OH * OW, Cout // bin, x1.device)
+  rows, nslab = ctypes.c_int(0), ctypes.c_int(0)
+  N.check(N.lib().gill_op_conv3x3_gn_stats(N.ptr(x1), C1, N.ptr(x2), C2, N.ptr(w), N.ptr(bias), N.ptr(rowvec), N.ptr(resid), N.ptr(xs1), CS1,
+                                           N.ptr(xs2), CS2, N.ptr(wsc), N.ptr(y), N.ptr(stats), bin, B, IH, IW, Cout, int(upsample), splitk,
+                                           ctypes.byref(rows), ctypes.byref(nslab), N.current_stream()))
+  return y, stats, rows.value, nslab.value
+
+
+def gemm_gn_stats(a: torch.Tensor, w: torch.Tensor, bin: int, rows_per_batch: int, bias: Optional[torch.Tensor] = None,
+                  resid: Optional[torch.Tensor] = None, splitk: int = 1):
+  """a (M,K) @ w (N,K).T + bias + resid launched with fused GroupNorm statistics (gill_op_gemm_gn_stats): the VAE decoder's conv_in (im2col,
+  K = 64) and attention to_out GEMMs.  Returns as conv3x3_gn_stats, y (M,N)."""
+  a, w = _bf(a), _bf(w)
+  M, K = a.shape
+  Nn = w.shape[0]
+  bias = None if bias is None else bias.float().contiguous()
+  resid = None if resid is None else _bf(resid)
+  y = torch.full((M, Nn), float("nan"), device=a.device, dtype=torch.bfloat16)
+  stats = _gn_stats_buffer(M // rows_per_batch, rows_per_batch, Nn // bin, a.device)
+  rows, nslab = ctypes.c_int(0), ctypes.c_int(0)
+  N.check(N.lib().gill_op_gemm_gn_stats(N.ptr(a), N.ptr(w), N.ptr(bias), N.ptr(resid), N.ptr(y), N.ptr(stats), bin, M, Nn, K, rows_per_batch,
+                                        splitk, ctypes.byref(rows), ctypes.byref(nslab), N.current_stream()))
+  return y, stats, rows.value, nslab.value
+
+
+def groupnorm_from_stats(x1: torch.Tensor, stats1: torch.Tensor, bin1: int, gamma: torch.Tensor, beta: torch.Tensor, groups: int = 32,
+                         eps: float = 1e-5, silu: bool = False, x2: Optional[torch.Tensor] = None, stats2: Optional[torch.Tensor] = None,
+                         bin2: int = 0, want_table: bool = False):
+  """GroupNorm(+SiLU) of x1 (B,HW,C1) [++ x2 (B,HW,C2)] bf16 from caller-supplied partial sums (gill_op_groupnorm_from_stats): stats1
+  (B,nslab1,C1 // bin1,2), stats2 (B,nslab2,C2 // bin2,2) fp32.  want_table (single source): the scale | shift table (B,2,C1) instead of y.
+  Returns (y or None, table or None, stats1, stats2): outputs NaN-prefilled, the statistics tensors as they are after the call."""
+  x1 = _bf(x1)
+  B, HW, C1 = x1.shape
+  C2 = 0
+  if x2 is not None:
+    x2 = _bf(x2)
+    C2 = x2.shape[-1]
+  chk = lambda st, nb: st.is_cuda and st.dtype == torch.float32 and st.is_contiguous() and st.dim() == 4 and st.shape[0] == B and tuple(st.shape[2:]) == (nb, 2)   # noqa: E731
+  assert chk(stats1, C1 // bin1) and (stats2 is None or chk(stats2, C2 // bin2))
+  g, b = gamma.float().contiguous(), beta.float().contiguous()
+  nan = float("nan")
+  y = None if want_table else torch.full((B, HW, C1 + C2), nan, device=x1.device, dtype=torch.bfloat16)
+  table = torch.full((B, 2, C1 + C2), nan, device=x1.device, dtype=torch.float32) if want_table else None
+  N.check(N.lib().gill_op_groupnorm_from_stats(N.ptr(x1), C1, N.ptr(x2), C2, B, HW, groups, N.ptr(g), N.ptr(b), float(eps), int(silu), N.ptr(stats1),
+                                               bin1, stats1.shape[1], N.ptr(stats2), bin2, 0 if stats2 is None else stats2.shape[1], N.ptr(y),
+                                               N.ptr(table), N.current_stream()))
+  return y, table, stats1, stats2
+
+
 def conv3x3_fp8(x: torch.Tensor, w_oihw: torch.Tensor, bias: Optional[torch.Tensor] = None, resid: Optional[torch.Tensor] = None,
                 splitk: int = 0) -> torch.Tensor:
   """3x3 / pad 1 / stride 1 conv with fp8 (e4m3) activations and weights on the fp8 MFMA (csrc/conv_fp8.hip): NHWC bf16 x

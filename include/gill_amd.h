@@ -368,6 +368,37 @@ int gill_op_layernorm(const void* x, int x_f32, const float* gamma, const float*
 int gill_op_groupnorm(const void* x1, int C1, const void* x2, int C2, int B, int HW, int groups, const float* gamma,
                       const float* beta, float eps, int silu, void* y, void* stream);
 
+/* Fused GroupNorm statistics, producer side: a GEMM / 3x3 convolution launched as the engines launch it with fused statistics, returning
+ * what it filed.  gn_stats: fp32 partial sums {sum, sum of squares} of the bf16 OUTPUT tensor in bins of `bin` channels (bin must divide
+ * Cout / N and pass the launcher's tile rules; an error otherwise), laid out [B][*nslab][Cout / bin][2]; the caller sizes the buffer for
+ * 16-row slabs (B * rows / 16 * (Cout / bin) * 2 floats, rows = output pixels per sample, a multiple of 64) and only the first
+ * B * *nslab * (Cout / bin) * 2 floats are written.  *slab_rows = rows per partial, *nslab = rows / *slab_rows.  Slab layout:
+ *   unsplit (splitk <= 1), stride-1 forms and the plain GEMM: slab j of sample b = output rows [64 j, 64 j + 64) of the sample, row-major
+ *     pixel order (*slab_rows = 64);
+ *   four-tap upsample form (ups = 1: nearest-2x upsample + conv as four 2x2-tap kernels on the SOURCE grid, one per output parity class
+ *     cls = 2 (oy % 2) + (ox % 2)): slab index = cls * (IH * IW / 64) + j, holding the output pixels (2 sy + cls / 2, 2 sx + cls % 2) of the
+ *     source pixels sy * IW + sx in [64 j, 64 j + 64) (*slab_rows = 64, *nslab = 4 IH IW / 64; IH * IW a multiple of 64);
+ *   split-K (splitk >= 2): the reducer files them, slab j = output rows [R j, R j + R) with R = *slab_rows = 64 where the reducer's grid is
+ *     large (ceil(N / block width) * ceil(M / 64) >= 1024 blocks), else 16.
+ * gill_op_conv3x3_gn_stats: 3x3 / pad 1 / stride 1 convolution of x1 (B,IH,IW,C1) [++ x2 (…,C2)], w (Cout,C1+C2,3,3) fp32, optional bias (Cout),
+ *   rowvec (B,Cout), resid (B,IH,IW,Cout) bf16; xs1 (…,CS1) [++ xs2 (…,CS2)] with w_sc (Cout,CS1+CS2) fp32: the fused 1x1 shortcut segment
+ *   (then no rowvec / resid); ups = 1: the four-tap upsample form (y (B,2IH,2IW,Cout); no rowvec / resid / shortcut).
+ * gill_op_gemm_gn_stats: C (M,N) bf16 = A (M,K) . W (N,K)^T + bias + resid (M,N), M = samples x rows_per_batch, ldc = N.
+ * Synchronise.  For the operator tests. */
+int gill_op_conv3x3_gn_stats(const void* x1, int C1, const void* x2, int C2, const float* w_oihw, const float* bias, const float* rowvec,
+                             const void* resid, const void* xs1, int CS1, const void* xs2, int CS2, const float* w_sc, void* y, float* gn_stats,
+                             int bin, int B, int IH, int IW, int Cout, int ups, int splitk, int* slab_rows, int* nslab, void* stream);
+int gill_op_gemm_gn_stats(const void* A_bf16, const void* W_bf16, const float* bias, const void* resid_bf16, void* C_bf16, float* gn_stats, int bin,
+                          int M, int N, int K, int rows_per_batch, int splitk, int* slab_rows, int* nslab, void* stream);
+/* ... consumer side: GroupNorm (+ SiLU) of x1 (B,HW,C1) [++ x2 (B,HW,C2)] from caller-supplied partials, never reading the tensors for
+ * statistics.  stats1 [B][nslab1][C1 / bin1][2] covers the channels of x1, stats2 [B][nslab2][C2 / bin2][2] those of x2 (NULL when C2 == 0);
+ * group boundaries must fall on bin boundaries of the block that holds them (an error otherwise); at most 128 bins per block; any partial
+ * counts (more than 64 go through an out-of-place totals pass; the partials themselves are never modified).  y (B,HW,C1+C2) bf16; ss_out
+ * (optional, single-source only): the scale | shift table [B][2][C1] fp32 (y = x * scale + shift) is written INSTEAD of y.  Synchronises. */
+int gill_op_groupnorm_from_stats(const void* x1, int C1, const void* x2, int C2, int B, int HW, int groups, const float* gamma, const float* beta,
+                                 float eps, int silu, const float* stats1, int bin1, int nslab1, const float* stats2, int bin2, int nslab2,
+                                 void* y, float* ss_out, void* stream);
+
 /* The feed-forward sub-block of a level-0 (C = 320) transformer block + proj_out + outer residual as one kernel (csrc/ffn.hip):
  * out = proj_out(ff2(geglu(ff1(LN(t)))) + t) + resid on natural (diffusers-layout) operands; gn_stats (optional): GroupNorm partial sums
  * of the output, [(b * rows_per_batch / 64 + slab) * 64 + bin][2], bins of 5 channels.  Replaces, inside gill_unet_forward, the

@@ -550,7 +550,9 @@ def test_layernorm(cuda, rows, C, f32):
 
 @pytest.mark.parametrize("B,H,W,C1,C2,silu", [(2, 16, 16, 320, 0, True), (2, 8, 8, 1280, 640, True),
                                                (1, 32, 32, 320, 0, False), (3, 8, 8, 640, 320, True),
-                                               (2, 64, 64, 320, 0, True)])
+                                               (2, 64, 64, 320, 0, True),
+                                               # maps that are not whole 32-pixel slabs of the statistics pass (the tiny configs' sizes)
+                                               (2, 2, 2, 320, 0, True), (1, 4, 4, 640, 320, True), (2, 10, 10, 128, 0, False)])
 def test_groupnorm(cuda, B, H, W, C1, C2, silu):
   from gill_amd import ops
   x1 = _bf(_rnd((B, H, W, C1), 50) * 2 + 3.0)   # large mean: exercises the shifted-variance path
