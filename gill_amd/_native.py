@@ -104,6 +104,12 @@ SYMBOLS: Dict[str, Tuple[object, List[object]]] = {
   "gill_vae_create": (_i, [C.POINTER(_vp), C.POINTER(gill_vae_config), C.POINTER(gill_tensor), _i]),
   "gill_vae_destroy": (None, [_vp]),
   "gill_vae_decode": (_i, [_vp, _vp, _i, _vp, _vp, _vp]),
+  "gill_vae_encode": (_i, [_vp, _vp, _i, _vp, _vp, _vp, _vp]),
+  "gill_sd_schedule_from": (_i, [_vp, _i, _i, _i, C.POINTER(C.c_float), C.POINTER(C.c_double), C.POINTER(C.c_double),
+                                 C.POINTER(C.c_double)]),
+  "gill_sd_denoise_from": (_i, [_vp, _vp, _vp, _vp, _i, _i, _vp, _vp, _i, _i, _f, _vp, _vp, _vp]),
+  "gill_op_sd_sampler_run_from": (_i, [_vp, _i, _i, _i, _f, _vp, _vp, _vp, _vp, _i, C.c_int64, _vp, _vp, _vp]),
+  "gill_op_conv3x3_ex": (_i, [_vp, _i, _vp, _i, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _vp]),
   "gill_op_conv3x3_fp8": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp]),
   "gill_pndm_schedule": (_i, [_i, C.POINTER(C.c_int32), C.POINTER(C.c_double)]),
   "gill_sd_denoise_ex": (_i, [_vp, _vp, _vp, _vp, _i, _vp, _i, _i, _f, _vp, _vp, _vp]),

@@ -95,10 +95,12 @@ extern "C" int gill_op_geglu(const void* A, const void* W, const float* bias, vo
   return 0;
 }
 
-extern "C" int gill_op_conv3x3(const void* x1, int C1, const void* x2, int C2, const float* w_oihw, const float* bias,
-                               const float* rowvec, const void* resid, void* y, int B, int IH, int IW, int Cout,
-                               int stride, int ups, int splitk, void* stream) {
+static int op_conv3x3(const void* x1, int C1, const void* x2, int C2, const float* w_oihw, const float* bias, const float* rowvec,
+                      const void* resid, void* y, int B, int IH, int IW, int Cout, int stride, int ups, int pad_shift, int splitk,
+                      void* stream) {
   hipStream_t s = (hipStream_t)stream;
+  GILL_REQUIRE(pad_shift == 0 || (pad_shift == 1 && stride == 2 && !ups && IH % 2 == 0 && IW % 2 == 0),
+               "conv3x3_ex: pad_shift is 0 or 1; 1 needs stride 2, no upsample and even IH and IW");
   const int Cin = C1 + C2;
   DevBuf wr, ws;
   GILL_TRY(wr.alloc(sizeof(bf16_t) * (size_t)Cout * 16 * Cin));     // 9 taps, or 4 classes x 4 taps
@@ -113,8 +115,9 @@ extern "C" int gill_op_conv3x3(const void* x1, int C1, const void* x2, int C2, c
   else GILL_TRY(conv_weight_relayout_launch(w_oihw, GILL_DTYPE_F32, Cout, Cin, (bf16_t*)wr.p, s));
   GemmArgs g;
   g.conv = 1;
-  g.IH = IH; g.IW = IW; g.Cin = Cin; g.stride = stride; g.ups = ups4 ? 2 : ups;
+  g.IH = IH; g.IW = IW; g.Cin = Cin; g.stride = stride; g.ups = ups4 ? 2 : ups; g.pad_shift = pad_shift;
   if (ups) { g.OH = 2 * IH; g.OW = 2 * IW; }
+  else if (pad_shift) { g.OH = IH / 2; g.OW = IW / 2; }
   else { g.OH = (IH + 2 - 3) / stride + 1; g.OW = (IW + 2 - 3) / stride + 1; }
   g.M = B * g.OH * g.OW; g.N = Cout; g.K = (ups4 ? 4 : 9) * Cin;
   g.A = (const bf16_t*)x1; g.A2 = (const bf16_t*)x2; g.K1 = C1;
@@ -131,6 +134,16 @@ extern "C" int gill_op_conv3x3(const void* x1, int C1, const void* x2, int C2, c
   for (int r = 0; r < op_repeat(); ++r) GILL_TRY(gemm_launch(g, s));
   GILL_CHECK_HIP(hipStreamSynchronize(s));
   return 0;
+}
+extern "C" int gill_op_conv3x3(const void* x1, int C1, const void* x2, int C2, const float* w_oihw, const float* bias,
+                               const float* rowvec, const void* resid, void* y, int B, int IH, int IW, int Cout,
+                               int stride, int ups, int splitk, void* stream) {
+  return op_conv3x3(x1, C1, x2, C2, w_oihw, bias, rowvec, resid, y, B, IH, IW, Cout, stride, ups, 0, splitk, stream);
+}
+extern "C" int gill_op_conv3x3_ex(const void* x1, int C1, const void* x2, int C2, const float* w_oihw, const float* bias,
+                                  const float* rowvec, const void* resid, void* y, int B, int IH, int IW, int Cout,
+                                  int stride, int ups, int pad_shift, int splitk, void* stream) {
+  return op_conv3x3(x1, C1, x2, C2, w_oihw, bias, rowvec, resid, y, B, IH, IW, Cout, stride, ups, pad_shift, splitk, stream);
 }
 
 // 3x3 convolution + the GroupNorm (+ SiLU) that consumes its output, without a GroupNorm launch of its own where the geometry allows:

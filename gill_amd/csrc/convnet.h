@@ -98,10 +98,11 @@ struct ConvRun {
     g.rows_per_batch = y.H * y.W;
   }
   // 3x3 conv (pad 1) over x1 (++ x2): stride 1|2, optional fused nearest-2x upsample; y = conv + bias + rowvec + resid
+  // pad_shift = 1 (stride 2): the window of Downsample2D(padding = 0), F.pad(x, (0, 1, 0, 1)) + conv(pad 0) — GemmArgs::pad_shift
   GemmArgs conv_args(const Tensor& x1, const Tensor* x2, const ConvW& w, int stride, int ups, const float* rowvec, int rv_bstride,
-                     const bf16_t* resid, const Tensor& y) const {
+                     const bf16_t* resid, const Tensor& y, int pad_shift = 0) const {
     GemmArgs g;
-    g.conv = 1; g.IH = x1.H; g.IW = x1.W; g.OH = y.H; g.OW = y.W; g.Cin = w.cin; g.stride = stride; g.ups = ups;
+    g.conv = 1; g.IH = x1.H; g.IW = x1.W; g.OH = y.H; g.OW = y.W; g.Cin = w.cin; g.stride = stride; g.ups = ups; g.pad_shift = pad_shift;
     g.M = Bx * y.H * y.W; g.N = w.cout; g.K = 9 * w.cin;
     g.A = x1.p; g.A2 = x2 ? x2->p : nullptr; g.K1 = x1.C;
     g.W = w.w; g.bias = w.b; g.k_chunked = w.chunked;

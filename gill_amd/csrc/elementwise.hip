@@ -537,6 +537,16 @@ int scale_f32_launch(const float* src, float scale, int64_t n, float* dst, hipSt
   return 0;
 }
 
+__global__ __launch_bounds__(256) void add_noise_f32_kernel(const float* __restrict__ x, const float* __restrict__ z, float a, float b, int64_t n,
+                                                            float* __restrict__ dst) {
+  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) dst[i] = a * x[i] + b * z[i];
+}
+int add_noise_f32_launch(const float* x, const float* z, float a, float b, int64_t n, float* dst, hipStream_t s) {
+  hipLaunchKernelGGL(add_noise_f32_kernel, dim3(grid_for(n)), dim3(256), 0, s, x, z, a, b, n, dst);
+  GILL_CHECK_HIP(hipGetLastError());
+  return 0;
+}
+
 // ---------------------------------------------------------------- weight conversion / re-layout (creation time)
 __device__ __forceinline__ float load_as_f32(const void* p, int dtype, int64_t i) {
   if (dtype == 0) return bf2f(((const bf16_t*)p)[i]);

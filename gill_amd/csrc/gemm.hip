@@ -476,7 +476,7 @@ __device__ __forceinline__ void gemm_tile(const GemmDev& d, const GemmTileCtx cx
         fl |= (ox - 1 >= 0) ? 4 : 0; fl |= (ox + 1 < p.OW) ? 8 : 0;
         fl |= (oy & 1) << 4; fl |= (ox & 1) << 5;
       } else {
-        const int cy = oy * p.stride, cx = ox * p.stride;
+        const int cy = oy * p.stride + p.pad_shift, cx = ox * p.stride + p.pad_shift;     // (pad_shift: GemmArgs — the centre moves, the flags follow)
         pc = (b * p.IH + cy) * p.IW + cx;
         fl |= (cy - 1 >= 0) ? 1 : 0; fl |= (cy + 1 < p.IH) ? 2 : 0;
         fl |= (cx - 1 >= 0) ? 4 : 0; fl |= (cx + 1 < p.IW) ? 8 : 0;
@@ -2151,6 +2151,10 @@ int gemm_launch(const GemmArgs& a, hipStream_t s) {
     GILL_REQUIRE(a.Cin / BK <= ZERO_PAGE_STEPS, "conv: Cin too large for the zero page");
     GILL_REQUIRE(a.K1 == a.Cin || a.A2 != nullptr, "conv: second source missing");
     GILL_REQUIRE(!(a.ups && a.stride != 1), "conv: upsample needs stride 1");
+    if (a.pad_shift) {
+      GILL_REQUIRE(a.pad_shift == 1 && a.stride == 2 && !a.ups && a.KX == 0, "conv: pad_shift is 0 or 1 and needs stride 2, no upsample, no fused 1x1 segment");
+      GILL_REQUIRE(a.IH % 2 == 0 && a.IW % 2 == 0 && a.OH == a.IH / 2 && a.OW == a.IW / 2, "conv: pad_shift needs even IH and IW and an output of half the size");
+    }
     GILL_REQUIRE(a.out_mode == OUT_BF16 && a.act == ACT_NONE && !a.resid_f32 && !a.row_stats,
                  "conv: bf16 row-major epilogue without activation / fp32 residual / row statistics only");
     GILL_REQUIRE((int64_t)(a.M / (a.OH * a.OW)) * a.IH * a.IW * a.Cin < (int64_t)1 << 31, "conv input too large for 32-bit offsets");

@@ -18,6 +18,10 @@ struct GemmArgs {
   int K1 = 0;                 // plain: columns taken from A (K1 == K when single source); conv: channels of A
   int conv = 0;               // 0 plain GEMM, 1 conv3x3 pad 1 over NHWC
   int IH = 0, IW = 0, OH = 0, OW = 0, Cin = 0, stride = 1, ups = 0;
+  // conv, stride 2 only: the window's origin moves one pixel down and right — output (oy, ox) reads rows 2 oy .. 2 oy + 2 and columns
+  // 2 ox .. 2 ox + 2, indices >= IH / IW read zero: diffusers' Downsample2D with padding 0, F.pad(x, (0, 1, 0, 1)) + conv(stride 2, pad 0)
+  // (the VAE encoder's downsamplers).  0: the symmetric pad-1 window.  IH, IW even; no upsample, no fused 1x1 segment.
+  int pad_shift = 0;
   // conv only: extra plain K segment appended after the 9 taps (a fused 1x1 conv of the tensor X1 ++ X2 at the same
   // pixel, i.e. ResnetBlock2D's conv_shortcut): KX channels in total, the first KX1 from X1
   const bf16_t* X1 = nullptr; const bf16_t* X2 = nullptr; int KX = 0, KX1 = 0;
@@ -344,6 +348,8 @@ int plms_step_launch(const SdLoopArgs& a, hipStream_t s);
 int sampler_step_launch(const SdLoopArgs& a, hipStream_t s);
 // dst = scale * src over n floats (latents * init_noise_sigma, custom_sd.py:472)
 int scale_f32_launch(const float* src, float scale, int64_t n, float* dst, hipStream_t s);
+// dst = a * x + b * z over n floats (the schedulers' add_noise: the first kernel of an image-to-image loop)
+int add_noise_f32_launch(const float* x, const float* z, float a, float b, int64_t n, float* dst, hipStream_t s);
 
 // weight re-layout helpers (run once at engine creation)
 int conv_weight_relayout_launch(const void* w, int dtype, int Cout, int Cin, bf16_t* out /*[Cout][9][Cin]*/, hipStream_t s);   // conv_in / conv_out

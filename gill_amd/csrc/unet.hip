@@ -1285,9 +1285,19 @@ struct SdSchedule {
   std::vector<PlmsRow> plms;          // kind 0
   std::vector<SamplerRow> rows;       // every other kind
   bool needs_noise = false;           // some row has c_n != 0
+  double add_a = 1.0, add_b = 0.0;    // the scheduler's add_noise() at the first timestep: x_start = add_a * init_latents + add_b * noise
 };
 
-static int sd_schedule(const gill_sd_sampler* sp, bool vpred, int num_steps, SdSchedule& out) {
+// start (image-to-image, include/gill_amd.h gill_sd_schedule_from): the loop begins at step `start` of the num_steps schedule.  start == 0 is the
+// text-to-image table, bit for bit.
+//   ddim, euler, euler_ancestral: the tail of the full table;
+//   dpmsolver++: the tail, its first row a first-order step (the solver's history is empty, as diffusers' scheduler starts); ring slots keep the
+//     full table's parity, so the rows that follow read the slot the rebuilt row wrote;
+//   pndm: the PLMS warm-up pair replayed at t_s: t_s, t_s - D, t_s - D, t_s - 2D, ... (num_steps - start + 1 calls).  DELIBERATELY not what
+//     diffusers 0.17's img2img does (it slices the already-duplicated list, so that from the third call on the model is evaluated one grid step
+//     ahead of the latents): this is the warm-up a fresh run on the same grid makes from t_s.  With start == num_steps - 1 the second timestep
+//     falls below the grid's end: the coefficients then use the final alpha (as every step below t = 0 does) and the model sees t = 0.
+static int sd_schedule(const gill_sd_sampler* sp, bool vpred, int num_steps, SdSchedule& out, int start = 0) {
   GILL_REQUIRE(sp != nullptr, "null sampler");
   GILL_REQUIRE(sp->kind >= SD_PNDM && sp->kind <= SD_EULER_A, "unknown sampler kind (0 pndm, 1 ddim, 2 dpmsolver++, 3 euler, 4 euler_ancestral)");
   out.kind = sp->kind;
@@ -1297,14 +1307,26 @@ static int sd_schedule(const gill_sd_sampler* sp, bool vpred, int num_steps, SdS
     GILL_REQUIRE(num_steps >= 2 && num_steps <= 1000, "num_steps out of range");
     GILL_REQUIRE(sp->steps_offset >= 0, "pndm: steps_offset must be >= 0");
     GILL_REQUIRE((num_steps - 1) * (T / num_steps) + sp->steps_offset < T, "pndm: num_steps and steps_offset put a timestep past the training range");
+    GILL_REQUIRE(start >= 0 && start < num_steps, "start must be in [0, num_steps)");
     std::vector<int> ts; int ratio;
     pndm_timesteps(num_steps, ts, &ratio, sp->steps_offset);
+    if (start > 0) {
+      // ts = [t_0, t_1, t_1, t_2, ...]: grid point k >= 1 sits at index k + 1
+      std::vector<int> tail;
+      const int ts_s = ts[start + 1];
+      tail.push_back(ts_s); tail.push_back(ts_s - ratio); tail.push_back(ts_s - ratio);
+      for (size_t k = (size_t)start + 3; k < ts.size(); ++k) tail.push_back(ts[k]);
+      tail.resize((size_t)(num_steps - start + 1));      // (start == num_steps - 1: the pair only)
+      ts.swap(tail);
+    }
     pndm_rows(ts, ratio, ac, vpred, sp->set_alpha_to_one != 0, out.plms);
     out.timesteps.resize(ts.size());
-    for (size_t i = 0; i < ts.size(); ++i) out.timesteps[i] = (float)ts[i];
+    for (size_t i = 0; i < ts.size(); ++i) out.timesteps[i] = (float)(ts[i] > 0 ? ts[i] : 0);
+    out.add_a = sqrt((double)ac[ts[0]]); out.add_b = sqrt(1.0 - (double)ac[ts[0]]);
     return 0;
   }
   GILL_REQUIRE(num_steps >= 1 && num_steps <= 1000, "num_steps out of range");
+  GILL_REQUIRE(start >= 0 && start < num_steps, "start must be in [0, num_steps)");
   const int N = num_steps;
   out.rows.assign(N, SamplerRow{-1, 0, 1.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f});
   out.timesteps.resize(N);
@@ -1324,6 +1346,7 @@ static int sd_schedule(const gill_sd_sampler* sp, bool vpred, int num_steps, SdS
       // m = eps;  x0 = (x - sqrt(1 - a_t) eps) / sqrt(a_t);  x_prev = sqrt(a_p) x0 + dir eps + sd z
       put(i, -1, 0, 1.0, vpred ? sqrt(1.0 - at) : 0.0, vpred ? sqrt(at) : 1.0, sqrt(ap / at), dir - sqrt(ap) * sqrt(1.0 - at) / sqrt(at), 0.0, sd);
       out.timesteps[i] = (float)t;
+      if (i == start) { out.add_a = sqrt(at); out.add_b = sqrt(1.0 - at); }
     }
   } else if (sp->kind == SD_DPMPP_2M) {
     GILL_REQUIRE(N <= 999, "dpmsolver++: num_steps above 999 repeats a timestep");
@@ -1338,7 +1361,7 @@ static int sd_schedule(const gill_sd_sampler* sp, bool vpred, int num_steps, SdS
       const int s0 = ts[i], t = ts[i + 1];
       const double h = lambda(t) - lambda(s0), E = exp(-h) - 1.0;
       const double p_x = vpred ? alpha(s0) : 1.0 / alpha(s0), p_e = vpred ? -sigma(s0) : -sigma(s0) / alpha(s0);   // m = x0
-      const bool first_order = i == 0 || (i == N - 1 && N < 15);    // lower_order_final
+      const bool first_order = i == start || (i == N - 1 && N < 15);    // empty history; lower_order_final (decided on the FULL schedule's length)
       double c_0 = -alpha(t) * E, c_1 = 0.0;
       if (!first_order) {
         const double r0 = (lambda(s0) - lambda(ts[i - 1])) / h;
@@ -1347,6 +1370,7 @@ static int sd_schedule(const gill_sd_sampler* sp, bool vpred, int num_steps, SdS
       }
       put(i, i & 1, (i + 1) & 1, 1.0, p_x, p_e, sigma(t) / sigma(s0), c_0, c_1, 0.0);
       out.timesteps[i] = (float)s0;
+      if (i == start) { out.add_a = alpha(s0); out.add_b = sigma(s0); }
     }
   } else {   // Euler, Euler ancestral
     std::vector<double> ls; linspace_999(N, ls);
@@ -1362,6 +1386,7 @@ static int sd_schedule(const gill_sd_sampler* sp, bool vpred, int num_steps, SdS
     }
     sg[N] = 0.0;
     out.init_noise_sigma = smax;
+    out.add_a = 1.0; out.add_b = sg[start];
     for (int i = 0; i < N; ++i) {
       const double s = sg[i], to = sg[i + 1], q = s * s + 1.0;
       // m = eps;  v-prediction: x0 = x / (s^2 + 1) - v s / sqrt(s^2 + 1), eps = (x - x0) / s
@@ -1373,6 +1398,10 @@ static int sd_schedule(const gill_sd_sampler* sp, bool vpred, int num_steps, SdS
       }
     }
   }
+  if (start > 0) {
+    out.rows.erase(out.rows.begin(), out.rows.begin() + start);
+    out.timesteps.erase(out.timesteps.begin(), out.timesteps.begin() + start);
+  }
   for (const SamplerRow& r : out.rows) {
     const float v[7] = {r.in_scale, r.p_x, r.p_e, r.c_x, r.c_0, r.c_1, r.c_n};
     for (float f : v) GILL_REQUIRE(std::isfinite(f), "sampler table: a coefficient is not finite for these arguments");
@@ -1381,10 +1410,11 @@ static int sd_schedule(const gill_sd_sampler* sp, bool vpred, int num_steps, SdS
   return 0;
 }
 
-extern "C" int gill_sd_schedule(const gill_sd_sampler* sampler, int v_prediction, int num_steps, float* timesteps_out,
-                                double* init_noise_sigma_out, double* rows_out) {
+extern "C" int gill_sd_schedule_from(const gill_sd_sampler* sampler, int v_prediction, int num_steps, int start, float* timesteps_out,
+                                     double* init_noise_sigma_out, double* rows_out, double* add_noise_out) {
   SdSchedule sc;
-  GILL_TRY(sd_schedule(sampler, v_prediction != 0, num_steps, sc));
+  GILL_TRY(sd_schedule(sampler, v_prediction != 0, num_steps, sc, start));
+  if (add_noise_out) { add_noise_out[0] = sc.add_a; add_noise_out[1] = sc.add_b; }
   const int ncalls = (int)sc.timesteps.size();
   if (timesteps_out) for (int i = 0; i < ncalls; ++i) timesteps_out[i] = sc.timesteps[i];
   if (init_noise_sigma_out) *init_noise_sigma_out = sc.init_noise_sigma;
@@ -1405,9 +1435,15 @@ extern "C" int gill_sd_schedule(const gill_sd_sampler* sampler, int v_prediction
   }
   return ncalls;
 }
+extern "C" int gill_sd_schedule(const gill_sd_sampler* sampler, int v_prediction, int num_steps, float* timesteps_out,
+                                double* init_noise_sigma_out, double* rows_out) {
+  return gill_sd_schedule_from(sampler, v_prediction, num_steps, 0, timesteps_out, init_noise_sigma_out, rows_out, nullptr);
+}
 
+// init_noise != nullptr: image-to-image — the loop starts at step `start` from add_noise(latents0, init_noise) instead of latents0 * init_noise_sigma
 static int sd_denoise_on(gill_unet* m, const gill_sd_sampler* sampler, const void* cond_bf16, const void* uncond_bf16, int n_uncond,
-                         const float* latents0, int B, int num_steps, float guidance, float* latents_out, const float* noise, hipStream_t s);
+                         const float* latents0, int B, int num_steps, float guidance, float* latents_out, const float* noise, hipStream_t s,
+                         int start = 0, const float* init_noise = nullptr);
 
 extern "C" int gill_sd_denoise_ex(gill_unet* m, const gill_sd_sampler* sampler, const void* cond_bf16, const void* uncond_bf16, int n_uncond,
                                   const float* latents0, int B, int num_steps, float guidance, float* latents_out, const float* noise,
@@ -1422,6 +1458,20 @@ extern "C" int gill_sd_denoise_ex(gill_unet* m, const gill_sd_sampler* sampler, 
   GILL_TRY(m->fence.leave(caller));
   return rc;
 }
+extern "C" int gill_sd_denoise_from(gill_unet* m, const gill_sd_sampler* sampler, const void* cond_bf16, const void* uncond_bf16, int n_uncond,
+                                    int start, const float* init_latents, const float* init_noise, int B, int num_steps, float guidance,
+                                    float* latents_out, const float* noise, void* stream) {
+  GILL_REQUIRE(m && sampler && cond_bf16 && init_latents && init_noise && latents_out, "null argument");
+  GILL_REQUIRE(guidance <= 1.0f || uncond_bf16 == nullptr || n_uncond == 1 || n_uncond == B,
+               "negative embeddings: batch must be 1 or B");
+  GILL_TRY(unet_coop_check());
+  hipStream_t caller = (hipStream_t)stream;
+  GILL_TRY(m->fence.enter(caller));
+  const int rc = sd_denoise_on(m, sampler, cond_bf16, uncond_bf16, n_uncond, init_latents, B, num_steps, guidance, latents_out, noise,
+                               m->fence.stream, start, init_noise);
+  GILL_TRY(m->fence.leave(caller));
+  return rc;
+}
 extern "C" int gill_sd_denoise(gill_unet* m, const void* cond_bf16, const void* uncond_bf16, int n_uncond, const float* latents0,
                                int B, int num_steps, float guidance, float* latents_out, void* stream) {
   const gill_sd_sampler pndm = {SD_PNDM, 1, 0, 0.f};
@@ -1429,7 +1479,8 @@ extern "C" int gill_sd_denoise(gill_unet* m, const void* cond_bf16, const void* 
 }
 
 static int sd_denoise_on(gill_unet* m, const gill_sd_sampler* sampler, const void* cond_bf16, const void* uncond_bf16, int n_uncond,
-                         const float* latents0, int B, int num_steps, float guidance, float* latents_out, const float* noise, hipStream_t s) {
+                         const float* latents0, int B, int num_steps, float guidance, float* latents_out, const float* noise, hipStream_t s,
+                         int start, const float* init_noise) {
   const bool cfg = guidance > 1.0f;     // do_classifier_free_guidance (custom_sd.py:588)
   const int Bx = cfg ? 2 * B : B;
   GILL_REQUIRE(B >= 1 && Bx <= m->cfg.max_batch, "batch exceeds the UNet handle's max_batch");
@@ -1440,7 +1491,7 @@ static int sd_denoise_on(gill_unet* m, const gill_sd_sampler* sampler, const voi
   const size_t ctx_elems = (size_t)c.ctx_len * c.cross_attention_dim;
 
   SdSchedule sched;
-  GILL_TRY(sd_schedule(sampler, c.v_prediction != 0, num_steps, sched));
+  GILL_TRY(sd_schedule(sampler, c.v_prediction != 0, num_steps, sched, start));
   const bool linear = sched.kind != SD_PNDM;
   const int ncalls = (int)sched.timesteps.size();
   GILL_REQUIRE(ncalls <= m->temb_rows_cap, "too many steps for the time-embedding scratch");
@@ -1467,7 +1518,8 @@ static int sd_denoise_on(gill_unet* m, const gill_sd_sampler* sampler, const voi
     GILL_CHECK_HIP(hipMemcpyAsync(m->ctx_full, cond_bf16, sizeof(bf16_t) * ctx_elems * B, hipMemcpyDeviceToDevice, s));
   }
   GILL_TRY(unet_ctx_cache(m, m->ctx_full, Bx, s));
-  GILL_TRY(scale_f32_launch(latents0, (float)sched.init_noise_sigma, n_lat * B, m->lat, s));    // custom_sd.py:472
+  if (init_noise) GILL_TRY(add_noise_f32_launch(latents0, init_noise, (float)sched.add_a, (float)sched.add_b, n_lat * B, m->lat, s));
+  else GILL_TRY(scale_f32_launch(latents0, (float)sched.init_noise_sigma, n_lat * B, m->lat, s));    // custom_sd.py:472
 
   // One loop step = stage kernel (latents -> UNet input, time-embedding row of the device-side step counter) + UNet forward
   // (~390 launches at ~10+ us of host time each: at small batch the GPU outruns the host) + CFG/PLMS kernel (reads its
@@ -1518,14 +1570,14 @@ static int sd_denoise_on(gill_unet* m, const gill_sd_sampler* sampler, const voi
 // ------------------------------------------------------------------------------------------------------------------
 // Operator-level entry for the loop's sampler arithmetic: the schedule, the stage and step kernels and the device-side step counter exactly as
 // sd_denoise_on drives them, the UNet replaced by the caller's model outputs.  For tests/test_samplers_gpu.py; synchronises.
-extern "C" int gill_op_sd_sampler_run(const gill_sd_sampler* sampler, int v_prediction, int num_steps, float guidance, const float* latents0,
-                                      const float* model_out, const float* noise, int B, int64_t n, float* lat_out, float* unet_in_out,
-                                      void* stream) {
+static int op_sd_sampler_run(const gill_sd_sampler* sampler, int v_prediction, int num_steps, int start, float guidance, const float* latents0,
+                             const float* init_noise, const float* model_out, const float* noise, int B, int64_t n, float* lat_out,
+                             float* unet_in_out, void* stream) {
   hipStream_t s = (hipStream_t)stream;
   GILL_REQUIRE(sampler && latents0 && model_out && lat_out && unet_in_out, "null argument");
   GILL_REQUIRE(B >= 1 && n >= 1 && (int64_t)B * n <= ((int64_t)1 << 28), "B, n out of range");
   SdSchedule sched;
-  GILL_TRY(sd_schedule(sampler, v_prediction != 0, num_steps, sched));
+  GILL_TRY(sd_schedule(sampler, v_prediction != 0, num_steps, sched, start));
   GILL_REQUIRE(!sched.needs_noise || noise != nullptr, "this sampler draws noise in its steps: a [ncalls][B][n] noise table is required");
   const bool linear = sched.kind != SD_PNDM, cfg = guidance > 1.0f;
   const int ncalls = (int)sched.timesteps.size(), Bx = cfg ? 2 * B : B;
@@ -1541,7 +1593,8 @@ extern "C" int gill_op_sd_sampler_run(const gill_sd_sampler* sampler, int v_pred
   GILL_TRY(lat.alloc(sizeof(float) * total)); GILL_TRY(lat2.alloc(sizeof(float) * total * 2));
   GILL_TRY(saved.alloc(sizeof(float) * total)); GILL_TRY(ring.alloc(sizeof(float) * total * 4));
   GILL_CHECK_HIP(hipStreamSynchronize(s));     // the host-side sources above are locals
-  GILL_TRY(scale_f32_launch(latents0, (float)sched.init_noise_sigma, (int64_t)total, (float*)lat.p, s));
+  if (init_noise) GILL_TRY(add_noise_f32_launch(latents0, init_noise, (float)sched.add_a, (float)sched.add_b, (int64_t)total, (float*)lat.p, s));
+  else GILL_TRY(scale_f32_launch(latents0, (float)sched.init_noise_sigma, (int64_t)total, (float*)lat.p, s));
   SdLoopArgs la;
   la.rows = linear ? nullptr : (const PlmsRow*)rows.p; la.ctr = (int*)ctr.p; la.temb_table = nullptr; la.temb_total = 0; la.temb_cur = nullptr;
   la.lat = (float*)lat.p; la.lat2 = (float*)lat2.p; la.cur_sample = (float*)saved.p; la.ets = (float*)ring.p;
@@ -1556,6 +1609,18 @@ extern "C" int gill_op_sd_sampler_run(const gill_sd_sampler* sampler, int v_pred
   }
   GILL_CHECK_HIP(hipStreamSynchronize(s));
   return 0;
+}
+extern "C" int gill_op_sd_sampler_run(const gill_sd_sampler* sampler, int v_prediction, int num_steps, float guidance, const float* latents0,
+                                      const float* model_out, const float* noise, int B, int64_t n, float* lat_out, float* unet_in_out,
+                                      void* stream) {
+  return op_sd_sampler_run(sampler, v_prediction, num_steps, 0, guidance, latents0, nullptr, model_out, noise, B, n, lat_out, unet_in_out, stream);
+}
+extern "C" int gill_op_sd_sampler_run_from(const gill_sd_sampler* sampler, int v_prediction, int num_steps, int start, float guidance,
+                                           const float* latents0, const float* init_noise, const float* model_out, const float* noise, int B,
+                                           int64_t n, float* lat_out, float* unet_in_out, void* stream) {
+  GILL_REQUIRE(init_noise != nullptr, "null argument");
+  return op_sd_sampler_run(sampler, v_prediction, num_steps, start, guidance, latents0, init_noise, model_out, noise, B, n, lat_out, unet_in_out,
+                           stream);
 }
 
 // ------------------------------------------------------------------------------------------------------------------

@@ -13,8 +13,37 @@
 // the nearest-2x upsample folded in, GroupNorm statistics accumulated by the producing conv's epilogue.  The single
 // 512-wide attention head does not fit the flash kernel's register budget, so it runs as two MFMA GEMMs per image
 // (S = Q K^T, O = P V) around a row-softmax kernel: 68 GFLOP per image, once per image — not a hot spot.
+//
+// The encoder half (image-to-image: AutoencoderKL.encode(image).latent_dist.sample() * scaling_factor) is the mirror image on the same
+// pieces: conv_in 3 -> ch[0] as im2col (K = 27 padded to 64) + GEMM from fp32 NCHW pixels, four down blocks of two resnets
+// ("encoder.down_blocks.{i}.resnets.{j}", the 1x1 shortcut fused into conv2) with, below the last, "downsamplers.0.conv": diffusers'
+// Downsample2D(padding = 0), F.pad(x, (0, 1, 0, 1)) + conv(stride 2, pad 0), run as the stride-2 gather with its origin shifted
+// (GemmArgs::pad_shift); the mid block (resnet, the same single-head attention, resnet); conv_norm_out + SiLU; conv_out to
+// 2 * latent_channels fp32 NCHW; and one finishing kernel for quant_conv, the mean | logvar split, the clamp and the sample.
+// It lives INSIDE gill_vae (VaeEncoder, built only when the weight table holds "encoder.conv_in.weight") with an arena and a
+// statistics pool of its own, sized by its own dry run: see DESIGN.md "VAE encoder".
 #include "convnet.h"
 #include <math.h>
+#include <memory>
+
+struct AttnW {      // the mid block's single-head attention
+  NormW gn;
+  bf16_t* wqkv = nullptr; float* bqkv = nullptr;   // [3C][C]
+  bf16_t* wo = nullptr; float* bo = nullptr;
+};
+
+// the encoder half: its weights and its own workspace (arena + GroupNorm statistics pool); the split-K workspace is the handle's
+struct VaeEncoder : ConvWorkspace {
+  bf16_t* conv_in_w = nullptr; float* conv_in_b = nullptr;   // [ch0][64] (im2col K = 27 padded to 64)
+  ResW down_res[4][2];
+  ConvW down_ds[3];
+  ResW mid_res[2];
+  AttnW attn;
+  NormW norm_out;
+  bf16_t* conv_out_w = nullptr; float* conv_out_b = nullptr; // [2 lc][9][ch3]
+  float* q_w = nullptr; float* q_b = nullptr;                // quant_conv ((2 lc) x (2 lc) + 2 lc), fp32
+  float* h_f32 = nullptr;                                    // [B][2 lc][L][L]: conv_out's output, quant_conv's input
+};
 
 struct gill_vae : ConvWorkspace {
   gill_vae_config cfg;
@@ -22,10 +51,9 @@ struct gill_vae : ConvWorkspace {
   float* pq_w = nullptr; float* pq_b = nullptr;        // post_quant_conv (4x4 + 4), fp32
   bf16_t* conv_in_w = nullptr; float* conv_in_b = nullptr;   // [C][64] (im2col K = 36 padded to 64)
   ResW mid_res[2];
-  NormW attn_gn;
-  bf16_t* attn_wqkv = nullptr; float* attn_bqkv = nullptr;   // [3C][C]
-  bf16_t* attn_wo = nullptr; float* attn_bo = nullptr;
+  AttnW attn;
   std::vector<ResW> up_res[4];
+  std::unique_ptr<VaeEncoder> enc;                     // null: decoder-only weights
   ConvW up_us[3];
   NormW norm_out;
   bf16_t* conv_out_w = nullptr; float* conv_out_b = nullptr;
@@ -45,6 +73,32 @@ __global__ __launch_bounds__(256) void vae_latent_prep_kernel(const float* __res
     float acc = b[c];
     for (int k = 0; k < C; ++k) acc += w[c * C + k] * (z[(bb * C + k) * HW + p] * inv_scale);
     out[i] = acc;
+  }
+}
+
+// Encoder finish on fp32 NCHW: moments = quant_conv(h) (per-pixel (2C)x(2C) matrix), mean | logvar = split, logvar clamped to [-30, 20],
+// z = scale * (mean + exp(0.5 logvar) * noise) — noise == nullptr: the posterior mode, z = scale * mean.  One thread per (sample, latent
+// channel, pixel) forms its mean and its logvar row.  moments (optional): [B][2C][HW] = mean | clamped logvar.
+__global__ __launch_bounds__(256) void vae_encode_finish_kernel(const float* __restrict__ h, const float* __restrict__ w, const float* __restrict__ b,
+                                                                const float* __restrict__ noise, float scale, int C, int HW, int64_t total,
+                                                                float* __restrict__ z, float* __restrict__ moments) {
+  const int C2 = 2 * C;
+  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (int64_t)gridDim.x * blockDim.x) {
+    const int p = (int)(i % HW);
+    const int c = (int)((i / HW) % C);
+    const int64_t bb = i / ((int64_t)HW * C);
+    float mean = b[c], logvar = b[C + c];
+    for (int k = 0; k < C2; ++k) {
+      const float v = h[(bb * C2 + k) * HW + p];
+      mean += w[c * C2 + k] * v;
+      logvar += w[(C + c) * C2 + k] * v;
+    }
+    logvar = fminf(fmaxf(logvar, -30.f), 20.f);
+    z[i] = noise ? scale * (mean + __expf(0.5f * logvar) * noise[i]) : scale * mean;
+    if (moments) {
+      moments[(bb * C2 + c) * HW + p] = mean;
+      moments[(bb * C2 + C + c) * HW + p] = logvar;
+    }
   }
 }
 
@@ -132,9 +186,10 @@ struct Loader {
   }
 };
 
+// One forward of either half: `ws` (ConvRun) is that half's workspace — the handle itself for the decoder, m->enc for the encoder
 struct VRun : ConvRun {
   gill_vae* m;
-  VRun(gill_vae* m, hipStream_t s, int B, bool dry) : ConvRun{m, m->cfg.norm_num_groups, s, B, dry}, m(m) {}
+  VRun(gill_vae* m, ConvWorkspace* w, hipStream_t s, int B, bool dry) : ConvRun{w, m->cfg.norm_num_groups, s, B, dry}, m(m) {}
 
   // want_stats: the producer files this tensor's GroupNorm partial sums, one bin per group
   Tensor talloc(int H, int W, int C, bool want_stats) { return tensor(H, W, C, want_stats && C % groups == 0 ? C / groups : 0); }
@@ -142,8 +197,8 @@ struct VRun : ConvRun {
   int gemm(GemmArgs& g, Tensor* ys = nullptr) {
     if (dry) return 0;
     g.splitk = gemm_pick_splitk(g.M, g.N, g.K, g.act);
-    while (g.splitk > 1 && (size_t)g.splitk * g.M * g.N > m->splitk_ws_floats) --g.splitk;
-    g.ws = m->splitk_ws;
+    while (g.splitk > 1 && (size_t)g.splitk * g.M * g.N > ws->splitk_ws_floats) --g.splitk;
+    g.ws = ws->splitk_ws;
     if (ys && ys->stats) ys->nslab = ys->H * ys->W / gemm_gn_slab_rows(g);
     return gemm_launch(g, s);
   }
@@ -152,10 +207,15 @@ struct VRun : ConvRun {
     GemmArgs g = conv_args(x, nullptr, w, 1, ups, nullptr, 0, resid, y);
     return gemm(g, &y);
   }
+  // Downsample2D(padding = 0): the stride-2 window with its origin shifted (GemmArgs::pad_shift)
+  int down(const Tensor& x, const ConvW& w, Tensor& y) {
+    GemmArgs g = conv_args(x, nullptr, w, 2, 0, nullptr, 0, nullptr, y, 1);
+    return gemm(g, &y);
+  }
   int resnet(const Tensor& x, const ResW& w, Tensor* out, bool out_stats) {
     const int H = x.H, Wd = x.W;
     *out = talloc(H, Wd, w.cout, out_stats);
-    const size_t mk = m->arena.mark();
+    const size_t mk = ws->arena.mark();
     Tensor n1 = talloc(H, Wd, w.cin, false);
     GILL_TRY(gnorm(x, w.n1, 1, n1));
     Tensor h = talloc(H, Wd, w.cout, true);
@@ -168,25 +228,25 @@ struct VRun : ConvRun {
     } else {
       GILL_TRY(conv(n2, w.c2, 0, x.p, *out));
     }
-    m->arena.release(mk);
+    ws->arena.release(mk);
     return 0;
   }
   // single-head attention over the HW tokens of a C-channel map (+ residual)
-  int attention(const Tensor& x, Tensor* out, bool out_stats) {
+  int attention(const Tensor& x, const AttnW& a, Tensor* out, bool out_stats) {
     const int C = x.C, HW = x.H * x.W, M = Bx * HW;
     *out = talloc(x.H, x.W, C, out_stats);
-    const size_t mk = m->arena.mark();
+    const size_t mk = ws->arena.mark();
     Tensor n = talloc(x.H, x.W, C, false);
-    GILL_TRY(gnorm(x, m->attn_gn, 0, n));
-    bf16_t* q = (bf16_t*)m->arena.alloc(sizeof(bf16_t) * (size_t)M * C);
-    bf16_t* k = (bf16_t*)m->arena.alloc(sizeof(bf16_t) * (size_t)M * C);
-    bf16_t* vt = (bf16_t*)m->arena.alloc(sizeof(bf16_t) * (size_t)M * C);
-    bf16_t* sc = (bf16_t*)m->arena.alloc(sizeof(bf16_t) * (size_t)HW * HW);   // scores of ONE image at a time
-    bf16_t* o = (bf16_t*)m->arena.alloc(sizeof(bf16_t) * (size_t)M * C);
+    GILL_TRY(gnorm(x, a.gn, 0, n));
+    bf16_t* q = (bf16_t*)ws->arena.alloc(sizeof(bf16_t) * (size_t)M * C);
+    bf16_t* k = (bf16_t*)ws->arena.alloc(sizeof(bf16_t) * (size_t)M * C);
+    bf16_t* vt = (bf16_t*)ws->arena.alloc(sizeof(bf16_t) * (size_t)M * C);
+    bf16_t* sc = (bf16_t*)ws->arena.alloc(sizeof(bf16_t) * (size_t)HW * HW);   // scores of ONE image at a time
+    bf16_t* o = (bf16_t*)ws->arena.alloc(sizeof(bf16_t) * (size_t)M * C);
     {
       // heads = 1, dp = C: Q and K come out plain row-major [B*HW][C], V transposed [B][C][HW]
       GemmArgs g;
-      g.M = M; g.N = 3 * C; g.K = C; g.K1 = C; g.A = n.p; g.lda = C; g.W = m->attn_wqkv; g.bias = m->attn_bqkv;
+      g.M = M; g.N = 3 * C; g.K = C; g.K1 = C; g.A = n.p; g.lda = C; g.W = a.wqkv; g.bias = a.bqkv;
       g.out_mode = OUT_QKV; g.Cq = q; g.Ck = k; g.Cvt = vt; g.heads = 1; g.dp = C; g.dpv = C; g.ntok = HW;
       g.ntok_pad_q = HW; g.ntok_pad_kv = HW; g.seg_base = 0;
       g.qscale = 1.0f / sqrtf((float)C);
@@ -207,11 +267,11 @@ struct VRun : ConvRun {
       GILL_TRY(gemm(g2));
     }
     GemmArgs g3;   // to_out + residual
-    g3.M = M; g3.N = C; g3.K = C; g3.K1 = C; g3.A = o; g3.lda = C; g3.W = m->attn_wo; g3.bias = m->attn_bo;
+    g3.M = M; g3.N = C; g3.K = C; g3.K1 = C; g3.A = o; g3.lda = C; g3.W = a.wo; g3.bias = a.bo;
     g3.resid = x.p; g3.ldr = C; g3.C = out->p; g3.ldc = C;
     fuse_stats(g3, *out);
     GILL_TRY(gemm(g3, out));
-    m->arena.release(mk);
+    ws->arena.release(mk);
     return 0;
   }
 
@@ -220,8 +280,8 @@ struct VRun : ConvRun {
     const int* ch = c.block_out_channels;
     const int L = c.latent_size;
     const int ctop = ch[3];
-    m->arena.off = 0;
-    m->gn_next = 0;
+    ws->arena.off = 0;
+    ws->gn_next = 0;
     if (!dry) {
       const int64_t total = (int64_t)Bx * c.latent_channels * L * L;
       int blocks = (int)((total + 255) / 256);
@@ -231,7 +291,7 @@ struct VRun : ConvRun {
     }
     Tensor x = talloc(L, L, ctop, true);
     {
-      bf16_t* col = (bf16_t*)m->arena.alloc(sizeof(bf16_t) * (size_t)Bx * L * L * 64);
+      bf16_t* col = (bf16_t*)ws->arena.alloc(sizeof(bf16_t) * (size_t)Bx * L * L * 64);
       if (!dry) GILL_TRY(im2col_nchw_launch(m->lat_prep, Bx, c.latent_channels, L, L, 64, col, s));
       GemmArgs g;
       g.M = Bx * L * L; g.N = ctop; g.K = 64; g.K1 = 64; g.A = col; g.lda = 64; g.W = m->conv_in_w; g.bias = m->conv_in_b;
@@ -240,7 +300,7 @@ struct VRun : ConvRun {
       GILL_TRY(gemm(g, &x));
     }
     { Tensor y; GILL_TRY(resnet(x, m->mid_res[0], &y, true)); x = y; }
-    { Tensor y; GILL_TRY(attention(x, &y, true)); x = y; }
+    { Tensor y; GILL_TRY(attention(x, m->attn, &y, true)); x = y; }
     { Tensor y; GILL_TRY(resnet(x, m->mid_res[1], &y, true)); x = y; }
     for (int i = 0; i < 4; ++i) {
       for (int j = 0; j < 3; ++j) {
@@ -261,7 +321,97 @@ struct VRun : ConvRun {
     if (!dry) GILL_TRY(conv_out_launch(n.p, m->conv_out_w, m->conv_out_b, Bx, x.C, x.H, x.W, c.out_channels, img_out_f32, s));
     return 0;
   }
+
+  // image (B,3,8L,8L) fp32 -> e->h_f32 (B,2 lc,L,L): everything in front of quant_conv
+  int encode(const float* image) {
+    VaeEncoder* e = m->enc.get();
+    const gill_vae_config& c = m->cfg;
+    const int* ch = c.block_out_channels;
+    const int side = 8 * c.latent_size;
+    ws->arena.off = 0;
+    ws->gn_next = 0;
+    Tensor x = talloc(side, side, ch[0], true);
+    {
+      const size_t mk = ws->arena.mark();
+      bf16_t* col = (bf16_t*)ws->arena.alloc(sizeof(bf16_t) * (size_t)Bx * side * side * 64);
+      if (!dry) GILL_TRY(im2col_nchw_launch(image, Bx, c.out_channels, side, side, 64, col, s));
+      GemmArgs g;
+      g.M = Bx * side * side; g.N = ch[0]; g.K = 64; g.K1 = 64; g.A = col; g.lda = 64; g.W = e->conv_in_w; g.bias = e->conv_in_b;
+      g.C = x.p; g.ldc = ch[0];
+      fuse_stats(g, x);
+      GILL_TRY(gemm(g, &x));
+      ws->arena.release(mk);
+    }
+    for (int i = 0; i < 4; ++i) {
+      for (int j = 0; j < 2; ++j) {
+        Tensor y;
+        // the output feeds the next resnet's norm1 (or the mid block's), except in front of a downsampling conv
+        GILL_TRY(resnet(x, e->down_res[i][j], &y, !(j == 1 && i < 3)));
+        x = y;
+      }
+      if (i < 3) {
+        Tensor y = talloc(x.H / 2, x.W / 2, x.C, true);
+        GILL_TRY(down(x, e->down_ds[i], y));
+        x = y;
+      }
+    }
+    { Tensor y; GILL_TRY(resnet(x, e->mid_res[0], &y, true)); x = y; }
+    { Tensor y; GILL_TRY(attention(x, e->attn, &y, true)); x = y; }
+    { Tensor y; GILL_TRY(resnet(x, e->mid_res[1], &y, true)); x = y; }
+    Tensor n = talloc(x.H, x.W, x.C, false);
+    GILL_TRY(gnorm(x, e->norm_out, 1, n));
+    if (!dry) GILL_TRY(conv_out_launch(n.p, e->conv_out_w, e->conv_out_b, Bx, x.C, x.H, x.W, 2 * c.latent_channels, e->h_f32, s));
+    return 0;
+  }
 };
+
+int load_attn(Loader& L, DevPool& pool, const std::string& a, int C, AttnW* w) {
+  GILL_TRY(load_norm(L.wt, pool, L.s, a + ".group_norm", C, &w->gn));
+  GILL_TRY(pool.alloc(&w->wqkv, (size_t)3 * C * C, false));
+  GILL_TRY(pool.alloc(&w->bqkv, (size_t)3 * C, false));
+  GILL_TRY(pool.alloc(&w->wo, (size_t)C * C, false));
+  GILL_TRY(pool.alloc(&w->bo, (size_t)C, false));
+  GILL_TRY(L.attn_lin(a, "to_q", "query", C, w->wqkv, w->bqkv));
+  GILL_TRY(L.attn_lin(a, "to_k", "key", C, w->wqkv + (size_t)C * C, w->bqkv + C));
+  GILL_TRY(L.attn_lin(a, "to_v", "value", C, w->wqkv + (size_t)2 * C * C, w->bqkv + 2 * C));
+  return L.attn_lin(a, "to_out.0", "proj_attn", C, w->wo, w->bo);
+}
+
+// the encoder half of a handle whose decoder half (and split-K workspace) is already built
+int build_encoder(gill_vae* m, Loader& L) {
+  const gill_vae_config& c = m->cfg;
+  const int* ch = c.block_out_channels;
+  const int lc = c.latent_channels;
+  GILL_REQUIRE(c.out_channels * 9 <= 64 && 2 * lc <= 8, "vae encoder: image / latent channel counts too large");
+  GILL_REQUIRE(c.latent_size % 8 == 0, "vae encoder: latent_size must be a multiple of 8");
+  m->enc.reset(new VaeEncoder());
+  VaeEncoder* e = m->enc.get();
+  DevPool& pool = m->pool;
+  GILL_TRY(load_conv_in_im2col(L.wt, pool, L.s, "encoder.conv_in", c.out_channels, ch[0], &e->conv_in_w, &e->conv_in_b));
+  for (int i = 0; i < 4; ++i) {
+    const std::string b = "encoder.down_blocks." + std::to_string(i);
+    for (int j = 0; j < 2; ++j)
+      GILL_TRY(L.resnet(b + ".resnets." + std::to_string(j), (j == 0 && i > 0) ? ch[i - 1] : ch[i], ch[i], &e->down_res[i][j]));
+    if (i < 3) GILL_TRY(load_conv3(L.wt, pool, L.s, b + ".downsamplers.0.conv", ch[i], ch[i], 0, &e->down_ds[i]));
+  }
+  GILL_TRY(L.resnet("encoder.mid_block.resnets.0", ch[3], ch[3], &e->mid_res[0]));
+  GILL_TRY(L.resnet("encoder.mid_block.resnets.1", ch[3], ch[3], &e->mid_res[1]));
+  GILL_TRY(load_attn(L, pool, "encoder.mid_block.attentions.0", ch[3], &e->attn));
+  GILL_TRY(load_norm(L.wt, pool, L.s, "encoder.conv_norm_out", ch[3], &e->norm_out));
+  GILL_TRY(load_conv_out(L.wt, pool, L.s, "encoder.conv_out", ch[3], 2 * lc, &e->conv_out_w, &e->conv_out_b));
+  GILL_TRY(load_f32(L.wt, pool, "quant_conv.weight", (int64_t)4 * lc * lc, &e->q_w, L.s));
+  GILL_TRY(load_f32(L.wt, pool, "quant_conv.bias", 2 * lc, &e->q_b, L.s));
+  // its own arena and statistics pool, sized by its own dry run; the split-K workspace is shared with the decoder half (one call at a time)
+  e->splitk_ws = m->splitk_ws; e->splitk_ws_floats = m->splitk_ws_floats;
+  e->arena.dry = true; e->arena.off = 0; e->arena.high = 0;
+  VRun r{m, e, nullptr, c.max_batch, true};
+  GILL_TRY(r.encode(nullptr));
+  GILL_TRY(pool.alloc(&e->arena_mem, e->arena.high + (1 << 20), true));
+  e->arena.base = e->arena_mem; e->arena.cap = e->arena.high + (1 << 20); e->arena.dry = false;
+  e->gn_floats = e->gn_next + 64;
+  GILL_TRY(pool.alloc(&e->gn_stats, e->gn_floats));
+  return pool.alloc(&e->h_f32, (size_t)c.max_batch * 2 * lc * c.latent_size * c.latent_size);
+}
 
 }  // namespace
 
@@ -285,18 +435,7 @@ extern "C" int gill_vae_create(gill_vae** out, const gill_vae_config* cfg, const
   if ((rc = load_conv_in_im2col(wt, m->pool, s, "decoder.conv_in", lc, ctop, &m->conv_in_w, &m->conv_in_b))) return fail(rc);
   if ((rc = L.resnet("decoder.mid_block.resnets.0", ctop, ctop, &m->mid_res[0]))) return fail(rc);
   if ((rc = L.resnet("decoder.mid_block.resnets.1", ctop, ctop, &m->mid_res[1]))) return fail(rc);
-  {
-    const std::string a = "decoder.mid_block.attentions.0";
-    if ((rc = load_norm(wt, m->pool, s, a + ".group_norm", ctop, &m->attn_gn))) return fail(rc);
-    if ((rc = m->pool.alloc(&m->attn_wqkv, (size_t)3 * ctop * ctop, false))) return fail(rc);
-    if ((rc = m->pool.alloc(&m->attn_bqkv, (size_t)3 * ctop, false))) return fail(rc);
-    if ((rc = m->pool.alloc(&m->attn_wo, (size_t)ctop * ctop, false))) return fail(rc);
-    if ((rc = m->pool.alloc(&m->attn_bo, (size_t)ctop, false))) return fail(rc);
-    if ((rc = L.attn_lin(a, "to_q", "query", ctop, m->attn_wqkv, m->attn_bqkv))) return fail(rc);
-    if ((rc = L.attn_lin(a, "to_k", "key", ctop, m->attn_wqkv + (size_t)ctop * ctop, m->attn_bqkv + ctop))) return fail(rc);
-    if ((rc = L.attn_lin(a, "to_v", "value", ctop, m->attn_wqkv + (size_t)2 * ctop * ctop, m->attn_bqkv + 2 * ctop))) return fail(rc);
-    if ((rc = L.attn_lin(a, "to_out.0", "proj_attn", ctop, m->attn_wo, m->attn_bo))) return fail(rc);
-  }
+  if ((rc = load_attn(L, m->pool, "decoder.mid_block.attentions.0", ctop, &m->attn))) return fail(rc);
   // up blocks walk the channel list backwards: [512, 512, 256, 128]
   int prev = ctop;
   for (int i = 0; i < 4; ++i) {
@@ -316,7 +455,7 @@ extern "C" int gill_vae_create(gill_vae** out, const gill_vae_config* cfg, const
   // workspace: dry run sizes the arena and counts the GroupNorm slots
   const int B = cfg->max_batch, Lz = cfg->latent_size;
   m->arena.dry = true; m->arena.off = 0; m->arena.high = 0;
-  VRun r{m, nullptr, B, true};
+  VRun r{m, m, nullptr, B, true};
   if ((rc = r.decode(nullptr, nullptr))) return fail(rc);
   if ((rc = m->pool.alloc(&m->arena_mem, m->arena.high + (1 << 20), true))) return fail(rc);
   m->arena.base = m->arena_mem; m->arena.cap = m->arena.high + (1 << 20); m->arena.dry = false;
@@ -326,6 +465,8 @@ extern "C" int gill_vae_create(gill_vae** out, const gill_vae_config* cfg, const
   if ((rc = m->pool.alloc(&m->splitk_ws, m->splitk_ws_floats, false))) return fail(rc);
   if ((rc = m->pool.alloc(&m->lat_prep, (size_t)B * cfg->latent_channels * Lz * Lz))) return fail(rc);
   if ((rc = m->pool.alloc(&m->img_f32, (size_t)B * cfg->out_channels * 64 * Lz * Lz))) return fail(rc);
+  if (wt.find("encoder.conv_in.weight"))
+    if ((rc = build_encoder(m, L))) return fail(rc);
   if (hipDeviceSynchronize() != hipSuccess) { gill_set_error("vae create: device sync failed"); return fail(-1); }
   *out = m;
   return 0;
@@ -338,7 +479,7 @@ extern "C" int gill_vae_decode(gill_vae* m, const float* latents, int B, float* 
   GILL_REQUIRE(B >= 1 && B <= m->cfg.max_batch, "batch exceeds the VAE handle's max_batch");
   hipStream_t s = (hipStream_t)stream;
   float* img = image_f32 ? image_f32 : m->img_f32;
-  VRun r{m, s, B, false};
+  VRun r{m, m, s, B, false};
   GILL_TRY(r.decode(latents, img));
   if (image_u8) {
     const int side = 8 * m->cfg.latent_size;
@@ -348,5 +489,21 @@ extern "C" int gill_vae_decode(gill_vae* m, const float* latents, int B, float* 
     hipLaunchKernelGGL(vae_to_uint8_kernel, dim3(blocks), dim3(256), 0, s, img, m->cfg.out_channels, side * side, total, image_u8);
     GILL_CHECK_HIP(hipGetLastError());
   }
+  return 0;
+}
+
+extern "C" int gill_vae_encode(gill_vae* m, const float* image, int B, const float* noise, float* latents_out, float* moments_out, void* stream) {
+  GILL_REQUIRE(m && image && latents_out, "null argument");
+  GILL_REQUIRE(m->enc != nullptr, "this VAE handle was built without encoder weights (encoder.* / quant_conv.*)");
+  GILL_REQUIRE(B >= 1 && B <= m->cfg.max_batch, "batch exceeds the VAE handle's max_batch");
+  hipStream_t s = (hipStream_t)stream;
+  VRun r{m, m->enc.get(), s, B, false};
+  GILL_TRY(r.encode(image));
+  const gill_vae_config& c = m->cfg;
+  const int hw = c.latent_size * c.latent_size;
+  const int64_t total = (int64_t)B * c.latent_channels * hw;
+  hipLaunchKernelGGL(vae_encode_finish_kernel, dim3((int)((total + 255) / 256)), dim3(256), 0, s, m->enc->h_f32, m->enc->q_w, m->enc->q_b, noise,
+                     c.scaling_factor, c.latent_channels, hw, total, latents_out, moments_out);
+  GILL_CHECK_HIP(hipGetLastError());
   return 0;
 }

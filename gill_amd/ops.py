@@ -67,8 +67,9 @@ def geglu(a: torch.Tensor, w: torch.Tensor, bias: Optional[torch.Tensor]) -> tor
 
 def conv3x3(x1: torch.Tensor, w_oihw: torch.Tensor, bias: Optional[torch.Tensor] = None, x2: Optional[torch.Tensor] = None,
             rowvec: Optional[torch.Tensor] = None, resid: Optional[torch.Tensor] = None, stride: int = 1,
-            upsample: bool = False, splitk: int = 0) -> torch.Tensor:
-  """3x3 / pad 1 conv over NHWC bf16 x1 (B,H,W,C1) [channel-concat x2], weights OIHW fp32 -> NHWC bf16."""
+            upsample: bool = False, splitk: int = 0, pad_shift: Optional[int] = None) -> torch.Tensor:
+  """3x3 / pad 1 conv over NHWC bf16 x1 (B,H,W,C1) [channel-concat x2], weights OIHW fp32 -> NHWC bf16.
+  pad_shift (None: gill_op_conv3x3; 0 | 1: gill_op_conv3x3_ex): 1 with stride 2 is F.pad(x, (0, 1, 0, 1)) + conv(stride 2, pad 0)."""
   x1 = _bf(x1)
   B, IH, IW, C1 = x1.shape
   C2 = 0
@@ -82,6 +83,8 @@ def conv3x3(x1: torch.Tensor, w_oihw: torch.Tensor, bias: Optional[torch.Tensor]
     OH, OW = 2 * IH, 2 * IW
   else:
     OH, OW = (IH + 2 - 3) // stride + 1, (IW + 2 - 3) // stride + 1
+  if pad_shift:
+    OH, OW = IH // 2, IW // 2
   y = torch.empty((B, OH, OW, Cout), device=x1.device, dtype=torch.bfloat16)
   if bias is not None:
     bias = bias.float().contiguous()
@@ -89,9 +92,18 @@ def conv3x3(x1: torch.Tensor, w_oihw: torch.Tensor, bias: Optional[torch.Tensor]
     rowvec = rowvec.float().contiguous()
   if resid is not None:
     resid = _bf(resid)
+  if pad_shift is not None:
+    N.check(N.lib().gill_op_conv3x3_ex(N.ptr(x1), C1, N.ptr(x2), C2, N.ptr(w), N.ptr(bias), N.ptr(rowvec), N.ptr(resid),
+                                       N.ptr(y), B, IH, IW, Cout, stride, int(upsample), int(pad_shift), splitk, N.current_stream()))
+    return y
   N.check(N.lib().gill_op_conv3x3(N.ptr(x1), C1, N.ptr(x2), C2, N.ptr(w), N.ptr(bias), N.ptr(rowvec), N.ptr(resid),
                                   N.ptr(y), B, IH, IW, Cout, stride, int(upsample), splitk, N.current_stream()))
   return y
+
+
+def conv3x3_ex(x1: torch.Tensor, w_oihw: torch.Tensor, pad_shift: int, **kw) -> torch.Tensor:
+  """gill_op_conv3x3_ex: conv3x3 with the gather's origin shift stated."""
+  return conv3x3(x1, w_oihw, pad_shift=int(pad_shift), **kw)
 
 
 def conv3x3_gn(x: torch.Tensor, w_oihw: torch.Tensor, bias: Optional[torch.Tensor], gamma: torch.Tensor, beta: torch.Tensor,
@@ -447,4 +459,30 @@ def sd_sampler_run(sampler, v_prediction: bool, num_steps: int, guidance: float,
   uin = torch.empty_like(lat)
   N.check(N.lib().gill_op_sd_sampler_run(C.byref(sp), int(bool(v_prediction)), int(num_steps), float(guidance), N.ptr(lat0), N.ptr(mo),
                                          None if z is None else N.ptr(z), B, n, N.ptr(lat), N.ptr(uin), N.current_stream()))
+  return lat, uin
+
+
+def sd_sampler_run_from(sampler, v_prediction: bool, num_steps: int, start: int, guidance: float, latents0: torch.Tensor,
+                        init_noise: torch.Tensor, model_out: torch.Tensor, noise: Optional[torch.Tensor] = None, eta: float = 0.0):
+  """sd_sampler_run from step `start` of the schedule (gill_op_sd_sampler_run_from): the loop begins at a * latents0 + b * init_noise, (a, b)
+  the add-noise pair of gill_sd_schedule_from; model_out / noise have one row per call of THAT table."""
+  import ctypes as C
+  from .sd import as_sampler_config
+  sp = as_sampler_config(sampler).native(eta)
+  B, n = latents0.shape
+  ncalls = N.lib().gill_sd_schedule_from(C.byref(sp), int(bool(v_prediction)), int(num_steps), int(start), None, None, None, None)
+  if ncalls < 0:
+    N.check(ncalls)
+  Bx = 2 * B if guidance > 1.0 else B
+  if tuple(model_out.shape) != (ncalls, Bx, n) or (noise is not None and tuple(noise.shape) != (ncalls, B, n)):
+    raise ValueError(f"model_out must be {(ncalls, Bx, n)} and noise {(ncalls, B, n)}")
+  if tuple(init_noise.shape) != (B, n):
+    raise ValueError(f"init_noise must be {(B, n)}")
+  lat0, z0, mo = latents0.float().contiguous(), init_noise.float().contiguous(), model_out.float().contiguous()
+  z = None if noise is None else noise.float().contiguous()
+  lat = torch.empty((ncalls, B, n), device=lat0.device, dtype=torch.float32)
+  uin = torch.empty_like(lat)
+  N.check(N.lib().gill_op_sd_sampler_run_from(C.byref(sp), int(bool(v_prediction)), int(num_steps), int(start), float(guidance), N.ptr(lat0),
+                                              N.ptr(z0), N.ptr(mo), None if z is None else N.ptr(z), B, n, N.ptr(lat), N.ptr(uin),
+                                              N.current_stream()))
   return lat, uin

@@ -62,16 +62,26 @@ class SamplerConfig:
     return N.gill_sd_sampler(kind=SAMPLER_KINDS.index(self.kind), steps_offset=int(self.steps_offset),
                              set_alpha_to_one=int(bool(self.set_alpha_to_one)), eta=float(eta) if self.kind == "ddim" else 0.0)
 
-  def schedule(self, num_steps: int, v_prediction: bool = False, eta: float = 0.0):
-    """(timesteps [ncalls] float32, init_noise_sigma, rows [ncalls][12] float64 in the layout of include/gill_amd.h) — host only."""
+  def schedule(self, num_steps: int, v_prediction: bool = False, eta: float = 0.0, start: int = 0):
+    """(timesteps [ncalls] float32, init_noise_sigma, rows [ncalls][12] float64 in the layout of include/gill_amd.h) — host only.
+    start > 0: the table of an image-to-image loop that begins at sampler step `start` (gill_sd_schedule_from)."""
+    ts, sig, rows, _ = self._schedule_from(num_steps, v_prediction, eta, start)
+    return ts, sig, rows
+
+  def add_noise_pair(self, num_steps: int, start: int, v_prediction: bool = False, eta: float = 0.0):
+    """(a, b) of x_start = a * init_latents + b * noise at the first timestep of the loop that begins at step `start`."""
+    return self._schedule_from(num_steps, v_prediction, eta, start)[3]
+
+  def _schedule_from(self, num_steps, v_prediction, eta, start):
     cap = int(num_steps) + 1 if num_steps >= 1 else 1
     ts, sig, rows = (C.c_float * cap)(), C.c_double(), (C.c_double * (cap * N.SD_ROW_DOUBLES))()
+    ab = (C.c_double * 2)()
     sp = self.native(eta)
-    n = N.lib().gill_sd_schedule(C.byref(sp), int(bool(v_prediction)), int(num_steps), ts, C.byref(sig), rows)
+    n = N.lib().gill_sd_schedule_from(C.byref(sp), int(bool(v_prediction)), int(num_steps), int(start), ts, C.byref(sig), rows, ab)
     if n < 0:
       N.check(n)
     return (torch.tensor(list(ts)[:n], dtype=torch.float32), float(sig.value),
-            torch.tensor(list(rows)[:n * N.SD_ROW_DOUBLES], dtype=torch.float64).reshape(n, N.SD_ROW_DOUBLES))
+            torch.tensor(list(rows)[:n * N.SD_ROW_DOUBLES], dtype=torch.float64).reshape(n, N.SD_ROW_DOUBLES), (float(ab[0]), float(ab[1])))
 
 
 def as_sampler_config(scheduler: Union[None, str, SamplerConfig]) -> SamplerConfig:
@@ -176,14 +186,16 @@ class GillSDPipeline:
     return self
 
   def load_vae(self, vae_state: Dict[str, torch.Tensor], vae_cfg: VAEConfig) -> None:
-    """AutoencoderKL decoder half (state-dict keys post_quant_conv.* / decoder.*) -> gill_vae handle."""
+    """AutoencoderKL (state-dict keys post_quant_conv.* / decoder.*, and encoder.* / quant_conv.* when present: the encoder half
+    is built only then — image-to-image needs it) -> gill_vae handle."""
     v = N.gill_vae_config(latent_channels=vae_cfg.latent_channels, out_channels=vae_cfg.out_channels,
                           layers_per_block=vae_cfg.layers_per_block, norm_num_groups=vae_cfg.norm_num_groups,
                           latent_size=vae_cfg.latent_size, scaling_factor=vae_cfg.scaling_factor,
                           max_batch=max(1, self.max_batch // 2))
     for i in range(4):
       v.block_out_channels[i] = vae_cfg.block_out_channels[i]
-    dec = {k: t for k, t in vae_state.items() if k.startswith("decoder.") or k.startswith("post_quant_conv.")}
+    dec = {k: t for k, t in vae_state.items() if k.startswith(("decoder.", "post_quant_conv.", "encoder.", "quant_conv."))}
+    self._vae_has_encoder = "encoder.conv_in.weight" in dec
     arr, keep = N.make_tensor_table(dec, self.device)
     h = C.c_void_p()
     with torch.cuda.device(self.device):
@@ -209,6 +221,58 @@ class GillSDPipeline:
         N.check(N.lib().gill_vae_decode(self._vae, N.ptr(lat[i:i + b]), b, None if f32 is None else N.ptr(f32[i:i + b]),
                                         None if u8 is None else N.ptr(u8[i:i + b]), N.current_stream()))
     return (f32, u8) if both else (u8 if as_uint8 else f32)
+
+  def encode_image(self, image, generator=None, sample: bool = True) -> torch.Tensor:
+    """vae.encode(image).latent_dist.sample(generator) * scaling_factor (sample=False: the posterior mode) on the device
+    (gill_vae_encode: csrc/vae.hip): image in any form `preprocess_image` takes -> latents (B,4,L,L) fp32.  The posterior noise is drawn on
+    the CPU generator(s) like every other draw of this pipeline."""
+    if self._vae is None or not getattr(self, "_vae_has_encoder", False):
+      raise N.GillNativeError("this pipeline was built without VAE encoder weights (encoder.* / quant_conv.* in vae_state= / from_pretrained)")
+    img = self.preprocess_image(image).to(self.device).contiguous()
+    B, L, lc = img.shape[0], self.vae_cfg.latent_size, self.vae_cfg.latent_channels
+    noise = self._randn((B, lc, L, L), generator).to(self.device).contiguous() if sample else None
+    out = torch.empty((B, lc, L, L), device=self.device, dtype=torch.float32)
+    cap = max(1, self.max_batch // 2)
+    with torch.cuda.device(self.device):
+      for i in range(0, B, cap):
+        b = min(cap, B - i)
+        N.check(N.lib().gill_vae_encode(self._vae, N.ptr(img[i:i + b]), b, None if noise is None else N.ptr(noise[i:i + b]),
+                                        N.ptr(out[i:i + b]), None, N.current_stream()))
+    return out
+
+  def preprocess_image(self, image) -> torch.Tensor:
+    """A PIL image, a list of them, a (B,H,W,3) array in [0,1] or a (B,3,H,W) tensor in [-1,1] -> (B,3,8L,8L) fp32 in [-1,1] on the
+    host (plumbing).  The handle is built for one size: anything else raises, as `height=` does."""
+    import numpy as np
+    side = 8 * self.cfg.sample_size
+    if isinstance(image, torch.Tensor):
+      t = image.detach().to("cpu", torch.float32)
+      if t.dim() == 3:
+        t = t[None]
+    else:
+      if not isinstance(image, (list, tuple, np.ndarray)):
+        image = [image]
+      if not isinstance(image, np.ndarray):
+        image = np.stack([np.asarray(im.convert("RGB"), dtype=np.float32) / 255.0 if hasattr(im, "convert") else np.asarray(im, dtype=np.float32)
+                          for im in image], 0)
+      if image.ndim == 3:
+        image = image[None]
+      t = torch.from_numpy(np.ascontiguousarray(image, dtype=np.float32)).permute(0, 3, 1, 2) * 2.0 - 1.0
+    if t.dim() != 4 or t.shape[1] != 3 or t.shape[2] != side or t.shape[3] != side:
+      raise ValueError(f"this handle was built for {side}x{side} images, got an image batch of shape {tuple(t.shape)}")
+    return t.contiguous()
+
+  @staticmethod
+  def _randn(shape, generator=None) -> torch.Tensor:
+    """One unit-variance draw of `shape` (batch first) from the CPU generator, or one sample from each generator of a list."""
+    if isinstance(generator, list):
+      if len(generator) != shape[0]:
+        raise ValueError(f"You have passed a list of generators of length {len(generator)}, but requested an effective batch"
+                         f" size of {shape[0]}. Make sure the batch size matches the length of the generators.")
+      return torch.cat([torch.randn((1,) + tuple(shape[1:]), generator=g, device=g.device if g is not None else "cpu", dtype=torch.float32).cpu()
+                        for g in generator], 0)
+    gdev = generator.device if generator is not None else torch.device("cpu")
+    return torch.randn(tuple(shape), generator=generator, device=gdev, dtype=torch.float32).cpu()
 
   # ---- construction from a local diffusers directory (no diffusers import: safetensors + json only)
   @classmethod
@@ -389,8 +453,22 @@ class GillSDPipeline:
                negative_prompt=None, num_images_per_prompt: int = 1, eta: float = 0.0, generator=None,
                latents: Optional[torch.Tensor] = None, prompt_embeds: Optional[torch.Tensor] = None,
                negative_prompt_embeds: Optional[torch.Tensor] = None, output_type: Optional[str] = None, return_dict: bool = True,
-               return_prompts_only: bool = False, scheduler: Union[None, str, SamplerConfig] = None, **_ignored):
-    """scheduler: this call's sampler instead of `self.scheduler`.  eta reaches DDIM only (custom_sd.py:395-403)."""
+               return_prompts_only: bool = False, scheduler: Union[None, str, SamplerConfig] = None, image=None, strength: float = 0.8,
+               **_ignored):
+    """scheduler: this call's sampler instead of `self.scheduler`.  eta reaches DDIM only (custom_sd.py:395-403).
+    image= / strength=: image-to-image (diffusers' StableDiffusionImg2ImgPipeline): the image is encoded by the VAE encoder, noised to the
+    timestep of step `num_inference_steps - min(int(num_inference_steps * strength), num_inference_steps)` and denoised from there
+    (gill_sd_denoise_from).  Draw order on the generator(s): posterior noise, add-noise noise, step noise."""
+    if image is not None:
+      if latents is not None:
+        raise ValueError("Cannot forward both `image` and `latents`: image-to-image starts from the encoded image.")
+      if not (0.0 <= float(strength) <= 1.0):
+        raise ValueError(f"The value of strength should in [0.0, 1.0] but is {strength}")
+      init_timestep = min(int(num_inference_steps * strength), int(num_inference_steps))
+      if init_timestep < 1:
+        raise ValueError(f"strength {strength} with {num_inference_steps} steps leaves no step to run")
+      if self._vae is None or not getattr(self, "_vae_has_encoder", False):
+        raise N.GillNativeError("image= needs the VAE encoder weights (encoder.* / quant_conv.* in vae_state= / from_pretrained)")
     text = getattr(self, "text_encoder", None) is not None
     if prompt is not None and not text:
       raise ValueError("GillSDPipeline is driven by prompt_embeds (gill/models.py:730); text prompts need the CLIP text "
@@ -451,14 +529,32 @@ class GillSDPipeline:
                          f"{tuple(negative_prompt_embeds.shape)} for prompt_embeds {tuple(prompt_embeds.shape)}")
     sampler = self.scheduler if scheduler is None else as_sampler_config(scheduler)
     _, _, rows = sampler.schedule(int(num_inference_steps), self.cfg.prediction_type == "v_prediction", eta)   # (raises on bad arguments)
-    lat0 = self.prepare_latents(B, generator, latents)
-    noise = self._step_noise(rows.shape[0], B, generator) if bool((rows[:, 11] != 0).any()) else None
-    out = torch.empty_like(lat0)
     sp = sampler.native(eta)
-    with torch.cuda.device(self.device):
-      N.check(N.lib().gill_sd_denoise_ex(self._h, C.byref(sp), N.ptr(cond), N.ptr(uncond), int(uncond.shape[0]), N.ptr(lat0), B,
-                                         int(num_inference_steps), float(guidance_scale), N.ptr(out),
-                                         None if noise is None else N.ptr(noise), N.current_stream()))
+    if image is not None:
+      start = int(num_inference_steps) - init_timestep
+      _, _, rows = sampler.schedule(int(num_inference_steps), self.cfg.prediction_type == "v_prediction", eta, start=start)
+      img = self.preprocess_image(image)
+      if img.shape[0] != B:
+        if B % img.shape[0] != 0:
+          raise ValueError(f"Cannot duplicate `image` of batch size {img.shape[0]} to {B} text prompts.")
+        img = img.repeat(B // img.shape[0], 1, 1, 1)
+      x0 = self.encode_image(img, generator)                     # draw 1: the posterior's noise
+      L = self.cfg.sample_size
+      z0 = self._randn((B, self.cfg.in_channels, L, L), generator).to(self.device).contiguous()      # draw 2: add_noise
+      noise = self._step_noise(rows.shape[0], B, generator) if bool((rows[:, 11] != 0).any()) else None    # draw 3
+      out = torch.empty_like(x0)
+      with torch.cuda.device(self.device):
+        N.check(N.lib().gill_sd_denoise_from(self._h, C.byref(sp), N.ptr(cond), N.ptr(uncond), int(uncond.shape[0]), start, N.ptr(x0),
+                                             N.ptr(z0), B, int(num_inference_steps), float(guidance_scale), N.ptr(out),
+                                             None if noise is None else N.ptr(noise), N.current_stream()))
+    else:
+      lat0 = self.prepare_latents(B, generator, latents)
+      noise = self._step_noise(rows.shape[0], B, generator) if bool((rows[:, 11] != 0).any()) else None
+      out = torch.empty_like(lat0)
+      with torch.cuda.device(self.device):
+        N.check(N.lib().gill_sd_denoise_ex(self._h, C.byref(sp), N.ptr(cond), N.ptr(uncond), int(uncond.shape[0]), N.ptr(lat0), B,
+                                           int(num_inference_steps), float(guidance_scale), N.ptr(out),
+                                           None if noise is None else N.ptr(noise), N.current_stream()))
     has_nsfw = None
     if output_type in ("pil", "np"):      # custom_sd.py:654-661: decode_latents -> run_safety_checker -> numpy_to_pil
       from PIL import Image

@@ -392,6 +392,42 @@ def vae_decoder_state_dict(cfg: VAEConfig, seed: int = 0) -> Dict[str, torch.Ten
   return sd
 
 
+def vae_encoder_state_dict(cfg: VAEConfig, seed: int = 0) -> Dict[str, torch.Tensor]:
+  """diffusers AutoencoderKL keys needed by encode(): encoder.* and quant_conv.*"""
+  sd: Dict[str, torch.Tensor] = {}
+  ch = cfg.block_out_channels
+
+  def conv(p, cout, cin, k=3):
+    sd[p + ".weight"] = _matrix(p + ".weight", (cout, cin, k, k), seed)
+    sd[p + ".bias"] = _bias(p + ".bias", cout, seed)
+
+  def resnet(p, cin, cout):
+    _norm(sd, p + ".norm1", cin, seed)
+    conv(p + ".conv1", cout, cin)
+    _norm(sd, p + ".norm2", cout, seed)
+    conv(p + ".conv2", cout, cout)
+    if cin != cout:
+      conv(p + ".conv_shortcut", cout, cin, 1)
+
+  conv("encoder.conv_in", ch[0], cfg.out_channels)
+  for i in range(4):
+    for j in range(2):
+      resnet(f"encoder.down_blocks.{i}.resnets.{j}", ch[i - 1] if (j == 0 and i > 0) else ch[i], ch[i])
+    if i < 3:
+      conv(f"encoder.down_blocks.{i}.downsamplers.0.conv", ch[i], ch[i])
+  top = ch[3]
+  resnet("encoder.mid_block.resnets.0", top, top)
+  a = "encoder.mid_block.attentions.0"
+  _norm(sd, a + ".group_norm", top, seed)
+  for n in ("to_q", "to_k", "to_v", "to_out.0"):
+    _linear(sd, f"{a}.{n}", top, top, seed)
+  resnet("encoder.mid_block.resnets.1", top, top)
+  _norm(sd, "encoder.conv_norm_out", top, seed)
+  conv("encoder.conv_out", 2 * cfg.latent_channels, top)
+  conv("quant_conv", 2 * cfg.latent_channels, 2 * cfg.latent_channels, 1)
+  return sd
+
+
 # ---------------------------------------------------------------------------------------------- inputs
 IMG_TOKEN_IDS = list(range(50266, 50274))  # checkpoints/gill_opt/model_args.json:19-36
 

@@ -286,6 +286,27 @@ int gill_sd_denoise_ex(gill_unet* h, const gill_sd_sampler* sampler, const void*
 int gill_sd_schedule(const gill_sd_sampler* sampler, int v_prediction, int num_steps, float* timesteps_out, double* init_noise_sigma_out,
                      double* rows_out);
 
+/* Image-to-image: the loop started part-way.  `start` counts sampler steps, 0 <= start < num_steps (negative return otherwise); start == 0 gives
+ * gill_sd_schedule's tables bit for bit.  The loop then begins at the timestep t_s of step `start` of the full schedule:
+ *   ddim, euler, euler_ancestral: the tail of the full table (num_steps - start calls);
+ *   dpmsolver++: the tail with its first row rebuilt as a first-order step — the solver starts with an empty history, as diffusers' scheduler does
+ *     when it is handed the sliced timestep list; the ring slots of the following rows stay those of the full table;
+ *   pndm: the PLMS warm-up pair replayed at t_s — timesteps t_s, t_s - D, t_s - D, t_s - 2D, ... (D = 1000 / num_steps), num_steps - start + 1
+ *     calls.  A DELIBERATE difference from diffusers 0.17's img2img pipeline, which slices the already-duplicated list [t_0, t_1, t_1, t_2, ...]
+ *     at `start`: for start >= 2 PNDMScheduler.step_plms then takes the first timestep it sees for the warm-up and from the third call on
+ *     evaluates the model one grid step ahead of the latents.  Here the warm-up is what a fresh num_steps-grid run from t_s would do.
+ * add_noise_out (optional, 2 doubles): the pair (a, b) of x_start = a * init_latents + b * init_noise, the schedulers' add_noise() at the
+ * first timestep: pndm, ddim, dpmsolver++ (sqrt(abar_t), sqrt(1 - abar_t)); euler, euler_ancestral (1, sigma of the first call).  The other outputs as
+ * gill_sd_schedule (init_noise_sigma_out: unchanged by start — not used by a loop that starts from an image). */
+int gill_sd_schedule_from(const gill_sd_sampler* sampler, int v_prediction, int num_steps, int start, float* timesteps_out,
+                          double* init_noise_sigma_out, double* rows_out, double* add_noise_out);
+/* gill_sd_denoise_ex from step `start`: the first kernel forms x_start = a * init_latents + b * init_noise (both (B,4,L,L) fp32, init_latents the
+ * scaled VAE latents of the image, init_noise a unit-variance draw) in place of latents0 * init_noise_sigma; noise: as gill_sd_denoise_ex, one row
+ * per call of THIS table.  The captured step, the step counter and the time-embedding table are those of gill_sd_denoise_ex. */
+int gill_sd_denoise_from(gill_unet* h, const gill_sd_sampler* sampler, const void* cond_bf16, const void* uncond_bf16, int n_uncond,
+                         int start, const float* init_latents, const float* init_noise, int B, int num_steps, float guidance,
+                         float* latents_out, const float* noise, void* stream);
+
 /* ------------------------------------------------------------------------------------------
  * Stage 3b — VAE decode of the final latents.  Replaces StableDiffusionPipeline.decode_latents
  * (gill/custom_sd.py:385-392: latents / 0.18215 -> vae.decode -> (x/2+0.5).clamp(0,1)) and the uint8 conversion
@@ -309,6 +330,12 @@ void gill_vae_destroy(gill_vae* h);
 /* latents (B,4,L,L) fp32 -> image_f32 (B,3,8L,8L) fp32 in [-1,1] (vae.decode(...).sample; may be NULL) and/or
  * image_u8 (B,8L,8L,3) uint8 = round(255 * clamp(x/2+0.5, 0, 1)) (may be NULL). */
 int gill_vae_decode(gill_vae* h, const float* latents, int B, float* image_f32, uint8_t* image_u8, void* stream);
+/* The encoder half (AutoencoderKL.encode(image).latent_dist, then * scaling_factor): present in the handle when the weight table holds
+ * "encoder.conv_in.weight" (then all of encoder.* and quant_conv.* must be there); a decoder-only handle allocates nothing for it and refuses
+ * this call.  image (B,3,8L,8L) fp32 NCHW in [-1,1]; noise (B,latent_channels,L,L) fp32 unit variance, or NULL for the posterior mode
+ *   -> latents_out (B,latent_channels,L,L) = scaling_factor * (mean + exp(0.5 * logvar) * noise)      (NULL noise: scaling_factor * mean)
+ *      moments_out (B,2*latent_channels,L,L) = [mean | clamp(logvar, -30, 20)], unscaled; may be NULL. */
+int gill_vae_encode(gill_vae* h, const float* image, int B, const float* noise, float* latents_out, float* moments_out, void* stream);
 
 /* PNDM schedule known-answers for tests (host arrays): timesteps_out must hold num_steps+1 ints;
  * returns the number written.  alphas_cumprod_out (optional) must hold 1000 doubles. */
@@ -341,6 +368,12 @@ int gill_op_geglu(const void* A, const void* W, const float* bias, void* C, int 
 int gill_op_conv3x3(const void* x1, int C1, const void* x2, int C2, const float* w_oihw, const float* bias,
                     const float* rowvec, const void* resid, void* y, int B, int IH, int IW, int Cout, int stride, int ups,
                     int splitk, void* stream);
+/* gill_op_conv3x3 with the gather's origin shift: pad_shift = 1 (stride 2, even IH and IW, no upsample) is diffusers' Downsample2D with
+ * padding 0 — F.pad(x, (0, 1, 0, 1)) then conv(stride 2, pad 0): output (oy, ox) reads rows 2 oy .. 2 oy + 2, columns 2 ox .. 2 ox + 2, zero
+ * past the bottom / right edge.  pad_shift = 0 is gill_op_conv3x3 itself. */
+int gill_op_conv3x3_ex(const void* x1, int C1, const void* x2, int C2, const float* w_oihw, const float* bias,
+                       const float* rowvec, const void* resid, void* y, int B, int IH, int IW, int Cout, int stride, int ups,
+                       int pad_shift, int splitk, void* stream);
 /* 3x3 convolution (stride 1, pad 1) + the GroupNorm (+ SiLU) that consumes it, without a GroupNorm launch where the geometry allows (diffusers
  * ResnetBlock2D: conv1 -> norm2 -> silu, conv2 -> the next block's norm; reference call site gill/custom_sd.py:633-638):
  * y_raw (optional, may be NULL) = conv(x) + bias + rowvec[b] + resid, y_norm = [silu](GroupNorm(y_raw)).
@@ -469,6 +502,10 @@ int gill_op_conv3x3_fp8(const void* x_bf16, const float* w_oihw, const float* bi
  * call, unet_in_out (ncalls,B,n): the scaled UNet input of every call.  ncalls = gill_sd_schedule(...).  Synchronises. */
 int gill_op_sd_sampler_run(const gill_sd_sampler* sampler, int v_prediction, int num_steps, float guidance, const float* latents0,
                            const float* model_out, const float* noise, int B, int64_t n, float* lat_out, float* unet_in_out, void* stream);
+/* The same from step `start` (gill_sd_schedule_from's table): the first kernel is x = a * latents0 + b * init_noise, as in gill_sd_denoise_from. */
+int gill_op_sd_sampler_run_from(const gill_sd_sampler* sampler, int v_prediction, int num_steps, int start, float guidance,
+                                const float* latents0, const float* init_noise, const float* model_out, const float* noise, int B, int64_t n,
+                                float* lat_out, float* unet_in_out, void* stream);
 
 #ifdef __cplusplus
 }
