@@ -134,6 +134,8 @@ SYMBOLS: Dict[str, Tuple[object, List[object]]] = {
   "gill_op_cross_attention_folded": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp]),
   "gill_op_linear_rowstats": (_i, [_vp, _vp, _i, _vp, _vp, _vp, _vp, _vp, _i, C.POINTER(C.c_int), _i, _i, _i, _i, _vp]),
   "gill_op_ln_gemm": (_i, [_i, _vp, _vp, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _vp]),
+  "gill_op_vae_attention": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, C.POINTER(C.c_int), _vp]),
+  "gill_op_row_softmax": (_i, [_vp, _i, _i, _vp]),
 }
 
 _lib: Optional[C.CDLL] = None

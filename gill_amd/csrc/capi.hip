@@ -4,6 +4,7 @@
 #include "../../include/gill_amd.h"
 #include "ops.h"
 #include "engine_util.h"
+#include "convnet.h"
 #include <stdlib.h>
 #include <vector>
 
@@ -415,6 +416,43 @@ extern "C" int gill_op_groupnorm_from_stats(const void* x1, int C1, const void* 
   for (int r = 0; r < op_repeat(); ++r)
     GILL_TRY(groupnorm_apply_launch((const bf16_t*)x1, C1, (const bf16_t*)x2, C2, B, HW, groups, gamma, beta, eps, silu, (bf16_t*)y, stats1, bin1, C1,
                                     nslab1, stats2, C2 ? bin2 : 0, C2 ? nslab2 : 0, s, 0.f, (float*)tot.p, ss_out));
+  GILL_CHECK_HIP(hipStreamSynchronize(s));
+  return 0;
+}
+
+// ---- the VAE's single-head attention chain (vae.hip vae_attention_chain(), what VRun::attention runs behind its GroupNorm) on caller tensors.
+// The split-K workspace is held to the engine's 16 Mi floats, so every GEMM takes the split the engine gives that shape.
+extern "C" int gill_op_vae_attention(const void* n_bf16, const void* resid_bf16, const void* wqkv_bf16, const float* bqkv, const void* wo_bf16,
+                                     const float* bo, void* out_bf16, void* P_out_bf16, int B, int HW, int C, int* splits, void* stream) {
+  hipStream_t s = (hipStream_t)stream;
+  GILL_REQUIRE(n_bf16 && wqkv_bf16 && bqkv && wo_bf16 && bo && out_bf16 && splits, "vae_attention: null argument");
+  GILL_REQUIRE(B >= 1 && HW > 0 && C > 0 && HW % 64 == 0 && C % 64 == 0, "vae_attention: HW and C must be multiples of 64");
+  const size_t mc = (size_t)B * HW * C, ws_floats = (size_t)16 << 20;
+  DevBuf q, k, vt, o, sc;
+  GILL_TRY(q.alloc(sizeof(bf16_t) * mc));
+  GILL_TRY(k.alloc(sizeof(bf16_t) * mc));
+  GILL_TRY(vt.alloc(sizeof(bf16_t) * mc));
+  GILL_TRY(o.alloc(sizeof(bf16_t) * mc));
+  if (!P_out_bf16) GILL_TRY(sc.alloc(sizeof(bf16_t) * (size_t)HW * HW));
+  VaeAttnArgs a;
+  a.n = (const bf16_t*)n_bf16; a.wqkv = (const bf16_t*)wqkv_bf16; a.bqkv = bqkv; a.wo = (const bf16_t*)wo_bf16; a.bo = bo;
+  a.q = (bf16_t*)q.p; a.k = (bf16_t*)k.p; a.vt = (bf16_t*)vt.p; a.o = (bf16_t*)o.p;
+  a.sc = P_out_bf16 ? (bf16_t*)P_out_bf16 : (bf16_t*)sc.p;
+  a.sc_bstride = P_out_bf16 ? (size_t)HW * HW : 0;
+  a.ws = op_splitk_ws(ws_floats); a.ws_floats = ws_floats;
+  GILL_REQUIRE(a.ws != nullptr, "split-K workspace allocation failed");
+  a.B = B; a.HW = HW; a.C = C;
+  a.out.resid = resid_bf16; a.out.ldr = C; a.out.C = out_bf16; a.out.ldc = C;
+  for (int r = 0; r < op_repeat(); ++r) GILL_TRY(vae_attention_chain(a, s));
+  for (int i = 0; i < 3; ++i) splits[i] = a.splits[i];
+  GILL_CHECK_HIP(hipStreamSynchronize(s));
+  return 0;
+}
+
+extern "C" int gill_op_row_softmax(void* s_bf16, int rows, int n, void* stream) {
+  hipStream_t s = (hipStream_t)stream;
+  GILL_REQUIRE(s_bf16 && rows > 0 && n > 0, "row_softmax: bad argument");
+  GILL_TRY(vae_row_softmax_launch((bf16_t*)s_bf16, rows, n, s));
   GILL_CHECK_HIP(hipStreamSynchronize(s));
   return 0;
 }

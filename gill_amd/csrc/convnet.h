@@ -155,3 +155,24 @@ struct ConvRun {
                             y8_scale);
   }
 };
+
+// ---- the VAE mid block's single-head attention behind its GroupNorm (vae.hip), shared by the engine (VRun::attention) and gill_op_vae_attention:
+// one OUT_QKV GEMM (heads = 1, dp = dpv = C, qscale = 1 / sqrt(C): the natural-exponent domain; V stored transposed [B][C][HW]), then per image
+// S = Q K^T (bf16, ldc = HW), vae_row_softmax_kernel in place, O = P V, and to_out over all B * HW rows.
+struct VaeAttnArgs {
+  const bf16_t* n = nullptr;                                   // [B * HW][C]: the normalised input
+  const bf16_t* wqkv = nullptr; const float* bqkv = nullptr;   // [3C][C] = to_q | to_k | to_v, [3C]
+  const bf16_t* wo = nullptr; const float* bo = nullptr;       // [C][C], [C]
+  bf16_t *q = nullptr, *k = nullptr, *vt = nullptr, *o = nullptr;   // B * HW * C elements each
+  bf16_t* sc = nullptr;      // scores, then probabilities, of image b at sc + b * sc_bstride ([HW][HW])
+  size_t sc_bstride = 0;     // 0: one buffer reused by every image (the engine); HW * HW: every image's P is kept
+  float* ws = nullptr; size_t ws_floats = 0;                   // split-K partials and how many floats they may take
+  int B = 0, HW = 0, C = 0;
+  // to_out: the caller fills C / ldc, the residual (resid / ldr) and the fused GroupNorm statistics hookup; the chain fills the rest and,
+  // as for every GEMM, the split (read back for gemm_gn_slab_rows())
+  GemmArgs out;
+  int splits[3] = {0, 0, 0};   // the split factors used: QKV, S, PV (of the last image; they depend on the shape alone)
+};
+int vae_gemm_launch(GemmArgs& g, float* ws, size_t ws_floats, hipStream_t s);   // gemm_pick_splitk(), capped by ws_floats, then gemm_launch()
+int vae_row_softmax_launch(bf16_t* sc, int rows, int n, hipStream_t s);         // in place over [rows][n] bf16; n % 8 == 0 or an error
+int vae_attention_chain(VaeAttnArgs& a, hipStream_t s);

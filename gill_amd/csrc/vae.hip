@@ -139,6 +139,54 @@ __global__ __launch_bounds__(256) void vae_row_softmax_kernel(bf16_t* __restrict
   }
 }
 
+int vae_row_softmax_launch(bf16_t* sc, int rows, int n, hipStream_t s) {
+  GILL_REQUIRE(sc && rows > 0 && n > 0 && n % 8 == 0, "row softmax: the row length must be a multiple of 8 (the kernel reads 8 elements at a time)");
+  hipLaunchKernelGGL(vae_row_softmax_kernel, dim3(cdiv(rows, 4)), dim3(256), 0, s, sc, rows, n);
+  GILL_CHECK_HIP(hipGetLastError());
+  return 0;
+}
+
+// every GEMM of the VAE, the attention's included: the conv split rule, capped by the partials the workspace holds
+int vae_gemm_launch(GemmArgs& g, float* ws, size_t ws_floats, hipStream_t s) {
+  g.splitk = gemm_pick_splitk(g.M, g.N, g.K, g.act);
+  while (g.splitk > 1 && (size_t)g.splitk * g.M * g.N > ws_floats) --g.splitk;
+  g.ws = ws;
+  return gemm_launch(g, s);
+}
+
+// The single-head attention behind its GroupNorm (convnet.h VaeAttnArgs): the engine's VRun::attention and gill_op_vae_attention both run this.
+int vae_attention_chain(VaeAttnArgs& a, hipStream_t s) {
+  const int B = a.B, HW = a.HW, C = a.C, M = B * HW;
+  GILL_REQUIRE(B >= 1 && HW > 0 && C > 0 && HW % 64 == 0 && C % 64 == 0, "vae attention: HW and C must be multiples of 64");
+  GILL_REQUIRE(a.n && a.wqkv && a.bqkv && a.wo && a.bo && a.q && a.k && a.vt && a.sc && a.o && a.out.C, "vae attention: null argument");
+  {
+    // heads = 1, dp = C: Q and K come out plain row-major [B*HW][C], V transposed [B][C][HW]
+    GemmArgs g;
+    g.M = M; g.N = 3 * C; g.K = C; g.K1 = C; g.A = a.n; g.lda = C; g.W = a.wqkv; g.bias = a.bqkv;
+    g.out_mode = OUT_QKV; g.Cq = a.q; g.Ck = a.k; g.Cvt = a.vt; g.heads = 1; g.dp = C; g.dpv = C; g.ntok = HW;
+    g.ntok_pad_q = HW; g.ntok_pad_kv = HW; g.seg_base = 0;
+    g.qscale = 1.0f / sqrtf((float)C);   // the natural-exponent domain: vae_row_softmax_kernel takes __expf of the stored scores
+    GILL_TRY(vae_gemm_launch(g, a.ws, a.ws_floats, s));
+    a.splits[0] = g.splitk;
+  }
+  for (int b = 0; b < B; ++b) {
+    bf16_t* sc = a.sc + (size_t)b * a.sc_bstride;
+    GemmArgs g1;   // S = Q K^T
+    g1.M = HW; g1.N = HW; g1.K = C; g1.K1 = C; g1.A = a.q + (size_t)b * HW * C; g1.lda = C; g1.W = a.k + (size_t)b * HW * C;
+    g1.C = sc; g1.ldc = HW;
+    GILL_TRY(vae_gemm_launch(g1, a.ws, a.ws_floats, s));
+    GILL_TRY(vae_row_softmax_launch(sc, HW, HW, s));
+    GemmArgs g2;   // O = P V
+    g2.M = HW; g2.N = C; g2.K = HW; g2.K1 = HW; g2.A = sc; g2.lda = HW; g2.W = a.vt + (size_t)b * C * HW;
+    g2.C = a.o + (size_t)b * HW * C; g2.ldc = C;
+    GILL_TRY(vae_gemm_launch(g2, a.ws, a.ws_floats, s));
+    a.splits[1] = g1.splitk; a.splits[2] = g2.splitk;
+  }
+  GemmArgs& g3 = a.out;   // to_out (+ the caller's residual and GroupNorm statistics hookup)
+  g3.M = M; g3.N = C; g3.K = C; g3.K1 = C; g3.A = a.o; g3.lda = C; g3.W = a.wo; g3.bias = a.bo;
+  return vae_gemm_launch(g3, a.ws, a.ws_floats, s);
+}
+
 // image = (x / 2 + 0.5).clamp(0, 1): NCHW fp32 -> NHWC uint8 (round(x * 255), what numpy_to_pil produces)
 __global__ __launch_bounds__(256) void vae_to_uint8_kernel(const float* __restrict__ x, int C, int HW, int64_t total,
                                                            uint8_t* __restrict__ out) {
@@ -196,11 +244,9 @@ struct VRun : ConvRun {
   // every GEMM, the attention's included: the conv split rule, 16 Mi floats of partials
   int gemm(GemmArgs& g, Tensor* ys = nullptr) {
     if (dry) return 0;
-    g.splitk = gemm_pick_splitk(g.M, g.N, g.K, g.act);
-    while (g.splitk > 1 && (size_t)g.splitk * g.M * g.N > ws->splitk_ws_floats) --g.splitk;
-    g.ws = ws->splitk_ws;
+    GILL_TRY(vae_gemm_launch(g, ws->splitk_ws, ws->splitk_ws_floats, s));
     if (ys && ys->stats) ys->nslab = ys->H * ys->W / gemm_gn_slab_rows(g);
-    return gemm_launch(g, s);
+    return 0;
   }
   int gnorm(const Tensor& x, const NormW& n, int silu, const Tensor& y) { return ConvRun::gnorm(x, nullptr, n, 1e-6f, silu, y); }
   int conv(const Tensor& x, const ConvW& w, int ups, const bf16_t* resid, Tensor& y) {
@@ -243,34 +289,16 @@ struct VRun : ConvRun {
     bf16_t* vt = (bf16_t*)ws->arena.alloc(sizeof(bf16_t) * (size_t)M * C);
     bf16_t* sc = (bf16_t*)ws->arena.alloc(sizeof(bf16_t) * (size_t)HW * HW);   // scores of ONE image at a time
     bf16_t* o = (bf16_t*)ws->arena.alloc(sizeof(bf16_t) * (size_t)M * C);
-    {
-      // heads = 1, dp = C: Q and K come out plain row-major [B*HW][C], V transposed [B][C][HW]
-      GemmArgs g;
-      g.M = M; g.N = 3 * C; g.K = C; g.K1 = C; g.A = n.p; g.lda = C; g.W = a.wqkv; g.bias = a.bqkv;
-      g.out_mode = OUT_QKV; g.Cq = q; g.Ck = k; g.Cvt = vt; g.heads = 1; g.dp = C; g.dpv = C; g.ntok = HW;
-      g.ntok_pad_q = HW; g.ntok_pad_kv = HW; g.seg_base = 0;
-      g.qscale = 1.0f / sqrtf((float)C);
-      GILL_TRY(gemm(g));
+    if (!dry) {
+      VaeAttnArgs v;
+      v.n = n.p; v.wqkv = a.wqkv; v.bqkv = a.bqkv; v.wo = a.wo; v.bo = a.bo;
+      v.q = q; v.k = k; v.vt = vt; v.sc = sc; v.sc_bstride = 0; v.o = o;
+      v.ws = ws->splitk_ws; v.ws_floats = ws->splitk_ws_floats; v.B = Bx; v.HW = HW; v.C = C;
+      v.out.resid = x.p; v.out.ldr = C; v.out.C = out->p; v.out.ldc = C;
+      fuse_stats(v.out, *out);
+      GILL_TRY(vae_attention_chain(v, s));
+      if (out->stats) out->nslab = HW / gemm_gn_slab_rows(v.out);
     }
-    for (int b = 0; b < Bx; ++b) {
-      GemmArgs g1;   // S = Q K^T
-      g1.M = HW; g1.N = HW; g1.K = C; g1.K1 = C; g1.A = q + (size_t)b * HW * C; g1.lda = C; g1.W = k + (size_t)b * HW * C;
-      g1.C = sc; g1.ldc = HW;
-      GILL_TRY(gemm(g1));
-      if (!dry) {
-        hipLaunchKernelGGL(vae_row_softmax_kernel, dim3(cdiv(HW, 4)), dim3(256), 0, s, sc, HW, HW);
-        GILL_CHECK_HIP(hipGetLastError());
-      }
-      GemmArgs g2;   // O = P V
-      g2.M = HW; g2.N = C; g2.K = HW; g2.K1 = HW; g2.A = sc; g2.lda = HW; g2.W = vt + (size_t)b * C * HW;
-      g2.C = o + (size_t)b * HW * C; g2.ldc = C;
-      GILL_TRY(gemm(g2));
-    }
-    GemmArgs g3;   // to_out + residual
-    g3.M = M; g3.N = C; g3.K = C; g3.K1 = C; g3.A = o; g3.lda = C; g3.W = a.wo; g3.bias = a.bo;
-    g3.resid = x.p; g3.ldr = C; g3.C = out->p; g3.ldc = C;
-    fuse_stats(g3, *out);
-    GILL_TRY(gemm(g3, out));
     ws->arena.release(mk);
     return 0;
   }

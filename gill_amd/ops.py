@@ -486,3 +486,38 @@ def sd_sampler_run_from(sampler, v_prediction: bool, num_steps: int, start: int,
                                               N.ptr(z0), N.ptr(mo), None if z is None else N.ptr(z), B, n, N.ptr(lat), N.ptr(uin),
                                               N.current_stream()))
   return lat, uin
+
+
+def vae_attention(n: torch.Tensor, wqkv: torch.Tensor, bqkv: torch.Tensor, wo: torch.Tensor, bo: torch.Tensor,
+                  resid: Optional[torch.Tensor] = None, want_p: bool = False):
+  """The VAE mid block's single-head attention behind its GroupNorm, as the engine launches it (gill_op_vae_attention): n (B,HW,C) bf16, the
+  normalised input; wqkv (3C,C) bf16 = to_q | to_k | to_v rows, bqkv (3C); wo (C,C) bf16, bo (C); resid (B,HW,C) bf16 or None.  Returns
+  (out (B,HW,C) bf16, P (B,HW,HW) bf16 — the stored probabilities of every image — or None, (split-K factors of the QKV, S and PV GEMMs)); out and
+  P NaN-prefilled.  want_p = False: one score buffer reused by every image, as in the engine."""
+  n, wqkv, wo = _bf(n), _bf(wqkv), _bf(wo)
+  B, HW, Cc = n.shape
+  assert tuple(wqkv.shape) == (3 * Cc, Cc) and tuple(wo.shape) == (Cc, Cc)
+  bqkv, bo = bqkv.float().contiguous(), bo.float().contiguous()
+  assert bqkv.numel() == 3 * Cc and bo.numel() == Cc
+  resid = None if resid is None else _bf(resid)
+  assert resid is None or resid.shape == n.shape
+  nan = float("nan")
+  out = torch.full((B, HW, Cc), nan, device=n.device, dtype=torch.bfloat16)
+  P = torch.full((B, HW, HW), nan, device=n.device, dtype=torch.bfloat16) if want_p else None
+  splits = (ctypes.c_int * 3)()
+  N.check(N.lib().gill_op_vae_attention(N.ptr(n), N.ptr(resid), N.ptr(wqkv), N.ptr(bqkv), N.ptr(wo), N.ptr(bo), N.ptr(out), N.ptr(P), B, HW, Cc,
+                                        splits, N.current_stream()))
+  return out, P, tuple(splits)
+
+
+def row_softmax(s: torch.Tensor, guard_rows: int = 2):
+  """Softmax over the rows of s (rows,n) bf16 with the VAE attention's in-place kernel (gill_op_row_softmax), run on a copy of s followed by
+  `guard_rows` rows the kernel must not touch.  Returns (P (rows,n) bf16, the guard rows after the call, the guard rows as they were filled)."""
+  s = _bf(s)
+  rows, n = s.shape
+  buf = torch.empty((rows + guard_rows, n), device=s.device, dtype=torch.bfloat16)
+  buf[:rows] = s
+  buf[rows:] = torch.arange(guard_rows * n, device=s.device).reshape(guard_rows, n).remainder(251).to(torch.bfloat16) - 125.0
+  guard = buf[rows:].clone()
+  N.check(N.lib().gill_op_row_softmax(N.ptr(buf), rows, n, N.current_stream()))
+  return buf[:rows].clone(), buf[rows:].clone(), guard

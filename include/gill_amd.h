@@ -432,6 +432,18 @@ int gill_op_groupnorm_from_stats(const void* x1, int C1, const void* x2, int C2,
                                  float eps, int silu, const float* stats1, int bin1, int nslab1, const float* stats2, int bin2, int nslab2,
                                  void* y, float* ss_out, void* stream);
 
+/* The VAE mid block's single-head attention behind its GroupNorm, launched as the engine launches it (diffusers AutoencoderKL
+ * mid_block.attentions.0 without group_norm): out (B*HW, C) bf16 = to_out(softmax(to_q(n) to_k(n)^T / sqrt(C)) to_v(n)) + resid.  n (B*HW, C)
+ * bf16: the normalised input; resid (B*HW, C) bf16 or NULL; wqkv (3C, C) bf16 = to_q | to_k | to_v rows, bqkv (3C) fp32; wo (C, C) bf16,
+ * bo (C) fp32.  P_out (B, HW, HW) bf16 or NULL: every image's probabilities as stored (NULL: one score buffer reused by every image, as in
+ * the engine).  splits: three ints, the split-K factors used by the QKV, S = Q K^T and O = P V GEMMs (the engine's rule under its 16 Mi-float
+ * workspace).  HW and C must be multiples of 64 (an error otherwise).  Synchronises.  For the operator tests. */
+int gill_op_vae_attention(const void* n_bf16, const void* resid_bf16, const void* wqkv_bf16, const float* bqkv, const void* wo_bf16,
+                          const float* bo, void* out_bf16, void* P_out_bf16, int B, int HW, int C, int* splits, void* stream);
+/* In-place softmax over the rows of s (rows, n) bf16, the VAE attention's kernel with the engine's launch geometry.  n must be a multiple of
+ * 8 (an error otherwise: nothing is launched).  Synchronises. */
+int gill_op_row_softmax(void* s_bf16, int rows, int n, void* stream);
+
 /* The feed-forward sub-block of a level-0 (C = 320) transformer block + proj_out + outer residual as one kernel (csrc/ffn.hip):
  * out = proj_out(ff2(geglu(ff1(LN(t)))) + t) + resid on natural (diffusers-layout) operands; gn_stats (optional): GroupNorm partial sums
  * of the output, [(b * rows_per_batch / 64 + slab) * 64 + bin][2], bins of 5 channels.  Replaces, inside gill_unet_forward, the
