@@ -136,6 +136,12 @@ SYMBOLS: Dict[str, Tuple[object, List[object]]] = {
   "gill_op_ln_gemm": (_i, [_i, _vp, _vp, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _vp]),
   "gill_op_vae_attention": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, C.POINTER(C.c_int), _vp]),
   "gill_op_row_softmax": (_i, [_vp, _i, _i, _vp]),
+  "gill_op_conv_out": (_i, [_vp, _vp, _i, _vp, _vp, _i, _i, _i, _i, _i, _i, C.POINTER(C.c_int), _vp]),
+  "gill_op_conv_in": (_i, [_vp, _vp, _i, _vp, _vp, _i, _i, _i, _i, _i, _vp, _i, _vp]),
+  "gill_op_timestep_embed": (_i, [_vp, _i, _i, _vp, _vp]),
+  "gill_op_reduce_ln": (_i, [_vp, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _f, _vp]),
+  "gill_op_linear_reduce_ln": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp]),
+  "gill_op_skinny_gemm": (_i, [_vp, _vp, _vp, _i, _i, _i, _vp]),
 }
 
 _lib: Optional[C.CDLL] = None

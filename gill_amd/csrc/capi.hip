@@ -5,6 +5,7 @@
 #include "ops.h"
 #include "engine_util.h"
 #include "convnet.h"
+#include "tfm.h"
 #include <stdlib.h>
 #include <vector>
 
@@ -453,6 +454,85 @@ extern "C" int gill_op_row_softmax(void* s_bf16, int rows, int n, void* stream) 
   hipStream_t s = (hipStream_t)stream;
   GILL_REQUIRE(s_bf16 && rows > 0 && n > 0, "row_softmax: bad argument");
   GILL_TRY(vae_row_softmax_launch((bf16_t*)s_bf16, rows, n, s));
+  GILL_CHECK_HIP(hipStreamSynchronize(s));
+  return 0;
+}
+
+// ---- the kernels at the ends of the engines (tests/test_ends_gpu.py): conv_out, conv_in (im2col + the K = 64 GEMM), the timestep embedding,
+// the transformer block's split-K reducer + LayerNorm, and the lm_head GEMV, each launched the way its engine launches it.
+extern "C" int gill_op_conv_out(const void* x_bf16, const void* w_oihw, int w_dtype, const float* bias, float* y_f32, int B, int H, int W, int Cin,
+                                int Cout, int force_general, int* path, void* stream) {
+  hipStream_t s = (hipStream_t)stream;
+  GILL_REQUIRE(x_bf16 && w_oihw && y_f32 && path && B > 0 && H > 0 && W > 0 && Cin > 0 && Cout > 0, "conv_out: bad argument");
+  DevBuf wr;      // load_conv_out's form: [Cout][9][Cin]
+  GILL_TRY(wr.alloc(sizeof(bf16_t) * (size_t)Cout * 9 * Cin));
+  GILL_TRY(conv_weight_relayout_launch(w_oihw, w_dtype, Cout, Cin, (bf16_t*)wr.p, s));
+  for (int r = 0; r < op_repeat(); ++r)
+    GILL_TRY(conv_out_launch((const bf16_t*)x_bf16, (const bf16_t*)wr.p, bias, B, Cin, H, W, Cout, y_f32, s, force_general, path));
+  GILL_CHECK_HIP(hipStreamSynchronize(s));
+  return 0;
+}
+
+extern "C" int gill_op_conv_in(const float* x_f32, const void* w_oihw, int w_dtype, const float* bias, void* y_bf16, int B, int Cin, int H, int W,
+                               int Cout, uint32_t* counters, int ncounters, void* stream) {
+  hipStream_t s = (hipStream_t)stream;
+  GILL_REQUIRE(x_f32 && w_oihw && y_bf16 && B > 0 && Cin > 0 && H > 0 && W > 0 && Cout > 0 && ncounters >= 0, "conv_in: bad argument");
+  GILL_REQUIRE(Cin * 9 <= 64, "conv_in: in_channels * 9 must fit one 64-wide K step");
+  const int M = B * H * W;
+  DevBuf tmp, w64, col;
+  GILL_TRY(tmp.alloc(sizeof(bf16_t) * (size_t)Cout * 9 * Cin));
+  GILL_TRY(w64.alloc_zero(sizeof(bf16_t) * (size_t)Cout * 64, s));
+  GILL_TRY(col.alloc(sizeof(bf16_t) * (size_t)M * 64));
+  GILL_TRY(conv_in_im2col_weight(w_oihw, w_dtype, Cin, Cout, (bf16_t*)tmp.p, (bf16_t*)w64.p, s));
+  GemmArgs g;      // the UNet's linear(col, 64, ...)
+  g.M = M; g.N = Cout; g.K = 64; g.K1 = 64; g.A = (const bf16_t*)col.p; g.lda = 64; g.W = (const bf16_t*)w64.p; g.bias = bias;
+  g.ldr = Cout; g.act = ACT_NONE; g.C = y_bf16; g.ldc = Cout;
+  g.splitk = gemm_pick_splitk(M, Cout, 64, ACT_NONE, true);
+  GILL_REQUIRE(g.splitk == 1, "conv_in: one K step cannot split");
+  for (int r = 0; r < op_repeat(); ++r) {
+    GILL_TRY(im2col_nchw_launch(x_f32, B, Cin, H, W, 64, (bf16_t*)col.p, s, counters, ncounters));
+    GILL_TRY(gemm_launch(g, s));
+  }
+  GILL_CHECK_HIP(hipStreamSynchronize(s));
+  return 0;
+}
+
+extern "C" int gill_op_timestep_embed(const float* t, int n, int dim, void* out_bf16, void* stream) {
+  hipStream_t s = (hipStream_t)stream;
+  GILL_REQUIRE(t && out_bf16 && n > 0 && dim > 0, "timestep_embed: bad argument");
+  GILL_TRY(timestep_embed_launch(t, n, dim, (bf16_t*)out_bf16, s));
+  GILL_CHECK_HIP(hipStreamSynchronize(s));
+  return 0;
+}
+
+extern "C" int gill_op_reduce_ln(const float* ws, int sk, int M, int D, const float* bias, float* h, const float* g, const float* b, void* nb_bf16,
+                                 float eps, void* stream) {
+  hipStream_t s = (hipStream_t)stream;
+  GILL_REQUIRE(ws && bias && h && g && b && nb_bf16 && M > 0 && D > 0, "reduce_ln: bad argument");
+  GILL_TRY(opt_reduce_ln_launch(ws, sk, M, D, bias, h, g, b, (bf16_t*)nb_bf16, eps, s));      // (h is updated in place: no repeat loop)
+  GILL_CHECK_HIP(hipStreamSynchronize(s));
+  return 0;
+}
+
+// The two ways TfmRun::linear runs an in-place residual GEMM into the fp32 stream with the LayerNorm behind it, `splitk` ways on row-major weights:
+// fuse = 1: partials + opt_reduce_ln_kernel; fuse = 0: the GEMM with its own reducer + layernorm_launch.  eps is the block's 1e-5.
+extern "C" int gill_op_linear_reduce_ln(const void* A_bf16, const void* W_bf16, const float* bias, float* h, const float* g, const float* b,
+                                        void* nb_bf16, int M, int N, int K, int splitk, int fuse, void* stream) {
+  hipStream_t s = (hipStream_t)stream;
+  GILL_REQUIRE(A_bf16 && W_bf16 && bias && h && g && b && nb_bf16 && M > 0, "linear_reduce_ln: bad argument");
+  GILL_REQUIRE(splitk > 1 && N % 4 == 0 && N <= 8192, "linear_reduce_ln: splitk > 1, N a multiple of 4, at most 8192");
+  float* ws = op_splitk_ws((size_t)splitk * M * N);
+  GILL_REQUIRE(ws != nullptr, "split-K workspace allocation failed");
+  GILL_TRY(tfm_linear_launch((const bf16_t*)A_bf16, M, (const bf16_t*)W_bf16, 0, bias, N, K, h, ACT_NONE, h, true, splitk, ws, fuse != 0, g, b,
+                             (bf16_t*)nb_bf16, s));
+  GILL_CHECK_HIP(hipStreamSynchronize(s));
+  return 0;
+}
+
+extern "C" int gill_op_skinny_gemm(const void* x_bf16, const void* W_bf16, float* out_f32, int M, int N, int K, void* stream) {
+  hipStream_t s = (hipStream_t)stream;
+  GILL_REQUIRE(x_bf16 && W_bf16 && out_f32 && N > 0 && K > 0, "skinny_gemm: bad argument");
+  for (int r = 0; r < op_repeat(); ++r) GILL_TRY(skinny_gemm_launch((const bf16_t*)x_bf16, (const bf16_t*)W_bf16, M, N, K, out_f32, s));
   GILL_CHECK_HIP(hipStreamSynchronize(s));
   return 0;
 }

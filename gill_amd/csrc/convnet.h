@@ -61,6 +61,8 @@ int load_norm(const WeightTable& wt, DevPool& pool, hipStream_t s, const std::st
 int load_conv3(const WeightTable& wt, DevPool& pool, hipStream_t s, const std::string& p, int cin, int cout, int hw, ConvW* c,
                bool f8 = false, bool ups4 = false);
 // conv_in as im2col + the MFMA GEMM: weights [cout][tap*cin + c], K = 9 cin zero-padded to one 64-wide K step
+// the part behind the weight lookup: OIHW of any loader dtype -> tmp [cout][9][cin] -> the first 9 cin columns of w64 [cout][64] (zeroed by the caller)
+int conv_in_im2col_weight(const void* w_oihw, int dtype, int cin, int cout, bf16_t* tmp, bf16_t* w64, hipStream_t s);
 int load_conv_in_im2col(const WeightTable& wt, DevPool& pool, hipStream_t s, const std::string& p, int cin, int cout, bf16_t** w, float** b);
 int load_conv_out(const WeightTable& wt, DevPool& pool, hipStream_t s, const std::string& p, int cin, int cout, bf16_t** w, float** b);   // [cout][9][cin] for conv_out_launch
 // r->c2f_w rows = [conv2 taps (9*cout, r->c2's K order) | shortcut (cin)], r->c2f_b = conv2 bias + shortcut bias

@@ -156,46 +156,7 @@ int silu_bf16_launch(const bf16_t* x, bf16_t* y, int64_t n, hipStream_t s) {
   return 0;
 }
 
-// ---------------------------------------------------------------- conv_in / conv_out (direct)
-// conv_in: thread = (pixel, 8 output channels); input latents are fp32 NCHW (tiny: Cin = 4).
-__global__ __launch_bounds__(256) void conv_in_kernel(const float* __restrict__ x, const bf16_t* __restrict__ w,
-                                                      const float* __restrict__ bias, int B, int Cin, int H, int W,
-                                                      int Cout, bf16_t* __restrict__ y) {
-  const int groups = Cout / 8;
-  const int64_t total = (int64_t)B * H * W * groups;
-  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (int64_t)gridDim.x * blockDim.x) {
-    const int g = (int)(i % groups);
-    const int64_t pix = i / groups;
-    const int xw = (int)(pix % W);
-    const int yh = (int)((pix / W) % H);
-    const int b = (int)(pix / ((int64_t)W * H));
-    float acc[8];
-#pragma unroll
-    for (int o = 0; o < 8; ++o) acc[o] = bias ? bias[g * 8 + o] : 0.f;
-    for (int tap = 0; tap < 9; ++tap) {
-      const int iy = yh + tap / 3 - 1, ix = xw + tap % 3 - 1;
-      if (iy < 0 || iy >= H || ix < 0 || ix >= W) continue;
-      for (int c = 0; c < Cin; ++c) {
-        // the oracle rounds the conv input to bf16 like every other activation entering an MFMA
-        const float v = bf2f(f2bf(x[(((size_t)b * Cin + c) * H + iy) * W + ix]));
-#pragma unroll
-        for (int o = 0; o < 8; ++o) acc[o] += v * bf2f(w[((size_t)(g * 8 + o) * 9 + tap) * Cin + c]);
-      }
-    }
-    uint4 u;
-    u.x = pack_bf2(acc[0], acc[1]); u.y = pack_bf2(acc[2], acc[3]); u.z = pack_bf2(acc[4], acc[5]); u.w = pack_bf2(acc[6], acc[7]);
-    *reinterpret_cast<uint4*>(y + (size_t)pix * Cout + g * 8) = u;
-  }
-}
-int conv_in_launch(const float* x, const bf16_t* w, const float* bias, int B, int Cin, int H, int W, int Cout, bf16_t* y,
-                   hipStream_t s) {
-  GILL_REQUIRE(Cout % 8 == 0, "conv_in: Cout must be a multiple of 8");
-  const int64_t total = (int64_t)B * H * W * (Cout / 8);
-  hipLaunchKernelGGL(conv_in_kernel, dim3(grid_for(total)), dim3(256), 0, s, x, w, bias, B, Cin, H, W, Cout, y);
-  GILL_CHECK_HIP(hipGetLastError());
-  return 0;
-}
-
+// ---------------------------------------------------------------- conv_in (im2col for the K = 64 GEMM) / conv_out (direct)
 // zero / nzero: a range of 32-bit words this kernel also clears — the UNet forward's COOP arrival counters (GemmArgs::coop_ctr), reset by the
 // forward's first kernel instead of a launch (or a memset node) of their own
 __global__ __launch_bounds__(256) void im2col_nchw_kernel(const float* __restrict__ x, int B, int Cin, int H, int W, int kpad,
@@ -329,11 +290,13 @@ __global__ __launch_bounds__(256) void conv_out_mfma_kernel(const bf16_t* __rest
   }
 }
 
+// force_general: skip the matrix-pipe branch; path (optional): which kernel ran — 0 = one wave per pixel, 1 = MFMA with the run-time K loop,
+// 2 | 4 | 10 = MFMA with that compile-time KS (both for the operator tests)
 int conv_out_launch(const bf16_t* x, const bf16_t* w, const float* bias, int B, int Cin, int H, int W, int Cout, float* y,
-                    hipStream_t s) {
+                    hipStream_t s, int force_general, int* path) {
   const size_t wbytes = (size_t)Cout * 9 * Cin * sizeof(bf16_t);
   // matrix-pipe kernel where its geometry holds; the one-wave-per-pixel kernel is the general path (rows not a multiple of 16 wide, ...)
-  if (Cout <= 16 && Cin % 32 == 0 && W % 16 == 0 && wbytes <= 64 * 1024 && (((uintptr_t)w | (uintptr_t)x) & 15) == 0) {
+  if (!force_general && Cout <= 16 && Cin % 32 == 0 && W % 16 == 0 && wbytes <= 64 * 1024 && (((uintptr_t)w | (uintptr_t)x) & 15) == 0) {
     const int64_t groups = (int64_t)B * H * (W / 16);
     const dim3 grid((unsigned)cdiv64(groups, 4));
     if (Cin == 320) hipLaunchKernelGGL(conv_out_mfma_kernel<10>, grid, dim3(256), wbytes, s, x, w, bias, B, Cin, H, W, Cout, y);
@@ -341,9 +304,11 @@ int conv_out_launch(const bf16_t* x, const bf16_t* w, const float* bias, int B, 
     else if (Cin == 64) hipLaunchKernelGGL(conv_out_mfma_kernel<2>, grid, dim3(256), wbytes, s, x, w, bias, B, Cin, H, W, Cout, y);
     else hipLaunchKernelGGL(conv_out_mfma_kernel<0>, grid, dim3(256), wbytes, s, x, w, bias, B, Cin, H, W, Cout, y);
     GILL_CHECK_HIP(hipGetLastError());
+    if (path) *path = Cin == 320 ? 10 : Cin == 128 ? 4 : Cin == 64 ? 2 : 1;
     return 0;
   }
   GILL_REQUIRE(Cout <= 8 && Cin % 8 == 0, "conv_out: Cout <= 8 and Cin % 8 == 0 required");
+  if (path) *path = 0;
   const int64_t pix = (int64_t)B * H * W;
   hipLaunchKernelGGL(conv_out_kernel, dim3((unsigned)cdiv64(pix, 4)), dim3(256), 0, s, x, w, bias, B, Cin, H, W, Cout, y);
   GILL_CHECK_HIP(hipGetLastError());

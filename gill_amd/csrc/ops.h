@@ -266,14 +266,11 @@ int cast_f32_to_bf16_launch(const float* x, bf16_t* y, int64_t n, hipStream_t s)
 int cast_bf16_to_f32_launch(const bf16_t* x, float* y, int64_t n, hipStream_t s);
 int timestep_embed_launch(const float* t, int n, int dim, bf16_t* out, hipStream_t s);  // [n][dim] = [cos | sin]
 int silu_bf16_launch(const bf16_t* x, bf16_t* y, int64_t n, hipStream_t s);
-// conv_in: NCHW fp32 (B,Cin,H,W) -> NHWC bf16 (B,H,W,Cout), 3x3 pad 1, direct (Cin tiny)
-int conv_in_launch(const float* x, const bf16_t* w /*[Cout][9][Cin]*/, const float* bias, int B, int Cin, int H, int W,
-                   int Cout, bf16_t* y, hipStream_t s);
 // im2col of a tiny-Cin NCHW fp32 tensor for conv_in: out [B*H*W][kpad] bf16, k = tap*Cin + c (zero beyond 9*Cin)
 int im2col_nchw_launch(const float* x, int B, int Cin, int H, int W, int kpad, bf16_t* out, hipStream_t s, unsigned* zero = nullptr, int nzero = 0);
 // conv_out: NHWC bf16 (B,H,W,Cin) -> NCHW fp32 (B,Cout,H,W), 3x3 pad 1, direct (Cout tiny)
 int conv_out_launch(const bf16_t* x, const bf16_t* w /*[Cout][9][Cin]*/, const float* bias, int B, int Cin, int H, int W,
-                    int Cout, float* y, hipStream_t s);
+                    int Cout, float* y, hipStream_t s, int force_general = 0, int* path = nullptr);
 // skinny GEMV-ish: out[M][N] (f32) = x[M][K] (bf16) . W[N][K]^T ; M <= 8, any N (lm_head)
 int skinny_gemm_launch(const bf16_t* x, const bf16_t* W, int M, int N, int K, float* out, hipStream_t s);
 // ---- decode decision of the generate loop (decode.hip; models.py:471-520) ----

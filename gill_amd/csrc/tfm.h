@@ -41,6 +41,14 @@ struct Tfm {
 // a K / Vt cache of one layer: K [B][H][pad][dp], Vt [B][H][dpv][pad]
 struct TfmKv { bf16_t* k = nullptr; bf16_t* vt = nullptr; int pad = 0; };
 
+// split-K reducer + bias + fp32 residual (h, updated in place) + LayerNorm -> nb (opt_reduce_ln_kernel): ws [sk][M][D] fp32, D % 4 == 0, D <= 8192
+int opt_reduce_ln_launch(const float* ws, int sk, int M, int D, const float* bias, float* h, const float* g, const float* b, bf16_t* nb,
+                         float eps, hipStream_t s);
+// TfmRun::linear with the split factor, its workspace and the fuse_ln switch stated (the operator tests force them): fuse_ln and a split-K
+// in-place residual GEMM into the fp32 stream -> partials + opt_reduce_ln_launch, every other launch -> the GEMM (its own reducer) + layernorm_launch
+int tfm_linear_launch(const bf16_t* A, int M, const bf16_t* W, int blk, const float* b, int N, int K, const float* resid, int act, void* out,
+                      bool out_f32, int splitk, float* ws, bool fuse_ln, const float* ln_g, const float* ln_b, bf16_t* ln_out, hipStream_t s);
+
 struct TfmRun {
   const Tfm& t;
   hipStream_t s;

@@ -6,7 +6,8 @@
 // for the LayerNorm that follows them (the next sub-block's pre-LN): one workgroup per row adds the row's fp32 partials in split order, the
 // bias and the fp32 residual stream (the order of gemm.hip's reducer epilogue), stores the new stream row, and — the row being complete in its
 // registers — normalises it (two-pass variance like layernorm_kernel) into the bf16 operand of the next GEMM.  Two launches per layer gone
-// (the LayerNorm passes) and the stream row is not re-read.  Fixed summation order: bit-repeatable.
+// (the LayerNorm passes) and the stream row is not re-read.  Fixed summation order: bit-repeatable.  (tests/test_ends_gpu.py holds the stream row to
+// the bits of that order, and to the bits of the unfused way on the same operands.)
 template <int VPT>      // float4 vectors per thread: D <= 1024 * VPT
 __global__ __launch_bounds__(256) void opt_reduce_ln_kernel(const float* __restrict__ ws, int sk, int M, int D, const float* __restrict__ bias,
                                                             float* __restrict__ h, const float* __restrict__ g, const float* __restrict__ b,
@@ -77,8 +78,8 @@ __global__ __launch_bounds__(256) void opt_reduce_ln_kernel(const float* __restr
     }
   }
 }
-static int opt_reduce_ln_launch(const float* ws, int sk, int M, int D, const float* bias, float* h, const float* g, const float* b, bf16_t* nb,
-                                float eps, hipStream_t s) {
+int opt_reduce_ln_launch(const float* ws, int sk, int M, int D, const float* bias, float* h, const float* g, const float* b, bf16_t* nb,
+                         float eps, hipStream_t s) {
   GILL_REQUIRE(D % 4 == 0 && D <= 8192 && sk >= 1, "reduce + LayerNorm: D must be a multiple of 4, at most 8192");
   if (D <= 1024) hipLaunchKernelGGL((opt_reduce_ln_kernel<1>), dim3(M), dim3(256), 0, s, ws, sk, M, D, bias, h, g, b, nb, eps);
   else if (D <= 4096) hipLaunchKernelGGL((opt_reduce_ln_kernel<4>), dim3(M), dim3(256), 0, s, ws, sk, M, D, bias, h, g, b, nb, eps);
@@ -146,23 +147,28 @@ int TfmRun::splitk(int M, int N, int K, int act, int blk) const {
   return (size_t)sk * M * N > t.splitk_ws_floats ? 1 : sk;
 }
 
-int TfmRun::linear(const bf16_t* A, int M, const bf16_t* W, int blk, const float* b, int N, int K, const float* resid, int act, void* out,
-                   bool out_f32, const float* ln_g, const float* ln_b, bf16_t* ln_out) const {
+int tfm_linear_launch(const bf16_t* A, int M, const bf16_t* W, int blk, const float* b, int N, int K, const float* resid, int act, void* out,
+                      bool out_f32, int splitk, float* ws, bool fuse_ln, const float* ln_g, const float* ln_b, bf16_t* ln_out, hipStream_t s) {
   GemmArgs g;
   g.M = M; g.N = N; g.K = K; g.K1 = K; g.A = A; g.lda = K; g.W = W; g.bias = b;
   g.resid = resid; g.ldr = N; g.resid_f32 = 1;
   g.act = act; g.out_mode = out_f32 ? OUT_F32 : OUT_BF16; g.C = out; g.ldc = N;
   g.w_blk64 = blk;
-  g.splitk = splitk(M, N, K, act, blk);
-  g.ws = t.splitk_ws;
-  if (t.fuse_ln && ln_out && g.splitk > 1 && out_f32 && resid == (const float*)out && act == ACT_NONE && b && N % 4 == 0 && N <= 8192) {
+  g.splitk = splitk;
+  g.ws = ws;
+  if (fuse_ln && ln_out && g.splitk > 1 && out_f32 && resid == (const float*)out && act == ACT_NONE && b && N % 4 == 0 && N <= 8192) {
     g.partials_only = 1;
     GILL_TRY(gemm_launch(g, s));
-    return opt_reduce_ln_launch(t.splitk_ws, g.splitk, M, N, b, (float*)out, ln_g, ln_b, ln_out, 1e-5f, s);
+    return opt_reduce_ln_launch(ws, g.splitk, M, N, b, (float*)out, ln_g, ln_b, ln_out, 1e-5f, s);
   }
   GILL_TRY(gemm_launch(g, s));
   if (ln_out) GILL_TRY(layernorm_launch(out, 1, ln_g, ln_b, ln_out, M, N, 1e-5f, s));
   return 0;
+}
+
+int TfmRun::linear(const bf16_t* A, int M, const bf16_t* W, int blk, const float* b, int N, int K, const float* resid, int act, void* out,
+                   bool out_f32, const float* ln_g, const float* ln_b, bf16_t* ln_out) const {
+  return tfm_linear_launch(A, M, W, blk, b, N, K, resid, act, out, out_f32, splitk(M, N, K, act, blk), t.splitk_ws, t.fuse_ln, ln_g, ln_b, ln_out, s);
 }
 
 int TfmRun::qkv(const bf16_t* A, int B, int ntok, const bf16_t* W, const float* b, int nseg, int seg_base, int npad_q, int npad_kv,

@@ -521,3 +521,109 @@ def row_softmax(s: torch.Tensor, guard_rows: int = 2):
   guard = buf[rows:].clone()
   N.check(N.lib().gill_op_row_softmax(N.ptr(buf), rows, n, N.current_stream()))
   return buf[:rows].clone(), buf[rows:].clone(), guard
+
+
+# ---- the kernels at the ends of the engines (tests/test_ends_gpu.py).  Every output is NaN-prefilled and followed by GUARD_WORDS sentinel elements
+# in the same allocation; each wrapper returns, last, whether those still hold what they were filled with.
+GUARD_WORDS = 256
+_GUARD_VALUE = -12352.0      # exact in bf16
+
+
+def _guarded(shape, dtype, device):
+  n = 1
+  for d in shape:
+    n *= int(d)
+  buf = torch.full((n + GUARD_WORDS,), float("nan"), device=device, dtype=dtype)
+  buf[n:] = _GUARD_VALUE
+  return buf, buf[:n].view(*shape)
+
+
+def _guard_ok(buf: torch.Tensor) -> bool:
+  return bool((buf[-GUARD_WORDS:] == _GUARD_VALUE).all())
+
+
+def conv_out(x: torch.Tensor, w_oihw: torch.Tensor, bias: Optional[torch.Tensor] = None, force_general: bool = False):
+  """conv_out of the UNet / VAE (gill_op_conv_out): x (B,H,W,Cin) bf16 NHWC, w (Cout,Cin,3,3) fp32 | fp16 | bf16, bias (Cout) or None ->
+  (y (B,Cout,H,W) fp32, path, guard_ok); path: 0 one wave per pixel, 1 MFMA with a run-time K loop, 2 | 4 | 10 MFMA with that compile-time KS."""
+  x = _bf(x)
+  B, H, W, Cin = x.shape
+  w = w_oihw.contiguous()
+  Cout = w.shape[0]
+  assert tuple(w.shape) == (Cout, Cin, 3, 3) and w.dtype in N._DTYPES
+  bias = None if bias is None else bias.float().contiguous()
+  buf, y = _guarded((B, Cout, H, W), torch.float32, x.device)
+  path = ctypes.c_int(-1)
+  N.check(N.lib().gill_op_conv_out(N.ptr(x), N.ptr(w), N._DTYPES[w.dtype], N.ptr(bias), N.ptr(buf), B, H, W, Cin, Cout, int(force_general),
+                                   ctypes.byref(path), N.current_stream()))
+  return y, path.value, _guard_ok(buf)
+
+
+def conv_in(x: torch.Tensor, w_oihw: torch.Tensor, bias: Optional[torch.Tensor] = None, counters: Optional[torch.Tensor] = None, nzero: int = 0):
+  """conv_in of the UNet / VAE (gill_op_conv_in: im2col + the K = 64 GEMM): x (B,Cin,H,W) fp32 NCHW, w (Cout,Cin,3,3) -> (y (B,H,W,Cout) bf16
+  NHWC, guard_ok).  counters: an int32 tensor whose first nzero words the im2col launch clears (in place)."""
+  assert x.dtype == torch.float32 and x.is_cuda
+  x = x.contiguous()
+  B, Cin, H, W = x.shape
+  w = w_oihw.contiguous()
+  Cout = w.shape[0]
+  assert tuple(w.shape) == (Cout, Cin, 3, 3) and w.dtype in N._DTYPES
+  bias = None if bias is None else bias.float().contiguous()
+  assert counters is None or (counters.dtype == torch.int32 and counters.numel() >= nzero)
+  buf, y = _guarded((B, H, W, Cout), torch.bfloat16, x.device)
+  N.check(N.lib().gill_op_conv_in(N.ptr(x), N.ptr(w), N._DTYPES[w.dtype], N.ptr(bias), N.ptr(buf), B, Cin, H, W, Cout, N.ptr(counters), int(nzero),
+                                  N.current_stream()))
+  return y, _guard_ok(buf)
+
+
+def timestep_embed(t: torch.Tensor, dim: int):
+  """diffusers Timesteps (gill_op_timestep_embed): t (n) fp32 -> (out (n, dim) bf16 = [cos | sin], guard_ok)."""
+  assert t.dtype == torch.float32 and t.is_cuda and t.dim() == 1
+  t = t.contiguous()
+  buf, out = _guarded((t.numel(), dim), torch.bfloat16, t.device)
+  N.check(N.lib().gill_op_timestep_embed(N.ptr(t), t.numel(), int(dim), N.ptr(buf), N.current_stream()))
+  return out, _guard_ok(buf)
+
+
+def reduce_ln(ws: torch.Tensor, sk: int, bias: torch.Tensor, h: torch.Tensor, g: torch.Tensor, b: torch.Tensor, eps: float = 1e-5):
+  """The transformer block's split-K reducer + bias + fp32 residual + LayerNorm (gill_op_reduce_ln): ws (>= sk, M, D) fp32 of which the first sk
+  slices are summed, h (M, D) fp32 (not modified: the kernel updates a copy) -> (new h (M,D) fp32, nb (M,D) bf16, guard_ok)."""
+  M, D = h.shape
+  assert ws.dtype == torch.float32 and ws.is_cuda and ws.is_contiguous() and ws.shape[0] >= sk and tuple(ws.shape[1:]) == (M, D)
+  f = lambda x: x.float().contiguous()   # noqa: E731
+  bias, g, b = f(bias), f(g), f(b)
+  hbuf, hn = _guarded((M, D), torch.float32, h.device)
+  hn.copy_(h)
+  nbuf, nb = _guarded((M, D), torch.bfloat16, h.device)
+  N.check(N.lib().gill_op_reduce_ln(N.ptr(ws), int(sk), M, D, N.ptr(bias), N.ptr(hbuf), N.ptr(g), N.ptr(b), N.ptr(nbuf), float(eps),
+                                    N.current_stream()))
+  return hn, nb, _guard_ok(hbuf) and _guard_ok(nbuf)
+
+
+def linear_reduce_ln(a: torch.Tensor, w: torch.Tensor, bias: torch.Tensor, h: torch.Tensor, g: torch.Tensor, b: torch.Tensor, splitk: int,
+                     fuse: bool):
+  """h + a @ w.T + bias into the fp32 stream and the LayerNorm (eps 1e-5) behind it, split `splitk` ways, as the pre-LN transformer block runs it
+  (gill_op_linear_reduce_ln): fuse=True partials + the reducer of reduce_ln, fuse=False the GEMM's own reducer + the stand-alone LayerNorm.
+  a (M,K) bf16, w (N,K) bf16, h (M,N) fp32 (not modified) -> (new h, nb (M,N) bf16, guard_ok)."""
+  a, w = _bf(a), _bf(w)
+  M, K = a.shape
+  Nn = w.shape[0]
+  assert tuple(h.shape) == (M, Nn) and w.shape[1] == K
+  f = lambda x: x.float().contiguous()   # noqa: E731
+  bias, g, b = f(bias), f(g), f(b)
+  hbuf, hn = _guarded((M, Nn), torch.float32, a.device)
+  hn.copy_(h)
+  nbuf, nb = _guarded((M, Nn), torch.bfloat16, a.device)
+  N.check(N.lib().gill_op_linear_reduce_ln(N.ptr(a), N.ptr(w), N.ptr(bias), N.ptr(hbuf), N.ptr(g), N.ptr(b), N.ptr(nbuf), M, Nn, K, int(splitk),
+                                           int(bool(fuse)), N.current_stream()))
+  return hn, nb, _guard_ok(hbuf) and _guard_ok(nbuf)
+
+
+def skinny_gemm(x: torch.Tensor, w: torch.Tensor):
+  """The lm_head GEMV (gill_op_skinny_gemm): x (M,K) bf16, w (N,K) bf16 -> (out (M,N) fp32, guard_ok)."""
+  x, w = _bf(x), _bf(w)
+  M, K = x.shape
+  Nn = w.shape[0]
+  assert w.shape[1] == K
+  buf, out = _guarded((M, Nn), torch.float32, x.device)
+  N.check(N.lib().gill_op_skinny_gemm(N.ptr(x), N.ptr(w), N.ptr(buf), M, Nn, K, N.current_stream()))
+  return out, _guard_ok(buf)

@@ -519,6 +519,31 @@ int gill_op_sd_sampler_run_from(const gill_sd_sampler* sampler, int v_prediction
                                 const float* latents0, const float* init_noise, const float* model_out, const float* noise, int B, int64_t n,
                                 float* lat_out, float* unet_in_out, void* stream);
 
+/* The kernels at the ends of the engines, each launched the way its engine launches it.  All synchronise.  For the operator tests.
+ * conv_out (the UNet's predicted noise, the VAE's image and moments): x (B,H,W,Cin) bf16 NHWC, w (Cout,Cin,3,3) of w_dtype (GILL_DTYPE_*), optional
+ * bias (Cout) fp32 -> y (B,Cout,H,W) fp32, 3x3 / pad 1.  The weights are re-laid as the loaders do; *path = the kernel that ran: 0 one wave per
+ * pixel, 1 the matrix-pipe kernel with a run-time K loop, 2 | 4 | 10 the same with Cin / 32 fixed at compile time.  force_general: always path 0. */
+int gill_op_conv_out(const void* x_bf16, const void* w_oihw, int w_dtype, const float* bias, float* y_f32, int B, int H, int W, int Cin, int Cout,
+                     int force_general, int* path, void* stream);
+/* conv_in of the UNet and the VAE: x (B,Cin,H,W) fp32 NCHW, w (Cout,Cin,3,3) of w_dtype, optional bias -> y (B,H,W,Cout) bf16 NHWC, as im2col
+ * (pixels rounded to bf16, K = 9 Cin zero-padded to 64: 9 Cin <= 64, an error otherwise) + one GEMM.  counters (optional, ncounters 32-bit words):
+ * cleared by the im2col launch, as the UNet forward clears its arrival counters. */
+int gill_op_conv_in(const float* x_f32, const void* w_oihw, int w_dtype, const float* bias, void* y_bf16, int B, int Cin, int H, int W, int Cout,
+                    uint32_t* counters, int ncounters, void* stream);
+/* diffusers Timesteps(dim, flip_sin_to_cos = True, downscale_freq_shift = 0): t (n) fp32 -> out (n, dim) bf16 = [cos(t f_i) | sin(t f_i)],
+ * f_i = 10000^(-i / (dim / 2)); dim even (an error otherwise). */
+int gill_op_timestep_embed(const float* t, int n, int dim, void* out_bf16, void* stream);
+/* The pre-LN transformer block's split-K reducer (csrc/tfm.hip): h (M,D) fp32 += sum of the sk slices of ws (sk,M,D) fp32 in slice order + bias,
+ * in place; nb (M,D) bf16 = LayerNorm(h; g, b, eps).  D a multiple of 4, at most 8192 (an error otherwise). */
+int gill_op_reduce_ln(const float* ws, int sk, int M, int D, const float* bias, float* h, const float* g, const float* b, void* nb_bf16, float eps,
+                      void* stream);
+/* h (M,N) fp32 += A (M,K) bf16 . W (N,K)^T + bias in place and nb (M,N) bf16 = LayerNorm(h; g, b, 1e-5), split `splitk` > 1 ways, the two ways
+ * the block runs it: fuse = 1 partials + the reducer above, fuse = 0 the GEMM's own reducer + the stand-alone LayerNorm. */
+int gill_op_linear_reduce_ln(const void* A_bf16, const void* W_bf16, const float* bias, float* h, const float* g, const float* b, void* nb_bf16,
+                             int M, int N, int K, int splitk, int fuse, void* stream);
+/* The tied lm_head: out (M,N) fp32 = x (M,K) bf16 . W (N,K)^T, 1 <= M <= 8, K a multiple of 8 (an error otherwise). */
+int gill_op_skinny_gemm(const void* x_bf16, const void* W_bf16, float* out_f32, int M, int N, int K, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
