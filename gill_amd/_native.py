@@ -109,6 +109,10 @@ SYMBOLS: Dict[str, Tuple[object, List[object]]] = {
                                  C.POINTER(C.c_double)]),
   "gill_sd_denoise_from": (_i, [_vp, _vp, _vp, _vp, _i, _i, _vp, _vp, _i, _i, _f, _vp, _vp, _vp]),
   "gill_op_sd_sampler_run_from": (_i, [_vp, _i, _i, _i, _f, _vp, _vp, _vp, _vp, _i, C.c_int64, _vp, _vp, _vp]),
+  "gill_sd_inpaint_prepare": (_i, [_vp, _vp, _i, _i, _i, _i, _vp, _vp, _vp]),
+  "gill_sd_inpaint_keep": (_i, [_vp, _i, _i, _i, C.POINTER(C.c_double)]),
+  "gill_sd_inpaint": (_i, [_vp, _vp, _vp, _vp, _i, _i, _vp, _vp, _vp, _vp, _i, _i, _f, _vp, _vp, _vp]),
+  "gill_op_sd_inpaint_run": (_i, [_vp, _i, _i, _i, _f, _vp, _vp, _vp, _vp, _vp, _vp, _i, C.c_int64, C.c_int64, _vp, _vp, _vp]),
   "gill_op_conv3x3_ex": (_i, [_vp, _i, _vp, _i, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _vp]),
   "gill_op_conv3x3_fp8": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp]),
   "gill_pndm_schedule": (_i, [_i, C.POINTER(C.c_int32), C.POINTER(C.c_double)]),
@@ -138,6 +142,7 @@ SYMBOLS: Dict[str, Tuple[object, List[object]]] = {
   "gill_op_row_softmax": (_i, [_vp, _i, _i, _vp]),
   "gill_op_conv_out": (_i, [_vp, _vp, _i, _vp, _vp, _i, _i, _i, _i, _i, _i, C.POINTER(C.c_int), _vp]),
   "gill_op_conv_in": (_i, [_vp, _vp, _i, _vp, _vp, _i, _i, _i, _i, _i, _vp, _i, _vp]),
+  "gill_op_conv_in_wide": (_i, [_vp, _vp, _i, _vp, _vp, _i, _i, _i, _i, _i, _vp, _i, _vp]),
   "gill_op_timestep_embed": (_i, [_vp, _i, _i, _vp, _vp]),
   "gill_op_reduce_ln": (_i, [_vp, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _f, _vp]),
   "gill_op_linear_reduce_ln": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp]),

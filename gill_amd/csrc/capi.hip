@@ -473,28 +473,38 @@ extern "C" int gill_op_conv_out(const void* x_bf16, const void* w_oihw, int w_dt
   return 0;
 }
 
-extern "C" int gill_op_conv_in(const float* x_f32, const void* w_oihw, int w_dtype, const float* bias, void* y_bf16, int B, int Cin, int H, int W,
-                               int Cout, uint32_t* counters, int ncounters, void* stream) {
-  hipStream_t s = (hipStream_t)stream;
-  GILL_REQUIRE(x_f32 && w_oihw && y_bf16 && B > 0 && Cin > 0 && H > 0 && W > 0 && Cout > 0 && ncounters >= 0, "conv_in: bad argument");
-  GILL_REQUIRE(Cin * 9 <= 64, "conv_in: in_channels * 9 must fit one 64-wide K step");
-  const int M = B * H * W;
-  DevBuf tmp, w64, col;
+// conv_in as the engines run it, K = conv_in_kpad(Cin): one 64-wide step up to 7 input channels, two up to 14 (the inpainting UNet's 9)
+static int op_conv_in(const float* x_f32, const void* w_oihw, int w_dtype, const float* bias, void* y_bf16, int B, int Cin, int H, int W, int Cout,
+                      uint32_t* counters, int ncounters, hipStream_t s) {
+  const int M = B * H * W, kpad = conv_in_kpad(Cin);
+  DevBuf tmp, wk, col;
   GILL_TRY(tmp.alloc(sizeof(bf16_t) * (size_t)Cout * 9 * Cin));
-  GILL_TRY(w64.alloc_zero(sizeof(bf16_t) * (size_t)Cout * 64, s));
-  GILL_TRY(col.alloc(sizeof(bf16_t) * (size_t)M * 64));
-  GILL_TRY(conv_in_im2col_weight(w_oihw, w_dtype, Cin, Cout, (bf16_t*)tmp.p, (bf16_t*)w64.p, s));
-  GemmArgs g;      // the UNet's linear(col, 64, ...)
-  g.M = M; g.N = Cout; g.K = 64; g.K1 = 64; g.A = (const bf16_t*)col.p; g.lda = 64; g.W = (const bf16_t*)w64.p; g.bias = bias;
+  GILL_TRY(wk.alloc_zero(sizeof(bf16_t) * (size_t)Cout * kpad, s));      // rows of kpad: what conv_in_im2col_weight writes
+  GILL_TRY(col.alloc(sizeof(bf16_t) * (size_t)M * kpad));
+  GILL_TRY(conv_in_im2col_weight(w_oihw, w_dtype, Cin, Cout, (bf16_t*)tmp.p, (bf16_t*)wk.p, s));
+  GemmArgs g;      // the UNet's linear(col, kpad, ...)
+  g.M = M; g.N = Cout; g.K = kpad; g.K1 = kpad; g.A = (const bf16_t*)col.p; g.lda = kpad; g.W = (const bf16_t*)wk.p; g.bias = bias;
   g.ldr = Cout; g.act = ACT_NONE; g.C = y_bf16; g.ldc = Cout;
-  g.splitk = gemm_pick_splitk(M, Cout, 64, ACT_NONE, true);
-  GILL_REQUIRE(g.splitk == 1, "conv_in: one K step cannot split");
+  g.splitk = gemm_pick_splitk(M, Cout, kpad, ACT_NONE, true);
+  GILL_REQUIRE(g.splitk == 1, "conv_in: one or two K steps cannot split");
   for (int r = 0; r < op_repeat(); ++r) {
-    GILL_TRY(im2col_nchw_launch(x_f32, B, Cin, H, W, 64, (bf16_t*)col.p, s, counters, ncounters));
+    GILL_TRY(im2col_nchw_launch(x_f32, B, Cin, H, W, kpad, (bf16_t*)col.p, s, counters, ncounters));
     GILL_TRY(gemm_launch(g, s));
   }
   GILL_CHECK_HIP(hipStreamSynchronize(s));
   return 0;
+}
+extern "C" int gill_op_conv_in(const float* x_f32, const void* w_oihw, int w_dtype, const float* bias, void* y_bf16, int B, int Cin, int H, int W,
+                               int Cout, uint32_t* counters, int ncounters, void* stream) {
+  GILL_REQUIRE(x_f32 && w_oihw && y_bf16 && B > 0 && Cin > 0 && H > 0 && W > 0 && Cout > 0 && ncounters >= 0, "conv_in: bad argument");
+  GILL_REQUIRE(Cin * 9 <= 64, "conv_in: in_channels * 9 must fit one 64-wide K step");      // (this entry stays the K = 64 form)
+  return op_conv_in(x_f32, w_oihw, w_dtype, bias, y_bf16, B, Cin, H, W, Cout, counters, ncounters, (hipStream_t)stream);
+}
+extern "C" int gill_op_conv_in_wide(const float* x_f32, const void* w_oihw, int w_dtype, const float* bias, void* y_bf16, int B, int Cin, int H,
+                                    int W, int Cout, uint32_t* counters, int ncounters, void* stream) {
+  GILL_REQUIRE(x_f32 && w_oihw && y_bf16 && B > 0 && Cin > 0 && H > 0 && W > 0 && Cout > 0 && ncounters >= 0, "conv_in: bad argument");
+  GILL_REQUIRE(Cin <= CONV_IN_MAX_CIN, "conv_in: in_channels must be 1 .. 14 (9 * in_channels fits two 64-wide K steps)");
+  return op_conv_in(x_f32, w_oihw, w_dtype, bias, y_bf16, B, Cin, H, W, Cout, counters, ncounters, (hipStream_t)stream);
 }
 
 extern "C" int gill_op_timestep_embed(const float* t, int n, int dim, void* out_bf16, void* stream) {

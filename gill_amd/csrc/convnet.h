@@ -60,7 +60,10 @@ int load_norm(const WeightTable& wt, DevPool& pool, hipStream_t s, const std::st
 // GILL_CONV_UPS4 = 0 keeps the 9-tap gather over the upsampled grid)
 int load_conv3(const WeightTable& wt, DevPool& pool, hipStream_t s, const std::string& p, int cin, int cout, int hw, ConvW* c,
                bool f8 = false, bool ups4 = false);
-// conv_in as im2col + the MFMA GEMM: weights [cout][tap*cin + c], K = 9 cin zero-padded to one 64-wide K step
+// conv_in as im2col + the MFMA GEMM: weights [cout][tap*cin + c], K = 9 cin zero-padded to whole 64-wide K steps: 64 up to 7 input channels (the
+// UNet's 4, the VAE's 3 and 4), 128 up to 14 (the 9-channel inpainting UNet)
+constexpr int CONV_IN_MAX_CIN = 14;
+static inline int conv_in_kpad(int cin) { return (9 * cin + 63) / 64 * 64; }
 // the part behind the weight lookup: OIHW of any loader dtype -> tmp [cout][9][cin] -> the first 9 cin columns of w64 [cout][64] (zeroed by the caller)
 int conv_in_im2col_weight(const void* w_oihw, int dtype, int cin, int cout, bf16_t* tmp, bf16_t* w64, hipStream_t s);
 int load_conv_in_im2col(const WeightTable& wt, DevPool& pool, hipStream_t s, const std::string& p, int cin, int cout, bf16_t** w, float** b);

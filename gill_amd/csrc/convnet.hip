@@ -48,17 +48,17 @@ int copy_rows_bf16(const bf16_t* src, int rows, int cols, bf16_t* dst, int dst_l
 
 int conv_in_im2col_weight(const void* w_oihw, int dtype, int cin, int cout, bf16_t* tmp, bf16_t* w64, hipStream_t s) {
   GILL_TRY(conv_weight_relayout_launch(w_oihw, dtype, cout, cin, tmp, s));
-  return copy_rows_bf16(tmp, cout, cin * 9, w64, 64, s);
+  return copy_rows_bf16(tmp, cout, cin * 9, w64, conv_in_kpad(cin), s);
 }
 
 int load_conv_in_im2col(const WeightTable& wt, DevPool& pool, hipStream_t s, const std::string& p, int cin, int cout, bf16_t** w, float** b) {
   const int kk = cin * 9;
-  GILL_REQUIRE(kk <= 64, "conv_in: in_channels * 9 must fit one 64-wide K step");
+  GILL_REQUIRE(cin >= 1 && cin <= CONV_IN_MAX_CIN, "conv_in: in_channels must be 1 .. 14 (9 * in_channels fits two 64-wide K steps)");
   const gill_tensor* t;
   bf16_t* tmp;
   GILL_TRY(wt.get(p + ".weight", (int64_t)cout * kk, &t));
   GILL_TRY(pool.alloc(&tmp, (size_t)cout * kk, false));
-  GILL_TRY(pool.alloc(w, (size_t)cout * 64, true));
+  GILL_TRY(pool.alloc(w, (size_t)cout * conv_in_kpad(cin), true));
   GILL_TRY(conv_in_im2col_weight(t->data, t->dtype, cin, cout, tmp, *w, s));
   return load_f32(wt, pool, p + ".bias", cout, b, s);
 }

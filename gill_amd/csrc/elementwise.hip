@@ -512,6 +512,88 @@ int add_noise_f32_launch(const float* x, const float* z, float a, float b, int64
   return 0;
 }
 
+// ---------------------------------------------------------------- inpainting (include/gill_amd.h gill_sd_inpaint)
+// mask preprocessing: mb = mask >= 0.5 (1 = repaint);  masked = image * (1 - mb);  latent mask = mb at the top-left pixel of every 8 x 8 cell
+// (torch's nearest interpolation for a factor of exactly 8)
+__global__ __launch_bounds__(256) void inpaint_prepare_kernel(const float* __restrict__ image, const float* __restrict__ mask, int B, int Bm, int H,
+                                                              int W, float* __restrict__ masked, float* __restrict__ lmask) {
+  const int64_t plane = (int64_t)H * W, total = (int64_t)B * 3 * plane;
+  const int64_t stride = (int64_t)gridDim.x * blockDim.x, t0 = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  for (int64_t i = t0; i < total; i += stride) {
+    const int64_t b = i / (3 * plane), p = i % plane;
+    const float mb = mask[(Bm == 1 ? 0 : b) * plane + p] >= 0.5f ? 1.f : 0.f;
+    masked[i] = image[i] * (1.f - mb);
+  }
+  const int Lh = H / 8, Lw = W / 8;
+  const int64_t ltotal = (int64_t)B * Lh * Lw;
+  for (int64_t i = t0; i < ltotal; i += stride) {
+    const int64_t b = i / ((int64_t)Lh * Lw);
+    const int y = (int)((i / Lw) % Lh), x = (int)(i % Lw);
+    lmask[i] = mask[(Bm == 1 ? 0 : b) * plane + (int64_t)(8 * y) * W + 8 * x] >= 0.5f ? 1.f : 0.f;
+  }
+}
+int inpaint_prepare_launch(const float* image, const float* mask, int B, int Bm, int H, int W, float* masked, float* lmask, hipStream_t s) {
+  GILL_REQUIRE(B >= 1 && (Bm == 1 || Bm == B), "inpaint_prepare: the mask's batch must be 1 or B");
+  GILL_REQUIRE(H >= 8 && W >= 8 && H % 8 == 0 && W % 8 == 0, "inpaint_prepare: H and W must be positive multiples of 8");
+  hipLaunchKernelGGL(inpaint_prepare_kernel, dim3(grid_for((int64_t)B * 3 * H * W)), dim3(256), 0, s, image, mask, B, Bm, H, W, masked, lmask);
+  GILL_CHECK_HIP(hipGetLastError());
+  return 0;
+}
+
+// blend mode: after the step kernel of call `step`, lat = m * lat + (1 - m) * (ka * x0 + kb * z0) with (ka, kb) = keep[step].  Reads ctr[1] (this
+// step's index, written by the stage kernel): ctr[0] has already been advanced by the step kernel.
+__global__ __launch_bounds__(256) void sd_blend_kernel(const SdInpaintArgs a) {
+  kernarg_warm<sizeof(SdInpaintArgs)>();
+  const int step = a.l.ctr[1];
+  const float ka = a.keep[2 * step], kb = a.keep[2 * step + 1];
+  const int64_t total = (int64_t)a.l.B * a.l.n;
+  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (int64_t)gridDim.x * blockDim.x) {
+    const int64_t b = i / a.l.n, r = i - b * a.l.n;
+    const float m = a.mask[b * a.hw + r % a.hw];      // one mask plane per sample, broadcast over the channels
+    // the kept value within one fp32 ulp of ka * x0 + kb * z0 even where the two terms cancel: both products are exact in double, so the sum is
+    // rounded once to double and once to fp32 (this kernel is bound by its five memory streams, not by the two fp64 operations)
+    const float keep = (float)((double)ka * (double)a.x0[i] + (double)kb * (double)a.z0[i]);
+    a.l.lat[i] = m * a.l.lat[i] + (1.f - m) * keep;
+  }
+}
+int sd_blend_launch(const SdInpaintArgs& a, hipStream_t s) {
+  GILL_REQUIRE(a.keep && a.x0 && a.z0 && a.mask && a.hw >= 1 && a.l.n % a.hw == 0, "sd_blend: keep table, x0, z0, mask and hw | n required");
+  hipLaunchKernelGGL(sd_blend_kernel, dim3(grid_for((int64_t)a.l.B * a.l.n)), dim3(256), 0, s, a);
+  GILL_CHECK_HIP(hipGetLastError());
+  return 0;
+}
+
+// concat mode: sd_stage_kernel with the UNet input [in_scale * lat (C) | m (1) | xm (C)] per sample, n_in = (2 C + 1) hw floats, C = n / hw
+__global__ __launch_bounds__(256) void sd_stage_concat_kernel(const SdInpaintArgs a) {
+  kernarg_warm<sizeof(SdInpaintArgs)>();
+  const int step = a.l.ctr[0];          // nobody writes ctr[0] while this kernel runs
+  const int64_t n = a.l.n, hw = a.hw, n_in = 2 * n + hw;
+  const int64_t total = (int64_t)a.l.B * n_in;
+  const int64_t stride = (int64_t)gridDim.x * blockDim.x;
+  const int64_t t0 = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  const float in_scale = a.l.srows ? a.l.srows[step].in_scale : 1.f;
+  for (int64_t i = t0; i < total; i += stride) {
+    const int64_t b = i / n_in, r = i - b * n_in;
+    float v;
+    if (r < n) {
+      v = a.l.lat[b * n + r];
+      if (a.l.srows) v *= in_scale;
+    } else if (r < n + hw) v = a.mask[b * hw + (r - n)];
+    else v = a.xm[b * n + (r - n - hw)];
+    a.l.lat2[i] = v;
+    if (a.l.cfg) a.l.lat2[total + i] = v;
+  }
+  const float* row = a.l.temb_table + (size_t)step * a.l.temb_total;
+  for (int64_t i = t0; i < a.l.temb_total; i += stride) a.l.temb_cur[i] = row[i];
+  if (t0 == 0) a.l.ctr[1] = step;
+}
+int sd_stage_concat_launch(const SdInpaintArgs& a, hipStream_t s) {
+  GILL_REQUIRE(a.mask && a.xm && a.hw >= 1 && a.l.n % a.hw == 0, "sd_stage_concat: mask, masked-image latents and hw | n required");
+  hipLaunchKernelGGL(sd_stage_concat_kernel, dim3(grid_for((int64_t)a.l.B * (2 * a.l.n + a.hw))), dim3(256), 0, s, a);
+  GILL_CHECK_HIP(hipGetLastError());
+  return 0;
+}
+
 // ---------------------------------------------------------------- weight conversion / re-layout (creation time)
 __device__ __forceinline__ float load_as_f32(const void* p, int dtype, int64_t i) {
   if (dtype == 0) return bf2f(((const bf16_t*)p)[i]);

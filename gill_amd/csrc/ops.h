@@ -347,6 +347,23 @@ int sampler_step_launch(const SdLoopArgs& a, hipStream_t s);
 int scale_f32_launch(const float* src, float scale, int64_t n, float* dst, hipStream_t s);
 // dst = a * x + b * z over n floats (the schedulers' add_noise: the first kernel of an image-to-image loop)
 int add_noise_f32_launch(const float* x, const float* z, float a, float b, int64_t n, float* dst, hipStream_t s);
+// Inpainting (include/gill_amd.h gill_sd_inpaint).  The loop's arguments plus the inpaint fields, as a struct of its own: SdLoopArgs, and with it
+// the argument block of the three loop kernels above, stays what it was.
+struct SdInpaintArgs {
+  SdLoopArgs l;          // l.n = C * hw: the LATENTS' floats per sample (the UNet input of concat mode has (2 C + 1) * hw)
+  const float* x0 = nullptr;     // [B][n] scaled VAE latents of the image (blend)
+  const float* z0 = nullptr;     // [B][n] the add-noise draw that formed the start (blend)
+  const float* mask = nullptr;   // [B][hw] latent mask, 1 = repaint
+  const float* xm = nullptr;     // [B][n] scaled VAE latents of the masked image (concat)
+  const float* keep = nullptr;   // [ncalls][2] on device: add_noise pair at the noise level the latents have after each call (blend)
+  int64_t hw = 0;
+};
+// image (B,3,H,W), mask (Bm,1,H,W), Bm 1 or B -> masked image (B,3,H,W) = image * (mask < 0.5), latent mask (B,1,H/8,W/8) = mask[8y][8x] >= 0.5
+int inpaint_prepare_launch(const float* image, const float* mask, int B, int Bm, int H, int W, float* masked, float* lmask, hipStream_t s);
+// blend mode, after the step kernel: lat = m * lat + (1 - m) * (ka * x0 + kb * z0), (ka, kb) = keep[ctr[1]]
+int sd_blend_launch(const SdInpaintArgs& a, hipStream_t s);
+// concat mode, in place of sd_stage_launch: lat2 = [in_scale * lat | mask | xm] per sample, both CFG halves; the rest as sd_stage_launch
+int sd_stage_concat_launch(const SdInpaintArgs& a, hipStream_t s);
 
 // weight re-layout helpers (run once at engine creation)
 int conv_weight_relayout_launch(const void* w, int dtype, int Cout, int Cin, bf16_t* out /*[Cout][9][Cin]*/, hipStream_t s);   // conv_in / conv_out

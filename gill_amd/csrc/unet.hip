@@ -65,10 +65,12 @@ struct RowStats { float* p = nullptr; int planes = 1; };
 struct GraphKey {     // (the guidance scale and the noise table's address are device-side scalars, not part of the captured step)
   int Bx, cfg;
   int linear;         // which step kernel the step ends with: 0 plms_step_kernel, 1 sampler_step_kernel (and the stage kernel's row table)
+  int inpaint;        // 0: none (text-to-image, image-to-image), 1: sd_blend_kernel after the step kernel, 2: sd_stage_concat_kernel stages
   bool operator<(const GraphKey& o) const {
     if (Bx != o.Bx) return Bx < o.Bx;
     if (cfg != o.cfg) return cfg < o.cfg;
-    return linear < o.linear;
+    if (linear != o.linear) return linear < o.linear;
+    return inpaint < o.inpaint;
   }
 };
 
@@ -108,7 +110,7 @@ struct gill_unet : ConvWorkspace {
   int temb_rows_cap = 0;
   // loop state
   float* lat = nullptr;         // [B][4*L*L]
-  float* lat2 = nullptr;        // [2B][4*L*L]
+  float* lat2 = nullptr;        // [2B][in_channels*L*L]: the UNet input (9 channels on an inpainting UNet; everything else here has out_channels)
   float* eps = nullptr;         // [2B][4*L*L]
   float* cur_sample = nullptr;
   float* ets = nullptr;         // [4][B][4*L*L]
@@ -119,6 +121,12 @@ struct gill_unet : ConvWorkspace {
   const float** noise_slot = nullptr;   // [1]: address of the running loop's noise table (SdLoopArgs::noise)
   int* step_ctr = nullptr;      // [2]: next / current step of the running loop (SdLoopArgs::ctr)
   float* guidance_dev = nullptr; // [1]: guidance scale of the running loop (SdLoopArgs::guidance)
+  // inpainting (gill_sd_inpaint): the running loop's operands, copied here so that the captured step holds the handle's addresses
+  float* inp_x0 = nullptr;      // [B][4*L*L] image latents
+  float* inp_z0 = nullptr;      // [B][4*L*L] add-noise draw
+  float* inp_xm = nullptr;      // [B][4*L*L] masked-image latents (concat mode)
+  float* inp_mask = nullptr;    // [B][L*L]
+  float* keep_rows = nullptr;   // [temb_rows_cap][2] (SdInpaintArgs::keep)
   // hipGraph of one UNet forward per UNet batch size (captured after the first eager forward of that size)
   std::map<GraphKey, hipGraphExec_t> graphs;
   std::set<GraphKey> warmed;
@@ -935,11 +943,12 @@ struct UNetRun : ConvRun {
     std::vector<Tensor> skips;
     Tensor x = talloc(L, L, ch[0], true);
     {
-      // conv_in: im2col (K = 9*Cin padded to 64) + MFMA GEMM
+      // conv_in: im2col (K = 9*Cin padded to whole 64-wide steps: 64 for 4 channels, 128 for the inpainting UNet's 9) + MFMA GEMM
       const size_t mk = m->arena.mark();
-      bf16_t* col = (bf16_t*)m->arena.alloc(sizeof(bf16_t) * (size_t)Bx * L * L * 64);
-      if (!dry) GILL_TRY(im2col_nchw_launch(sample, Bx, c.in_channels, L, L, 64, col, s, m->coop_ctr, (int)m->coop_n));
-      GILL_TRY(linear(col, 64, nullptr, 0, 64, Bx * L * L, m->conv_in_w, m->conv_in_b, ch[0], 64, nullptr, ACT_NONE, x.p, ch[0], &x));
+      const int kpad = conv_in_kpad(c.in_channels);
+      bf16_t* col = (bf16_t*)m->arena.alloc(sizeof(bf16_t) * (size_t)Bx * L * L * kpad);
+      if (!dry) GILL_TRY(im2col_nchw_launch(sample, Bx, c.in_channels, L, L, kpad, col, s, m->coop_ctr, (int)m->coop_n));
+      GILL_TRY(linear(col, kpad, nullptr, 0, kpad, Bx * L * L, m->conv_in_w, m->conv_in_b, ch[0], kpad, nullptr, ACT_NONE, x.p, ch[0], &x));
       m->arena.release(mk);
     }
     skips.push_back(x);
@@ -1026,7 +1035,7 @@ static int unet_plan_and_alloc(gill_unet* m) {
   const gill_unet_config& c = m->cfg;
   const int Bx = c.max_batch;
   const int L = c.sample_size;
-  const size_t n_lat = (size_t)c.in_channels * L * L;
+  const size_t n_lat = (size_t)c.out_channels * L * L, n_in = (size_t)c.in_channels * L * L;
   m->ctx_pad = round_up(c.ctx_len, 64);     // whole 64-key tiles: the LDS-DMA attention kernel streams them unclamped (attention.hip)
   // dry run to size the activation arena
   m->arena.dry = true; m->arena.off = 0; m->arena.high = 0;
@@ -1083,7 +1092,7 @@ static int unet_plan_and_alloc(gill_unet* m) {
   GILL_TRY(m->pool.alloc(&m->temb_table, (size_t)m->temb_rows_cap * m->temb_total));
   // loop state
   GILL_TRY(m->pool.alloc(&m->lat, (size_t)Bx * n_lat));
-  GILL_TRY(m->pool.alloc(&m->lat2, (size_t)Bx * n_lat));
+  GILL_TRY(m->pool.alloc(&m->lat2, (size_t)Bx * n_in));
   GILL_TRY(m->pool.alloc(&m->eps, (size_t)Bx * n_lat));
   GILL_TRY(m->pool.alloc(&m->cur_sample, (size_t)Bx * n_lat));
   GILL_TRY(m->pool.alloc(&m->ets, (size_t)4 * Bx * n_lat));
@@ -1094,6 +1103,15 @@ static int unet_plan_and_alloc(gill_unet* m) {
   GILL_TRY(m->pool.alloc(&m->noise_slot, (size_t)1));
   GILL_TRY(m->pool.alloc(&m->step_ctr, (size_t)2));
   GILL_TRY(m->pool.alloc(&m->guidance_dev, (size_t)4));
+  // inpainting operands, by the mode this handle can run (a loop without CFG holds max_batch samples)
+  GILL_TRY(m->pool.alloc(&m->inp_mask, (size_t)Bx * L * L));
+  if (c.in_channels == c.out_channels) {      // blend
+    GILL_TRY(m->pool.alloc(&m->inp_x0, (size_t)Bx * n_lat));
+    GILL_TRY(m->pool.alloc(&m->inp_z0, (size_t)Bx * n_lat));
+    GILL_TRY(m->pool.alloc(&m->keep_rows, (size_t)m->temb_rows_cap * 2));
+  } else {                                    // concat
+    GILL_TRY(m->pool.alloc(&m->inp_xm, (size_t)Bx * n_lat));
+  }
   { const char* e = getenv("GILL_NO_GRAPH"); m->use_graph = !(e && e[0] == '1'); }
   if (getenv("GILL_DEBUG_SYNC")) m->use_graph = false;   // dbg_sync() synchronises the stream after every launch: illegal inside a capture
   return 0;
@@ -1440,10 +1458,47 @@ extern "C" int gill_sd_schedule(const gill_sd_sampler* sampler, int v_prediction
   return gill_sd_schedule_from(sampler, v_prediction, num_steps, 0, timesteps_out, init_noise_sigma_out, rows_out, nullptr);
 }
 
+// Inpainting, blend mode: the add_noise pair (ka, kb) at the noise level the latents have AFTER call i of the table sd_schedule(..., start) builds,
+// so that ka * x0 + kb * z0 is the image at that level.  i < ncalls - 1: the pair at the timestep of call i + 1 (for the linear kinds that equals
+// sd_schedule's own add_noise pair at start + i + 1, built here from the same values without a table per step; for pndm sqrt(abar), sqrt(1 - abar) at the table's timestep i + 1, which repeats after the
+// warm-up pair: calls 0 and 1 both leave the latents at t_s - D).  The last call leaves the clean latents: (1, 0).
+static int sd_inpaint_keep(const gill_sd_sampler* sp, bool vpred, int num_steps, int start, const SdSchedule& sched, std::vector<double>& keep) {
+  const int ncalls = (int)sched.timesteps.size();
+  keep.assign((size_t)ncalls * 2, 0.0);
+  std::vector<float> ac; pndm_alphas_cumprod(ac);
+  std::vector<double> ls;
+  const bool euler = sched.kind == SD_EULER || sched.kind == SD_EULER_A;
+  if (euler) linspace_999(num_steps, ls);
+  for (int i = 0; i + 1 < ncalls; ++i) {
+    if (euler) {      // (1, sigma of full-table step start + i + 1), interpolated as sd_schedule does
+      const double t = ls[num_steps - 1 - (start + i + 1)];
+      int j = (int)floor(t); if (j > 998) j = 998;
+      const double f0 = sqrt((1.0 - (double)ac[j]) / (double)ac[j]), f1 = sqrt((1.0 - (double)ac[j + 1]) / (double)ac[j + 1]);
+      keep[2 * i] = 1.0; keep[2 * i + 1] = (f1 - f0) * (t - (double)j) + f0;
+    } else {          // pndm, ddim, dpmsolver++: integer timesteps (pndm's clamped at 0, as the table's are)
+      const double at = ac[(int)sched.timesteps[i + 1]];
+      keep[2 * i] = sqrt(at); keep[2 * i + 1] = sqrt(1.0 - at);
+    }
+  }
+  keep[2 * (ncalls - 1)] = 1.0; keep[2 * (ncalls - 1) + 1] = 0.0;
+  return 0;
+}
+extern "C" int gill_sd_inpaint_keep(const gill_sd_sampler* sampler, int v_prediction, int num_steps, int start, double* keep_out) {
+  SdSchedule sc;
+  GILL_TRY(sd_schedule(sampler, v_prediction != 0, num_steps, sc, start));
+  std::vector<double> keep;
+  GILL_TRY(sd_inpaint_keep(sampler, v_prediction != 0, num_steps, start, sc, keep));
+  if (keep_out) for (size_t i = 0; i < keep.size(); ++i) keep_out[i] = (double)(float)keep[i];     // the fp32 values the device reads, widened
+  return (int)sc.timesteps.size();
+}
+
 // init_noise != nullptr: image-to-image — the loop starts at step `start` from add_noise(latents0, init_noise) instead of latents0 * init_noise_sigma
+// inpaint (needs init_noise): 1 blend — latent_mask given, the handle's UNet takes the latents alone; 2 concat — latent_mask and masked_latents
+// given, the handle's UNet takes [latents | mask | masked-image latents]
 static int sd_denoise_on(gill_unet* m, const gill_sd_sampler* sampler, const void* cond_bf16, const void* uncond_bf16, int n_uncond,
                          const float* latents0, int B, int num_steps, float guidance, float* latents_out, const float* noise, hipStream_t s,
-                         int start = 0, const float* init_noise = nullptr);
+                         int start = 0, const float* init_noise = nullptr, int inpaint = 0, const float* latent_mask = nullptr,
+                         const float* masked_latents = nullptr);
 
 extern "C" int gill_sd_denoise_ex(gill_unet* m, const gill_sd_sampler* sampler, const void* cond_bf16, const void* uncond_bf16, int n_uncond,
                                   const float* latents0, int B, int num_steps, float guidance, float* latents_out, const float* noise,
@@ -1472,6 +1527,30 @@ extern "C" int gill_sd_denoise_from(gill_unet* m, const gill_sd_sampler* sampler
   GILL_TRY(m->fence.leave(caller));
   return rc;
 }
+extern "C" int gill_sd_inpaint(gill_unet* m, const gill_sd_sampler* sampler, const void* cond_bf16, const void* uncond_bf16, int n_uncond,
+                               int start, const float* init_latents, const float* init_noise, const float* latent_mask,
+                               const float* masked_latents, int B, int num_steps, float guidance, float* latents_out, const float* noise,
+                               void* stream) {
+  GILL_REQUIRE(m && sampler && cond_bf16 && init_latents && init_noise && latent_mask && latents_out, "null argument");
+  GILL_REQUIRE(guidance <= 1.0f || uncond_bf16 == nullptr || n_uncond == 1 || n_uncond == B,
+               "negative embeddings: batch must be 1 or B");
+  const gill_unet_config& c = m->cfg;
+  if (masked_latents)
+    GILL_REQUIRE(c.in_channels == 2 * c.out_channels + 1,
+                 "inpaint: masked_latents given (concat mode), but this handle's UNet does not take [latents | mask | masked-image latents] "
+                 "(in_channels != 2 * out_channels + 1): pass NULL to blend with the mask instead");
+  else
+    GILL_REQUIRE(c.in_channels == c.out_channels,
+                 "inpaint: masked_latents is NULL (blend mode), but this handle's UNet takes more than the latents "
+                 "(in_channels != out_channels): an inpainting UNet needs the masked image's latents");
+  GILL_TRY(unet_coop_check());
+  hipStream_t caller = (hipStream_t)stream;
+  GILL_TRY(m->fence.enter(caller));
+  const int rc = sd_denoise_on(m, sampler, cond_bf16, uncond_bf16, n_uncond, init_latents, B, num_steps, guidance, latents_out, noise,
+                               m->fence.stream, start, init_noise, masked_latents ? 2 : 1, latent_mask, masked_latents);
+  GILL_TRY(m->fence.leave(caller));
+  return rc;
+}
 extern "C" int gill_sd_denoise(gill_unet* m, const void* cond_bf16, const void* uncond_bf16, int n_uncond, const float* latents0,
                                int B, int num_steps, float guidance, float* latents_out, void* stream) {
   const gill_sd_sampler pndm = {SD_PNDM, 1, 0, 0.f};
@@ -1480,14 +1559,17 @@ extern "C" int gill_sd_denoise(gill_unet* m, const void* cond_bf16, const void* 
 
 static int sd_denoise_on(gill_unet* m, const gill_sd_sampler* sampler, const void* cond_bf16, const void* uncond_bf16, int n_uncond,
                          const float* latents0, int B, int num_steps, float guidance, float* latents_out, const float* noise, hipStream_t s,
-                         int start, const float* init_noise) {
+                         int start, const float* init_noise, int inpaint, const float* latent_mask, const float* masked_latents) {
   const bool cfg = guidance > 1.0f;     // do_classifier_free_guidance (custom_sd.py:588)
   const int Bx = cfg ? 2 * B : B;
   GILL_REQUIRE(B >= 1 && Bx <= m->cfg.max_batch, "batch exceeds the UNet handle's max_batch");
   GILL_REQUIRE(!cfg || uncond_bf16 != nullptr, "uncond embedding required when guidance > 1");
   const gill_unet_config& c = m->cfg;
   const int L = c.sample_size;
-  const int64_t n_lat = (int64_t)c.in_channels * L * L;
+  const int64_t n_lat = (int64_t)c.out_channels * L * L;     // the latents; the UNet input of a concat-mode handle has in_channels
+  GILL_REQUIRE(inpaint == 2 || c.in_channels == c.out_channels,
+               "this handle's UNet takes [latents | mask | masked-image latents] (in_channels != out_channels): use gill_sd_inpaint with masked_latents");
+  GILL_REQUIRE(inpaint == 0 || (init_noise && latent_mask && (inpaint == 1 || masked_latents)), "inpaint: null argument");
   const size_t ctx_elems = (size_t)c.ctx_len * c.cross_attention_dim;
 
   SdSchedule sched;
@@ -1504,6 +1586,21 @@ static int sd_denoise_on(gill_unet* m, const gill_sd_sampler* sampler, const voi
   GILL_CHECK_HIP(hipMemcpyAsync(m->plms_rows, sched.plms.data(), sizeof(PlmsRow) * ncalls, hipMemcpyHostToDevice, s));
   GILL_CHECK_HIP(hipMemsetAsync(m->step_ctr, 0, sizeof(int) * 2, s));
   GILL_CHECK_HIP(hipMemcpyAsync(m->guidance_dev, &guidance, sizeof(float), hipMemcpyHostToDevice, s));   // (synchronised below)
+  std::vector<float> keep32;
+  if (inpaint) {
+    // the loop's operands into the handle's buffers, as ctx_full: the captured step then holds the handle's addresses and serves every call
+    GILL_CHECK_HIP(hipMemcpyAsync(m->inp_mask, latent_mask, sizeof(float) * (size_t)B * L * L, hipMemcpyDeviceToDevice, s));
+    if (inpaint == 1) {
+      std::vector<double> keep;
+      GILL_TRY(sd_inpaint_keep(sampler, c.v_prediction != 0, num_steps, start, sched, keep));
+      keep32.assign(keep.begin(), keep.end());
+      GILL_CHECK_HIP(hipMemcpyAsync(m->keep_rows, keep32.data(), sizeof(float) * keep32.size(), hipMemcpyHostToDevice, s));   // (synchronised below)
+      GILL_CHECK_HIP(hipMemcpyAsync(m->inp_x0, latents0, sizeof(float) * n_lat * B, hipMemcpyDeviceToDevice, s));
+      GILL_CHECK_HIP(hipMemcpyAsync(m->inp_z0, init_noise, sizeof(float) * n_lat * B, hipMemcpyDeviceToDevice, s));
+    } else {
+      GILL_CHECK_HIP(hipMemcpyAsync(m->inp_xm, masked_latents, sizeof(float) * n_lat * B, hipMemcpyDeviceToDevice, s));
+    }
+  }
   // hoisted: time-embedding table for every call (its stream sync also covers the host `rows` buffer), prompt K/V caches
   GILL_TRY(unet_time_table(m, sched.timesteps.data(), ncalls, s));
   // prompt_embeds = cat([negative_prompt_embeds.repeat(B), prompt_embeds])  (custom_sd.py:365-371)
@@ -1530,14 +1627,17 @@ static int sd_denoise_on(gill_unet* m, const gill_sd_sampler* sampler, const voi
   la.temb_cur = m->temb_cur; la.eps = m->eps; la.lat = m->lat; la.lat2 = m->lat2; la.cur_sample = m->cur_sample; la.ets = m->ets;
   la.B = B; la.n = n_lat; la.guidance = m->guidance_dev; la.cfg = cfg ? 1 : 0;
   if (linear) { la.srows = m->sampler_rows; la.noise = m->noise_slot; }
-  // the graph bakes in B, the CFG flag and the step's two loop kernels (with their row table) besides the buffer addresses
-  const GraphKey gkey{Bx, cfg ? 1 : 0, linear ? 1 : 0};
+  SdInpaintArgs ia;
+  ia.l = la; ia.x0 = m->inp_x0; ia.z0 = m->inp_z0; ia.mask = m->inp_mask; ia.xm = m->inp_xm; ia.keep = m->keep_rows; ia.hw = (int64_t)L * L;
+  // the graph bakes in B, the CFG flag and the step's loop kernels (with their row table) besides the buffer addresses
+  const GraphKey gkey{Bx, cfg ? 1 : 0, linear ? 1 : 0, inpaint};
   auto one_step = [&](hipStream_t st) -> int {
-    GILL_TRY(sd_stage_launch(la, st));
+    GILL_TRY(inpaint == 2 ? sd_stage_concat_launch(ia, st) : sd_stage_launch(la, st));
     UNetRun r{m, st, Bx, m->temb_cur, 0, false};
     r.cfg_pair = cfg;
     GILL_TRY(r.forward(m->lat2, m->eps));
-    return linear ? sampler_step_launch(la, st) : plms_step_launch(la, st);
+    GILL_TRY(linear ? sampler_step_launch(la, st) : plms_step_launch(la, st));
+    return inpaint == 1 ? sd_blend_launch(ia, st) : 0;      // (a kernel, not a memcpy node: ops.h)
   };
   for (int i = 0; i < ncalls; ++i) {
     auto git = m->graphs.find(gkey);
@@ -1570,19 +1670,32 @@ static int sd_denoise_on(gill_unet* m, const gill_sd_sampler* sampler, const voi
 // ------------------------------------------------------------------------------------------------------------------
 // Operator-level entry for the loop's sampler arithmetic: the schedule, the stage and step kernels and the device-side step counter exactly as
 // sd_denoise_on drives them, the UNet replaced by the caller's model outputs.  For tests/test_samplers_gpu.py; synchronises.
+// inpaint 1 / 2 (gill_op_sd_inpaint_run): the blend kernel after every step / the concat stage kernel, and unet_in_out (ncalls,Bx,n_in) holds BOTH
+// CFG halves of the UNet input; inpaint 0 is the entry as it was.
 static int op_sd_sampler_run(const gill_sd_sampler* sampler, int v_prediction, int num_steps, int start, float guidance, const float* latents0,
                              const float* init_noise, const float* model_out, const float* noise, int B, int64_t n, float* lat_out,
-                             float* unet_in_out, void* stream) {
+                             float* unet_in_out, void* stream, int inpaint = 0, const float* latent_mask = nullptr,
+                             const float* masked_latents = nullptr, int64_t hw = 0) {
   hipStream_t s = (hipStream_t)stream;
   GILL_REQUIRE(sampler && latents0 && model_out && lat_out && unet_in_out, "null argument");
   GILL_REQUIRE(B >= 1 && n >= 1 && (int64_t)B * n <= ((int64_t)1 << 28), "B, n out of range");
+  GILL_REQUIRE(inpaint == 0 || (init_noise && latent_mask && hw >= 1 && n % hw == 0), "inpaint: init_noise, latent_mask and hw dividing n required");
   SdSchedule sched;
   GILL_TRY(sd_schedule(sampler, v_prediction != 0, num_steps, sched, start));
   GILL_REQUIRE(!sched.needs_noise || noise != nullptr, "this sampler draws noise in its steps: a [ncalls][B][n] noise table is required");
   const bool linear = sched.kind != SD_PNDM, cfg = guidance > 1.0f;
   const int ncalls = (int)sched.timesteps.size(), Bx = cfg ? 2 * B : B;
   const size_t total = (size_t)B * n;
-  DevBuf rows, ctr, gd, slot, lat, lat2, saved, ring;
+  const size_t n_in = inpaint == 2 ? (size_t)(2 * n + hw) : (size_t)n;     // the UNet input's floats per sample
+  DevBuf rows, ctr, gd, slot, lat, lat2, saved, ring, keepd;
+  std::vector<float> keep32;
+  if (inpaint == 1) {
+    std::vector<double> keep;
+    GILL_TRY(sd_inpaint_keep(sampler, v_prediction != 0, num_steps, start, sched, keep));
+    keep32.assign(keep.begin(), keep.end());
+    GILL_TRY(keepd.alloc(sizeof(float) * keep32.size()));
+    GILL_CHECK_HIP(hipMemcpyAsync(keepd.p, keep32.data(), keepd.bytes, hipMemcpyHostToDevice, s));
+  }
   GILL_TRY(rows.alloc(linear ? sizeof(SamplerRow) * ncalls : sizeof(PlmsRow) * ncalls));
   GILL_CHECK_HIP(hipMemcpyAsync(rows.p, linear ? (const void*)sched.rows.data() : (const void*)sched.plms.data(), rows.bytes, hipMemcpyHostToDevice, s));
   GILL_TRY(ctr.alloc_zero(sizeof(int) * 2, s));
@@ -1590,7 +1703,7 @@ static int op_sd_sampler_run(const gill_sd_sampler* sampler, int v_prediction, i
   GILL_CHECK_HIP(hipMemcpyAsync(gd.p, &guidance, sizeof(float), hipMemcpyHostToDevice, s));
   GILL_TRY(slot.alloc(sizeof(noise)));
   GILL_CHECK_HIP(hipMemcpyAsync(slot.p, &noise, sizeof(noise), hipMemcpyHostToDevice, s));
-  GILL_TRY(lat.alloc(sizeof(float) * total)); GILL_TRY(lat2.alloc(sizeof(float) * total * 2));
+  GILL_TRY(lat.alloc(sizeof(float) * total)); GILL_TRY(lat2.alloc(sizeof(float) * (size_t)B * n_in * 2));
   GILL_TRY(saved.alloc(sizeof(float) * total)); GILL_TRY(ring.alloc(sizeof(float) * total * 4));
   GILL_CHECK_HIP(hipStreamSynchronize(s));     // the host-side sources above are locals
   if (init_noise) GILL_TRY(add_noise_f32_launch(latents0, init_noise, (float)sched.add_a, (float)sched.add_b, (int64_t)total, (float*)lat.p, s));
@@ -1600,11 +1713,16 @@ static int op_sd_sampler_run(const gill_sd_sampler* sampler, int v_prediction, i
   la.lat = (float*)lat.p; la.lat2 = (float*)lat2.p; la.cur_sample = (float*)saved.p; la.ets = (float*)ring.p;
   la.B = B; la.n = n; la.guidance = (const float*)gd.p; la.cfg = cfg ? 1 : 0;
   if (linear) { la.srows = (const SamplerRow*)rows.p; la.noise = (const float* const*)slot.p; }
+  SdInpaintArgs ia;
+  ia.x0 = latents0; ia.z0 = init_noise; ia.mask = latent_mask; ia.xm = masked_latents; ia.keep = (const float*)keepd.p; ia.hw = hw;
   for (int i = 0; i < ncalls; ++i) {
-    GILL_TRY(sd_stage_launch(la, s));
-    GILL_CHECK_HIP(hipMemcpyAsync(unet_in_out + (size_t)i * total, lat2.p, sizeof(float) * total, hipMemcpyDeviceToDevice, s));
+    ia.l = la;
+    GILL_TRY(inpaint == 2 ? sd_stage_concat_launch(ia, s) : sd_stage_launch(la, s));
+    const size_t in_floats = inpaint ? (size_t)Bx * n_in : total;      // (the plain entries return the first CFG half only)
+    GILL_CHECK_HIP(hipMemcpyAsync(unet_in_out + (size_t)i * in_floats, lat2.p, sizeof(float) * in_floats, hipMemcpyDeviceToDevice, s));
     la.eps = model_out + (size_t)i * Bx * n;
     GILL_TRY(linear ? sampler_step_launch(la, s) : plms_step_launch(la, s));
+    if (inpaint == 1) GILL_TRY(sd_blend_launch(ia, s));
     GILL_CHECK_HIP(hipMemcpyAsync(lat_out + (size_t)i * total, lat.p, sizeof(float) * total, hipMemcpyDeviceToDevice, s));
   }
   GILL_CHECK_HIP(hipStreamSynchronize(s));
@@ -1621,6 +1739,19 @@ extern "C" int gill_op_sd_sampler_run_from(const gill_sd_sampler* sampler, int v
   GILL_REQUIRE(init_noise != nullptr, "null argument");
   return op_sd_sampler_run(sampler, v_prediction, num_steps, start, guidance, latents0, init_noise, model_out, noise, B, n, lat_out, unet_in_out,
                            stream);
+}
+extern "C" int gill_op_sd_inpaint_run(const gill_sd_sampler* sampler, int v_prediction, int num_steps, int start, float guidance,
+                                      const float* latents0, const float* init_noise, const float* latent_mask, const float* masked_latents,
+                                      const float* model_out, const float* noise, int B, int64_t n, int64_t hw, float* lat_out,
+                                      float* unet_in_out, void* stream) {
+  GILL_REQUIRE(init_noise != nullptr && latent_mask != nullptr, "null argument");
+  return op_sd_sampler_run(sampler, v_prediction, num_steps, start, guidance, latents0, init_noise, model_out, noise, B, n, lat_out, unet_in_out,
+                           stream, masked_latents ? 2 : 1, latent_mask, masked_latents, hw);
+}
+extern "C" int gill_sd_inpaint_prepare(const float* image, const float* mask, int B, int Bm, int H, int W, float* masked_image_out,
+                                       float* latent_mask_out, void* stream) {
+  GILL_REQUIRE(image && mask && masked_image_out && latent_mask_out, "null argument");
+  return inpaint_prepare_launch(image, mask, B, Bm, H, W, masked_image_out, latent_mask_out, (hipStream_t)stream);
 }
 
 // ------------------------------------------------------------------------------------------------------------------

@@ -875,7 +875,7 @@ class GILL(nn.Module):
                        dtype=self.model.logit_scale.dtype)
     local = None
     if self.load_sd:
-      local = torch.zeros((0, self.sd_pipe.cfg.in_channels, self.sd_pipe.cfg.sample_size, self.sd_pipe.cfg.sample_size),
+      local = torch.zeros((0, self.sd_pipe.cfg.out_channels, self.sd_pipe.cfg.sample_size, self.sd_pipe.cfg.sample_size),
                           device=dev, dtype=torch.float32)
     if B > 0:
       raw, emb = self.model.img_hidden_states(full.to(dev), last_idx)
@@ -886,7 +886,7 @@ class GILL(nn.Module):
           lat0 = latents[lo:hi]
         else:
           from .synth import initial_latents
-          lat0 = initial_latents(B_total, self.sd_pipe.cfg.in_channels, self.sd_pipe.cfg.sample_size, seed)[lo:hi]
+          lat0 = initial_latents(B_total, self.sd_pipe.cfg.out_channels, self.sd_pipe.cfg.sample_size, seed)[lo:hi]
         outs = []
         for i in range(0, B, 8):                                    # gen_max_bs = 8 (models.py:726)
           outs.append(self.sd_pipe(prompt_embeds=embs[i:i + 8], latents=lat0[i:i + 8], guidance_scale=guidance_scale,

@@ -488,6 +488,97 @@ def sd_sampler_run_from(sampler, v_prediction: bool, num_steps: int, start: int,
   return lat, uin
 
 
+def sd_inpaint_prepare(image: torch.Tensor, mask: torch.Tensor):
+  """Mask preprocessing of the inpainting loop (gill_sd_inpaint_prepare): image (B,3,H,W) fp32 in [-1,1], mask (Bm,1,H,W) fp32 in [0,1] with
+  Bm 1 or B, 1 = repaint from 0.5 up -> (masked image (B,3,H,W) = image where mask < 0.5 else 0, latent mask (B,1,H/8,W/8) in {0,1})."""
+  image, mask = image.float().contiguous(), mask.float().contiguous()
+  if not (image.is_cuda and mask.is_cuda and image.dim() == 4 and image.shape[1] == 3):
+    raise ValueError("image must be a (B,3,H,W) tensor on the GPU, mask a (Bm,1,H,W) tensor on the GPU")
+  B, _, H, W = image.shape
+  if mask.dim() != 4 or mask.shape[0] not in (1, B) or tuple(mask.shape[1:]) != (1, H, W):
+    raise ValueError(f"mask must be {(B, 1, H, W)} or {(1, 1, H, W)}, got {tuple(mask.shape)}")
+  masked = torch.empty_like(image)
+  lmask = torch.empty((B, 1, H // 8, W // 8), device=image.device, dtype=torch.float32)
+  N.check(N.lib().gill_sd_inpaint_prepare(N.ptr(image), N.ptr(mask), B, int(mask.shape[0]), H, W, N.ptr(masked), N.ptr(lmask), N.current_stream()))
+  return masked, lmask
+
+
+def sd_inpaint_keep(sampler, v_prediction: bool, num_steps: int, start: int = 0, eta: float = 0.0) -> torch.Tensor:
+  """The blend table of gill_sd_inpaint (gill_sd_inpaint_keep; host only): (ncalls,2) float64, row i the add_noise pair (ka, kb) at the noise
+  level the latents have after call i; the last row is (1, 0)."""
+  import ctypes as C
+  from .sd import as_sampler_config
+  sp = as_sampler_config(sampler).native(eta)
+  n = N.lib().gill_sd_inpaint_keep(C.byref(sp), int(bool(v_prediction)), int(num_steps), int(start), None)
+  if n < 0:
+    N.check(n)
+  buf = (C.c_double * (2 * n))()
+  N.check(min(0, N.lib().gill_sd_inpaint_keep(C.byref(sp), int(bool(v_prediction)), int(num_steps), int(start), buf)))
+  return torch.tensor(list(buf), dtype=torch.float64).reshape(n, 2)
+
+
+def sd_inpaint(handle, sampler, cond: torch.Tensor, uncond: torch.Tensor, start: int, init_latents: torch.Tensor, init_noise: torch.Tensor,
+               latent_mask: torch.Tensor, masked_latents: Optional[torch.Tensor], num_steps: int, guidance: float,
+               noise: Optional[torch.Tensor] = None, eta: float = 0.0) -> torch.Tensor:
+  """gill_sd_inpaint on a gill_unet handle (GillSDPipeline._h): cond (B,77,D) / uncond (1|B,77,D) bf16, init_latents / init_noise (B,4,L,L) fp32,
+  latent_mask (B,1,L,L) fp32 (1 = repaint), masked_latents (B,4,L,L) fp32 or None -> latents (B,4,L,L).  None selects blend mode and needs a
+  handle whose UNet takes the latents alone; a tensor selects concat mode and needs a 9-channel handle: the library refuses any other pairing.
+  sampler: kind string, SamplerConfig, or a gill_sd_sampler already built (eta then ignored)."""
+  import ctypes as C
+  from .sd import as_sampler_config
+  sp = sampler if isinstance(sampler, N.gill_sd_sampler) else as_sampler_config(sampler).native(eta)
+  x0, z0, lm = init_latents.float().contiguous(), init_noise.float().contiguous(), latent_mask.float().contiguous()
+  B = x0.shape[0]
+  if tuple(z0.shape) != tuple(x0.shape) or tuple(lm.shape) != (B, 1) + tuple(x0.shape[2:]):
+    raise ValueError(f"init_noise must be {tuple(x0.shape)} and latent_mask {(B, 1) + tuple(x0.shape[2:])}")
+  xm = None if masked_latents is None else masked_latents.float().contiguous()
+  if xm is not None and tuple(xm.shape) != tuple(x0.shape):
+    raise ValueError(f"masked_latents must be {tuple(x0.shape)}")
+  cond, uncond = cond.to(torch.bfloat16).contiguous(), uncond.to(torch.bfloat16).contiguous()
+  z = None if noise is None else noise.float().contiguous()
+  out = torch.empty_like(x0)
+  N.check(N.lib().gill_sd_inpaint(handle, C.byref(sp), N.ptr(cond), N.ptr(uncond), int(uncond.shape[0]), int(start), N.ptr(x0), N.ptr(z0), N.ptr(lm),
+                                  None if xm is None else N.ptr(xm), B, int(num_steps), float(guidance), N.ptr(out),
+                                  None if z is None else N.ptr(z), N.current_stream()))
+  return out
+
+
+def sd_inpaint_run(sampler, v_prediction: bool, num_steps: int, start: int, guidance: float, latents0: torch.Tensor, init_noise: torch.Tensor,
+                   latent_mask: torch.Tensor, model_out: torch.Tensor, noise: Optional[torch.Tensor] = None, eta: float = 0.0,
+                   masked_latents: Optional[torch.Tensor] = None, hw: Optional[int] = None):
+  """sd_sampler_run_from with the inpainting kernels (gill_op_sd_inpaint_run): latent_mask (B,hw), 1 = repaint.  masked_latents None: blend mode
+  (the blend kernel after every step); masked_latents (B,n): concat mode (the UNet input is [in_scale * latents | mask | masked_latents], no
+  blend).  -> (latents after every call (ncalls,B,n), UNet input of every call (ncalls,Bx,n_in), BOTH CFG halves; n_in = n or (2 n / hw + 1) hw)."""
+  import ctypes as C
+  from .sd import as_sampler_config
+  sp = as_sampler_config(sampler).native(eta)
+  B, n = latents0.shape
+  hw = int(latent_mask.shape[-1] if hw is None else hw)
+  ncalls = N.lib().gill_sd_schedule_from(C.byref(sp), int(bool(v_prediction)), int(num_steps), int(start), None, None, None, None)
+  if ncalls < 0:
+    N.check(ncalls)
+  Bx = 2 * B if guidance > 1.0 else B
+  if tuple(model_out.shape) != (ncalls, Bx, n) or (noise is not None and tuple(noise.shape) != (ncalls, B, n)):
+    raise ValueError(f"model_out must be {(ncalls, Bx, n)} and noise {(ncalls, B, n)}")
+  if tuple(init_noise.shape) != (B, n):
+    raise ValueError(f"init_noise must be {(B, n)}")
+  if hw < 1 or n % hw != 0 or tuple(latent_mask.shape) != (B, hw):
+    raise ValueError(f"latent_mask must be {(B, hw)} with hw dividing n = {n}, got {tuple(latent_mask.shape)}")
+  if masked_latents is not None and tuple(masked_latents.shape) != (B, n):
+    raise ValueError(f"masked_latents must be {(B, n)}")
+  f = lambda x: x.float().contiguous()   # noqa: E731
+  lat0, z0, mo, lm = f(latents0), f(init_noise), f(model_out), f(latent_mask)
+  xm = None if masked_latents is None else f(masked_latents)
+  z = None if noise is None else f(noise)
+  n_in = n if xm is None else 2 * n + hw
+  lat = torch.empty((ncalls, B, n), device=lat0.device, dtype=torch.float32)
+  uin = torch.empty((ncalls, Bx, n_in), device=lat0.device, dtype=torch.float32)
+  N.check(N.lib().gill_op_sd_inpaint_run(C.byref(sp), int(bool(v_prediction)), int(num_steps), int(start), float(guidance), N.ptr(lat0), N.ptr(z0),
+                                         N.ptr(lm), None if xm is None else N.ptr(xm), N.ptr(mo), None if z is None else N.ptr(z), B, n, hw,
+                                         N.ptr(lat), N.ptr(uin), N.current_stream()))
+  return lat, uin
+
+
 def vae_attention(n: torch.Tensor, wqkv: torch.Tensor, bqkv: torch.Tensor, wo: torch.Tensor, bo: torch.Tensor,
                   resid: Optional[torch.Tensor] = None, want_p: bool = False):
   """The VAE mid block's single-head attention behind its GroupNorm, as the engine launches it (gill_op_vae_attention): n (B,HW,C) bf16, the
@@ -558,9 +649,11 @@ def conv_out(x: torch.Tensor, w_oihw: torch.Tensor, bias: Optional[torch.Tensor]
   return y, path.value, _guard_ok(buf)
 
 
-def conv_in(x: torch.Tensor, w_oihw: torch.Tensor, bias: Optional[torch.Tensor] = None, counters: Optional[torch.Tensor] = None, nzero: int = 0):
+def conv_in(x: torch.Tensor, w_oihw: torch.Tensor, bias: Optional[torch.Tensor] = None, counters: Optional[torch.Tensor] = None, nzero: int = 0,
+            wide: bool = False):
   """conv_in of the UNet / VAE (gill_op_conv_in: im2col + the K = 64 GEMM): x (B,Cin,H,W) fp32 NCHW, w (Cout,Cin,3,3) -> (y (B,H,W,Cout) bf16
-  NHWC, guard_ok).  counters: an int32 tensor whose first nzero words the im2col launch clears (in place)."""
+  NHWC, guard_ok).  counters: an int32 tensor whose first nzero words the im2col launch clears (in place).  wide: gill_op_conv_in_wide, K padded
+  to a multiple of 64 (up to 14 input channels: the 9-channel inpainting UNet's conv_in)."""
   assert x.dtype == torch.float32 and x.is_cuda
   x = x.contiguous()
   B, Cin, H, W = x.shape
@@ -570,8 +663,8 @@ def conv_in(x: torch.Tensor, w_oihw: torch.Tensor, bias: Optional[torch.Tensor] 
   bias = None if bias is None else bias.float().contiguous()
   assert counters is None or (counters.dtype == torch.int32 and counters.numel() >= nzero)
   buf, y = _guarded((B, H, W, Cout), torch.bfloat16, x.device)
-  N.check(N.lib().gill_op_conv_in(N.ptr(x), N.ptr(w), N._DTYPES[w.dtype], N.ptr(bias), N.ptr(buf), B, Cin, H, W, Cout, N.ptr(counters), int(nzero),
-                                  N.current_stream()))
+  fn = N.lib().gill_op_conv_in_wide if wide else N.lib().gill_op_conv_in
+  N.check(fn(N.ptr(x), N.ptr(w), N._DTYPES[w.dtype], N.ptr(bias), N.ptr(buf), B, Cin, H, W, Cout, N.ptr(counters), int(nzero), N.current_stream()))
   return y, _guard_ok(buf)
 
 

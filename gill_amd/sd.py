@@ -228,7 +228,10 @@ class GillSDPipeline:
     the CPU generator(s) like every other draw of this pipeline."""
     if self._vae is None or not getattr(self, "_vae_has_encoder", False):
       raise N.GillNativeError("this pipeline was built without VAE encoder weights (encoder.* / quant_conv.* in vae_state= / from_pretrained)")
-    img = self.preprocess_image(image).to(self.device).contiguous()
+    return self._encode_preprocessed(self.preprocess_image(image).to(self.device).contiguous(), generator, sample)
+
+  def _encode_preprocessed(self, img: torch.Tensor, generator=None, sample: bool = True) -> torch.Tensor:
+    """encode_image behind its host plumbing: img (B,3,8L,8L) fp32 in [-1,1], contiguous, on the device."""
     B, L, lc = img.shape[0], self.vae_cfg.latent_size, self.vae_cfg.latent_channels
     noise = self._randn((B, lc, L, L), generator).to(self.device).contiguous() if sample else None
     out = torch.empty((B, lc, L, L), device=self.device, dtype=torch.float32)
@@ -261,6 +264,38 @@ class GillSDPipeline:
     if t.dim() != 4 or t.shape[1] != 3 or t.shape[2] != side or t.shape[3] != side:
       raise ValueError(f"this handle was built for {side}x{side} images, got an image batch of shape {tuple(t.shape)}")
     return t.contiguous()
+
+  def preprocess_mask(self, mask_image) -> torch.Tensor:
+    """A PIL image (converted to "L", / 255), a list of them, a (B|1,H,W) or (B|1,H,W,1) array in [0,1] or a (B|1,1,H,W) tensor in [0,1]
+    -> (Bm,1,8L,8L) fp32 on the host (plumbing), 1 = repaint.  Binarising (>= 0.5) is the device's work (`prepare_mask`)."""
+    import numpy as np
+    side = 8 * self.cfg.sample_size
+    if isinstance(mask_image, torch.Tensor):
+      t = mask_image.detach().to("cpu", torch.float32)
+      if t.dim() == 3:
+        t = t[:, None]
+    else:
+      if not isinstance(mask_image, (list, tuple, np.ndarray)):
+        mask_image = [mask_image]
+      if not isinstance(mask_image, np.ndarray):
+        mask_image = np.stack([np.asarray(im.convert("L"), dtype=np.float32) / 255.0 if hasattr(im, "convert") else np.asarray(im, dtype=np.float32)
+                               for im in mask_image], 0)
+      if mask_image.ndim == 4 and mask_image.shape[-1] == 1:
+        mask_image = mask_image[..., 0]
+      t = torch.from_numpy(np.ascontiguousarray(mask_image, dtype=np.float32))
+      if t.dim() == 3:
+        t = t[:, None]
+    if t.dim() != 4 or t.shape[1] != 1 or t.shape[2] != side or t.shape[3] != side:
+      raise ValueError(f"this handle was built for {side}x{side} images: `mask_image` must be (B|1,1,{side},{side}), got a mask batch of shape "
+                       f"{tuple(t.shape)}")
+    return t.contiguous()
+
+  def prepare_mask(self, image: torch.Tensor, mask: torch.Tensor):
+    """gill_sd_inpaint_prepare on the device: image (B,3,8L,8L) in [-1,1] and mask (B|1,1,8L,8L) in [0,1] (the outputs of `preprocess_image` /
+    `preprocess_mask`) -> (masked image (B,3,8L,8L) = image where mask < 0.5 else 0, latent mask (B,1,L,L) in {0,1} = mask[8y,8x] >= 0.5)."""
+    from . import ops
+    with torch.cuda.device(self.device):
+      return ops.sd_inpaint_prepare(image.to(self.device, torch.float32), mask.to(self.device, torch.float32))
 
   @staticmethod
   def _randn(shape, generator=None) -> torch.Tensor:
@@ -374,7 +409,9 @@ class GillSDPipeline:
     if ts.numel() == 1:
       ts = ts.expand(Bx).contiguous()
     tarr = (C.c_float * Bx)(*[float(v) for v in ts])
-    out = torch.empty_like(sample)
+    if sample.dim() != 4 or sample.shape[1] != self.cfg.in_channels:
+      raise ValueError(f"this UNet takes {self.cfg.in_channels} input channels, got a sample of shape {tuple(sample.shape)}")
+    out = torch.empty((Bx, self.cfg.out_channels) + tuple(sample.shape[2:]), device=self.device, dtype=torch.float32)
     with torch.cuda.device(self.device):
       N.check(N.lib().gill_unet_forward(self._h, N.ptr(sample), tarr, N.ptr(ctx), Bx, N.ptr(out), N.current_stream()))
     return out
@@ -383,7 +420,7 @@ class GillSDPipeline:
     """custom_sd.py:458-472.  Latents are drawn on the CPU generator (cuRAND Philox streams of the reference
     notebooks are not reproducible off-NVIDIA); the multiplication by init_noise_sigma (:472) is gill_sd_denoise_ex's first kernel."""
     L = self.cfg.sample_size
-    shape = (batch_size, self.cfg.in_channels, L, L)
+    shape = (batch_size, self.cfg.out_channels, L, L)      # the latents (an inpainting UNet's input has more channels)
     if isinstance(generator, list) and len(generator) != batch_size:
       raise ValueError(f"You have passed a list of generators of length {len(generator)}, but requested an effective batch"
                        f" size of {batch_size}. Make sure the batch size matches the length of the generators.")
@@ -400,7 +437,7 @@ class GillSDPipeline:
     """The variance noise of a stochastic sampler: one randn per UNet call, in call order, from the generator(s) the latents came from
     (so: after them), as the schedulers' step() draws it; uploaded once."""
     L = self.cfg.sample_size
-    one = (self.cfg.in_channels, L, L)
+    one = (self.cfg.out_channels, L, L)
     calls = []
     for _ in range(ncalls):
       if isinstance(generator, list):
@@ -454,11 +491,17 @@ class GillSDPipeline:
                latents: Optional[torch.Tensor] = None, prompt_embeds: Optional[torch.Tensor] = None,
                negative_prompt_embeds: Optional[torch.Tensor] = None, output_type: Optional[str] = None, return_dict: bool = True,
                return_prompts_only: bool = False, scheduler: Union[None, str, SamplerConfig] = None, image=None, strength: float = 0.8,
-               **_ignored):
+               mask_image=None, **_ignored):
     """scheduler: this call's sampler instead of `self.scheduler`.  eta reaches DDIM only (custom_sd.py:395-403).
     image= / strength=: image-to-image (diffusers' StableDiffusionImg2ImgPipeline): the image is encoded by the VAE encoder, noised to the
     timestep of step `num_inference_steps - min(int(num_inference_steps * strength), num_inference_steps)` and denoised from there
-    (gill_sd_denoise_from).  Draw order on the generator(s): posterior noise, add-noise noise, step noise."""
+    (gill_sd_denoise_from).  Draw order on the generator(s): posterior noise, add-noise noise, step noise.
+    mask_image= (needs image=; any form `preprocess_mask` takes; 1 = repaint, 0 = keep; batch 1 serves every prompt): inpainting
+    (gill_sd_inpaint) on the image-to-image loop.  A handle whose UNet takes the latents alone blends the kept region back after every step; a
+    handle with a 9-channel inpainting UNet feeds [latents | mask | masked-image latents] instead and cannot be called without a mask.  Draw
+    order: the image's posterior noise, the masked image's posterior noise (9-channel handle only), add-noise noise, step noise."""
+    if mask_image is not None and image is None:
+      raise ValueError("`mask_image` needs `image`: inpainting repaints a region of an image.")
     if image is not None:
       if latents is not None:
         raise ValueError("Cannot forward both `image` and `latents`: image-to-image starts from the encoded image.")
@@ -505,6 +548,13 @@ class GillSDPipeline:
       # the reference's default is "pil" (gill/custom_sd.py:491: `.images` is a list of PIL images); a handle built WITHOUT VAE
       # weights (UNet-only parity rigs) can only return latents
       output_type = "pil" if self._vae is not None else "latent"
+    concat = self.cfg.in_channels != self.cfg.out_channels
+    if concat and self.cfg.in_channels != 2 * self.cfg.out_channels + 1:
+      raise ValueError(f"a UNet with {self.cfg.in_channels} input and {self.cfg.out_channels} output channels is neither a text-to-image "
+                       "nor an inpainting UNet")
+    if concat and mask_image is None:
+      raise ValueError(f"this handle's UNet takes {self.cfg.in_channels} channels ([latents | mask | masked-image latents]): pass `image` and "
+                       "`mask_image`")
     L = self.cfg.sample_size
     if (height is not None and height != L * 8) or (width is not None and width != L * 8):
       raise ValueError(f"this handle was built for {L * 8}x{L * 8} images")
@@ -538,13 +588,26 @@ class GillSDPipeline:
         if B % img.shape[0] != 0:
           raise ValueError(f"Cannot duplicate `image` of batch size {img.shape[0]} to {B} text prompts.")
         img = img.repeat(B // img.shape[0], 1, 1, 1)
+      lmask = xm = None
+      if mask_image is not None:
+        side = 8 * self.cfg.sample_size
+        mk = self.preprocess_mask(mask_image)
+        if mk.shape[0] not in (1, B):
+          raise ValueError(f"`mask_image` must be (B|1,1,{side},{side}) with B = {B} prompts, got a mask batch of shape {tuple(mk.shape)}")
+        masked, lmask = self.prepare_mask(img, mk)
       x0 = self.encode_image(img, generator)                     # draw 1: the posterior's noise
+      if concat:
+        xm = self._encode_preprocessed(masked.contiguous(), generator)      # (9-channel handle) the masked image's posterior noise
       L = self.cfg.sample_size
-      z0 = self._randn((B, self.cfg.in_channels, L, L), generator).to(self.device).contiguous()      # draw 2: add_noise
+      z0 = self._randn((B, self.cfg.out_channels, L, L), generator).to(self.device).contiguous()      # draw 2: add_noise
       noise = self._step_noise(rows.shape[0], B, generator) if bool((rows[:, 11] != 0).any()) else None    # draw 3
       out = torch.empty_like(x0)
       with torch.cuda.device(self.device):
-        N.check(N.lib().gill_sd_denoise_from(self._h, C.byref(sp), N.ptr(cond), N.ptr(uncond), int(uncond.shape[0]), start, N.ptr(x0),
+        if lmask is not None:
+          from . import ops
+          out = ops.sd_inpaint(self._h, sp, cond, uncond, start, x0, z0, lmask, xm, int(num_inference_steps), float(guidance_scale), noise)
+        else:
+          N.check(N.lib().gill_sd_denoise_from(self._h, C.byref(sp), N.ptr(cond), N.ptr(uncond), int(uncond.shape[0]), start, N.ptr(x0),
                                              N.ptr(z0), B, int(num_inference_steps), float(guidance_scale), N.ptr(out),
                                              None if noise is None else N.ptr(noise), N.current_stream()))
     else:

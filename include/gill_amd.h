@@ -218,7 +218,7 @@ int gill_mapper_forward(gill_mapper* h, const void* x_bf16, const void* input_em
  * ------------------------------------------------------------------------------------------ */
 typedef struct gill_unet gill_unet;
 typedef struct {
-  int32_t in_channels;          /* 4 */
+  int32_t in_channels;          /* 4; 9 = 2 * out_channels + 1 for an inpainting UNet ([latents | mask | masked-image latents]); at most 14 */
   int32_t out_channels;         /* 4 */
   int32_t block_out_channels[4];/* 320,640,1280,1280 */
   int32_t layers_per_block;     /* 2 */
@@ -239,7 +239,7 @@ typedef struct {
 int gill_unet_create(gill_unet** out, const gill_unet_config* cfg, const gill_tensor* weights, int n_weights);
 void gill_unet_destroy(gill_unet* h);
 
-/* One UNet forward (custom_sd.py:633-638): sample (Bx,4,L,L) fp32 NCHW, timesteps (Bx) fp32 HOST,
+/* One UNet forward (custom_sd.py:633-638): sample (Bx,in_channels,L,L) fp32 NCHW (4; 9 on an inpainting handle), timesteps (Bx) fp32 HOST,
  * ctx (Bx,77,768) bf16 -> eps_out (Bx,4,L,L) fp32 NCHW. */
 int gill_unet_forward(gill_unet* h, const float* sample, const float* timesteps_host, const void* ctx_bf16, int Bx,
                       float* eps_out, void* stream);
@@ -306,6 +306,33 @@ int gill_sd_schedule_from(const gill_sd_sampler* sampler, int v_prediction, int 
 int gill_sd_denoise_from(gill_unet* h, const gill_sd_sampler* sampler, const void* cond_bf16, const void* uncond_bf16, int n_uncond,
                          int start, const float* init_latents, const float* init_noise, int B, int num_steps, float guidance,
                          float* latents_out, const float* noise, void* stream);
+
+/* Inpainting: repaint where the mask is 1, keep the image where it is 0.  Mask values are in [0,1]; a pixel counts as repaint when it is >= 0.5.
+ * gill_sd_inpaint_prepare (device pointers, one kernel on `stream`, no synchronisation): image (B,3,H,W) fp32 in [-1,1], mask (Bm,1,H,W) fp32 with
+ * Bm == 1 (one mask for every sample) or Bm == B; H, W multiples of 8 -> masked_image_out (B,3,H,W) = image where mask < 0.5, else 0, and
+ * latent_mask_out (B,1,H/8,W/8) in {0,1} = (mask[b][0][8y][8x] >= 0.5): what torch's nearest interpolation to 1/8 size gives, one channel. */
+int gill_sd_inpaint_prepare(const float* image, const float* mask, int B, int Bm, int H, int W, float* masked_image_out, float* latent_mask_out,
+                            void* stream);
+/* The blend table of gill_sd_inpaint (host arrays, no GPU needed).  keep_out (optional): [ncalls][2] doubles, the fp32 values the device reads,
+ * widened: row i is the schedulers' add_noise pair (ka, kb) at the noise level the latents have AFTER call i of gill_sd_schedule_from(...,
+ * start)'s table, so that ka * init_latents + kb * init_noise is the image at that level.  Rows i < ncalls - 1 are the pair at the timestep of call
+ * i + 1: ddim, dpmsolver++ (sqrt(abar_t), sqrt(1 - abar_t)); euler, euler_ancestral (1, sigma of call i + 1); pndm (sqrt(abar_t), sqrt(1 - abar_t))
+ * at timestep i + 1 of the replayed warm-up list, so rows 0 and 1 are equal (both calls leave the latents at t_s - D).  The last row is (1, 0): the
+ * kept region ends as the clean image latents.  Returns ncalls, negative on the arguments gill_sd_schedule_from refuses. */
+int gill_sd_inpaint_keep(const gill_sd_sampler* sampler, int v_prediction, int num_steps, int start, double* keep_out);
+/* gill_sd_denoise_from with a mask: the same start x_start = a * init_latents + b * init_noise at step `start`, the same tables, step counter and
+ * noise rows.  latent_mask (B,1,L,L) fp32, 1 = repaint (gill_sd_inpaint_prepare's output; one plane per sample, broadcast over the channels).
+ * The handle decides what masked_latents must be, and anything else is an error that says which:
+ *   masked_latents == NULL, handle with in_channels == out_channels (every text-to-image checkpoint) — BLEND mode: after the sampler step of call
+ *     i one more kernel sets latents = m * latents + (1 - m) * (ka[i] * init_latents + kb[i] * init_noise), (ka, kb) = gill_sd_inpaint_keep's row i;
+ *   masked_latents (B,4,L,L) fp32 = the scaled VAE latents of the masked image, handle with in_channels == 2 * out_channels + 1 — CONCAT mode: no
+ *     blend; the UNet input of every call is [in_scale * latents (4) | latent_mask (1) | masked_latents (4)] per sample, in both CFG halves.
+ * Latents, sampler state, noise and latents_out keep out_channels channels in both modes.  init_latents, init_noise, latent_mask and
+ * masked_latents are copied into the handle before the loop: the captured step (one per mode, apart from the graphs of gill_sd_denoise*, which
+ * are unchanged) serves every call.  gill_sd_denoise* on a concat-mode handle is refused. */
+int gill_sd_inpaint(gill_unet* h, const gill_sd_sampler* sampler, const void* cond_bf16, const void* uncond_bf16, int n_uncond, int start,
+                    const float* init_latents, const float* init_noise, const float* latent_mask, const float* masked_latents, int B,
+                    int num_steps, float guidance, float* latents_out, const float* noise, void* stream);
 
 /* ------------------------------------------------------------------------------------------
  * Stage 3b — VAE decode of the final latents.  Replaces StableDiffusionPipeline.decode_latents
@@ -518,6 +545,13 @@ int gill_op_sd_sampler_run(const gill_sd_sampler* sampler, int v_prediction, int
 int gill_op_sd_sampler_run_from(const gill_sd_sampler* sampler, int v_prediction, int num_steps, int start, float guidance,
                                 const float* latents0, const float* init_noise, const float* model_out, const float* noise, int B, int64_t n,
                                 float* lat_out, float* unet_in_out, void* stream);
+/* gill_sd_inpaint's kernels under the same teacher: the schedule, the stage / step / blend kernels, the keep table and the device step counter as
+ * the loop drives them.  latent_mask (B,hw) fp32, hw dividing n (n = C * hw); masked_latents NULL: blend mode, n_in = n; masked_latents (B,n): concat
+ * mode, n_in = (2 C + 1) * hw.  -> lat_out (ncalls,B,n) and unet_in_out (ncalls,Bx,n_in): BOTH CFG halves of every call's UNet input (Bx as for
+ * model_out).  Synchronises. */
+int gill_op_sd_inpaint_run(const gill_sd_sampler* sampler, int v_prediction, int num_steps, int start, float guidance, const float* latents0,
+                           const float* init_noise, const float* latent_mask, const float* masked_latents, const float* model_out,
+                           const float* noise, int B, int64_t n, int64_t hw, float* lat_out, float* unet_in_out, void* stream);
 
 /* The kernels at the ends of the engines, each launched the way its engine launches it.  All synchronise.  For the operator tests.
  * conv_out (the UNet's predicted noise, the VAE's image and moments): x (B,H,W,Cin) bf16 NHWC, w (Cout,Cin,3,3) of w_dtype (GILL_DTYPE_*), optional
@@ -530,6 +564,10 @@ int gill_op_conv_out(const void* x_bf16, const void* w_oihw, int w_dtype, const 
  * cleared by the im2col launch, as the UNet forward clears its arrival counters. */
 int gill_op_conv_in(const float* x_f32, const void* w_oihw, int w_dtype, const float* bias, void* y_bf16, int B, int Cin, int H, int W, int Cout,
                     uint32_t* counters, int ncounters, void* stream);
+/* The same with K = 9 Cin zero-padded to a multiple of 64, as the engines' loaders do: 64 up to Cin = 7 (then gill_op_conv_in itself), 128 up to
+ * Cin = 14 (the 9-channel inpainting UNet), an error beyond. */
+int gill_op_conv_in_wide(const float* x_f32, const void* w_oihw, int w_dtype, const float* bias, void* y_bf16, int B, int Cin, int H, int W, int Cout,
+                         uint32_t* counters, int ncounters, void* stream);
 /* diffusers Timesteps(dim, flip_sin_to_cos = True, downscale_freq_shift = 0): t (n) fp32 -> out (n, dim) bf16 = [cos(t f_i) | sin(t f_i)],
  * f_i = 10000^(-i / (dim / 2)); dim even (an error otherwise). */
 int gill_op_timestep_embed(const float* t, int n, int dim, void* out_bf16, void* stream);
