@@ -1,12 +1,11 @@
 // extern "C" surface of libgill_amd (see include/gill_amd.h): error plumbing and the operator-level
 // entry points.  The three stage engines export their own entry points from opt.hip / mapper.hip /
-// unet.hip.
+// unet.hip; the UNet's operator entries are in unet_ops.hip.
 #include "../../include/gill_amd.h"
 #include "ops.h"
-#include "engine_util.h"
 #include "convnet.h"
 #include "tfm.h"
-#include <stdlib.h>
+#include "xf_weights.h"
 #include <vector>
 
 static thread_local std::string g_last_error;
@@ -14,14 +13,6 @@ void gill_set_error(const std::string& msg) { g_last_error = msg; }
 
 extern "C" const char* gill_last_error(void) { return g_last_error.c_str(); }
 extern "C" int gill_version(void) { return 100; }
-
-// GILL_OP_REPEAT=n makes the operator entry points launch their kernel n times per call (tools/bench_ops.py: amortises
-// the wrapper's allocation / re-layout so the kernel itself can be timed); default 1.
-static int op_repeat() {
-  const char* v = getenv("GILL_OP_REPEAT");     // read at every call: bench.py times a call at two repeat counts and takes the difference
-  const int r = v ? (atoi(v) < 1 ? 1 : atoi(v)) : 1;
-  return r;
-}
 
 // One grow-only split-K workspace for the operator entry points (they synchronise before they return and the reference's threading model is one
 // request at a time — SURVEY 8b — so one buffer serves them all): a per-call hipMalloc / hipFree of up to 100 MB sat inside every timed call
@@ -80,11 +71,8 @@ extern "C" int gill_op_geglu(const void* A, const void* W, const float* bias, vo
   DevBuf wperm, bperm, idx;
   GILL_TRY(wperm.alloc(sizeof(bf16_t) * (size_t)2 * inner * K));
   GILL_TRY(bperm.alloc(sizeof(float) * (size_t)2 * inner));
-  std::vector<int32_t> map = geglu_row_permutation(inner);
-  GILL_TRY(idx.alloc(sizeof(int32_t) * map.size()));
-  GILL_CHECK_HIP(hipMemcpyAsync(idx.p, map.data(), sizeof(int32_t) * map.size(), hipMemcpyHostToDevice, s));
-  GILL_TRY(scatter_rows_bf16_launch((const bf16_t*)W, 2 * inner, K, (const int32_t*)idx.p, (bf16_t*)wperm.p, K, s));
-  if (bias) GILL_TRY(permute_f32_launch(bias, (const int32_t*)idx.p, 2 * inner, (float*)bperm.p, s));
+  GILL_TRY(idx.alloc(sizeof(int32_t) * 2 * inner));
+  GILL_TRY(xf_geglu_weights((const bf16_t*)W, bias, inner, K, nullptr, nullptr, (int32_t*)idx.p, (bf16_t*)wperm.p, (float*)bperm.p, nullptr, s));   // (no LayerNorm to fold)
   GemmArgs g;
   g.M = M; g.N = 2 * inner; g.K = K; g.K1 = K;
   g.A = (const bf16_t*)A; g.lda = K;

@@ -3,6 +3,7 @@
 #pragma once
 #include "../../include/gill_amd.h"
 #include "ops.h"
+#include <stdlib.h>
 #include <string>
 #include <unordered_map>
 #include <vector>
@@ -103,6 +104,13 @@ struct WeightTable {
     return 0;
   }
 };
+
+// GILL_OP_REPEAT=n makes the operator entry points (capi.hip, unet_ops.hip) launch their kernel n times per call (tools/bench_ops.py: amortises
+// the wrapper's allocation / re-layout so the kernel itself can be timed); default 1.
+static inline int op_repeat() {
+  const char* v = getenv("GILL_OP_REPEAT");     // read at every call: bench.py times a call at two repeat counts and takes the difference
+  return v && atoi(v) > 1 ? atoi(v) : 1;
+}
 
 // dst row of each source row for the GEGLU projection weight: 16-row value blocks interleaved with
 // the 16-row gate blocks of the same output columns (see gemm.hip ACT_GEGLU epilogue).

@@ -1,7 +1,7 @@
 // The feed-forward sub-block of a BasicTransformerBlock (diffusers: norm3 -> GEGLU -> ff.net.2 -> + residual, followed in the UNet by
 // proj_out + the outer residual) as ONE kernel per 128-row tile, for C = 320 (hidden 1280: SD-1.5 / SD-2.1 level 0):
 //   out[m] = [Wp.W2 | Wp] . [ value(m) * gelu(gate(m)) | t(m) ] + b + x_in(m),     [value | gate](m) = W1' . LN(t(m)) + b1'
-// (W1' / b1' carry norm3's gain / shift: ln_fold_rows_launch; [Wp.W2 | Wp], b: ffo_fuse_kernel in unet.hip.)
+// (W1' / b1' carry norm3's gain / shift: ln_fold_rows_launch; [Wp.W2 | Wp], b: ffo_fuse_kernel in xf_weights.hip.)
 // It replaces the GEGLU GEMM (97 us at M = 32768) and the two-source ffo GEMM (50 us) and the 84 MB tensor between them.
 //
 // Structure (prototype and measurements: tools/ubench/ffn_fused.hip, profiles/r03_ffn_fused_prototype.md).  Inside the 256-register

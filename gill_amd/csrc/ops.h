@@ -69,7 +69,7 @@ struct GemmArgs {
   //            ln_rows (0 = M): rows per plane; rows m >= ln_rows read the sums of row m - ln_rows (a batch whose second half
   //            repeats the first: the shared classifier-free-guidance prefix).
   const float* ln_stats = nullptr; int ln_planes = 1; int ln_rows = 0; const float* ln_colsum = nullptr; float ln_eps = 1e-5f;
-  // Per-sample operands (the cross-attention of UNet levels 1-3 as two GEMMs, unet.hip "XALG"): rows [b * wb_rows, (b + 1) * wb_rows)
+  // Per-sample operands (the cross-attention of UNet levels 1-3 as two GEMMs, xf_weights.hip "XALG"): rows [b * wb_rows, (b + 1) * wb_rows)
   // multiply W + b * wb_stride (elements); OUT_SOFTMAX80 also reads bias / ln_colsum at + b * vb_stride.  Tiles must not straddle
   // samples (wb_rows % tile rows == 0).  0 = one weight matrix for all rows.
   int wb_rows = 0; int64_t wb_stride = 0; int vb_stride = 0;
@@ -295,7 +295,7 @@ int decode_rule_launch(float* logits, int B, int V, const DecodeRuleDev& r, hipS
 // out = in / temperature (reciprocal: in * fp32(1 / temperature)), then the top-p filter when top_p < 1
 int decode_filter_launch(const float* in, float* out, int B, int V, double temperature, int reciprocal, double top_p,
                          double filter_value, hipStream_t s);
-// classifier-free guidance + PLMS update on fp32 NCHW latents (see unet.hip for the coefficient layout)
+// classifier-free guidance + PLMS update on fp32 NCHW latents (see sd_schedule.hip for the coefficient layout)
 // One row per UNet call of a denoise loop, computed on the host once per call of gill_sd_denoise and read by the
 // device: the loop's only per-step inputs.  The step index itself lives on the device (SdLoopArgs::ctr), so replaying one
 // captured UNet step N times needs no host-side per-step argument and no copy between replays.
@@ -306,7 +306,7 @@ struct PlmsRow {
   float sample_coeff, eps_coeff;   // x_prev = sample_coeff * sample - eps_coeff * eps'
 };
 // The same for every sampler that is a linear update in (sample, model output, one step of history, noise): DDIM, DPM-Solver++(2M), Euler,
-// Euler ancestral (unet.hip builds the rows in double and rounds them to fp32 once).  With e the guided model output and x the latents:
+// Euler ancestral (sd_schedule.hip builds the rows in double and rounds them to fp32 once).  With e the guided model output and x the latents:
 //   m = p_x * x + p_e * e ;  if slot_new >= 0: ring[slot_new] = m ;  x_next = c_x * x + c_0 * m + c_1 * ring[s1] + c_n * z[step]
 // ring[s1] is read only where c_1 != 0 and the noise only where c_n != 0.  in_scale is scale_model_input, applied by the stage kernel.
 struct SamplerRow {

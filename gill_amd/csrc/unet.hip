@@ -19,11 +19,11 @@
 // time projections for every timestep (one batched GEMM chain -> a [steps][sum Cout] table that the
 // conv epilogues add as a per-channel row vector).
 #include "convnet.h"
+#include "sd_schedule.h"
+#include "xf_weights.h"
 #include <math.h>
-#include <stdlib.h>
 #include <map>
 #include <set>
-#include <hip/hip_fp16.h>
 
 namespace {
 
@@ -52,7 +52,7 @@ struct XfW {  // Transformer2DModel with one BasicTransformerBlock
   bf16_t *wqkv1p = nullptr, *wq2p = nullptr;   // wqkv1 / wq2 (LayerNorm-folded) with the K order of the fused projection pairs (lnproj.hip; C = 320 only)
   // norm1/2/3 are folded into wqkv1 / wq2 / wff1 at load (GemmArgs::ln_stats): column sums of g*W and beta.W^T (+ bias)
   float *s_qkv1 = nullptr, *c_qkv1 = nullptr, *s_q2 = nullptr, *c_q2 = nullptr, *s_ff1 = nullptr;
-  bf16_t* xg = nullptr; float* xgb = nullptr;   // XALG (see xalg_fold_kernel): [2 H C][ctx_dim] = G | G2, and gb [H][ctx_dim]; null = attention-kernel form
+  bf16_t* xg = nullptr; float* xgb = nullptr;   // XALG (xf_weights.hip): [2 H C][ctx_dim] = G | G2, and gb [H][ctx_dim]; null = attention-kernel form
   LinW ff2;                   // [C][4C]
   bf16_t* wfo = nullptr; float* bfo = nullptr;   // ff2 and proj_out as one map: [C][4C + C] = [Wp W2 | Wp], bias Wp b2 + bp
 };
@@ -139,156 +139,6 @@ struct gill_unet : ConvWorkspace {
   }
 };
 
-// dst[r][h*dp + dd] = src[r][h*d + dd] (dd < d), zero elsewhere.  dst pre-zeroed.
-__global__ __launch_bounds__(256) void pad_head_cols_kernel(const void* src, int dtype, int rows, int H, int d, int dp,
-                                                            bf16_t* dst) {
-  const int64_t total = (int64_t)rows * H * d;
-  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (int64_t)gridDim.x * blockDim.x) {
-    const int dd = (int)(i % d);
-    const int h = (int)((i / d) % H);
-    const int64_t r = i / ((int64_t)d * H);
-    float v;
-    if (dtype == 0) v = bf2f(((const bf16_t*)src)[i]);
-    else if (dtype == 1) v = ((const float*)src)[i];
-    else v = (float)(((const __half*)src)[i]);
-    dst[r * (int64_t)H * dp + h * dp + dd] = f2bf(v);
-  }
-}
-// dst[(h*dp + dd)][:] = src[(h*d + dd)][:]  (row padding of q/k/v projection weights).  dst pre-zeroed.
-__global__ __launch_bounds__(256) void pad_head_rows_kernel(const void* src, int dtype, int H, int d, int dp, int cols,
-                                                            bf16_t* dst) {
-  const int64_t total = (int64_t)H * d * cols;
-  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (int64_t)gridDim.x * blockDim.x) {
-    const int c = (int)(i % cols);
-    const int64_t r = i / cols;
-    const int h = (int)(r / d), dd = (int)(r % d);
-    float v;
-    if (dtype == 0) v = bf2f(((const bf16_t*)src)[i]);
-    else if (dtype == 1) v = ((const float*)src)[i];
-    else v = (float)(((const __half*)src)[i]);
-    dst[((int64_t)h * dp + dd) * cols + c] = f2bf(v);
-  }
-}
-
-// Feed-forward output and proj_out are two linear maps with only a residual add in between:
-//   out = proj_out(ff2(h) + t) + x_in = h (Wp W2)^T + t Wp^T + (Wp b2 + bp) + x_in
-// so they run as ONE two-source GEMM over K = [h (4C) | t (C)].  This builds its weight rows [Wp W2 | Wp] ([C][5C], products in
-// fp32 from the checkpoint's own dtype, one rounding to bf16) and its bias Wp b2 + bp.  Load time only: plain loops.
-__device__ __forceinline__ float ld_any(const void* p, int dtype, int64_t i) {
-  if (dtype == 0) return bf2f(((const bf16_t*)p)[i]);
-  if (dtype == 1) return ((const float*)p)[i];
-  return (float)(((const __half*)p)[i]);
-}
-__global__ __launch_bounds__(256) void ffo_fuse_kernel(const void* wp, int dt_p, const void* w2, int dt_2, const void* b2, int dt_b2,
-                                                       const void* bp, int dt_bp, int C, bf16_t* w_out, float* b_out) {
-  const int n = blockIdx.y;                       // output row
-  const int k = blockIdx.x * 256 + threadIdx.x;   // column of [4C | C | 1 (bias)]
-  const int K4 = 4 * C;
-  if (k < K4) {
-    float a = 0.f;
-    for (int j = 0; j < C; ++j) a = fmaf(ld_any(wp, dt_p, (int64_t)n * C + j), ld_any(w2, dt_2, (int64_t)j * K4 + k), a);
-    w_out[(size_t)n * 5 * C + k] = f2bf(a);
-  } else if (k < 5 * C) {
-    w_out[(size_t)n * 5 * C + k] = f2bf(ld_any(wp, dt_p, (int64_t)n * C + (k - K4)));
-  } else if (k == 5 * C) {
-    float a = ld_any(bp, dt_bp, n);
-    for (int j = 0; j < C; ++j) a = fmaf(ld_any(wp, dt_p, (int64_t)n * C + j), ld_any(b2, dt_b2, j), a);
-    b_out[n] = a;
-  }
-}
-
-// CROSS-ATTENTION AS TWO GEMMs ("XALG": UNet levels 1-3, head dim >= 80).  The keys and values of attn2 are linear maps of the 77 prompt
-// tokens, fixed for the whole denoising loop, so per sample b and head h
-//   scores[m][j] = qs LN(t)[m] . Wq_h^T K_bh[j]            = LN(t)[m] . (ctx_b[j] G_h)^T,     G_h  = qs (g o Wq_h)^T Wk_h      [C][768]
-//   out[m]       = sum_h softmax(scores)[m][h][:] V_bh Wo_h^T = sum_h P[m][h][:] (ctx_b G2_h)^T, G2_h = Wo_h Wv_h             [C][768]
-// G / G2 depend on the weights only (built here at load, fp32 products of the bf16 weights, one rounding); once per prompt the
-// context turns them into per-sample weight matrices (unet_ctx_cache) and every UNet call then runs attn2 as
-//   P = softmax80(LN(t) Mq_b^T)  (GEMM, N = 80 H: GemmArgs::OUT_SOFTMAX80)   and   t += P Wo_b^T + bias  (GEMM, K = 80 H)
-// instead of to_q + the attention kernel + to_out: at d = 160 (levels 2-3) both GEMMs are half the size of the projections they
-// replace, and the attention launch is gone.  GILL_UNET_XALG = 0 keeps the three-kernel form.
-// rows [0, H C): G[h][c][:]; rows [H C, 2 H C): G2[h][co][:].  8 rows per workgroup (one head), threads over the 768 context features.
-__global__ __launch_bounds__(256) void xalg_fold_kernel(const bf16_t* __restrict__ wq, const bf16_t* __restrict__ wkv, const bf16_t* __restrict__ wo,
-                                                        int H, int C, int dp, int E, float qs, bf16_t* __restrict__ G) {
-  __shared__ float a[8][160];
-  const int r0 = blockIdx.x * 8;                  // first of 8 rows (C % 8 == 0: one head, one half)
-  const int half = r0 >= H * C;
-  const int rr = r0 - half * H * C;
-  const int h = rr / C, c0 = rr - h * C;
-  const int hdp = H * dp;
-  for (int i = threadIdx.x; i < 8 * dp; i += 256) {
-    const int r = i / dp, n = i - r * dp;
-    a[r][n] = half ? bf2f(wo[(size_t)(c0 + r) * hdp + h * dp + n]) : qs * bf2f(wq[(size_t)(h * dp + n) * C + c0 + r]);
-  }
-  __syncthreads();
-  const bf16_t* wb = wkv + (size_t)(half * hdp + h * dp) * E;      // Wk_h | Wv_h: [dp][E]
-  for (int e = threadIdx.x; e < E; e += 256) {
-    float acc[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-    for (int n = 0; n < dp; ++n) {
-      const float b = bf2f(wb[(size_t)n * E + e]);
-#pragma unroll
-      for (int r = 0; r < 8; ++r) acc[r] = fmaf(a[r][n], b, acc[r]);
-    }
-#pragma unroll
-    for (int r = 0; r < 8; ++r) G[(size_t)(r0 + r) * E + e] = f2bf(acc[r]);
-  }
-}
-// gb[h][e] = qs sum_n c_q[h dp + n] Wk[h dp + n][e]   (c_q = beta . Wq^T: the constant part of the folded norm2 -> to_q)
-__global__ __launch_bounds__(256) void xalg_fold_bias_kernel(const float* __restrict__ cq, const bf16_t* __restrict__ wk, int dp, int E, float qs,
-                                                             float* __restrict__ gb) {
-  const int h = blockIdx.y, e = blockIdx.x * 256 + threadIdx.x;
-  if (e >= E) return;
-  float acc = 0.f;
-  for (int n = 0; n < dp; ++n) acc = fmaf(cq[h * dp + n], bf2f(wk[(size_t)(h * dp + n) * E + e]), acc);
-  gb[(size_t)h * E + e] = qs * acc;
-}
-// Once per prompt: T [Bx ctx_len][2 H C] = ctx [G | G2]^T (one GEMM) is dealt into the per-sample operands of the two GEMMs.
-// Scores operand: Mq[b][80 h + j][:] = T[b ctx_len + j][h C ..], its row sums (folded LayerNorm) and the constant term ctx_b[j] . gb[h];
-// key slots j >= ctx_len: zero rows with constant -1e30 (softmax weight 0).  One workgroup per (b, h, j).
-__global__ __launch_bounds__(256) void xalg_scores_operand_kernel(const bf16_t* __restrict__ T, const bf16_t* __restrict__ ctx, const float* __restrict__ gb,
-                                                                  int H, int C, int E, int ctx_len, bf16_t* __restrict__ Mq, float* __restrict__ cs,
-                                                                  float* __restrict__ cb) {
-  __shared__ float red[2][4];
-  const int j = blockIdx.x % 80, h = (blockIdx.x / 80) % H, b = blockIdx.x / (80 * H);
-  bf16_t* dst = Mq + (size_t)blockIdx.x * C;
-  float sum = 0.f, dot = 0.f;
-  if (j < ctx_len) {
-    const bf16_t* src = T + (size_t)(b * ctx_len + j) * (2 * H * C) + (size_t)h * C;
-    for (int c = threadIdx.x * 8; c < C; c += 2048) {
-      const uint4 v = *reinterpret_cast<const uint4*>(src + c);
-      *reinterpret_cast<uint4*>(dst + c) = v;
-      const uint32_t w[4] = {v.x, v.y, v.z, v.w};
-#pragma unroll
-      for (int i = 0; i < 4; ++i) sum += __uint_as_float(w[i] << 16) + __uint_as_float(w[i] & 0xffff0000u);
-    }
-    const bf16_t* cr = ctx + (size_t)(b * ctx_len + j) * E;
-    for (int e = threadIdx.x; e < E; e += 256) dot = fmaf(bf2f(cr[e]), gb[(size_t)h * E + e], dot);
-  } else {
-    for (int c = threadIdx.x * 8; c < C; c += 2048) *reinterpret_cast<uint4*>(dst + c) = make_uint4(0, 0, 0, 0);
-  }
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) { sum += __shfl_xor(sum, o, 64); dot += __shfl_xor(dot, o, 64); }
-  if ((threadIdx.x & 63) == 0) { red[0][threadIdx.x >> 6] = sum; red[1][threadIdx.x >> 6] = dot; }
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    cs[blockIdx.x] = red[0][0] + red[0][1] + red[0][2] + red[0][3];
-    cb[blockIdx.x] = j < ctx_len ? red[1][0] + red[1][1] + red[1][2] + red[1][3] : -1e30f;
-  }
-}
-// Values operand: Wo_b[co][80 h + j] = T[b ctx_len + j][H C + h C + co] (0 for j >= ctx_len): an 80 x 64 transpose per workgroup (b, h, co / 64).
-__global__ __launch_bounds__(256) void xalg_values_operand_kernel(const bf16_t* __restrict__ T, int H, int C, int ctx_len, bf16_t* __restrict__ Wo) {
-  __shared__ bf16_t tile[80][66];
-  const int cb = blockIdx.x % (C / 64), h = (blockIdx.x / (C / 64)) % H, b = blockIdx.x / ((C / 64) * H);
-  for (int i = threadIdx.x; i < 80 * 64; i += 256) {
-    const int j = i >> 6, c = i & 63;
-    tile[j][c] = j < ctx_len ? T[(size_t)(b * ctx_len + j) * (2 * H * C) + (size_t)H * C + (size_t)h * C + cb * 64 + c] : (bf16_t)0;
-  }
-  __syncthreads();
-  for (int i = threadIdx.x; i < 64 * 80; i += 256) {
-    const int c = i / 80, j = i - c * 80;
-    Wo[((size_t)b * C + cb * 64 + c) * (80 * H) + h * 80 + j] = tile[j][c];
-  }
-}
-
 // The feed-forward sub-blocks at C = 320 (level 0) run as one kernel (ffn.hip) instead of GEGLU + the two-source ffo GEMM: loop
 // 528.9 -> 522.8 ms.  GILL_UNET_FFN_FUSED = 0 restores the two GEMMs.
 // GILL_UNET_LNPROJ=0: proj_in / QKV and attn1.to_out / attn2.to_q of the level-0 blocks as the separate GEMMs
@@ -296,7 +146,7 @@ static bool lnproj_on() {
   static const bool on = [] { const char* e = getenv("GILL_UNET_LNPROJ"); return !(e && e[0] == '0'); }();
   return on;
 }
-// GILL_UNET_XALG=0: attn2 of levels 1-3 as to_q + attention kernel + to_out instead of the two per-sample GEMMs (xalg_fold_kernel)
+// GILL_UNET_XALG=0: attn2 of levels 1-3 as to_q + attention kernel + to_out instead of the two per-sample GEMMs ("XALG": xf_weights.hip)
 static bool xalg_on() {
   static const bool on = [] { const char* e = getenv("GILL_UNET_XALG"); return !(e && e[0] == '0'); }();
   return on;
@@ -322,14 +172,6 @@ struct Loader {
     l->out = out; l->in = in;
     GILL_TRY(load_bf16(wt, pool, p + ".weight", (int64_t)out * in, &l->w, s));
     if (bias) return load_f32(wt, pool, p + ".bias", out, &l->b, s);
-    return 0;
-  }
-  // projection weight [H*d][cols] -> [H*dp][cols] into a caller-provided slot
-  int head_rows(const std::string& name, int H, int d, int dp, int cols, bf16_t* dst) {
-    const gill_tensor* t;
-    GILL_TRY(wt.get(name, (int64_t)H * d * cols, &t));
-    hipLaunchKernelGGL(pad_head_rows_kernel, dim3(1024), dim3(256), 0, s, t->data, t->dtype, H, d, dp, cols, dst);
-    GILL_CHECK_HIP(hipGetLastError());
     return 0;
   }
   int resnet(const std::string& p, int cin, int cout, int hw, int temb_dim, int* temb_off, bf16_t* temb_w, float* temb_b,
@@ -367,15 +209,19 @@ struct Loader {
     GILL_TRY(norm(b + ".norm1", C, &x->ln1));
     GILL_TRY(norm(b + ".norm2", C, &x->ln2));
     GILL_TRY(norm(b + ".norm3", C, &x->ln3));
+    const char* proj[6] = {".attn1.to_q", ".attn1.to_k", ".attn1.to_v", ".attn2.to_q", ".attn2.to_k", ".attn2.to_v"};
+    HeadRows hr[6];   // attn1's q | k | v, attn2's q, attn2's k | v (over the context): segments of the xf_weights.h recipes, which the operator entries run too (here step by step: the launches keep this loader's order)
+    for (int i = 0; i < 6; ++i) {
+      const gill_tensor* t;
+      GILL_TRY(wt.get(b + proj[i] + ".weight", (int64_t)C * (i < 4 ? C : ctx_dim), &t));
+      hr[i] = HeadRows{t->data, t->dtype};
+    }
     GILL_TRY(pool.alloc(&x->wqkv1, (size_t)3 * hdp * C, true));
-    GILL_TRY(head_rows(b + ".attn1.to_q.weight", H, x->d, x->dp, C, x->wqkv1));
-    GILL_TRY(head_rows(b + ".attn1.to_k.weight", H, x->d, x->dp, C, x->wqkv1 + (size_t)hdp * C));
-    GILL_TRY(head_rows(b + ".attn1.to_v.weight", H, x->d, x->dp, C, x->wqkv1 + (size_t)2 * hdp * C));
     GILL_TRY(pool.alloc(&x->wq2, (size_t)hdp * C, true));
-    GILL_TRY(head_rows(b + ".attn2.to_q.weight", H, x->d, x->dp, C, x->wq2));
     GILL_TRY(pool.alloc(&x->wkv2, (size_t)2 * hdp * ctx_dim, true));
-    GILL_TRY(head_rows(b + ".attn2.to_k.weight", H, x->d, x->dp, ctx_dim, x->wkv2));
-    GILL_TRY(head_rows(b + ".attn2.to_v.weight", H, x->d, x->dp, ctx_dim, x->wkv2 + (size_t)hdp * ctx_dim));
+    GILL_TRY(xf_qkv_weights(hr, 3, nullptr, H, x->d, x->dp, C, x->ln1.g, x->ln1.b, x->wqkv1, x->s_qkv1, x->c_qkv1, x->wqkv1p, s, XF_LAYOUT));
+    GILL_TRY(xf_qkv_weights(hr + 3, 1, nullptr, H, x->d, x->dp, C, x->ln2.g, x->ln2.b, x->wq2, x->s_q2, x->c_q2, x->wq2p, s, XF_LAYOUT));
+    GILL_TRY(xf_qkv_weights(hr + 4, 2, nullptr, H, x->d, x->dp, ctx_dim, nullptr, nullptr, x->wkv2, nullptr, nullptr, nullptr, s));   // (no LayerNorm in front of to_k / to_v)
     for (int a = 1; a <= 2; ++a) {
       LinW* o = (a == 1) ? &x->out1 : &x->out2;
       const std::string on = b + ".attn" + std::to_string(a) + ".to_out.0";
@@ -383,44 +229,32 @@ struct Loader {
       const gill_tensor* t;
       GILL_TRY(wt.get(on + ".weight", (int64_t)C * C, &t));
       GILL_TRY(pool.alloc(&o->w, (size_t)C * hdp, true));
-      hipLaunchKernelGGL(pad_head_cols_kernel, dim3(1024), dim3(256), 0, s, t->data, t->dtype, C, H, x->d, x->dp, o->w);
-      GILL_CHECK_HIP(hipGetLastError());
+      GILL_TRY(pad_head_cols_launch(t->data, t->dtype, C, H, x->d, x->dp, o->w, s));
       GILL_TRY(load_f32(wt, pool, on + ".bias", C, &o->b, s));
     }
-    // GEGLU projection: permute rows (value/gate 16-row interleave)
-    {
-      const int inner = 4 * C;
-      bf16_t* tmpw; float* tmpb; int32_t* idx;
-      GILL_TRY(load_bf16(wt, pool, b + ".ff.net.0.proj.weight", (int64_t)2 * inner * C, &tmpw, s));
-      GILL_TRY(load_f32(wt, pool, b + ".ff.net.0.proj.bias", 2 * inner, &tmpb, s));
-      std::vector<int32_t> map = geglu_row_permutation(inner);
-      GILL_TRY(pool.alloc(&idx, map.size(), false));
-      GILL_CHECK_HIP(hipMemcpy(idx, map.data(), sizeof(int32_t) * map.size(), hipMemcpyHostToDevice));
-      GILL_TRY(pool.alloc(&x->wff1, (size_t)2 * inner * C, false));
-      GILL_TRY(pool.alloc(&x->bff1, (size_t)2 * inner, false));
-      GILL_TRY(scatter_rows_bf16_launch(tmpw, 2 * inner, C, idx, x->wff1, C, s));
-      GILL_TRY(permute_f32_launch(tmpb, idx, 2 * inner, x->bff1, s));
-    }
+    // GEGLU projection: its rows in the value / gate 16-row interleave
+    const int inner = 4 * C; bf16_t* tmpw; float* tmpb; int32_t* idx;
+    GILL_TRY(load_bf16(wt, pool, b + ".ff.net.0.proj.weight", (int64_t)2 * inner * C, &tmpw, s));
+    GILL_TRY(load_f32(wt, pool, b + ".ff.net.0.proj.bias", 2 * inner, &tmpb, s));
+    GILL_TRY(pool.alloc(&idx, (size_t)2 * inner, false));
+    GILL_TRY(pool.alloc(&x->wff1, (size_t)2 * inner * C, false));
+    GILL_TRY(pool.alloc(&x->bff1, (size_t)2 * inner, false));
+    GILL_TRY(xf_geglu_weights(tmpw, tmpb, inner, C, x->ln3.g, x->ln3.b, idx, x->wff1, x->bff1, x->s_ff1, s, XF_LAYOUT));
     GILL_TRY(lin(b + ".ff.net.2", C, 4 * C, &x->ff2));
-    {
-      const gill_tensor *tp, *t2, *tb2, *tbp;
-      GILL_TRY(wt.get(p + ".proj_out.weight", (int64_t)C * C, &tp));
-      GILL_TRY(wt.get(b + ".ff.net.2.weight", (int64_t)C * 4 * C, &t2));
-      GILL_TRY(wt.get(b + ".ff.net.2.bias", C, &tb2));
-      GILL_TRY(wt.get(p + ".proj_out.bias", C, &tbp));
-      GILL_TRY(pool.alloc(&x->wfo, (size_t)C * 5 * C, false));
-      GILL_TRY(pool.alloc(&x->bfo, (size_t)C, false));
-      hipLaunchKernelGGL(ffo_fuse_kernel, dim3(cdiv(5 * C + 1, 256), C), dim3(256), 0, s, tp->data, tp->dtype, t2->data, t2->dtype,
-                         tb2->data, tb2->dtype, tbp->data, tbp->dtype, C, x->wfo, x->bfo);
-      GILL_CHECK_HIP(hipGetLastError());
-    }
-    // fold the three LayerNorms into the projections that consume them
+    const gill_tensor *tp, *t2, *tb2, *tbp;      // ff2 and proj_out once more, as one map
+    GILL_TRY(wt.get(p + ".proj_out.weight", (int64_t)C * C, &tp));
+    GILL_TRY(wt.get(b + ".ff.net.2.weight", (int64_t)C * 4 * C, &t2));
+    GILL_TRY(wt.get(b + ".ff.net.2.bias", C, &tb2));
+    GILL_TRY(wt.get(p + ".proj_out.bias", C, &tbp));
+    GILL_TRY(pool.alloc(&x->wfo, (size_t)C * 5 * C, false)); GILL_TRY(pool.alloc(&x->bfo, (size_t)C, false));
+    GILL_TRY(xf_ffo_weights(tp->data, tp->dtype, t2->data, t2->dtype, tb2->data, tb2->dtype, tbp->data, tbp->dtype, C, x->wfo, x->bfo, s));
+    // the three LayerNorms are folded into the projections that consume them (zeroed: the fold ADDS its constant part to the bias it is given)
     GILL_TRY(pool.alloc(&x->s_qkv1, (size_t)3 * hdp)); GILL_TRY(pool.alloc(&x->c_qkv1, (size_t)3 * hdp));
     GILL_TRY(pool.alloc(&x->s_q2, (size_t)hdp)); GILL_TRY(pool.alloc(&x->c_q2, (size_t)hdp));
     GILL_TRY(pool.alloc(&x->s_ff1, (size_t)8 * C));
-    GILL_TRY(ln_fold_rows_launch(x->wqkv1, 3 * hdp, C, x->ln1.g, x->ln1.b, x->s_qkv1, x->c_qkv1, s));
-    GILL_TRY(ln_fold_rows_launch(x->wq2, hdp, C, x->ln2.g, x->ln2.b, x->s_q2, x->c_q2, s));
-    GILL_TRY(ln_fold_rows_launch(x->wff1, 8 * C, C, x->ln3.g, x->ln3.b, x->s_ff1, x->bff1, s));
+    GILL_TRY(xf_qkv_weights(hr, 3, nullptr, H, x->d, x->dp, C, x->ln1.g, x->ln1.b, x->wqkv1, x->s_qkv1, x->c_qkv1, x->wqkv1p, s, XF_FOLD));
+    GILL_TRY(xf_qkv_weights(hr + 3, 1, nullptr, H, x->d, x->dp, C, x->ln2.g, x->ln2.b, x->wq2, x->s_q2, x->c_q2, x->wq2p, s, XF_FOLD));
+    GILL_TRY(xf_geglu_weights(tmpw, tmpb, inner, C, x->ln3.g, x->ln3.b, idx, x->wff1, x->bff1, x->s_ff1, s, XF_FOLD));
     // fp8 mode (BASELINE configs[4]): the GEGLU projection of the blocks that run it as a GEMM (levels 1-3; level 0 has the fused feed-forward
     // kernel) on the fp8 matrix instruction — the folded rows quantised per output row
     if (f8 && C % 128 == 0 && !(ffn_fused_on() && ffn_fused_supported(C, 128))) {
@@ -434,11 +268,7 @@ struct Loader {
     if (xalg_on() && H % 2 == 0 && ctx_len <= 80 && 80 * H <= hdp && x->dp <= 160 && C % 64 == 0 && ctx_dim % 64 == 0 && hw % 64 == 0) {
       GILL_TRY(pool.alloc(&x->xg, (size_t)2 * H * C * ctx_dim, false));
       GILL_TRY(pool.alloc(&x->xgb, (size_t)H * ctx_dim));
-      const float qs = 1.4426950408889634f / sqrtf((float)x->d);
-      hipLaunchKernelGGL(xalg_fold_kernel, dim3(2 * H * C / 8), dim3(256), 0, s, x->wq2, x->wkv2, x->out2.w, H, C, x->dp, ctx_dim, qs, x->xg);
-      GILL_CHECK_HIP(hipGetLastError());
-      hipLaunchKernelGGL(xalg_fold_bias_kernel, dim3(cdiv(ctx_dim, 256), H), dim3(256), 0, s, x->c_q2, x->wkv2, x->dp, ctx_dim, qs, x->xgb);
-      GILL_CHECK_HIP(hipGetLastError());
+      GILL_TRY(xalg_fold_launch(x->wq2, x->c_q2, x->wkv2, x->out2.w, H, C, x->d, x->dp, ctx_dim, x->xg, x->xgb, s));
     }
     if (ffn_fused_on() && ffn_fused_supported(C, 128)) {
       GILL_TRY(pool.alloc(&x->w1c, (size_t)8 * C * C, false));
@@ -451,8 +281,8 @@ struct Loader {
     if (lnproj_on() && lnproj_supported(C, 128, H, x->dp)) {
       GILL_TRY(pool.alloc(&x->wqkv1p, (size_t)3 * hdp * C, false));
       GILL_TRY(pool.alloc(&x->wq2p, (size_t)hdp * C, false));
-      GILL_TRY(lnproj_kperm_launch(x->wqkv1, 3 * hdp, x->wqkv1p, s));
-      GILL_TRY(lnproj_kperm_launch(x->wq2, hdp, x->wq2p, s));
+      GILL_TRY(xf_qkv_weights(hr, 3, nullptr, H, x->d, x->dp, C, x->ln1.g, x->ln1.b, x->wqkv1, x->s_qkv1, x->c_qkv1, x->wqkv1p, s, XF_KPERM));
+      GILL_TRY(xf_qkv_weights(hr + 3, 1, nullptr, H, x->d, x->dp, C, x->ln2.g, x->ln2.b, x->wq2, x->s_q2, x->c_q2, x->wq2p, s, XF_KPERM));
     }
     return 0;
   }
@@ -856,7 +686,7 @@ struct UNetRun : ConvRun {
     }
     // --- cross attention (K/V cached per prompt)
     if (w.xg) {
-      // ... as P = softmax80(LN(t) Mq_b^T), t += P Wo_b^T + bias on per-sample weights (xalg_fold_kernel)
+      // ... as P = softmax80(LN(t) Mq_b^T), t += P Wo_b^T + bias on per-sample weights (xf_weights.hip)
       const int n80 = 80 * nh, id = w.layer_id;
       GemmArgs g;
       g.M = M; g.N = n80; g.K = C; g.K1 = C; g.A = t.p; g.lda = C; g.W = m->xq_w[id];
@@ -922,7 +752,7 @@ struct UNetRun : ConvRun {
       g.act = ACT_GEGLU; g.C = ffh; g.ldc = 4 * C;
       GILL_TRY(gemm(g));
     }
-    // --- feed-forward output, its residual, proj_out and the outer residual: one GEMM over K = [h | t] (see ffo_fuse_kernel; the
+    // --- feed-forward output, its residual, proj_out and the outer residual: one GEMM over K = [h | t] (see ffo_fuse_kernel in xf_weights.hip; the
     // reference graph's two GEMMs measured 604.3 -> 588.9 ms against it, profiles/HISTORY.md)
     GILL_TRY(linear(ffh, 4 * C, tres, C, 4 * C, M, w.wfo, w.bfo, C, 5 * C, xd.p, ACT_NONE, out->p, C, out, nullptr, next));
     m->arena.release(mk);
@@ -1145,16 +975,7 @@ static int unet_ctx_cache(gill_unet* m, const bf16_t* ctx, int Bx, hipStream_t s
   auto one = [&](const XfW& w) -> int {
     if (w.xg) {
       const int H = w.heads, C = w.C, E = c.cross_attention_dim, id = w.layer_id;
-      bf16_t* T = (bf16_t*)m->arena.base;
-      GemmArgs g;
-      g.M = Bx * c.ctx_len; g.N = 2 * H * C; g.K = E; g.K1 = E; g.A = ctx; g.lda = E; g.W = w.xg; g.C = T; g.ldc = g.N;
-      GILL_TRY(gemm_launch(g, s));
-      hipLaunchKernelGGL(xalg_scores_operand_kernel, dim3(Bx * H * 80), dim3(256), 0, s, T, ctx, w.xgb, H, C, E, c.ctx_len, m->xq_w[id], m->xq_cs[id],
-                         m->xq_b[id]);
-      GILL_CHECK_HIP(hipGetLastError());
-      hipLaunchKernelGGL(xalg_values_operand_kernel, dim3(Bx * H * (C / 64)), dim3(256), 0, s, T, H, C, c.ctx_len, m->xo_w[id]);
-      GILL_CHECK_HIP(hipGetLastError());
-      return 0;
+      return xalg_operands_launch(ctx, w.xg, w.xgb, Bx, H, C, E, c.ctx_len, (bf16_t*)m->arena.base, m->xq_w[id], m->xq_cs[id], m->xq_b[id], m->xo_w[id], s);
     }
     GemmArgs g;
     g.M = Bx * c.ctx_len; g.N = 2 * w.heads * w.dp; g.K = c.cross_attention_dim; g.K1 = g.K;
@@ -1201,365 +1022,13 @@ extern "C" int gill_unet_forward(gill_unet* m, const float* sample, const float*
   return r.forward(sample, eps_out);
 }
 
-// ------------------------------------------------------------------------------------------------------------------
-// PNDM (PLMS, skip_prk_steps=True, steps_offset=1, scaled_linear betas 0.00085..0.012 over 1000 train steps).
-static void pndm_alphas_cumprod(std::vector<float>& ac) {
-  const int T = 1000;
-  ac.resize(T);
-  const float a = sqrtf(0.00085f), b = sqrtf(0.012f);
-  const float step = (b - a) / (float)(T - 1);
-  float prod = 1.f;
-  for (int i = 0; i < T; ++i) {
-    // torch.linspace (fp32): symmetric evaluation around the midpoint
-    const float v = (i < T / 2) ? a + step * (float)i : b - step * (float)(T - 1 - i);
-    const float beta = v * v;
-    prod *= (1.f - beta);
-    ac[i] = prod;
-  }
-}
-static void pndm_timesteps(int num_steps, std::vector<int>& ts, int* ratio_out, int steps_offset = 1) {
-  const int ratio = 1000 / num_steps;
-  std::vector<int> base(num_steps);
-  for (int i = 0; i < num_steps; ++i) base[i] = i * ratio + steps_offset;   // (1 for SD)
-  // plms_timesteps = concat(base[:-1], base[-2:-1], base[-1:])[::-1]
-  std::vector<int> seq(base.begin(), base.end() - 1);
-  if (num_steps >= 2) seq.push_back(base[num_steps - 2]);
-  seq.push_back(base[num_steps - 1]);
-  ts.assign(seq.rbegin(), seq.rend());
-  *ratio_out = ratio;
-}
-
-extern "C" int gill_pndm_schedule(int num_steps, int32_t* timesteps_out, double* alphas_cumprod_out) {
-  GILL_REQUIRE(num_steps >= 2 && num_steps <= 1000, "num_steps out of range");
-  std::vector<int> ts; int ratio;
-  pndm_timesteps(num_steps, ts, &ratio);
-  if (timesteps_out) for (size_t i = 0; i < ts.size(); ++i) timesteps_out[i] = ts[i];
-  if (alphas_cumprod_out) {
-    std::vector<float> ac; pndm_alphas_cumprod(ac);
-    for (int i = 0; i < 1000; ++i) alphas_cumprod_out[i] = (double)ac[i];
-  }
-  return (int)ts.size();
-}
-
-// the PLMS schedule of every call (host arithmetic in double, like the scheduler's numpy/torch-CPU tables)
-static void pndm_rows(const std::vector<int>& ts, int ratio, const std::vector<float>& ac, bool v_prediction, bool set_alpha_to_one,
-                      std::vector<PlmsRow>& rows) {
-  const int ncalls = (int)ts.size();
-  rows.resize(ncalls);
-  int counter = 0, n_ets = 0, last = -1;
-  for (int i = 0; i < ncalls; ++i) {
-    int t = ts[i];
-    int prev_t = t - ratio;
-    PlmsRow& a = rows[i];
-    a.slot_new = -1; a.s1 = a.s2 = a.s3 = 0;
-    if (counter != 1) {
-      a.slot_new = (last + 1) & 3;
-      a.s1 = last & 3; a.s2 = (last + 3) & 3; a.s3 = (last + 2) & 3;
-      last = a.slot_new;
-      if (n_ets < 4) ++n_ets;
-    } else {
-      prev_t = t; t = t + ratio;
-      a.s1 = last & 3;
-    }
-    if (n_ets == 1 && counter == 0) a.mode = 0;
-    else if (n_ets == 1 && counter == 1) a.mode = 1;
-    else if (n_ets == 2) a.mode = 2;
-    else if (n_ets == 3) a.mode = 3;
-    else a.mode = 4;
-    // _get_prev_sample
-    const double at = ac[t];
-    const double ap = prev_t >= 0 ? (double)ac[prev_t] : (set_alpha_to_one ? 1.0 : (double)ac[0]);   // (False for SD)
-    const double bt = 1.0 - at, bp = 1.0 - ap;
-    const double sample_coeff = sqrt(ap / at);
-    const double denom = at * sqrt(bp) + sqrt(at * bt * ap);
-    double sc = sample_coeff, ec = (ap - at) / denom;
-    if (v_prediction) {   // the model output is v: eps' = sqrt(a_t) v + sqrt(1 - a_t) sample, folded into the two coefficients
-      sc -= ec * sqrt(bt);
-      ec *= sqrt(at);
-    }
-    a.sample_coeff = (float)sc;
-    a.eps_coeff = (float)ec;
-    ++counter;
-  }
-}
-
-// ------------------------------------------------------------------------------------------------------------------
-// The linear samplers (diffusers 0.17.1 as configured for SD: scaled_linear betas, no clipping / thresholding / Karras sigmas).  Every table is
-// built in double from the fp32 alphas_cumprod above and rounded to fp32 once, into SamplerRow.
-enum { SD_PNDM = 0, SD_DDIM = 1, SD_DPMPP_2M = 2, SD_EULER = 3, SD_EULER_A = 4 };
-
-// np.linspace(0, 999, num): arange(num) * step, the last element set to the end point
-static void linspace_999(int num, std::vector<double>& v) {
-  v.resize(num);
-  const double step = num > 1 ? 999.0 / (double)(num - 1) : 0.0;
-  for (int i = 0; i < num; ++i) v[i] = (double)i * step;
-  if (num > 1) v[num - 1] = 999.0;
-}
-
-struct SdSchedule {
-  int kind = 0;
-  std::vector<float> timesteps;       // one per UNet call, as the time embedding sees them
-  double init_noise_sigma = 1.0;
-  std::vector<PlmsRow> plms;          // kind 0
-  std::vector<SamplerRow> rows;       // every other kind
-  bool needs_noise = false;           // some row has c_n != 0
-  double add_a = 1.0, add_b = 0.0;    // the scheduler's add_noise() at the first timestep: x_start = add_a * init_latents + add_b * noise
-};
-
-// start (image-to-image, include/gill_amd.h gill_sd_schedule_from): the loop begins at step `start` of the num_steps schedule.  start == 0 is the
-// text-to-image table, bit for bit.
-//   ddim, euler, euler_ancestral: the tail of the full table;
-//   dpmsolver++: the tail, its first row a first-order step (the solver's history is empty, as diffusers' scheduler starts); ring slots keep the
-//     full table's parity, so the rows that follow read the slot the rebuilt row wrote;
-//   pndm: the PLMS warm-up pair replayed at t_s: t_s, t_s - D, t_s - D, t_s - 2D, ... (num_steps - start + 1 calls).  DELIBERATELY not what
-//     diffusers 0.17's img2img does (it slices the already-duplicated list, so that from the third call on the model is evaluated one grid step
-//     ahead of the latents): this is the warm-up a fresh run on the same grid makes from t_s.  With start == num_steps - 1 the second timestep
-//     falls below the grid's end: the coefficients then use the final alpha (as every step below t = 0 does) and the model sees t = 0.
-static int sd_schedule(const gill_sd_sampler* sp, bool vpred, int num_steps, SdSchedule& out, int start = 0) {
-  GILL_REQUIRE(sp != nullptr, "null sampler");
-  GILL_REQUIRE(sp->kind >= SD_PNDM && sp->kind <= SD_EULER_A, "unknown sampler kind (0 pndm, 1 ddim, 2 dpmsolver++, 3 euler, 4 euler_ancestral)");
-  out.kind = sp->kind;
-  std::vector<float> ac; pndm_alphas_cumprod(ac);
-  const int T = 1000;
-  if (sp->kind == SD_PNDM) {
-    GILL_REQUIRE(num_steps >= 2 && num_steps <= 1000, "num_steps out of range");
-    GILL_REQUIRE(sp->steps_offset >= 0, "pndm: steps_offset must be >= 0");
-    GILL_REQUIRE((num_steps - 1) * (T / num_steps) + sp->steps_offset < T, "pndm: num_steps and steps_offset put a timestep past the training range");
-    GILL_REQUIRE(start >= 0 && start < num_steps, "start must be in [0, num_steps)");
-    std::vector<int> ts; int ratio;
-    pndm_timesteps(num_steps, ts, &ratio, sp->steps_offset);
-    if (start > 0) {
-      // ts = [t_0, t_1, t_1, t_2, ...]: grid point k >= 1 sits at index k + 1
-      std::vector<int> tail;
-      const int ts_s = ts[start + 1];
-      tail.push_back(ts_s); tail.push_back(ts_s - ratio); tail.push_back(ts_s - ratio);
-      for (size_t k = (size_t)start + 3; k < ts.size(); ++k) tail.push_back(ts[k]);
-      tail.resize((size_t)(num_steps - start + 1));      // (start == num_steps - 1: the pair only)
-      ts.swap(tail);
-    }
-    pndm_rows(ts, ratio, ac, vpred, sp->set_alpha_to_one != 0, out.plms);
-    out.timesteps.resize(ts.size());
-    for (size_t i = 0; i < ts.size(); ++i) out.timesteps[i] = (float)(ts[i] > 0 ? ts[i] : 0);
-    out.add_a = sqrt((double)ac[ts[0]]); out.add_b = sqrt(1.0 - (double)ac[ts[0]]);
-    return 0;
-  }
-  GILL_REQUIRE(num_steps >= 1 && num_steps <= 1000, "num_steps out of range");
-  GILL_REQUIRE(start >= 0 && start < num_steps, "start must be in [0, num_steps)");
-  const int N = num_steps;
-  out.rows.assign(N, SamplerRow{-1, 0, 1.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f});
-  out.timesteps.resize(N);
-  auto put = [&](int i, int slot_new, int s1, double in_scale, double p_x, double p_e, double c_x, double c_0, double c_1, double c_n) {
-    out.rows[i] = SamplerRow{slot_new, s1, (float)in_scale, (float)p_x, (float)p_e, (float)c_x, (float)c_0, (float)c_1, (float)c_n};
-  };
-  if (sp->kind == SD_DDIM) {
-    GILL_REQUIRE(sp->eta >= 0.f, "ddim: eta must be >= 0");     // (a NaN fails this too)
-    GILL_REQUIRE(sp->steps_offset >= 0, "ddim: steps_offset must be >= 0");
-    const int r = T / N;
-    GILL_REQUIRE((N - 1) * r + sp->steps_offset < T, "ddim: num_steps and steps_offset put a timestep past the training range");
-    for (int i = 0; i < N; ++i) {
-      const int t = (N - 1 - i) * r + sp->steps_offset, prev = t - r;
-      const double at = ac[t], ap = prev >= 0 ? (double)ac[prev] : (sp->set_alpha_to_one ? 1.0 : (double)ac[0]);
-      const double sd = (double)sp->eta * sqrt((1.0 - ap) / (1.0 - at)) * sqrt(1.0 - at / ap);
-      const double dir = sqrt(1.0 - ap - sd * sd);
-      // m = eps;  x0 = (x - sqrt(1 - a_t) eps) / sqrt(a_t);  x_prev = sqrt(a_p) x0 + dir eps + sd z
-      put(i, -1, 0, 1.0, vpred ? sqrt(1.0 - at) : 0.0, vpred ? sqrt(at) : 1.0, sqrt(ap / at), dir - sqrt(ap) * sqrt(1.0 - at) / sqrt(at), 0.0, sd);
-      out.timesteps[i] = (float)t;
-      if (i == start) { out.add_a = sqrt(at); out.add_b = sqrt(1.0 - at); }
-    }
-  } else if (sp->kind == SD_DPMPP_2M) {
-    GILL_REQUIRE(N <= 999, "dpmsolver++: num_steps above 999 repeats a timestep");
-    std::vector<double> ls; linspace_999(N + 1, ls);
-    std::vector<int> ts(N + 1);       // ts[N] = 0: the target of the last call
-    for (int i = 0; i < N; ++i) ts[i] = (int)rint(ls[N - i]);     // np.round: half to even
-    ts[N] = 0;
-    auto alpha = [&](int t) { return sqrt((double)ac[t]); };
-    auto sigma = [&](int t) { return sqrt(1.0 - (double)ac[t]); };
-    auto lambda = [&](int t) { return log(alpha(t)) - log(sigma(t)); };
-    for (int i = 0; i < N; ++i) {
-      const int s0 = ts[i], t = ts[i + 1];
-      const double h = lambda(t) - lambda(s0), E = exp(-h) - 1.0;
-      const double p_x = vpred ? alpha(s0) : 1.0 / alpha(s0), p_e = vpred ? -sigma(s0) : -sigma(s0) / alpha(s0);   // m = x0
-      const bool first_order = i == start || (i == N - 1 && N < 15);    // empty history; lower_order_final (decided on the FULL schedule's length)
-      double c_0 = -alpha(t) * E, c_1 = 0.0;
-      if (!first_order) {
-        const double r0 = (lambda(s0) - lambda(ts[i - 1])) / h;
-        c_0 = -alpha(t) * E * (1.0 + 0.5 / r0);       // D1 = (m0 - m1) / r0
-        c_1 = 0.5 * alpha(t) * E / r0;
-      }
-      put(i, i & 1, (i + 1) & 1, 1.0, p_x, p_e, sigma(t) / sigma(s0), c_0, c_1, 0.0);
-      out.timesteps[i] = (float)s0;
-      if (i == start) { out.add_a = alpha(s0); out.add_b = sigma(s0); }
-    }
-  } else {   // Euler, Euler ancestral
-    std::vector<double> ls; linspace_999(N, ls);
-    std::vector<double> sg(N + 1);
-    double smax = 0.0;
-    for (int i = 0; i < N; ++i) {
-      const double t = ls[N - 1 - i];
-      int j = (int)floor(t); if (j > T - 2) j = T - 2;
-      const double f0 = sqrt((1.0 - (double)ac[j]) / (double)ac[j]), f1 = sqrt((1.0 - (double)ac[j + 1]) / (double)ac[j + 1]);
-      sg[i] = (f1 - f0) * (t - (double)j) + f0;      // np.interp
-      if (sg[i] > smax) smax = sg[i];
-      out.timesteps[i] = (float)t;
-    }
-    sg[N] = 0.0;
-    out.init_noise_sigma = smax;
-    out.add_a = 1.0; out.add_b = sg[start];
-    for (int i = 0; i < N; ++i) {
-      const double s = sg[i], to = sg[i + 1], q = s * s + 1.0;
-      // m = eps;  v-prediction: x0 = x / (s^2 + 1) - v s / sqrt(s^2 + 1), eps = (x - x0) / s
-      const double p_x = vpred ? s / q : 0.0, p_e = vpred ? 1.0 / sqrt(q) : 1.0;
-      if (sp->kind == SD_EULER) put(i, -1, 0, 1.0 / sqrt(q), p_x, p_e, 1.0, to - s, 0.0, 0.0);
-      else {
-        const double up = sqrt(to * to * (s * s - to * to) / (s * s)), down = sqrt(to * to - up * up);
-        put(i, -1, 0, 1.0 / sqrt(q), p_x, p_e, 1.0, down - s, 0.0, up);
-      }
-    }
-  }
-  if (start > 0) {
-    out.rows.erase(out.rows.begin(), out.rows.begin() + start);
-    out.timesteps.erase(out.timesteps.begin(), out.timesteps.begin() + start);
-  }
-  for (const SamplerRow& r : out.rows) {
-    const float v[7] = {r.in_scale, r.p_x, r.p_e, r.c_x, r.c_0, r.c_1, r.c_n};
-    for (float f : v) GILL_REQUIRE(std::isfinite(f), "sampler table: a coefficient is not finite for these arguments");
-    if (r.c_n != 0.f) out.needs_noise = true;
-  }
-  return 0;
-}
-
-extern "C" int gill_sd_schedule_from(const gill_sd_sampler* sampler, int v_prediction, int num_steps, int start, float* timesteps_out,
-                                     double* init_noise_sigma_out, double* rows_out, double* add_noise_out) {
-  SdSchedule sc;
-  GILL_TRY(sd_schedule(sampler, v_prediction != 0, num_steps, sc, start));
-  if (add_noise_out) { add_noise_out[0] = sc.add_a; add_noise_out[1] = sc.add_b; }
-  const int ncalls = (int)sc.timesteps.size();
-  if (timesteps_out) for (int i = 0; i < ncalls; ++i) timesteps_out[i] = sc.timesteps[i];
-  if (init_noise_sigma_out) *init_noise_sigma_out = sc.init_noise_sigma;
-  if (rows_out) {
-    for (int i = 0; i < ncalls; ++i) {
-      double* o = rows_out + (size_t)i * GILL_SD_ROW_DOUBLES;
-      for (int k = 0; k < GILL_SD_ROW_DOUBLES; ++k) o[k] = 0.0;
-      if (sc.kind == SD_PNDM) {
-        const PlmsRow& r = sc.plms[i];
-        o[0] = r.mode; o[1] = r.slot_new; o[2] = r.s1; o[3] = r.s2; o[4] = r.s3;
-        o[5] = 1.0; o[7] = 1.0; o[8] = r.sample_coeff; o[9] = -(double)r.eps_coeff;
-      } else {
-        const SamplerRow& r = sc.rows[i];
-        o[0] = -1.0; o[1] = r.slot_new; o[2] = r.s1;
-        o[5] = r.in_scale; o[6] = r.p_x; o[7] = r.p_e; o[8] = r.c_x; o[9] = r.c_0; o[10] = r.c_1; o[11] = r.c_n;
-      }
-    }
-  }
-  return ncalls;
-}
-extern "C" int gill_sd_schedule(const gill_sd_sampler* sampler, int v_prediction, int num_steps, float* timesteps_out,
-                                double* init_noise_sigma_out, double* rows_out) {
-  return gill_sd_schedule_from(sampler, v_prediction, num_steps, 0, timesteps_out, init_noise_sigma_out, rows_out, nullptr);
-}
-
-// Inpainting, blend mode: the add_noise pair (ka, kb) at the noise level the latents have AFTER call i of the table sd_schedule(..., start) builds,
-// so that ka * x0 + kb * z0 is the image at that level.  i < ncalls - 1: the pair at the timestep of call i + 1 (for the linear kinds that equals
-// sd_schedule's own add_noise pair at start + i + 1, built here from the same values without a table per step; for pndm sqrt(abar), sqrt(1 - abar) at the table's timestep i + 1, which repeats after the
-// warm-up pair: calls 0 and 1 both leave the latents at t_s - D).  The last call leaves the clean latents: (1, 0).
-static int sd_inpaint_keep(const gill_sd_sampler* sp, bool vpred, int num_steps, int start, const SdSchedule& sched, std::vector<double>& keep) {
-  const int ncalls = (int)sched.timesteps.size();
-  keep.assign((size_t)ncalls * 2, 0.0);
-  std::vector<float> ac; pndm_alphas_cumprod(ac);
-  std::vector<double> ls;
-  const bool euler = sched.kind == SD_EULER || sched.kind == SD_EULER_A;
-  if (euler) linspace_999(num_steps, ls);
-  for (int i = 0; i + 1 < ncalls; ++i) {
-    if (euler) {      // (1, sigma of full-table step start + i + 1), interpolated as sd_schedule does
-      const double t = ls[num_steps - 1 - (start + i + 1)];
-      int j = (int)floor(t); if (j > 998) j = 998;
-      const double f0 = sqrt((1.0 - (double)ac[j]) / (double)ac[j]), f1 = sqrt((1.0 - (double)ac[j + 1]) / (double)ac[j + 1]);
-      keep[2 * i] = 1.0; keep[2 * i + 1] = (f1 - f0) * (t - (double)j) + f0;
-    } else {          // pndm, ddim, dpmsolver++: integer timesteps (pndm's clamped at 0, as the table's are)
-      const double at = ac[(int)sched.timesteps[i + 1]];
-      keep[2 * i] = sqrt(at); keep[2 * i + 1] = sqrt(1.0 - at);
-    }
-  }
-  keep[2 * (ncalls - 1)] = 1.0; keep[2 * (ncalls - 1) + 1] = 0.0;
-  return 0;
-}
-extern "C" int gill_sd_inpaint_keep(const gill_sd_sampler* sampler, int v_prediction, int num_steps, int start, double* keep_out) {
-  SdSchedule sc;
-  GILL_TRY(sd_schedule(sampler, v_prediction != 0, num_steps, sc, start));
-  std::vector<double> keep;
-  GILL_TRY(sd_inpaint_keep(sampler, v_prediction != 0, num_steps, start, sc, keep));
-  if (keep_out) for (size_t i = 0; i < keep.size(); ++i) keep_out[i] = (double)(float)keep[i];     // the fp32 values the device reads, widened
-  return (int)sc.timesteps.size();
-}
-
 // init_noise != nullptr: image-to-image — the loop starts at step `start` from add_noise(latents0, init_noise) instead of latents0 * init_noise_sigma
 // inpaint (needs init_noise): 1 blend — latent_mask given, the handle's UNet takes the latents alone; 2 concat — latent_mask and masked_latents
 // given, the handle's UNet takes [latents | mask | masked-image latents]
 static int sd_denoise_on(gill_unet* m, const gill_sd_sampler* sampler, const void* cond_bf16, const void* uncond_bf16, int n_uncond,
                          const float* latents0, int B, int num_steps, float guidance, float* latents_out, const float* noise, hipStream_t s,
                          int start = 0, const float* init_noise = nullptr, int inpaint = 0, const float* latent_mask = nullptr,
-                         const float* masked_latents = nullptr);
-
-extern "C" int gill_sd_denoise_ex(gill_unet* m, const gill_sd_sampler* sampler, const void* cond_bf16, const void* uncond_bf16, int n_uncond,
-                                  const float* latents0, int B, int num_steps, float guidance, float* latents_out, const float* noise,
-                                  void* stream) {
-  GILL_REQUIRE(m && sampler && cond_bf16 && latents0 && latents_out, "null argument");
-  GILL_REQUIRE(guidance <= 1.0f || uncond_bf16 == nullptr || n_uncond == 1 || n_uncond == B,
-               "negative embeddings: batch must be 1 or B");
-  GILL_TRY(unet_coop_check());
-  hipStream_t caller = (hipStream_t)stream;
-  GILL_TRY(m->fence.enter(caller));
-  const int rc = sd_denoise_on(m, sampler, cond_bf16, uncond_bf16, n_uncond, latents0, B, num_steps, guidance, latents_out, noise, m->fence.stream);
-  GILL_TRY(m->fence.leave(caller));
-  return rc;
-}
-extern "C" int gill_sd_denoise_from(gill_unet* m, const gill_sd_sampler* sampler, const void* cond_bf16, const void* uncond_bf16, int n_uncond,
-                                    int start, const float* init_latents, const float* init_noise, int B, int num_steps, float guidance,
-                                    float* latents_out, const float* noise, void* stream) {
-  GILL_REQUIRE(m && sampler && cond_bf16 && init_latents && init_noise && latents_out, "null argument");
-  GILL_REQUIRE(guidance <= 1.0f || uncond_bf16 == nullptr || n_uncond == 1 || n_uncond == B,
-               "negative embeddings: batch must be 1 or B");
-  GILL_TRY(unet_coop_check());
-  hipStream_t caller = (hipStream_t)stream;
-  GILL_TRY(m->fence.enter(caller));
-  const int rc = sd_denoise_on(m, sampler, cond_bf16, uncond_bf16, n_uncond, init_latents, B, num_steps, guidance, latents_out, noise,
-                               m->fence.stream, start, init_noise);
-  GILL_TRY(m->fence.leave(caller));
-  return rc;
-}
-extern "C" int gill_sd_inpaint(gill_unet* m, const gill_sd_sampler* sampler, const void* cond_bf16, const void* uncond_bf16, int n_uncond,
-                               int start, const float* init_latents, const float* init_noise, const float* latent_mask,
-                               const float* masked_latents, int B, int num_steps, float guidance, float* latents_out, const float* noise,
-                               void* stream) {
-  GILL_REQUIRE(m && sampler && cond_bf16 && init_latents && init_noise && latent_mask && latents_out, "null argument");
-  GILL_REQUIRE(guidance <= 1.0f || uncond_bf16 == nullptr || n_uncond == 1 || n_uncond == B,
-               "negative embeddings: batch must be 1 or B");
-  const gill_unet_config& c = m->cfg;
-  if (masked_latents)
-    GILL_REQUIRE(c.in_channels == 2 * c.out_channels + 1,
-                 "inpaint: masked_latents given (concat mode), but this handle's UNet does not take [latents | mask | masked-image latents] "
-                 "(in_channels != 2 * out_channels + 1): pass NULL to blend with the mask instead");
-  else
-    GILL_REQUIRE(c.in_channels == c.out_channels,
-                 "inpaint: masked_latents is NULL (blend mode), but this handle's UNet takes more than the latents "
-                 "(in_channels != out_channels): an inpainting UNet needs the masked image's latents");
-  GILL_TRY(unet_coop_check());
-  hipStream_t caller = (hipStream_t)stream;
-  GILL_TRY(m->fence.enter(caller));
-  const int rc = sd_denoise_on(m, sampler, cond_bf16, uncond_bf16, n_uncond, init_latents, B, num_steps, guidance, latents_out, noise,
-                               m->fence.stream, start, init_noise, masked_latents ? 2 : 1, latent_mask, masked_latents);
-  GILL_TRY(m->fence.leave(caller));
-  return rc;
-}
-extern "C" int gill_sd_denoise(gill_unet* m, const void* cond_bf16, const void* uncond_bf16, int n_uncond, const float* latents0,
-                               int B, int num_steps, float guidance, float* latents_out, void* stream) {
-  const gill_sd_sampler pndm = {SD_PNDM, 1, 0, 0.f};
-  return gill_sd_denoise_ex(m, &pndm, cond_bf16, uncond_bf16, n_uncond, latents0, B, num_steps, guidance, latents_out, nullptr, stream);
-}
-
-static int sd_denoise_on(gill_unet* m, const gill_sd_sampler* sampler, const void* cond_bf16, const void* uncond_bf16, int n_uncond,
-                         const float* latents0, int B, int num_steps, float guidance, float* latents_out, const float* noise, hipStream_t s,
-                         int start, const float* init_noise, int inpaint, const float* latent_mask, const float* masked_latents) {
+                         const float* masked_latents = nullptr) {
   const bool cfg = guidance > 1.0f;     // do_classifier_free_guidance (custom_sd.py:588)
   const int Bx = cfg ? 2 * B : B;
   GILL_REQUIRE(B >= 1 && Bx <= m->cfg.max_batch, "batch exceeds the UNet handle's max_batch");
@@ -1667,386 +1136,57 @@ static int sd_denoise_on(gill_unet* m, const gill_sd_sampler* sampler, const voi
   return 0;
 }
 
-// ------------------------------------------------------------------------------------------------------------------
-// Operator-level entry for the loop's sampler arithmetic: the schedule, the stage and step kernels and the device-side step counter exactly as
-// sd_denoise_on drives them, the UNet replaced by the caller's model outputs.  For tests/test_samplers_gpu.py; synchronises.
-// inpaint 1 / 2 (gill_op_sd_inpaint_run): the blend kernel after every step / the concat stage kernel, and unet_in_out (ncalls,Bx,n_in) holds BOTH
-// CFG halves of the UNet input; inpaint 0 is the entry as it was.
-static int op_sd_sampler_run(const gill_sd_sampler* sampler, int v_prediction, int num_steps, int start, float guidance, const float* latents0,
-                             const float* init_noise, const float* model_out, const float* noise, int B, int64_t n, float* lat_out,
-                             float* unet_in_out, void* stream, int inpaint = 0, const float* latent_mask = nullptr,
-                             const float* masked_latents = nullptr, int64_t hw = 0) {
-  hipStream_t s = (hipStream_t)stream;
-  GILL_REQUIRE(sampler && latents0 && model_out && lat_out && unet_in_out, "null argument");
-  GILL_REQUIRE(B >= 1 && n >= 1 && (int64_t)B * n <= ((int64_t)1 << 28), "B, n out of range");
-  GILL_REQUIRE(inpaint == 0 || (init_noise && latent_mask && hw >= 1 && n % hw == 0), "inpaint: init_noise, latent_mask and hw dividing n required");
-  SdSchedule sched;
-  GILL_TRY(sd_schedule(sampler, v_prediction != 0, num_steps, sched, start));
-  GILL_REQUIRE(!sched.needs_noise || noise != nullptr, "this sampler draws noise in its steps: a [ncalls][B][n] noise table is required");
-  const bool linear = sched.kind != SD_PNDM, cfg = guidance > 1.0f;
-  const int ncalls = (int)sched.timesteps.size(), Bx = cfg ? 2 * B : B;
-  const size_t total = (size_t)B * n;
-  const size_t n_in = inpaint == 2 ? (size_t)(2 * n + hw) : (size_t)n;     // the UNet input's floats per sample
-  DevBuf rows, ctr, gd, slot, lat, lat2, saved, ring, keepd;
-  std::vector<float> keep32;
-  if (inpaint == 1) {
-    std::vector<double> keep;
-    GILL_TRY(sd_inpaint_keep(sampler, v_prediction != 0, num_steps, start, sched, keep));
-    keep32.assign(keep.begin(), keep.end());
-    GILL_TRY(keepd.alloc(sizeof(float) * keep32.size()));
-    GILL_CHECK_HIP(hipMemcpyAsync(keepd.p, keep32.data(), keepd.bytes, hipMemcpyHostToDevice, s));
-  }
-  GILL_TRY(rows.alloc(linear ? sizeof(SamplerRow) * ncalls : sizeof(PlmsRow) * ncalls));
-  GILL_CHECK_HIP(hipMemcpyAsync(rows.p, linear ? (const void*)sched.rows.data() : (const void*)sched.plms.data(), rows.bytes, hipMemcpyHostToDevice, s));
-  GILL_TRY(ctr.alloc_zero(sizeof(int) * 2, s));
-  GILL_TRY(gd.alloc(sizeof(float)));
-  GILL_CHECK_HIP(hipMemcpyAsync(gd.p, &guidance, sizeof(float), hipMemcpyHostToDevice, s));
-  GILL_TRY(slot.alloc(sizeof(noise)));
-  GILL_CHECK_HIP(hipMemcpyAsync(slot.p, &noise, sizeof(noise), hipMemcpyHostToDevice, s));
-  GILL_TRY(lat.alloc(sizeof(float) * total)); GILL_TRY(lat2.alloc(sizeof(float) * (size_t)B * n_in * 2));
-  GILL_TRY(saved.alloc(sizeof(float) * total)); GILL_TRY(ring.alloc(sizeof(float) * total * 4));
-  GILL_CHECK_HIP(hipStreamSynchronize(s));     // the host-side sources above are locals
-  if (init_noise) GILL_TRY(add_noise_f32_launch(latents0, init_noise, (float)sched.add_a, (float)sched.add_b, (int64_t)total, (float*)lat.p, s));
-  else GILL_TRY(scale_f32_launch(latents0, (float)sched.init_noise_sigma, (int64_t)total, (float*)lat.p, s));
-  SdLoopArgs la;
-  la.rows = linear ? nullptr : (const PlmsRow*)rows.p; la.ctr = (int*)ctr.p; la.temb_table = nullptr; la.temb_total = 0; la.temb_cur = nullptr;
-  la.lat = (float*)lat.p; la.lat2 = (float*)lat2.p; la.cur_sample = (float*)saved.p; la.ets = (float*)ring.p;
-  la.B = B; la.n = n; la.guidance = (const float*)gd.p; la.cfg = cfg ? 1 : 0;
-  if (linear) { la.srows = (const SamplerRow*)rows.p; la.noise = (const float* const*)slot.p; }
-  SdInpaintArgs ia;
-  ia.x0 = latents0; ia.z0 = init_noise; ia.mask = latent_mask; ia.xm = masked_latents; ia.keep = (const float*)keepd.p; ia.hw = hw;
-  for (int i = 0; i < ncalls; ++i) {
-    ia.l = la;
-    GILL_TRY(inpaint == 2 ? sd_stage_concat_launch(ia, s) : sd_stage_launch(la, s));
-    const size_t in_floats = inpaint ? (size_t)Bx * n_in : total;      // (the plain entries return the first CFG half only)
-    GILL_CHECK_HIP(hipMemcpyAsync(unet_in_out + (size_t)i * in_floats, lat2.p, sizeof(float) * in_floats, hipMemcpyDeviceToDevice, s));
-    la.eps = model_out + (size_t)i * Bx * n;
-    GILL_TRY(linear ? sampler_step_launch(la, s) : plms_step_launch(la, s));
-    if (inpaint == 1) GILL_TRY(sd_blend_launch(ia, s));
-    GILL_CHECK_HIP(hipMemcpyAsync(lat_out + (size_t)i * total, lat.p, sizeof(float) * total, hipMemcpyDeviceToDevice, s));
-  }
-  GILL_CHECK_HIP(hipStreamSynchronize(s));
-  return 0;
+// every public loop, its arguments checked: sd_denoise_on on the handle's private stream, between two fences to the caller's
+static int sd_denoise_fenced(gill_unet* m, const gill_sd_sampler* sampler, const void* cond_bf16, const void* uncond_bf16, int n_uncond, const float* latents0,
+                             int B, int num_steps, float guidance, float* latents_out, const float* noise, void* stream, int start = 0,
+                             const float* init_noise = nullptr, int inpaint = 0, const float* latent_mask = nullptr, const float* masked_latents = nullptr) {
+  GILL_TRY(unet_coop_check());
+  hipStream_t caller = (hipStream_t)stream;
+  GILL_TRY(m->fence.enter(caller));
+  const int rc = sd_denoise_on(m, sampler, cond_bf16, uncond_bf16, n_uncond, latents0, B, num_steps, guidance, latents_out, noise, m->fence.stream, start,
+                               init_noise, inpaint, latent_mask, masked_latents);
+  GILL_TRY(m->fence.leave(caller));
+  return rc;
 }
-extern "C" int gill_op_sd_sampler_run(const gill_sd_sampler* sampler, int v_prediction, int num_steps, float guidance, const float* latents0,
-                                      const float* model_out, const float* noise, int B, int64_t n, float* lat_out, float* unet_in_out,
-                                      void* stream) {
-  return op_sd_sampler_run(sampler, v_prediction, num_steps, 0, guidance, latents0, nullptr, model_out, noise, B, n, lat_out, unet_in_out, stream);
+extern "C" int gill_sd_denoise_ex(gill_unet* m, const gill_sd_sampler* sampler, const void* cond_bf16, const void* uncond_bf16, int n_uncond,
+                                  const float* latents0, int B, int num_steps, float guidance, float* latents_out, const float* noise,
+                                  void* stream) {
+  GILL_REQUIRE(m && sampler && cond_bf16 && latents0 && latents_out, "null argument");
+  GILL_REQUIRE(guidance <= 1.0f || uncond_bf16 == nullptr || n_uncond == 1 || n_uncond == B, "negative embeddings: batch must be 1 or B");
+  return sd_denoise_fenced(m, sampler, cond_bf16, uncond_bf16, n_uncond, latents0, B, num_steps, guidance, latents_out, noise, stream);
 }
-extern "C" int gill_op_sd_sampler_run_from(const gill_sd_sampler* sampler, int v_prediction, int num_steps, int start, float guidance,
-                                           const float* latents0, const float* init_noise, const float* model_out, const float* noise, int B,
-                                           int64_t n, float* lat_out, float* unet_in_out, void* stream) {
-  GILL_REQUIRE(init_noise != nullptr, "null argument");
-  return op_sd_sampler_run(sampler, v_prediction, num_steps, start, guidance, latents0, init_noise, model_out, noise, B, n, lat_out, unet_in_out,
-                           stream);
+extern "C" int gill_sd_denoise_from(gill_unet* m, const gill_sd_sampler* sampler, const void* cond_bf16, const void* uncond_bf16, int n_uncond,
+                                    int start, const float* init_latents, const float* init_noise, int B, int num_steps, float guidance,
+                                    float* latents_out, const float* noise, void* stream) {
+  GILL_REQUIRE(m && sampler && cond_bf16 && init_latents && init_noise && latents_out, "null argument");
+  GILL_REQUIRE(guidance <= 1.0f || uncond_bf16 == nullptr || n_uncond == 1 || n_uncond == B, "negative embeddings: batch must be 1 or B");
+  return sd_denoise_fenced(m, sampler, cond_bf16, uncond_bf16, n_uncond, init_latents, B, num_steps, guidance, latents_out, noise, stream, start, init_noise);
 }
-extern "C" int gill_op_sd_inpaint_run(const gill_sd_sampler* sampler, int v_prediction, int num_steps, int start, float guidance,
-                                      const float* latents0, const float* init_noise, const float* latent_mask, const float* masked_latents,
-                                      const float* model_out, const float* noise, int B, int64_t n, int64_t hw, float* lat_out,
-                                      float* unet_in_out, void* stream) {
-  GILL_REQUIRE(init_noise != nullptr && latent_mask != nullptr, "null argument");
-  return op_sd_sampler_run(sampler, v_prediction, num_steps, start, guidance, latents0, init_noise, model_out, noise, B, n, lat_out, unet_in_out,
-                           stream, masked_latents ? 2 : 1, latent_mask, masked_latents, hw);
+extern "C" int gill_sd_inpaint(gill_unet* m, const gill_sd_sampler* sampler, const void* cond_bf16, const void* uncond_bf16, int n_uncond,
+                               int start, const float* init_latents, const float* init_noise, const float* latent_mask,
+                               const float* masked_latents, int B, int num_steps, float guidance, float* latents_out, const float* noise,
+                               void* stream) {
+  GILL_REQUIRE(m && sampler && cond_bf16 && init_latents && init_noise && latent_mask && latents_out, "null argument");
+  GILL_REQUIRE(guidance <= 1.0f || uncond_bf16 == nullptr || n_uncond == 1 || n_uncond == B, "negative embeddings: batch must be 1 or B");
+  const gill_unet_config& c = m->cfg;
+  if (masked_latents)
+    GILL_REQUIRE(c.in_channels == 2 * c.out_channels + 1,
+                 "inpaint: masked_latents given (concat mode), but this handle's UNet does not take [latents | mask | masked-image latents] "
+                 "(in_channels != 2 * out_channels + 1): pass NULL to blend with the mask instead");
+  else
+    GILL_REQUIRE(c.in_channels == c.out_channels,
+                 "inpaint: masked_latents is NULL (blend mode), but this handle's UNet takes more than the latents "
+                 "(in_channels != out_channels): an inpainting UNet needs the masked image's latents");
+  return sd_denoise_fenced(m, sampler, cond_bf16, uncond_bf16, n_uncond, init_latents, B, num_steps, guidance, latents_out, noise, stream, start, init_noise,
+                           masked_latents ? 2 : 1, latent_mask, masked_latents);
+}
+extern "C" int gill_sd_denoise(gill_unet* m, const void* cond_bf16, const void* uncond_bf16, int n_uncond, const float* latents0,
+                               int B, int num_steps, float guidance, float* latents_out, void* stream) {
+  const gill_sd_sampler pndm = {SD_PNDM, 1, 0, 0.f};
+  return gill_sd_denoise_ex(m, &pndm, cond_bf16, uncond_bf16, n_uncond, latents0, B, num_steps, guidance, latents_out, nullptr, stream);
 }
 extern "C" int gill_sd_inpaint_prepare(const float* image, const float* mask, int B, int Bm, int H, int W, float* masked_image_out,
                                        float* latent_mask_out, void* stream) {
   GILL_REQUIRE(image && mask && masked_image_out && latent_mask_out, "null argument");
   return inpaint_prepare_launch(image, mask, B, Bm, H, W, masked_image_out, latent_mask_out, (hipStream_t)stream);
-}
-
-// ------------------------------------------------------------------------------------------------------------------
-// Operator-level entry for the fused feed-forward block (ffn.hip) on NATURAL operands (diffusers parameter layouts): folds norm3 into the
-// GEGLU projection, builds [Wp.W2 | Wp] and the kernel's weight layouts exactly as the engine's loader does, forms the LayerNorm row sums
-// of t, launches the kernel.  out = proj_out(ff2(geglu(ff1(LN(t)))) + t) + resid.  For tests/test_ops_gpu.py and tools; synchronises.
-__global__ __launch_bounds__(256) void ffn_op_rowsums_kernel(const bf16_t* __restrict__ t, int M, int C, float* __restrict__ stats) {
-  const int row = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
-  if (row >= M) return;
-  float a = 0.f, q = 0.f;
-  for (int k = lane; k < C; k += 64) { const float v = bf2f(t[(size_t)row * C + k]); a += v; q += v * v; }
-  a = wave_sum(a); q = wave_sum(q);
-  if (lane == 0) { stats[(size_t)row * 2] = a; stats[(size_t)row * 2 + 1] = q; }
-}
-// o2 / Wo / bo2 (optional, all or none): the PRE form — t := t + to_out(o2) first, inside the kernel (o2 [M][320] = the cross-attention
-// output, heads x 40; Wo [320][320], bo2 [320]: BasicTransformerBlock.attn2.to_out[0]).
-extern "C" int gill_op_ffn_fused(const void* t, const float* ln_g, const float* ln_b, const void* W1, const float* b1, const void* W2,
-                                 const float* b2, const void* Wp, const float* bp, const void* resid, void* out, float* gn_stats,
-                                 int M, int rows_per_batch, const void* o2, const void* Wo, const float* bo2, void* stream) {
-  hipStream_t s = (hipStream_t)stream;
-  const int C = 320, inner = 4 * C, heads = 8, d = 40, dp = attn_padded_dim(d), hdp = heads * dp;
-  GILL_REQUIRE(t && ln_g && ln_b && W1 && b1 && W2 && b2 && Wp && bp && resid && out, "null argument");
-  GILL_REQUIRE((o2 != nullptr) == (Wo != nullptr) && (o2 != nullptr) == (bo2 != nullptr), "o2 / Wo / bo2: all or none");
-  GILL_REQUIRE(ffn_fused_supported(C, M), "ffn_fused: M must be a multiple of 128");
-  DevBuf idx, wff1, bff1, sff1, wfo, bfo, w1c, b1c, w2p, st, wpp, o2p, wop;
-  if (o2) {
-    GILL_TRY(wpp.alloc(sizeof(bf16_t) * (size_t)C * C));
-    GILL_TRY(o2p.alloc_zero(sizeof(bf16_t) * (size_t)M * hdp, s));
-    GILL_TRY(wop.alloc_zero(sizeof(bf16_t) * (size_t)C * hdp, s));
-    hipLaunchKernelGGL(pad_head_cols_kernel, dim3(1024), dim3(256), 0, s, o2, 0, M, heads, d, dp, (bf16_t*)o2p.p);
-    hipLaunchKernelGGL(pad_head_cols_kernel, dim3(1024), dim3(256), 0, s, Wo, 0, C, heads, d, dp, (bf16_t*)wop.p);
-    GILL_CHECK_HIP(hipGetLastError());
-  }
-  std::vector<int32_t> map = geglu_row_permutation(inner);
-  GILL_TRY(idx.alloc(sizeof(int32_t) * map.size()));
-  GILL_CHECK_HIP(hipMemcpyAsync(idx.p, map.data(), sizeof(int32_t) * map.size(), hipMemcpyHostToDevice, s));
-  GILL_TRY(wff1.alloc(sizeof(bf16_t) * (size_t)2 * inner * C)); GILL_TRY(bff1.alloc(sizeof(float) * 2 * inner));
-  GILL_TRY(sff1.alloc(sizeof(float) * 2 * inner));
-  GILL_TRY(scatter_rows_bf16_launch((const bf16_t*)W1, 2 * inner, C, (const int32_t*)idx.p, (bf16_t*)wff1.p, C, s));
-  GILL_TRY(permute_f32_launch(b1, (const int32_t*)idx.p, 2 * inner, (float*)bff1.p, s));
-  GILL_TRY(ln_fold_rows_launch((bf16_t*)wff1.p, 2 * inner, C, ln_g, ln_b, (float*)sff1.p, (float*)bff1.p, s));
-  GILL_TRY(wfo.alloc(sizeof(bf16_t) * (size_t)C * 5 * C)); GILL_TRY(bfo.alloc(sizeof(float) * C));
-  hipLaunchKernelGGL(ffo_fuse_kernel, dim3(cdiv(5 * C + 1, 256), C), dim3(256), 0, s, Wp, 0, W2, 0, (const void*)b2, 1, (const void*)bp, 1, C,
-                     (bf16_t*)wfo.p, (float*)bfo.p);
-  GILL_CHECK_HIP(hipGetLastError());
-  GILL_TRY(w1c.alloc(sizeof(bf16_t) * (size_t)8 * C * C)); GILL_TRY(b1c.alloc(sizeof(float) * 8 * C));
-  GILL_TRY(w2p.alloc(sizeof(bf16_t) * (size_t)4 * C * C));
-  GILL_TRY(ffn_relayout_launch((const bf16_t*)wff1.p, (const float*)bff1.p, (const bf16_t*)wfo.p, (bf16_t*)w1c.p, (float*)b1c.p,
-                               (bf16_t*)w2p.p, o2 ? (bf16_t*)wpp.p : nullptr, s));
-  GILL_TRY(st.alloc(sizeof(float) * (size_t)M * 2));
-  hipLaunchKernelGGL(ffn_op_rowsums_kernel, dim3(cdiv(M, 4)), dim3(256), 0, s, (const bf16_t*)t, M, C, (float*)st.p);
-  GILL_CHECK_HIP(hipGetLastError());
-  FfnArgs fa;
-  fa.M = M; fa.T = (const bf16_t*)t; fa.ln_stats = (const float*)st.p; fa.ln_planes = 1;
-  fa.W1c = (const bf16_t*)w1c.p; fa.b1c = (const float*)b1c.p; fa.W2p = (const bf16_t*)w2p.p;
-  fa.Wfo = (const bf16_t*)wfo.p; fa.bo = (const float*)bfo.p; fa.resid = (const bf16_t*)resid; fa.out = (bf16_t*)out;
-  fa.gn_stats = gn_stats; fa.rows_per_batch = rows_per_batch;
-  if (o2) { fa.X = (const bf16_t*)o2p.p; fa.Wo = (const bf16_t*)wop.p; fa.bo2 = bo2; fa.Wpp = (const bf16_t*)wpp.p; }
-  const int rep = [] { const char* e = getenv("GILL_OP_REPEAT"); const int v = e ? atoi(e) : 1; return v > 0 ? v : 1; }();
-  for (int r = 0; r < rep; ++r) GILL_TRY(ffn_fused_launch(fa, s));
-  GILL_CHECK_HIP(hipStreamSynchronize(s));
-  return 0;
-}
-
-// ------------------------------------------------------------------------------------------------------------------
-// Operator-level entry for the fp8 GEGLU projection (linear_fp8.hip) on NATURAL operands (diffusers parameter layouts): permutes the rows into the
-// engine's value / gate interleave, folds norm3 into them, quantises rows and LayerNorm-ed activations to e4m3 exactly as the engine's fp8 mode does,
-// launches the kernel.  out [M][inner] = h * gelu(g), [h | g] = LN(t) W^T + b (W [2 inner][C], diffusers order [value rows | gate rows]).  C % 128 == 0.
-// For tests/test_fp8_gpu.py and tools; synchronises.
-extern "C" int gill_op_geglu_fp8(const void* t, const float* ln_g, const float* ln_b, const void* W, const float* b, void* out, int M, int inner, int C,
-                                 void* stream) {
-  hipStream_t s = (hipStream_t)stream;
-  GILL_REQUIRE(t && ln_g && ln_b && W && b && out && M > 0 && inner % 16 == 0 && C % 128 == 0, "geglu_fp8: null argument / inner % 16 / C % 128");
-  DevBuf idx, wperm, bperm, cs, w8, sc, st, t8;
-  std::vector<int32_t> map = geglu_row_permutation(inner);
-  GILL_TRY(idx.alloc(sizeof(int32_t) * map.size()));
-  GILL_CHECK_HIP(hipMemcpyAsync(idx.p, map.data(), sizeof(int32_t) * map.size(), hipMemcpyHostToDevice, s));
-  GILL_TRY(wperm.alloc(sizeof(bf16_t) * (size_t)2 * inner * C)); GILL_TRY(bperm.alloc(sizeof(float) * 2 * inner)); GILL_TRY(cs.alloc(sizeof(float) * 2 * inner));
-  GILL_TRY(scatter_rows_bf16_launch((const bf16_t*)W, 2 * inner, C, (const int32_t*)idx.p, (bf16_t*)wperm.p, C, s));
-  GILL_TRY(permute_f32_launch(b, (const int32_t*)idx.p, 2 * inner, (float*)bperm.p, s));
-  GILL_TRY(ln_fold_rows_launch((bf16_t*)wperm.p, 2 * inner, C, ln_g, ln_b, (float*)cs.p, (float*)bperm.p, s));
-  GILL_TRY(w8.alloc((size_t)2 * inner * C)); GILL_TRY(sc.alloc(sizeof(float) * 2 * inner));
-  GILL_TRY(linear_weight_quant_fp8_launch((const bf16_t*)wperm.p, 2 * inner, C, F8_LIN_ACT_SCALE, (unsigned char*)w8.p, (float*)sc.p, s));
-  GILL_TRY(st.alloc(sizeof(float) * (size_t)M * 2));
-  hipLaunchKernelGGL(ffn_op_rowsums_kernel, dim3(cdiv(M, 4)), dim3(256), 0, s, (const bf16_t*)t, M, C, (float*)st.p);
-  GILL_CHECK_HIP(hipGetLastError());
-  GILL_TRY(t8.alloc((size_t)M * C));
-  LinF8Args a;
-  a.M = M; a.N = 2 * inner; a.K = C; a.A8 = (const unsigned char*)t8.p; a.W8 = (const unsigned char*)w8.p; a.colscale = (const float*)sc.p;
-  a.bias = (const float*)bperm.p; a.C = (bf16_t*)out;
-  const int rep = [] { const char* e = getenv("GILL_OP_REPEAT"); const int v = e ? atoi(e) : 1; return v > 0 ? v : 1; }();
-  for (int r = 0; r < rep; ++r) {
-    GILL_TRY(ln_quant_fp8_launch((const bf16_t*)t, M, C, (const float*)st.p, 1, 0, 1e-5f, F8_LIN_ACT_SCALE, (unsigned char*)t8.p, s));
-    GILL_TRY(geglu_fp8_launch(a, s));
-  }
-  GILL_CHECK_HIP(hipStreamSynchronize(s));
-  return 0;
-}
-
-// ------------------------------------------------------------------------------------------------------------------
-// Operator-level entry for the fused projection pairs around norm1 / norm2 of a level-0 block (lnproj.hip) on NATURAL operands
-// (unpadded heads, plain LayerNorm parameters): pads / folds / permutes them exactly as the engine's loader does, launches the kernel.
-//   mode 0: t = W1 . x + b1;  [q | k | v] = W2 . LN(t)            x [M][320], W2 [3 * 320][320] = to_q | to_k | to_v rows
-//   mode 1: t = W1 . x + b1 + t;  q = W2 . LN(t)                  x [M][320] = the attention output (heads x 40), W2 [320][320]
-// q, k: [B][8][hw_pad][48] (q scaled by log2(e) / sqrt(40)); vt: [B][8][64][hw_pad] with row 48 = 1.  For tests and tools; synchronises.
-extern "C" int gill_op_lnproj(int mode, const void* x, void* t, const void* W1, const float* b1, const float* ln_g, const float* ln_b,
-                              const void* W2, void* q, void* k, void* vt, int B, int HW, void* stream) {
-  hipStream_t s = (hipStream_t)stream;
-  const int C = 320, heads = 8, d = 40, dp = attn_padded_dim(d), dpv = round_up(dp, 32), hdp = heads * dp, M = B * HW;
-  const int nseg = mode == 0 ? 3 : 1;
-  GILL_REQUIRE(mode == 0 || mode == 1, "mode must be 0 or 1");
-  GILL_REQUIRE(x && t && W1 && b1 && ln_g && ln_b && W2 && q && (mode == 1 || (k && vt)), "null argument");
-  GILL_REQUIRE(lnproj_supported(C, M, heads, dp), "lnproj: B * HW must be a multiple of 128");
-  DevBuf xp, w1p, w2, w2p, cs, cb;
-  GILL_TRY(w2.alloc_zero(sizeof(bf16_t) * (size_t)nseg * hdp * C, s));
-  GILL_TRY(w2p.alloc(sizeof(bf16_t) * (size_t)nseg * hdp * C));
-  GILL_TRY(cs.alloc_zero(sizeof(float) * (size_t)nseg * hdp, s));
-  GILL_TRY(cb.alloc_zero(sizeof(float) * (size_t)nseg * hdp, s));
-  for (int sg = 0; sg < nseg; ++sg)
-    hipLaunchKernelGGL(pad_head_rows_kernel, dim3(1024), dim3(256), 0, s, (const void*)((const bf16_t*)W2 + (size_t)sg * C * C), 0, heads, d, dp, C,
-                       (bf16_t*)w2.p + (size_t)sg * hdp * C);
-  GILL_CHECK_HIP(hipGetLastError());
-  GILL_TRY(ln_fold_rows_launch((bf16_t*)w2.p, nseg * hdp, C, ln_g, ln_b, (float*)cs.p, (float*)cb.p, s));
-  GILL_TRY(lnproj_kperm_launch((const bf16_t*)w2.p, nseg * hdp, (bf16_t*)w2p.p, s));
-  LnProjArgs a;
-  a.mode = mode; a.M = M; a.T = (bf16_t*)t; a.b1 = b1; a.W2p = (const bf16_t*)w2p.p; a.c2 = (const float*)cb.p;
-  a.Cq = (bf16_t*)q; a.Ck = (bf16_t*)k; a.Cvt = (bf16_t*)vt; a.heads = heads; a.dp = dp; a.dpv = dpv; a.ntok = HW; a.ntok_pad = round_up(HW, 32);
-  a.qscale = 1.4426950408889634f / sqrtf((float)d);
-  if (mode == 0) {
-    a.X = (const bf16_t*)x; a.W1 = (const bf16_t*)W1;
-  } else {
-    GILL_TRY(xp.alloc_zero(sizeof(bf16_t) * (size_t)M * hdp, s));
-    GILL_TRY(w1p.alloc_zero(sizeof(bf16_t) * (size_t)C * hdp, s));
-    hipLaunchKernelGGL(pad_head_cols_kernel, dim3(1024), dim3(256), 0, s, x, 0, M, heads, d, dp, (bf16_t*)xp.p);
-    hipLaunchKernelGGL(pad_head_cols_kernel, dim3(1024), dim3(256), 0, s, W1, 0, C, heads, d, dp, (bf16_t*)w1p.p);
-    GILL_CHECK_HIP(hipGetLastError());
-    a.X = (const bf16_t*)xp.p; a.W1 = (const bf16_t*)w1p.p;
-  }
-  const int rep = [] { const char* e = getenv("GILL_OP_REPEAT"); const int v = e ? atoi(e) : 1; return v > 0 ? v : 1; }();
-  for (int r = 0; r < rep; ++r) GILL_TRY(lnproj_launch(a, s));
-  GILL_CHECK_HIP(hipStreamSynchronize(s));
-  return 0;
-}
-
-// Op-level entry of the two-GEMM cross-attention (xalg_fold_kernel) on a torch-layout attn2 (to_q / to_out [C][C], to_k / to_v [C][E], heads
-// of d = C / H >= 80 features, norm2's gain and bias): folds the weights as the loader does, builds the per-sample operands from `ctx`
-// [B][ctx_len][E] as unet_ctx_cache does, then out = t + softmax(LN(t) Wq^T K^T / sqrt(d)) V Wo^T + bo on t [B * HW][C].  `P` (optional)
-// receives the softmax weights [B * HW][80 H] (key slot j of head h at column 80 h + j).  For tests and tools; synchronises.
-extern "C" int gill_op_cross_attention_folded(const void* t, const float* ln_g, const float* ln_b, const void* Wq, const void* Wk, const void* Wv,
-                                              const void* Wo, const float* bo, const void* ctx, void* out, void* P, int B, int HW, int C, int H,
-                                              int ctx_len, int E, void* stream) {
-  hipStream_t s = (hipStream_t)stream;
-  GILL_REQUIRE(t && ln_g && ln_b && Wq && Wk && Wv && Wo && bo && ctx && out, "null argument");
-  GILL_REQUIRE(H > 0 && H % 2 == 0 && C % H == 0, "cross_attention_folded: an even number of heads dividing C");
-  const int d = C / H, M = B * HW, n80 = 80 * H;
-  GILL_REQUIRE(d % 16 == 0 && d >= 80 && d <= 160 && C % 64 == 0 && E % 64 == 0 && ctx_len >= 1 && ctx_len <= 80 && HW % 64 == 0,
-               "cross_attention_folded: head dim 80..160 (multiple of 16), C and E multiples of 64, at most 80 context tokens, HW a multiple of 64");
-  DevBuf wq, wkv, cs, cq, xg, xgb, T, mq, mcs, mb, wo, st, p;
-  GILL_TRY(wq.alloc(sizeof(bf16_t) * (size_t)C * C));
-  GILL_TRY(wkv.alloc(sizeof(bf16_t) * (size_t)2 * C * E));
-  GILL_CHECK_HIP(hipMemcpyAsync(wq.p, Wq, sizeof(bf16_t) * (size_t)C * C, hipMemcpyDeviceToDevice, s));
-  GILL_CHECK_HIP(hipMemcpyAsync(wkv.p, Wk, sizeof(bf16_t) * (size_t)C * E, hipMemcpyDeviceToDevice, s));
-  GILL_CHECK_HIP(hipMemcpyAsync((bf16_t*)wkv.p + (size_t)C * E, Wv, sizeof(bf16_t) * (size_t)C * E, hipMemcpyDeviceToDevice, s));
-  GILL_TRY(cs.alloc(sizeof(float) * C)); GILL_TRY(cq.alloc_zero(sizeof(float) * C, s));      // (ln_fold_rows ADDS beta . W^T to the bias it is given)
-  GILL_TRY(ln_fold_rows_launch((bf16_t*)wq.p, C, C, ln_g, ln_b, (float*)cs.p, (float*)cq.p, s));
-  GILL_TRY(xg.alloc(sizeof(bf16_t) * (size_t)2 * H * C * E)); GILL_TRY(xgb.alloc(sizeof(float) * (size_t)H * E));
-  const float qs = 1.4426950408889634f / sqrtf((float)d);
-  hipLaunchKernelGGL(xalg_fold_kernel, dim3(2 * H * C / 8), dim3(256), 0, s, (const bf16_t*)wq.p, (const bf16_t*)wkv.p, (const bf16_t*)Wo, H, C, d, E, qs,
-                     (bf16_t*)xg.p);
-  hipLaunchKernelGGL(xalg_fold_bias_kernel, dim3(cdiv(E, 256), H), dim3(256), 0, s, (const float*)cq.p, (const bf16_t*)wkv.p, d, E, qs, (float*)xgb.p);
-  GILL_CHECK_HIP(hipGetLastError());
-  GILL_TRY(T.alloc(sizeof(bf16_t) * (size_t)B * ctx_len * 2 * H * C));
-  GILL_TRY(mq.alloc(sizeof(bf16_t) * (size_t)B * n80 * C)); GILL_TRY(wo.alloc(sizeof(bf16_t) * (size_t)B * n80 * C));
-  GILL_TRY(mcs.alloc(sizeof(float) * (size_t)B * n80)); GILL_TRY(mb.alloc(sizeof(float) * (size_t)B * n80));
-  {
-    GemmArgs g;
-    g.M = B * ctx_len; g.N = 2 * H * C; g.K = E; g.K1 = E; g.A = (const bf16_t*)ctx; g.lda = E; g.W = (const bf16_t*)xg.p; g.C = T.p; g.ldc = g.N;
-    GILL_TRY(gemm_launch(g, s));
-  }
-  hipLaunchKernelGGL(xalg_scores_operand_kernel, dim3(B * H * 80), dim3(256), 0, s, (const bf16_t*)T.p, (const bf16_t*)ctx, (const float*)xgb.p, H, C, E,
-                     ctx_len, (bf16_t*)mq.p, (float*)mcs.p, (float*)mb.p);
-  hipLaunchKernelGGL(xalg_values_operand_kernel, dim3(B * H * (C / 64)), dim3(256), 0, s, (const bf16_t*)T.p, H, C, ctx_len, (bf16_t*)wo.p);
-  GILL_CHECK_HIP(hipGetLastError());
-  GILL_TRY(st.alloc(sizeof(float) * (size_t)M * 2));
-  hipLaunchKernelGGL(ffn_op_rowsums_kernel, dim3(cdiv(M, 4)), dim3(256), 0, s, (const bf16_t*)t, M, C, (float*)st.p);
-  GILL_CHECK_HIP(hipGetLastError());
-  void* pp = P;
-  if (!pp) { GILL_TRY(p.alloc(sizeof(bf16_t) * (size_t)M * n80)); pp = p.p; }
-  GemmArgs g;
-  g.M = M; g.N = n80; g.K = C; g.K1 = C; g.A = (const bf16_t*)t; g.lda = C; g.W = (const bf16_t*)mq.p;
-  g.wb_rows = HW; g.wb_stride = (int64_t)n80 * C; g.vb_stride = n80;
-  g.ln_stats = (const float*)st.p; g.ln_planes = 1; g.ln_colsum = (const float*)mcs.p; g.bias = (const float*)mb.p;
-  g.out_mode = OUT_SOFTMAX80; g.C = pp; g.ldc = n80;
-  GemmArgs g2;
-  g2.M = M; g2.N = C; g2.K = n80; g2.K1 = n80; g2.A = (const bf16_t*)pp; g2.lda = n80; g2.W = (const bf16_t*)wo.p; g2.bias = bo;
-  g2.wb_rows = HW; g2.wb_stride = (int64_t)n80 * C;
-  g2.resid = t; g2.ldr = C; g2.C = out; g2.ldc = C;
-  const int rep = [] { const char* e = getenv("GILL_OP_REPEAT"); const int v = e ? atoi(e) : 1; return v > 0 ? v : 1; }();
-  for (int r = 0; r < rep; ++r) { GILL_TRY(gemm_launch(g, s)); GILL_TRY(gemm_launch(g2, s)); }
-  GILL_CHECK_HIP(hipStreamSynchronize(s));
-  return 0;
-}
-
-// ------------------------------------------------------------------------------------------------------------------
-// Operator-level entries for the folded-LayerNorm chain of UNet levels 1-3 (xf() above): the GEMM that writes the residual stream and files
-// its row-sum planes (GemmArgs::row_stats), and the GEMM that reads them back (GemmArgs::ln_stats) in its GEGLU / QKV epilogue or its split-K
-// reducer.  Both build their GemmArgs as UNetRun::linear() / xf() do and synchronise.  For tests/test_ln_gemm_gpu.py and tools.
-// splitk: 0 = the engine's heuristic (UNetRun::pick_sk), 1 = unsplit, n > 1 = forced.
-static int op_ln_splitk(GemmArgs& g, int splitk, DevBuf& ws) {
-  g.splitk = splitk > 0 ? splitk : gemm_pick_splitk(g.M, g.N, g.K, g.act, true, false);
-  if (g.splitk > 1) {
-    GILL_TRY(ws.alloc(sizeof(float) * (size_t)g.splitk * g.M * g.N));
-    g.ws = (float*)ws.p;
-  }
-  return 0;
-}
-// Producer.  T [M][N] bf16 = (A [M][K1] ++ A2 [M][K - K1]) . W [N][K]^T + bias + resid (resid may alias T: attn1 / attn2.to_out run in place),
-// planes [*nplanes][M][2] fp32 = {sum, sum of squares} of the stored row m over the columns of each plane; *nplanes = gemm_row_planes() of the
-// launch (an error when it exceeds planes_cap, the planes the caller's buffer holds).
-extern "C" int gill_op_linear_rowstats(const void* A, const void* A2, int K1, const void* W, const float* bias, const void* resid, void* T,
-                                       float* planes, int planes_cap, int* nplanes, int M, int N, int K, int splitk, void* stream) {
-  hipStream_t s = (hipStream_t)stream;
-  GILL_REQUIRE(A && W && T && planes && nplanes && M > 0 && N > 0 && K > 0, "linear_rowstats: null argument");
-  GILL_REQUIRE((A2 != nullptr) == (K1 < K) && K1 > 0 && K1 <= K, "linear_rowstats: A2 if and only if K1 < K");
-  DevBuf ws;
-  GemmArgs g;
-  g.M = M; g.N = N; g.K = K; g.K1 = K1; g.A = (const bf16_t*)A; g.lda = K1; g.A2 = (const bf16_t*)A2; g.lda2 = K - K1;
-  g.W = (const bf16_t*)W; g.bias = bias; g.resid = resid; g.ldr = N; g.act = ACT_NONE; g.C = T; g.ldc = N;
-  GILL_TRY(op_ln_splitk(g, splitk, ws));
-  g.row_stats = planes;
-  *nplanes = gemm_row_planes(g);
-  GILL_REQUIRE(*nplanes <= planes_cap, "linear_rowstats: the planes buffer is too small for this launch");
-  const int rep = [] { const char* e = getenv("GILL_OP_REPEAT"); const int v = e ? atoi(e) : 1; return v > 0 ? v : 1; }();
-  for (int r = 0; r < (resid == T ? 1 : rep); ++r) GILL_TRY(gemm_launch(g, s));      // (in place: a second launch would add the residual twice)
-  GILL_CHECK_HIP(hipStreamSynchronize(s));
-  return 0;
-}
-
-// dst[h * dp + dd] = src[h * d + dd] (a projection bias padded like the weight rows).  dst pre-zeroed.
-__global__ __launch_bounds__(256) void pad_head_vec_kernel(const float* __restrict__ src, int H, int d, int dp, float* __restrict__ dst) {
-  const int i = blockIdx.x * blockDim.x + threadIdx.x;
-  if (i < H * d) dst[(i / d) * dp + i % d] = src[i];
-}
-// Consumer.  LN(T; ln_g, ln_b) W^T + b on T [M][C] bf16 and the caller's row-sum planes [P][R][2] (R = ln_rows, or M when ln_rows == 0; rows
-// m >= R read the sums of row m - R), W / b in diffusers layout, folded by ln_fold_rows_launch as the loader folds them.
-//   mode 0 (GEGLU): W [2 inner][C] = [value rows | gate rows], b [2 inner] -> out [M][inner] bf16 = value * gelu(gate).
-//   mode 1 (QKV):   W [nseg C][C] = to_q (| to_k | to_v), nseg = 1 | 3, heads * d == C, b [nseg C] or null, M = B * ntok ->
-//                   q, k [B][heads][ntok_pad][dp], vt [B][heads][dpv][ntok_pad] (dp = attn_padded_dim(d), dpv = dp rounded up to 32, ntok_pad = ntok
-//                   rounded up to 32, q scaled by log2(e) / sqrt(d), row dp of vt = 1 where dpv > dp): what xf() passes.  k, vt unused for nseg = 1.
-extern "C" int gill_op_ln_gemm(int mode, const void* T, const float* planes, int P, int ln_rows, const float* ln_g, const float* ln_b, const void* W,
-                               const float* b, void* out, void* q, void* k, void* vt, int M, int C, int inner, int nseg, int heads, int d, int ntok,
-                               int splitk, void* stream) {
-  hipStream_t s = (hipStream_t)stream;
-  GILL_REQUIRE(mode == 0 || mode == 1, "ln_gemm: mode must be 0 (GEGLU) or 1 (QKV)");
-  GILL_REQUIRE(T && planes && ln_g && ln_b && W && M > 0 && C > 0 && P >= 1, "ln_gemm: null argument");
-  GILL_REQUIRE(ln_rows >= 0 && ln_rows <= M && (ln_rows == 0 || 2 * ln_rows >= M), "ln_gemm: ln_rows must cover at least half the rows");
-  DevBuf idx, wf, cs, cb, ws;
-  GemmArgs g;
-  g.M = M; g.K = C; g.K1 = C; g.A = (const bf16_t*)T; g.lda = C;
-  g.ln_stats = planes; g.ln_planes = P; g.ln_rows = ln_rows;
-  if (mode == 0) {
-    GILL_REQUIRE(out && b && inner > 0 && inner % 64 == 0, "ln_gemm (GEGLU): output / bias missing, or inner not a multiple of 64");
-    const int N = 2 * inner;
-    std::vector<int32_t> map = geglu_row_permutation(inner);
-    GILL_TRY(idx.alloc(sizeof(int32_t) * map.size()));
-    GILL_CHECK_HIP(hipMemcpyAsync(idx.p, map.data(), sizeof(int32_t) * map.size(), hipMemcpyHostToDevice, s));
-    GILL_TRY(wf.alloc(sizeof(bf16_t) * (size_t)N * C)); GILL_TRY(cb.alloc(sizeof(float) * N)); GILL_TRY(cs.alloc(sizeof(float) * N));
-    GILL_TRY(scatter_rows_bf16_launch((const bf16_t*)W, N, C, (const int32_t*)idx.p, (bf16_t*)wf.p, C, s));
-    GILL_TRY(permute_f32_launch(b, (const int32_t*)idx.p, N, (float*)cb.p, s));
-    GILL_TRY(ln_fold_rows_launch((bf16_t*)wf.p, N, C, ln_g, ln_b, (float*)cs.p, (float*)cb.p, s));
-    g.N = N; g.act = ACT_GEGLU; g.C = out; g.ldc = inner;
-  } else {
-    GILL_REQUIRE((nseg == 1 || nseg == 3) && heads > 0 && d > 0 && heads * d == C && ntok > 0 && M % ntok == 0,
-                 "ln_gemm (QKV): nseg 1 or 3, heads * d == C, M a multiple of ntok");
-    GILL_REQUIRE(q && (nseg == 1 || (k && vt)), "ln_gemm (QKV): output missing");
-    const int dp = attn_padded_dim(d);
-    GILL_REQUIRE(dp > 0, "ln_gemm (QKV): unsupported head dim");
-    const int dpv = round_up(dp, 32), hdp = heads * dp, N = nseg * hdp, ntok_pad = round_up(ntok, 32);
-    GILL_TRY(wf.alloc_zero(sizeof(bf16_t) * (size_t)N * C, s));
-    GILL_TRY(cs.alloc_zero(sizeof(float) * N, s)); GILL_TRY(cb.alloc_zero(sizeof(float) * N, s));
-    for (int sg = 0; sg < nseg; ++sg) {
-      hipLaunchKernelGGL(pad_head_rows_kernel, dim3(1024), dim3(256), 0, s, (const void*)((const bf16_t*)W + (size_t)sg * C * C), 0, heads, d, dp, C,
-                         (bf16_t*)wf.p + (size_t)sg * hdp * C);
-      if (b) hipLaunchKernelGGL(pad_head_vec_kernel, dim3(cdiv(C, 256)), dim3(256), 0, s, b + (size_t)sg * C, heads, d, dp, (float*)cb.p + (size_t)sg * hdp);
-    }
-    GILL_CHECK_HIP(hipGetLastError());
-    GILL_TRY(ln_fold_rows_launch((bf16_t*)wf.p, N, C, ln_g, ln_b, (float*)cs.p, (float*)cb.p, s));
-    g.N = N; g.out_mode = OUT_QKV; g.Cq = (bf16_t*)q; g.Ck = (bf16_t*)k; g.Cvt = (bf16_t*)vt; g.heads = heads; g.dp = dp; g.dpv = dpv;
-    g.ntok = ntok; g.ntok_pad_q = ntok_pad; g.ntok_pad_kv = ntok_pad; g.seg_base = 0;
-    g.qscale = 1.4426950408889634f / sqrtf((float)d);
-  }
-  g.W = (const bf16_t*)wf.p; g.ln_colsum = (const float*)cs.p; g.bias = (const float*)cb.p;
-  GILL_TRY(op_ln_splitk(g, splitk, ws));
-  const int rep = [] { const char* e = getenv("GILL_OP_REPEAT"); const int v = e ? atoi(e) : 1; return v > 0 ? v : 1; }();
-  for (int r = 0; r < rep; ++r) GILL_TRY(gemm_launch(g, s));
-  GILL_CHECK_HIP(hipStreamSynchronize(s));
-  return 0;
 }

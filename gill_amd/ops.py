@@ -338,7 +338,7 @@ def lnproj(mode: int, x: torch.Tensor, t, w1: torch.Tensor, b1: torch.Tensor, ln
 def cross_attention_folded(t: torch.Tensor, ln_g: torch.Tensor, ln_b: torch.Tensor, wq: torch.Tensor, wk: torch.Tensor, wv: torch.Tensor,
                            wo: torch.Tensor, bo: torch.Tensor, ctx: torch.Tensor, heads: int, B: int, HW: int):
   """norm2 + attn2 + residual of a BasicTransformerBlock with heads of 80..160 features as the engine runs it at UNet levels 1-3
-  (csrc/unet.hip "XALG"): out = t + softmax(LN(t) wq.T (ctx wk.T).T / sqrt(d)) (ctx wv.T) wo.T + bo, computed as two GEMMs on per-sample
+  (csrc/xf_weights.hip "XALG"): out = t + softmax(LN(t) wq.T (ctx wk.T).T / sqrt(d)) (ctx wv.T) wo.T + bo, computed as two GEMMs on per-sample
   weights folded from (wq, wk) and (wo, wv).  t (B * HW, C); wq, wo (C, C); wk, wv (C, E); ctx (B, ctx_len <= 80, E).
   Returns (out (B * HW, C) bf16, P (B * HW, 80 * heads) bf16: the softmax weights, key j of head h at column 80 h + j)."""
   t, wq, wk, wv, wo, ctx = (_bf(v) for v in (t, wq, wk, wv, wo, ctx))

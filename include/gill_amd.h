@@ -499,7 +499,7 @@ int gill_op_lnproj(int mode, const void* x_bf16, void* t_bf16, const void* W1_bf
                    const void* W2_bf16, void* q_bf16, void* k_bf16, void* vt_bf16, int B, int HW, void* stream);
 
 /* attn2 (cross-attention) of a UNet transformer block with heads of 80..160 features, as the two GEMMs on per-sample weights the engine
- * runs at UNet levels 1-3 (csrc/unet.hip "XALG"): K and V are linear in the prompt context, so qs (g o Wq_h)^T Wk_h and Wo_h Wv_h are
+ * runs at UNet levels 1-3 (csrc/xf_weights.hip "XALG"): K and V are linear in the prompt context, so qs (g o Wq_h)^T Wk_h and Wo_h Wv_h are
  * folded at load, multiplied by ctx once per prompt, and each UNet call computes P = softmax(LN(t) Mq_b^T) and out = t + P Wo_b^T + bo.
  * Operands in diffusers layout: t (B * HW, C) bf16, norm2 gain / bias (C) fp32, to_q / to_out.0 weights (C, C) bf16, to_k / to_v (C, E)
  * bf16, to_out.0 bias (C) fp32, ctx (B, ctx_len <= 80, E) bf16 -> out (B * HW, C) bf16; P_bf16 (optional, B * HW x 80 H): the softmax

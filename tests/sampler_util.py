@@ -1,7 +1,7 @@
 """Numpy restatements of the four schedulers the denoise loop can run besides PNDM — DDIM, DPM-Solver++(2M), Euler, Euler ancestral — as
 diffusers 0.17.1 configures them for Stable Diffusion, for tests/test_samplers_host.py and tests/test_samplers_gpu.py.
 
-They are written step by step (prediction -> x0 / eps -> update), NOT in the folded-coefficient form of the engine's tables (csrc/unet.hip:
+They are written step by step (prediction -> x0 / eps -> update), NOT in the folded-coefficient form of the engine's tables (csrc/sd_schedule.hip:
 sd_schedule), so that a folding mistake cannot be shared by both sides.  `dtype` is the arithmetic's precision: float64 is the reference, the
 float32 run measures how far fp32 rounding alone moves a trajectory (the GPU test's tolerance).
 

@@ -121,7 +121,7 @@ def test_sd21_768_full_size_forward_vs_oracle(cuda):
   # VERDICT r04 item 5(b) — why the loop distance (3.65e-2 in round 4) is 3x a single forward's: the oracle loop is unrolled here so
   # that every one of its UNet calls ALSO serves as a teacher-forced check (the oracle's latent through gill_unet_forward, bar 2.5e-2
   # like the SD-1.5 schedule test above): each call is ~1e-2 from the oracle on identical inputs, and the scheduler arithmetic is not
-  # where the rest comes from — the v-prediction fold (unet.hip: sample_coeff - c sqrt(b_t), c sqrt(a_t)) is formed in double and
+  # where the rest comes from — the v-prediction fold (sd_schedule.hip: sample_coeff - c sqrt(b_t), c sqrt(a_t)) is formed in double and
   # rounded once, and test_sd2_geometry_tiny_vs_oracle runs it over 4 steps at 2e-2.  The remainder is the recurrence: a random-weight
   # UNet is not a contraction, three calls fed their own outputs amplify a 1e-2 per-call difference ~3x (tools/chaos_probe.py: ANY
   # re-ordering of the fp32 sums reaches 3e-2 after 4 calls).  The printed amplification is loop distance / worst per-call distance.

@@ -1,4 +1,4 @@
-"""Host checks of inpainting (gill_sd_inpaint_keep: csrc/unet.hip; GillSDPipeline.preprocess_mask); no GPU.
+"""Host checks of inpainting (gill_sd_inpaint_keep: csrc/sd_schedule.hip; GillSDPipeline.preprocess_mask); no GPU.
 
 The keep table's row i is the add_noise pair at the noise level the latents have after call i: gill_sd_schedule_from's own pair one step on for
 ddim / dpmsolver++ / euler / euler_ancestral, (sqrt(abar), sqrt(1 - abar)) at timestep i + 1 of the replayed warm-up list for pndm, and (1, 0)

@@ -659,7 +659,7 @@ def test_lnproj_proj_in_qkv_vs_torch(cuda, B, HW):
   assert float(vt[:, :, d:48, :HW].float().abs().max()) == 0
 
 
-# ---------------------------------------------------------------- cross-attention as two GEMMs on per-sample weights (csrc/unet.hip "XALG")
+# ---------------------------------------------------------------- cross-attention as two GEMMs on per-sample weights (csrc/xf_weights.hip "XALG")
 @pytest.mark.parametrize("B,HW,C,nh,ctx_len", [(2, 64, 1280, 8, 77), (3, 256, 1280, 8, 77), (2, 1024, 640, 8, 77), (2, 128, 640, 4, 80), (1, 64, 640, 8, 5),
                                                  (8, 1024, 640, 8, 77)])     # (last: level 1 at the CFG batch 8 — both GEMMs on 256 ping-pong workgroups, per-sample weights)
 def test_cross_attention_folded_vs_torch(cuda, B, HW, C, nh, ctx_len):

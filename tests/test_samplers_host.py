@@ -1,4 +1,4 @@
-"""Host checks of the sampler tables (gill_sd_schedule: csrc/unet.hip) and of the scheduler_config.json parsing; no GPU.
+"""Host checks of the sampler tables (gill_sd_schedule: csrc/sd_schedule.hip) and of the scheduler_config.json parsing; no GPU.
 
 sampler_util restates DDIM, DPM-Solver++(2M), Euler and Euler ancestral step by step in float64 numpy; the engine's rows are folded
 coefficients rounded to fp32 once.  Applied in float64 to the same seeded model outputs and noise, the two trajectories may differ by that one

@@ -1,4 +1,4 @@
-"""Host checks of the image-to-image tables (gill_sd_schedule_from: csrc/unet.hip); no GPU.
+"""Host checks of the image-to-image tables (gill_sd_schedule_from: csrc/sd_schedule.hip); no GPU.
 
 start = 0 is gill_sd_schedule bit for bit; DDIM / Euler / Euler ancestral are the full table's tail; DPM-Solver++ and PNDM are compared, through
 sampler_util.apply_rows in float64, with the float64 steppers of vae_encoder_util started fresh at the tail — the same bar as

@@ -48,7 +48,7 @@ def xf(tag, hw, c):
     r += c; w += 2 * hq + heads * dpv                     # QKV: reads t, writes q, k, vt
     r += 2 * hq + heads * dpv; w += hq                    # self-attention
     r += hq + c; w += c                                   # out1 (+ residual t)
-    # cross-attention as two GEMMs on per-sample folded weights (unet.hip "XALG"): P = softmax80(LN(t) Mq^T) [80 x heads wide], t += P Wo^T
+    # cross-attention as two GEMMs on per-sample folded weights (xf_weights.hip "XALG"): P = softmax80(LN(t) Mq^T) [80 x heads wide], t += P Wo^T
     # (+ per call and sample the operands Mq, Wo: 2 x 80 x heads x c bf16 elements, added below as "weights")
     r += c; w += 80 * heads                               # scores + softmax GEMM: reads t, writes P
     r += 80 * heads + c; w += c                           # values + to_out GEMM (+ residual t)
