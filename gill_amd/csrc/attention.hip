@@ -336,6 +336,15 @@ __global__ __launch_bounds__(ATT_THREADS, (DP <= 64 ? 4 : 2)) void attention_ker
 //     exchange their maxima in the rare slow path.
 //   * The tile loop is unrolled by two so that the ring stage is a compile-time constant: every LDS address is a loop-invariant lane
 //     offset + an immediate.
+//   * P.V runs on v_mfma_f32_16x16x32_bf16 over 48 rows of O^T (three 16-row blocks x two 16-query blocks = 12 MFMAs of 16 cycles per
+//     tile) instead of 32x32x16 over 64 rows (8 of 32 cycles): d = 40 plus the row-sum row fit in 48, and rows 49..63 were padding.
+//     The packed P fragments move from the S layout (query = lane % 32) to the B layout of 16x16x32 (query = lane % 16, 8 keys per
+//     16-lane row) with one v_permlane16_swap_b32 per dword pair, 8 per tile; V^T is the A operand, read in the key order the swap
+//     leaves (chunks 4 hh + {0, 2, 1, 3}[lane / 16]): 6 ds_read_b128 per tile, each serving both query blocks.  LDS row 40 of the
+//     V^T image fetches V^T row 48 (the ones row: the DMA source address is per lane), so O^T row 40 is the row sum and only six
+//     8-row pieces of V^T are issued per tile; columns 40..47 of O are stored as the zeros they always were.  In the running-max
+//     jump each query block takes its rescale factor from its own lane rows (one swap of alpha with itself).
+//     Measured (profiles/attention_pv48.md): MFMA-busy of the kernel 52.9 -> 42.8 %, UNet loop -1.4 % on one box, alternating.
 // Everything else (transposed S^T / O^T, P in registers, ones-row of V^T carrying the row sum, XCD map, rotated tile walk) is as above.
 // Measured (8 x 8 heads x 4096^2, rocprofv3): 241-246 us against 290 us for the register-staged kernel; loop 479.8 -> 473.6 ms.
 // Two software-pipelined forms (scores of TWO tiles live: QK^T of tile t + 1 beside the softmax of tile t) were built, parity-green,
@@ -347,8 +356,9 @@ __global__ __launch_bounds__(ATT_THREADS, 4) void attention_dma_kernel(const Att
   static_assert(DP == 48, "QF3 needs three padding dims behind d = 40");
   constexpr int NW = ATT_THREADS / 64;            // waves per workgroup
   constexpr int ATT_QB = ATT_THREADS / 2;         // queries per workgroup
-  constexpr int KS = DP / 16, NDT = (DP + 31) / 32, NCH = DP / 8;
-  constexpr int PPW = 8 / NW;                     // K pieces (and V^T pieces) per wave and tile: 8 pieces of 8 rows each
+  constexpr int KS = DP / 16, NT3 = DP / 16, NCH = DP / 8;
+  constexpr int PPW = 8 / NW;                     // K pieces per wave and tile: 8 pieces of 8 rows each
+  constexpr int VPC = DP / 8;                     // V^T pieces per tile: rows 0 .. DP - 1 only (pieces w * PPW + j < VPC are issued)
   constexpr int K_BYTES = 64 * 128, STAGE = 2 * K_BYTES, CONST_OFF = 2 * STAGE;
   extern __shared__ __attribute__((aligned(16))) unsigned char att_smem_raw[];
   unsigned char* smem = att_smem_raw;
@@ -395,7 +405,8 @@ __global__ __launch_bounds__(ATT_THREADS, 4) void attention_dma_kernel(const Att
     const int key = (i & ~12) | ((i & 4) << 1) | ((i & 8) >> 1);   // K: LDS row i holds key swap23(i) of the tile
     const int ck = c >= NCH ? c - NCH : c;                      // (pad chunks: re-fetch chunk 0 / 1 — never read)
     koff[j] = (unsigned)((key * DP + ck * 8) * 2);
-    voff[j] = (unsigned)((i * p.nkv_pad + c * 8) * 2);
+    const int vrow = (i == 40) ? DP : i;                        // V^T: LDS row 40 holds the ones row (V^T row DP): O^T row 40 = sum_kv P
+    voff[j] = (unsigned)((vrow * p.nkv_pad + c * 8) * 2);
   }
   auto issue_tile = [&](int tile, int stage) {
     const char* kbase = (const char*)(Kb + (size_t)tile * ATT_KVT * DP);     // (uniform)
@@ -405,14 +416,21 @@ __global__ __launch_bounds__(ATT_THREADS, 4) void attention_dma_kernel(const Att
     for (int j = 0; j < PPW; ++j) {
       __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(kbase + koff[j]),
                                        (__attribute__((address_space(3))) void*)(dst + j * 1024), 16, 0, 0);
-      __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(vbase + voff[j]),
-                                       (__attribute__((address_space(3))) void*)(dst + K_BYTES + j * 1024), 16, 0, 0);
+      if (w * PPW + j < VPC)                                    // (wave-uniform: w is an SGPR)
+        __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(vbase + voff[j]),
+                                         (__attribute__((address_space(3))) void*)(dst + K_BYTES + j * 1024), 16, 0, 0);
     }
   };
-  // fragment reads: row (32 hh | 32 t) + lq, logical chunk 2 c4 + hi -> physical (2 c4 + hi) ^ ((lq >> 1) & 7): one lane offset per c4
-  int fo[4];
+  // K fragment reads: row 32 hh + lq, logical chunk 2 ks + hi -> physical (2 ks + hi) ^ ((lq >> 1) & 7): one lane offset per k step
+  int fo[KS];
 #pragma unroll
-  for (int c4 = 0; c4 < 4; ++c4) fo[c4] = lq * 128 + (((2 * c4 + hi) ^ ((lq >> 1) & 7)) * 16);
+  for (int c4 = 0; c4 < KS; ++c4) fo[c4] = lq * 128 + (((2 * c4 + hi) ^ ((lq >> 1) & 7)) * 16);
+  // V^T fragment reads (A operand of 16x16x32): row 16 t3 + m, logical chunk 4 hh + {0, 2, 1, 3}[g] — the key group that the
+  // permlane16_swap below leaves in lane row g of P; ((16 t3 + m) >> 1) & 7 = m >> 1, so t3 is an immediate
+  const int m16 = lane & 15, g4 = lane >> 4;
+  int vfo[2];
+#pragma unroll
+  for (int hh = 0; hh < 2; ++hh) vfo[hh] = m16 * 128 + (((4 * hh + ((g4 & 1) << 1 | (g4 >> 1))) ^ (m16 >> 1)) * 16);
   // k step 2 of QK^T: dims 32..39 (hi = 0) from the tile, dims 40..47 (hi = 1) from the constant slot — an address per (stage, half),
   // because the immediates of the other reads do not apply to the constant
   int k2a[2][2];
@@ -421,11 +439,12 @@ __global__ __launch_bounds__(ATT_THREADS, 4) void attention_dma_kernel(const Att
 #pragma unroll
     for (int hh = 0; hh < 2; ++hh) k2a[st][hh] = hi ? CONST_OFF : st * STAGE + hh * 4096 + fo[2];
 
-  f32x16 oacc[NDT];
+  // O^T in 16x16 blocks: oacc[t3][qb][r] of lane (m16, g4) is O^T[d = 16 t3 + 4 g4 + r][query 16 qb + m16 of the wave]
+  f32x4 oacc[NT3][2];
 #pragma unroll
-  for (int t = 0; t < NDT; ++t)
+  for (int t = 0; t < NT3; ++t)
 #pragma unroll
-    for (int r = 0; r < 16; ++r) oacc[t][r] = 0.f;
+    for (int qb = 0; qb < 2; ++qb) oacc[t][qb] = f32x4{0.f, 0.f, 0.f, 0.f};
   float m_run = 0.f;       // (q[40..42] = 0 so far)
 
   const int ntiles = (p.nkv + ATT_KVT - 1) / ATT_KVT;
@@ -492,11 +511,19 @@ __global__ __launch_bounds__(ATT_THREADS, 4) void attention_dma_kernel(const Att
         qf[2] = xq.v;
       }
       if (!first) {          // (first tile: O = 0, and exp2(-delta) may be inf)
+        // alpha sits in the S layout (query lane % 32, the same in both half waves); the accumulators of query block qb sit in
+        // lanes whose query is 16 qb + lane % 16.  One swap of alpha with itself gives [row 0, row 0, row 2, row 2] = queries
+        // 0..15 in every lane row (block 0) and [row 1, row 1, row 3, row 3] = queries 16..31 (block 1).
         const float alpha = __builtin_amdgcn_exp2f(-delta);
+        const auto ax = __builtin_amdgcn_permlane16_swap(__float_as_uint(alpha), __float_as_uint(alpha), false, false);
 #pragma unroll
-        for (int t = 0; t < NDT; ++t)
+        for (int qb = 0; qb < 2; ++qb) {
+          const float aq = __uint_as_float(ax[qb]);
 #pragma unroll
-          for (int r = 0; r < 16; ++r) oacc[t][r] *= alpha;
+          for (int t = 0; t < NT3; ++t)
+#pragma unroll
+            for (int r = 0; r < 4; ++r) oacc[t][qb][r] *= aq;
+        }
       }
 #pragma unroll
       for (int hh = 0; hh < 2; ++hh)
@@ -515,12 +542,31 @@ __global__ __launch_bounds__(ATT_THREADS, 4) void attention_dma_kernel(const Att
       for (int j = 0; j < 4; ++j) pk.u[j] = pack_bf2(s[h4 >> 1][(h4 & 1) * 8 + 2 * j], s[h4 >> 1][(h4 & 1) * 8 + 2 * j + 1]);
       pa[h4] = pk.v;
     }
+    // P as the B operand of 16x16x32: lane (lq, hi) holds in pa[2 hh + a] keys 32 hh + 16 a + 8 hi + 0..7 of query lq; the swap trades the
+    // odd 16-lane rows of pa[2 hh] for the even rows of pa[2 hh + 1], which leaves, for queries 16 qb + lane % 16, the key groups
+    // 32 hh + 8 {0, 2, 1, 3}[g] + 0..7 in lane rows g = 0..3 (vfo above reads V^T in that order)
+    bf16x8 pb[2][2];
 #pragma unroll
-    for (int t = 0; t < NDT; ++t) {
+    for (int hh = 0; hh < 2; ++hh) {
+      union { bf16x8 v; uint32_t u[4]; } x0, x1, y0, y1;
+      x0.v = pa[2 * hh];
+      x1.v = pa[2 * hh + 1];
 #pragma unroll
-      for (int h4 = 0; h4 < 4; ++h4) {
-        const bf16x8 vf = *reinterpret_cast<const bf16x8*>(Vs + t * 4096 + fo[h4]);
-        oacc[t] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(vf, pa[h4], oacc[t], 0, 0, 0);
+      for (int j = 0; j < 4; ++j) {
+        const auto sw = __builtin_amdgcn_permlane16_swap(x0.u[j], x1.u[j], false, false);
+        y0.u[j] = sw[0];
+        y1.u[j] = sw[1];
+      }
+      pb[hh][0] = y0.v;
+      pb[hh][1] = y1.v;
+    }
+#pragma unroll
+    for (int hh = 0; hh < 2; ++hh) {
+#pragma unroll
+      for (int t = 0; t < NT3; ++t) {
+        const bf16x8 vf = *reinterpret_cast<const bf16x8*>(Vs + t * 2048 + vfo[hh]);
+#pragma unroll
+        for (int qb = 0; qb < 2; ++qb) oacc[t][qb] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(vf, pb[hh][qb], oacc[t][qb], 0, 0, 0);
       }
     }
     // own pieces of the next tile have landed, AND every LDS read of this tile has returned: hipcc sinks the last PV fragment read's
@@ -536,22 +582,21 @@ __global__ __launch_bounds__(ATT_THREADS, 4) void attention_dma_kernel(const Att
     if (it + 1 < ntiles) tile_body(it + 1, std::integral_constant<int, 1>{});
   }
 
-  // V^T row DP is all ones (written by the QKV epilogue), so O^T row DP accumulated sum_kv P: register 8 of tile DP / 32, hi = 0 half
-  static_assert(DP % 32 == 16, "ones-row position");
-  const float l_run = __shfl(oacc[DP / 32][8], lq, 64);
-  const float inv = 1.f / l_run;
-  bf16_t* orow = p.O + (size_t)(b * p.nq + qrow) * p.ldo + h * DP;
+  // LDS row 40 of the V^T image held the ones row, so O^T row 40 accumulated sum_kv P: register 0 of block t3 = 2 in lane row g = 2
+  // (40 = 16 * 2 + 4 * 2 + 0).  Columns 40..47 of O are stored as the zeros that P times the zero rows 40..47 of V^T gave.
+  static_assert(DP == 48, "ones-row position");
 #pragma unroll
-  for (int t = 0; t < NDT; ++t) {
+  for (int qb = 0; qb < 2; ++qb) {
+    const float l_run = __shfl(oacc[2][qb][0], 32 + m16, 64);
+    const float inv = 1.f / l_run;
+    bf16_t* orow = p.O + (size_t)(b * p.nq + q0 + 16 * qb + m16) * p.ldo + h * DP + 4 * g4;
 #pragma unroll
-    for (int g = 0; g < 4; ++g) {
-      const int d = t * 32 + 8 * g + 4 * hi;
-      if (d < DP) {
-        uint2 o;
-        o.x = pack_bf2(oacc[t][g * 4 + 0] * inv, oacc[t][g * 4 + 1] * inv);
-        o.y = pack_bf2(oacc[t][g * 4 + 2] * inv, oacc[t][g * 4 + 3] * inv);
-        *reinterpret_cast<uint2*>(orow + d) = o;
-      }
+    for (int t = 0; t < NT3; ++t) {
+      uint2 o;
+      o.x = pack_bf2(oacc[t][qb][0] * inv, oacc[t][qb][1] * inv);
+      o.y = pack_bf2(oacc[t][qb][2] * inv, oacc[t][qb][3] * inv);
+      if (t == 2 && g4 >= 2) o = make_uint2(0u, 0u);
+      *reinterpret_cast<uint2*>(orow + 16 * t) = o;
     }
   }
 }
