@@ -115,6 +115,13 @@ SYMBOLS: Dict[str, Tuple[object, List[object]]] = {
   "gill_op_sd_inpaint_run": (_i, [_vp, _i, _i, _i, _f, _vp, _vp, _vp, _vp, _vp, _vp, _i, C.c_int64, C.c_int64, _vp, _vp, _vp]),
   "gill_op_conv3x3_ex": (_i, [_vp, _i, _vp, _i, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _vp]),
   "gill_op_conv3x3_fp8": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp]),
+  "gill_ret_index_create": (_i, [C.POINTER(_vp), _i, C.c_int64]),
+  "gill_ret_index_destroy": (None, [_vp]),
+  "gill_ret_index_add": (_i, [_vp, _vp, _i, C.c_int64, _i, _f, _vp]),
+  "gill_ret_index_size": (C.c_int64, [_vp]),
+  "gill_ret_index_rows": (_i, [_vp, C.c_int64, C.c_int64, _vp, _vp]),
+  "gill_ret_index_search": (_i, [_vp, _vp, _i, _i, _i, _vp, _i, _f, _vp, _vp, _vp]),
+  "gill_ret_index_slabs": (_i, [_vp, C.POINTER(C.c_int64), C.POINTER(C.c_int), C.POINTER(C.c_int64)]),
   "gill_pndm_schedule": (_i, [_i, C.POINTER(C.c_int32), C.POINTER(C.c_double)]),
   "gill_sd_denoise_ex": (_i, [_vp, _vp, _vp, _vp, _i, _vp, _i, _i, _f, _vp, _vp, _vp]),
   "gill_sd_schedule": (_i, [_vp, _i, _i, C.POINTER(C.c_float), C.POINTER(C.c_double), C.POINTER(C.c_double)]),

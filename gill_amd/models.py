@@ -590,6 +590,16 @@ class GILLModel(nn.Module):
     out = tokens[:, :col].clone() if max_len > 0 else None
     return out, output_embeddings, output_logits
 
+class _TopScores:
+  """The scores of the rows a fused search returned, indexed by row like the reference's full score vector (scores[img_idx].item())."""
+
+  def __init__(self, idx: Tensor, scores: Tensor):
+    self._by_row = {int(i): s for i, s in zip(idx.tolist(), scores)}
+
+  def __getitem__(self, row) -> Tensor:
+    return self._by_row[int(row)]
+
+
 class GILL(nn.Module):
   def __init__(self, tokenizer, model_args: Optional[GILLArgs] = None, path_array: Optional[List[str]] = None,
                emb_matrix: Optional[torch.tensor] = None, load_sd: bool = False, num_gen_images: int = 1,
@@ -598,6 +608,7 @@ class GILL(nn.Module):
     self.model = GILLModel(tokenizer, model_args)
     self.path_array = path_array
     self.emb_matrix = emb_matrix
+    self.ret_index = None            # device-resident retrieval index (build_retrieval_index); opt-in, not a reference attribute
     self.load_sd = load_sd
     self.num_gen_images = num_gen_images
     self.idx2dec = {0: 'gen', 1: 'ret', 2: 'same'}
@@ -700,10 +711,17 @@ class GILL(nn.Module):
             ret_emb = self.model.ret_text_hidden_fcs[0](raw_emb, None)[:, 0, :]  # (1, 256)
             ret_emb = ret_emb / ret_emb.norm(dim=-1, keepdim=True)
             ret_emb = ret_emb.type(self.emb_matrix.dtype)  # (1, 256)
-            scores = self._scores(self.emb_matrix, ret_emb)                         # emb_matrix @ ret_emb.T, (N, 1)
-            for seen_idx in seen_image_idx:   # Downweight seen images.
-              scores[seen_idx, :] -= 1000
-            _, top_image_idx = scores.squeeze().topk(3)
+            if self.ret_index is not None:
+              # the same three steps as one fused pass over the resident index: a seen image competes, and is reported, with its -1000
+              top_scores, top_idx = self.ret_index.search(ret_emb.float(), 3, normalize=False, penalty=1000.0,
+                                                          exclude=[[int(i) for i in seen_image_idx]] if seen_image_idx else None)
+              top_image_idx = top_idx[0][top_idx[0] >= 0]
+              scores = _TopScores(top_image_idx, top_scores[0])
+            else:
+              scores = self._scores(self.emb_matrix, ret_emb)                         # emb_matrix @ ret_emb.T, (N, 1)
+              for seen_idx in seen_image_idx:   # Downweight seen images.
+                scores[seen_idx, :] -= 1000
+              _, top_image_idx = scores.squeeze().topk(3)
             for img_idx in top_image_idx:     # Find the first image that does not error out.
               try:
                 seen_image_idx.append(img_idx)
@@ -836,6 +854,76 @@ class GILL(nn.Module):
     q4[0, :D] = query.reshape(-1).to(torch.bfloat16)
     return ops.gemm(a, q4, out_f32=True)[:, :1].to(matrix.dtype)
 
+  # ---- NEW, build-defined retrieval entries (not reference functions) -------------------------------------
+  def build_retrieval_index(self, raw=None, scale: Optional[float] = None):
+    """Put the retrieval matrix on the device as a GillRetrievalIndex (gill_amd/retrieval.py) and set self.ret_index.  raw (N, ret_emb_dim): the
+    rows as precomputed (the cc3m*.npy embeddings), normalised on the device to scale * row / ||row|| (gill/models.py:895-900; scale defaults to
+    exp(logit_scale)).  raw None: the rows of self.emb_matrix as they stand, no renormalisation.  With an index attached,
+    generate_for_images_and_texts ranks through it and retrieve_images becomes available; self.emb_matrix is not touched."""
+    from .retrieval import GillRetrievalIndex
+    dev = self.model.logit_scale.device
+    if raw is None:
+      if self.emb_matrix is None:
+        raise ValueError('build_retrieval_index: no raw rows given and the model has no emb_matrix')
+      self.ret_index = GillRetrievalIndex.from_embeddings(torch.as_tensor(self.emb_matrix), normalize=False, device=dev)
+    else:
+      if scale is None:
+        scale = float(self.model.logit_scale.detach().float().exp().item())
+      self.ret_index = GillRetrievalIndex.from_embeddings(raw, scale=float(scale), normalize=True, device=dev)
+    return self.ret_index
+
+  @torch.no_grad()
+  def retrieve_images(self, prompts, k: int = 3, exclude=None, distributed: bool = True, return_embeddings: bool = False):
+    """Batched text -> retrieved images.  `prompts` is a list of strings or a (B,T) id tensor as for generate_images.  Per prompt this equals the
+    'ret' branch of generate_for_images_and_texts([p], num_words=2, gen_scale_factor=1e5): the 8 [IMG] ids are appended, one OPT pass yields
+    their hidden states (models.py:384), ret_text_hidden_fcs[0] maps the first of them to the retrieval embedding (models.py:671-674, [:, 0, :]),
+    and one fused search of the resident index normalises it, scores every row and keeps the top k (models.py:675-691).  exclude: per prompt
+    the rows to downweight by 1000 (a list of lists or a (B, E) tensor, -1 = empty).  Returns a namespace with indices (B, k) int64 (-1 past
+    the index's size), scores (B, k) fp32 and paths (a list of B lists from path_array; None without one) — nothing is fetched or opened —
+    and, with return_embeddings, embeddings (B, ret_emb_dim) fp32 as handed to the search (before normalisation).  With torch.distributed
+    initialised the prompts are sharded contiguously over ranks, the index is replicated like the weights, and the two result tensors are
+    all-gathered; a rank with an empty shard still enters the collectives."""
+    from . import parallel
+    if self.ret_index is None:
+      raise RuntimeError('retrieve_images needs a retrieval index: call build_retrieval_index() (or load_gill(..., ret_index=True)) first')
+    dev = self.model.logit_scale.device
+    if (isinstance(prompts, torch.Tensor) and prompts.numel() == 0) or (not isinstance(prompts, torch.Tensor) and len(prompts) == 0):
+      raise ValueError('retrieve_images: empty prompt batch')
+    ids, lens = self._prompt_ids(prompts)
+    B_total = ids.shape[0]
+    if exclude is not None:
+      exclude = self.ret_index._exclude(exclude, B_total)
+    lo, hi = parallel.shard_range(B_total, distributed)
+    ids, lens = ids[lo:hi], lens[lo:hi]
+    B = ids.shape[0]
+    img = torch.tensor(self.model.retrieval_token_idx, dtype=torch.int64)
+    nt = self.model.num_tokens
+    T = int(lens.max().item()) + nt if B > 0 else nt
+    pad = self.model.tokenizer.pad_token_id
+    full = torch.full((B, T), pad if pad is not None else 1, dtype=torch.int64)
+    for b in range(B):
+      n = int(lens[b])
+      full[b, :n] = ids[b, :n]
+      full[b, n:n + nt] = img
+    last_idx = lens + nt - 1
+    scores = torch.zeros((0, k), device=dev, dtype=torch.float32)
+    indices = torch.zeros((0, k), device=dev, dtype=torch.int64)
+    embs = torch.zeros((0, self.ret_index.dim), device=dev, dtype=torch.float32)
+    if B > 0:
+      raw, _ = self.model.img_hidden_states(full.to(dev), last_idx)
+      embs = self.model.ret_text_hidden_fcs[0](raw, None)[:, 0, :].float().contiguous()     # (B, ret_emb_dim)
+      scores, indices = self.ret_index.search(embs, k, normalize=True, penalty=1000.0,
+                                              exclude=None if exclude is None else exclude[lo:hi])
+    scores = parallel.gather_rows(scores, B_total, distributed)
+    indices = parallel.gather_rows(indices, B_total, distributed)
+    paths = None
+    if self.path_array is not None:
+      paths = [[self.path_array[i] for i in row if i >= 0] for row in indices.cpu().tolist()]
+    out = SimpleNamespace(indices=indices, scores=scores, paths=paths)
+    if return_embeddings:
+      out.embeddings = parallel.gather_rows(embs, B_total, distributed)
+    return out
+
   # ---- NEW, build-defined batched entry (not a reference function) ---------------------------------------
   @torch.no_grad()
   def generate_images(self, prompts, num_inference_steps: int = 50, guidance_scale: float = 7.5,
@@ -932,8 +1020,10 @@ class GILL(nn.Module):
     return ids, lens
 
 
-def load_gill(model_dir: str, load_ret_embs: bool = True, decision_model_fn: str = 'decision_model.pth.tar') -> GILL:
-  """reference: gill/models.py:810-902.  Same files, same errors, same tokenizer surgery, same checkpoint format."""
+def load_gill(model_dir: str, load_ret_embs: bool = True, decision_model_fn: str = 'decision_model.pth.tar', ret_index: bool = False) -> GILL:
+  """reference: gill/models.py:810-902.  Same files, same errors, same tokenizer surgery, same checkpoint format.
+  ret_index (not a reference argument): also build model.ret_index from the raw cc3m rows with the device normalise (GILL.build_retrieval_index);
+  emb_matrix is set as without it."""
   model_args_path = os.path.join(model_dir, 'model_args.json')
   model_ckpt_path = os.path.join(model_dir, 'pretrained_ckpt.pth.tar')
   embs_paths = [s for s in glob.glob(os.path.join(model_dir, 'cc3m*.npy'))]
@@ -991,6 +1081,8 @@ def load_gill(model_dir: str, load_ret_embs: bool = True, decision_model_fn: str
     scale = model.model.logit_scale.exp()
     m = torch.as_tensor(emb_matrix).to(device=scale.device, dtype=scale.dtype)
     model.emb_matrix = scale * (m / m.norm(dim=1, keepdim=True))
+    if ret_index:
+      model.build_retrieval_index(emb_matrix)
   return model
 
 

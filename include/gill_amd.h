@@ -364,6 +364,44 @@ int gill_vae_decode(gill_vae* h, const float* latents, int B, float* image_f32, 
  *      moments_out (B,2*latent_channels,L,L) = [mean | clamp(logvar, -30, 20)], unscaled; may be NULL. */
 int gill_vae_encode(gill_vae* h, const float* image, int B, const float* noise, float* latents_out, float* moments_out, void* stream);
 
+/* ------------------------------------------------------------------------------------------
+ * Retrieval — the image-retrieval half of GILL.generate_for_images_and_texts (gill/models.py:671-696): ret_emb / ||ret_emb|| ->
+ * scores = emb_matrix @ ret_emb.T -> scores[seen] -= 1000 -> topk(3), and the index preparation of load_gill (gill/models.py:895-900):
+ * emb_matrix = exp(logit_scale) * m / ||m||.  Here the matrix lives on the device in a handle (bf16, in the A-operand order of the
+ * 16x16x32 bf16 matrix instruction: csrc/retrieval.hip), and one fused pass scores up to 16 queries against every row and keeps the top k.
+ * The full score vector is never written.
+ * DIVERGENCES from the reference, all deliberate: a zero row (and a zero query under normalize) stays zero where the reference's division
+ * gives NaN; the ranking is on the fp32 accumulated scores (the reference rounds the score vector to the matrix's dtype first) and a tie goes
+ * to the LOWER row index (torch.topk promises no order among equals); a row listed several times in `exclude` is penalised once.
+ * ------------------------------------------------------------------------------------------ */
+typedef struct gill_ret_index gill_ret_index;
+
+/* An empty index of `capacity` rows of `dim` columns: dim a multiple of 8, at most 1024; 1 <= capacity < 2^31 - 1.  Host only: the device memory
+ * (capacity rounded up to 16 rows x dim rounded up to 32 columns of bf16, plus a workspace of at most 16 MiB) is allocated by the first add / search. */
+int gill_ret_index_create(gill_ret_index** out, int dim, int64_t capacity);
+void gill_ret_index_destroy(gill_ret_index* h);
+/* Append rows (n, dim) of dtype GILL_DTYPE_* (device pointer, 16-byte aligned); models.py:895-900 with normalize = 1: every row becomes
+ * scale * row / ||row||_2, computed in fp32 and rounded once to bf16 (a zero row stays zero).  normalize = 0: the rows rounded to bf16 as they
+ * are (scale unused).  An error, with nothing written, when size + n would pass the capacity. */
+int gill_ret_index_add(gill_ret_index* h, const void* rows, int dtype, int64_t n, int normalize, float scale, void* stream);
+/* Rows held (-1 for a null handle).  Host only. */
+int64_t gill_ret_index_size(const gill_ret_index* h);
+/* Rows [first, first + n) as stored -> out (n, dim) bf16 row-major (device pointer, 16-byte aligned). */
+int gill_ret_index_rows(gill_ret_index* h, int64_t first, int64_t n, void* out_bf16, void* stream);
+/* models.py:671-696.  queries (Q, dim) fp32 on the device (16-byte aligned), any Q >= 1 (one pass over the matrix per 16 queries); normalize = 1:
+ * each query is divided by its fp32 L2 norm, then rounded to bf16; 0: rounded as it is.  Scores are fp32 sums of bf16 products.
+ * exclude (Q, E) int64 on the device or NULL, E <= 64, -1 = empty slot: a listed row competes with score - penalty (it is not removed:
+ * `scores[seen_idx] -= 1000`, :688-689) and is reported with it.  -> scores_out (Q, k) fp32, idx_out (Q, k) int64, 1 <= k <= 32: the exact top k
+ * by (score descending, row index ascending); when k > size the trailing slots hold index -1 and score -inf.  Scores are assumed finite.
+ * Three launches per 16 queries on `stream` (five from 16384 rows on: the first 1/64 of the rows is searched first and its k-th score is
+ * the floor the rest starts its filter from), no host synchronisation; the partial lists live in the handle (one search at a time). */
+int gill_ret_index_search(gill_ret_index* h, const float* queries, int Q, int normalize, int k, const int64_t* exclude, int E, float penalty,
+                          float* scores_out, int64_t* idx_out, void* stream);
+/* How a search of the index as it stands splits the rows (host only, for tests): rows below *first_row belong to the prefix pass; list j of the
+ * *nlists of the main pass scans rows *first_row + [j, j + 1) * *rows_per_list, one wave each.  The result never depends on it.  Any output may
+ * be NULL. */
+int gill_ret_index_slabs(const gill_ret_index* h, int64_t* first_row, int* nlists, int64_t* rows_per_list);
+
 /* PNDM schedule known-answers for tests (host arrays): timesteps_out must hold num_steps+1 ints;
  * returns the number written.  alphas_cumprod_out (optional) must hold 1000 doubles. */
 int gill_pndm_schedule(int num_steps, int32_t* timesteps_out, double* alphas_cumprod_out);
