@@ -83,6 +83,7 @@ SYMBOLS: Dict[str, Tuple[object, List[object]]] = {
   "gill_opt_forward": (_i, [_vp, _vp, _i, _i, _vp, _vp]),
   "gill_opt_forward_cached": (_i, [_vp, _vp, _i, _i, _i, _vp, _vp]),
   "gill_opt_img_hidden": (_i, [_vp, _vp, C.POINTER(C.c_int32), _i, _i, _i, _vp, _vp, _vp]),
+  "gill_opt_img_hidden_ex": (_i, [_vp, _vp, C.POINTER(C.c_int32), _i, _i, _i, _vp, _i, _vp, _vp, _vp]),
   "gill_opt_last_logits": (_i, [_vp, _vp, _i, _i, _vp, _vp]),
   "gill_opt_next_token": (_i, [_vp, _vp, _i, _i, C.POINTER(gill_decode_rule), _vp, _vp, _i, _i, _vp, _vp, _vp]),
   "gill_opt_pick_token": (_i, [_vp, _vp, _i, C.POINTER(gill_decode_rule), _vp, _i, _i, _vp, _vp, _vp]),
@@ -91,6 +92,10 @@ SYMBOLS: Dict[str, Tuple[object, List[object]]] = {
   "gill_clip_create": (_i, [C.POINTER(_vp), C.POINTER(gill_clip_config), C.POINTER(gill_tensor), _i]),
   "gill_clip_destroy": (None, [_vp]),
   "gill_clip_forward": (_i, [_vp, _vp, _i, _vp, _vp]),
+  "gill_clip_preprocess_workspace": (_i, [C.POINTER(C.c_int64), _i, _i, C.POINTER(C.c_int64)]),
+  "gill_clip_preprocess": (_i, [_vp, C.c_int64, C.POINTER(C.c_int64), _i, _i, _i, _vp, _vp, _vp, C.c_int64, _vp]),
+  "gill_clip_resize_ksize": (_i, [_i, _i]),
+  "gill_clip_resize_taps": (_i, [_i, _i, _i, _i, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_int32), _i]),
   "gill_clip_text_create": (_i, [C.POINTER(_vp), C.POINTER(gill_clip_text_config), C.POINTER(gill_tensor), _i]),
   "gill_clip_text_destroy": (None, [_vp]),
   "gill_clip_text_forward": (_i, [_vp, _vp, _i, _i, _vp, _vp, _vp]),

@@ -146,13 +146,55 @@ extern "C" int gill_opt_forward_cached(gill_opt* m, const void* inputs_embeds_bf
   return 0;
 }
 
-extern "C" int gill_opt_img_hidden(gill_opt* m, const int64_t* ids, const int32_t* last_idx_host, int B, int T,
-                                   int num_tokens, void* raw_out_bf16, void* emb_out_bf16, void* stream) {
+// embed_tokens_kernel with a second table: out[b][t][:] = row(ids[b][t])[:] + pos[t + pos_offset][:], where an id < 0 names row -(id + 1) of
+// extra (n_extra, D) bf16 — the visual embeddings of an image prompt (models.py:606-613, 625) — and an id >= 0 a row of table.  Ids outside either
+// range are clamped to the nearest valid row.  The same arithmetic as embed_tokens_kernel on either kind of row.
+__global__ __launch_bounds__(256) void opt_embed_tokens_ex_kernel(const int64_t* __restrict__ ids, const bf16_t* __restrict__ table, int vocab,
+                                                                  const bf16_t* __restrict__ extra, int n_extra, const bf16_t* __restrict__ pos,
+                                                                  int pos_offset, int T, int D, float* __restrict__ out) {
+  const int row = blockIdx.x;  // b*T + t
+  const int t = row % T;
+  int64_t id = ids[row];
+  const bf16_t* e;
+  if (id < 0) {
+    int64_t x = -(id + 1);
+    if (x >= n_extra) x = n_extra - 1;
+    e = extra + (size_t)x * D;
+  } else {
+    if (id >= vocab) id = vocab - 1;
+    e = table + (size_t)id * D;
+  }
+  const bf16_t* pe = pos ? pos + (size_t)(t + pos_offset) * D : nullptr;
+  float* o = out + (size_t)row * D;
+  for (int c = threadIdx.x * 2; c < D; c += blockDim.x * 2) {
+    const uint32_t u = *reinterpret_cast<const uint32_t*>(e + c);
+    float a = bf2f((bf16_t)(u & 0xffff)), bq = bf2f((bf16_t)(u >> 16));
+    if (pe) {
+      const uint32_t v = *reinterpret_cast<const uint32_t*>(pe + c);
+      a += bf2f((bf16_t)(v & 0xffff)); bq += bf2f((bf16_t)(v >> 16));
+    }
+    *reinterpret_cast<float2*>(o + c) = make_float2(a, bq);
+  }
+}
+
+// the two embedding passes of img_hidden: token rows only through the shared kernel (as ever), with extra rows through the kernel above
+static int img_hidden_embed(const gill_opt* m, const int64_t* ids, const bf16_t* extra, int n_extra, const bf16_t* pos, int B, int T, hipStream_t s) {
+  const int D = m->cfg.hidden_size;
+  if (n_extra == 0) return embed_tokens_launch(ids, m->embed, m->cfg.vocab_size, pos, 2, B, T, D, m->h, s);
+  hipLaunchKernelGGL(opt_embed_tokens_ex_kernel, dim3(B * T), dim3(256), 0, s, ids, m->embed, m->cfg.vocab_size, extra, n_extra, pos, 2, T, D, m->h);
+  GILL_CHECK_HIP(hipGetLastError());
+  return 0;
+}
+
+extern "C" int gill_opt_img_hidden_ex(gill_opt* m, const int64_t* ids, const int32_t* last_idx_host, int B, int T, int num_tokens,
+                                      const void* extra_rows_bf16, int n_extra, void* raw_out_bf16, void* emb_out_bf16, void* stream) {
   GILL_REQUIRE(m && ids && last_idx_host && raw_out_bf16, "null argument");
   GILL_REQUIRE(B >= 1 && B <= m->cfg.max_batch && T >= 1 && T <= m->cfg.max_seq, "B/T exceed the handle's workspace");
   GILL_REQUIRE(num_tokens >= 1 && num_tokens <= 64, "num_tokens out of range");
+  GILL_REQUIRE(n_extra >= 0 && (n_extra == 0 || extra_rows_bf16), "n_extra rows need a table");
   hipStream_t s = (hipStream_t)stream;
   const int D = m->cfg.hidden_size;
+  const bf16_t* extra = (const bf16_t*)extra_rows_bf16;
   std::vector<int32_t> idx((size_t)B * num_tokens);
   for (int b = 0; b < B; ++b) {
     GILL_REQUIRE(last_idx_host[b] - num_tokens + 1 >= 0 && last_idx_host[b] < T, "last_idx out of range");
@@ -161,16 +203,21 @@ extern "C" int gill_opt_img_hidden(gill_opt* m, const int64_t* ids, const int32_
   GILL_CHECK_HIP(hipMemcpyAsync(m->idx_dev, idx.data(), sizeof(int32_t) * idx.size(), hipMemcpyHostToDevice, s));
   GILL_CHECK_HIP(hipStreamSynchronize(s));  // idx is a stack-lifetime host buffer
   // input_embs = input_embeddings(labels)  (models.py:180), bf16 rows
-  GILL_TRY(embed_tokens_launch(ids, m->embed, m->cfg.vocab_size, nullptr, 0, B, T, D, m->h, s));
+  GILL_TRY(img_hidden_embed(m, ids, extra, n_extra, nullptr, B, T, s));
   GILL_TRY(cast_f32_to_bf16_launch(m->h, m->emb_tmp, (int64_t)B * T * D, s));
   if (emb_out_bf16) GILL_TRY(gather_rows_launch(m->emb_tmp, 0, m->idx_dev, B * num_tokens, D, emb_out_bf16, 0, s));
   // + learned positions -> fp32 stream
-  GILL_TRY(embed_tokens_launch(ids, m->embed, m->cfg.vocab_size, m->pos, 2, B, T, D, m->h, s));
+  GILL_TRY(img_hidden_embed(m, ids, extra, n_extra, m->pos, B, T, s));
   GILL_TRY(m->run_layers(B, T, s));
   // final LN only on the rows that are read (models.py:384)
   GILL_TRY(gather_rows_launch(m->h, 1, m->idx_dev, B * num_tokens, D, m->gath, 1, s));
   GILL_TRY(layernorm_launch(m->gath, 1, m->lnfg, m->lnfb, (bf16_t*)raw_out_bf16, B * num_tokens, D, 1e-5f, s));
   return 0;
+}
+
+extern "C" int gill_opt_img_hidden(gill_opt* m, const int64_t* ids, const int32_t* last_idx_host, int B, int T,
+                                   int num_tokens, void* raw_out_bf16, void* emb_out_bf16, void* stream) {
+  return gill_opt_img_hidden_ex(m, ids, last_idx_host, B, T, num_tokens, nullptr, 0, raw_out_bf16, emb_out_bf16, stream);
 }
 
 extern "C" int gill_opt_last_logits(gill_opt* m, const float* hidden, int B, int T, float* logits_out, void* stream) {

@@ -228,13 +228,16 @@ class GILLModel(nn.Module):
                         intermediate_size=c.intermediate_size), sd
     return None, None
 
+  def _require_vision(self):
+    if self.visual_model is None:
+      raise NotImplementedError('image prompts need the CLIP vision weights (args.clip_state_dict or a local '
+                                'openai/clip-vit-* directory): none were available when this model was built')
+
   def _clip_native(self, B: int):
     dev = self.logit_scale.device
     if dev.type != 'cuda':
       raise N.GillNativeError('GILLModel runs only on an MI355X through libgill_amd; call .cuda() first.')
-    if self.visual_model is None:
-      raise NotImplementedError('image prompts need the CLIP vision weights (args.clip_state_dict or a local '
-                                'openai/clip-vit-* directory): none were available when this model was built')
+    self._require_vision()
     if self._clip_handle is not None and B <= self._clip_cap:
       return self._clip_handle
     if self._clip_handle is not None:
@@ -349,19 +352,33 @@ class GILLModel(nn.Module):
       N.check(N.lib().gill_opt_forward_cached(h, N.ptr(x), B, Tn, past_len, N.ptr(out), N.current_stream()))
     return out
 
-  def img_hidden_states(self, labels: Tensor, last_embedding_idx: Tensor):
-    """Fast path of forward(mode='generation'): (B,T) ids, (B,) idx -> (raw (B,8,D), embs (B,8,D)) bf16."""
+  def img_hidden_states(self, labels: Tensor, last_embedding_idx: Tensor, extra_rows: Optional[Tensor] = None):
+    """Fast path of forward(mode='generation'): (B,T) ids, (B,) idx -> (raw (B,8,D), embs (B,8,D)) bf16.  extra_rows (n,D) bf16: the
+    embedding rows of image prompts (models.py:606-613, 625); an id < 0 selects row -(id + 1) of them (gill_opt_img_hidden_ex)."""
     B, T = labels.shape
     dev = self.logit_scale.device
+    D = self.opt_cfg.hidden_size
+    n_extra = 0
+    if extra_rows is not None:
+      if extra_rows.dim() != 2 or extra_rows.shape[1] != D or extra_rows.dtype != torch.bfloat16:
+        raise ValueError(f'extra_rows must be (n, {D}) bfloat16, got {tuple(extra_rows.shape)} {extra_rows.dtype}')
+      extra_rows = extra_rows.to(dev).contiguous()
+      n_extra = extra_rows.shape[0]
+      lowest = int(labels.min()) if labels.numel() else 0
+      if lowest < -n_extra:      # the library clamps what it cannot check (the ids live on the device): refuse here
+        raise ValueError(f'id {lowest} selects extra row {-(lowest + 1)} of {n_extra}')
     h = self._opt_native(B, T)
     ids = labels.to(dev, torch.int64).contiguous()
     li = [int(v) for v in last_embedding_idx.reshape(-1).tolist()]
     arr = (C.c_int32 * B)(*li)
-    D = self.opt_cfg.hidden_size
     raw = torch.empty((B, self.num_tokens, D), device=dev, dtype=torch.bfloat16)
     emb = torch.empty((B, self.num_tokens, D), device=dev, dtype=torch.bfloat16)
     with torch.cuda.device(dev):
-      N.check(N.lib().gill_opt_img_hidden(h, N.ptr(ids), arr, B, T, self.num_tokens, N.ptr(raw), N.ptr(emb), N.current_stream()))
+      if extra_rows is None:
+        N.check(N.lib().gill_opt_img_hidden(h, N.ptr(ids), arr, B, T, self.num_tokens, N.ptr(raw), N.ptr(emb), N.current_stream()))
+      else:
+        N.check(N.lib().gill_opt_img_hidden_ex(h, N.ptr(ids), arr, B, T, self.num_tokens, N.ptr(extra_rows) if n_extra else None, n_extra,
+                                               N.ptr(raw), N.ptr(emb), N.current_stream()))
     return raw, emb
 
   def forward(self, pixel_values: torch.FloatTensor, labels: Optional[torch.LongTensor] = None,
@@ -873,9 +890,10 @@ class GILL(nn.Module):
     return self.ret_index
 
   @torch.no_grad()
-  def retrieve_images(self, prompts, k: int = 3, exclude=None, distributed: bool = True, return_embeddings: bool = False):
-    """Batched text -> retrieved images.  `prompts` is a list of strings or a (B,T) id tensor as for generate_images.  Per prompt this equals the
-    'ret' branch of generate_for_images_and_texts([p], num_words=2, gen_scale_factor=1e5): the 8 [IMG] ids are appended, one OPT pass yields
+  def retrieve_images(self, prompts, k: int = 3, exclude=None, distributed: bool = True, return_embeddings: bool = False,
+                      always_add_bos: bool = False):
+    """Batched prompts -> retrieved images.  `prompts` is what generate_images takes: strings, lists mixing strings and images, or a (B,T) id
+    tensor.  Per prompt this equals the 'ret' branch of generate_for_images_and_texts([p], num_words=2, gen_scale_factor=1e5): the 8 [IMG] ids are appended, one OPT pass yields
     their hidden states (models.py:384), ret_text_hidden_fcs[0] maps the first of them to the retrieval embedding (models.py:671-674, [:, 0, :]),
     and one fused search of the resident index normalises it, scores every row and keeps the top k (models.py:675-691).  exclude: per prompt
     the rows to downweight by 1000 (a list of lists or a (B, E) tensor, -1 = empty).  Returns a namespace with indices (B, k) int64 (-1 past
@@ -889,12 +907,12 @@ class GILL(nn.Module):
     dev = self.model.logit_scale.device
     if (isinstance(prompts, torch.Tensor) and prompts.numel() == 0) or (not isinstance(prompts, torch.Tensor) and len(prompts) == 0):
       raise ValueError('retrieve_images: empty prompt batch')
-    ids, lens = self._prompt_ids(prompts)
+    ids, lens, images = self._interleaved_ids(prompts, always_add_bos)
     B_total = ids.shape[0]
     if exclude is not None:
       exclude = self.ret_index._exclude(exclude, B_total)
     lo, hi = parallel.shard_range(B_total, distributed)
-    ids, lens = ids[lo:hi], lens[lo:hi]
+    ids, lens, extra = self._shard_prompts(ids, lens, images, lo, hi)
     B = ids.shape[0]
     img = torch.tensor(self.model.retrieval_token_idx, dtype=torch.int64)
     nt = self.model.num_tokens
@@ -910,7 +928,7 @@ class GILL(nn.Module):
     indices = torch.zeros((0, k), device=dev, dtype=torch.int64)
     embs = torch.zeros((0, self.ret_index.dim), device=dev, dtype=torch.float32)
     if B > 0:
-      raw, _ = self.model.img_hidden_states(full.to(dev), last_idx)
+      raw, _ = self.model.img_hidden_states(full.to(dev), last_idx, **extra)
       embs = self.model.ret_text_hidden_fcs[0](raw, None)[:, 0, :].float().contiguous()     # (B, ret_emb_dim)
       scores, indices = self.ret_index.search(embs, k, normalize=True, penalty=1000.0,
                                               exclude=None if exclude is None else exclude[lo:hi])
@@ -928,10 +946,14 @@ class GILL(nn.Module):
   @torch.no_grad()
   def generate_images(self, prompts, num_inference_steps: int = 50, guidance_scale: float = 7.5,
                       latents: Optional[Tensor] = None, seed: int = 1337, return_latents: bool = True,
-                      return_embeddings: bool = False, distributed: bool = True, decode: bool = False, scheduler=None):
-    """Batched text -> image latents.  scheduler: the sampler of this call (GillSDPipeline.__call__), None = the pipeline's own; a stochastic
+                      return_embeddings: bool = False, distributed: bool = True, decode: bool = False, scheduler=None,
+                      always_add_bos: bool = False):
+    """Batched prompts -> image latents.  scheduler: the sampler of this call (GillSDPipeline.__call__), None = the pipeline's own; a stochastic
     one draws its step noise from a CPU generator seeded with `seed` and the chunk's first prompt index.  `prompts` is a list of strings (tokenized here) or an int64 tensor
-    (B,T) of prompt token ids WITHOUT the [IMG] tokens (right-padded with pad_token_id).  Per prompt this equals the
+    (B,T) of prompt token ids WITHOUT the [IMG] tokens (right-padded with pad_token_id).  A prompt may also be a list or tuple mixing strings and
+    images (PIL, (H,W,3) uint8 arrays or tensors), as generate_for_images_and_texts takes it (models.py:600-631): each image becomes the
+    n_visual_tokens rows of get_visual_embs(mode='captioning'), computed for this rank's shard only — preprocessing (ops.clip_preprocess), CLIP
+    tower and visual_embeddings all on the device — and <bos> goes on the first string only unless always_add_bos.  Per prompt this equals the
     'gen' branch of generate_for_images_and_texts([p], num_words=2, gen_scale_factor=1e5): the 8 [IMG] ids are
     appended, one OPT pass yields their hidden states (models.py:384), the GILLMapper maps them to the (77,768)
     SD conditioning (models.py:387/710) and the SD-1.5 UNet runs the CFG/PLMS loop (custom_sd.py:607-651).
@@ -943,10 +965,10 @@ class GILL(nn.Module):
     dev = self.model.logit_scale.device
     if (isinstance(prompts, torch.Tensor) and prompts.numel() == 0) or (not isinstance(prompts, torch.Tensor) and len(prompts) == 0):
       raise ValueError('generate_images: empty prompt batch')
-    ids, lens = self._prompt_ids(prompts)
+    ids, lens, images = self._interleaved_ids(prompts, always_add_bos)
     B_total = ids.shape[0]
     lo, hi = parallel.shard_range(B_total, distributed)
-    ids, lens = ids[lo:hi], lens[lo:hi]
+    ids, lens, extra = self._shard_prompts(ids, lens, images, lo, hi)
     B = ids.shape[0]
     img = torch.tensor(self.model.gen_token_idx, dtype=torch.int64)
     k = self.model.num_tokens
@@ -966,7 +988,7 @@ class GILL(nn.Module):
       local = torch.zeros((0, self.sd_pipe.cfg.out_channels, self.sd_pipe.cfg.sample_size, self.sd_pipe.cfg.sample_size),
                           device=dev, dtype=torch.float32)
     if B > 0:
-      raw, emb = self.model.img_hidden_states(full.to(dev), last_idx)
+      raw, emb = self.model.img_hidden_states(full.to(dev), last_idx, **extra)
       embs = self.model.gen_text_hidden_fcs[0](raw, emb)          # (B,77,768)
       if self.load_sd:
         lat0 = None
@@ -1018,6 +1040,79 @@ class GILL(nn.Module):
     for i, r in enumerate(rows):
       ids[i, :len(r)] = r
     return ids, lens
+
+  # ---- interleaved image + text prompts of the batched entries ------------------------------------------
+  @staticmethod
+  def _is_image(p) -> bool:
+    if type(p).__module__.startswith('PIL'):
+      return True
+    return isinstance(p, (np.ndarray, torch.Tensor)) and p.dtype in (np.uint8, torch.uint8) and p.ndim == 3
+
+  def _interleaved_ids(self, prompts, always_add_bos: bool = False):
+    """_prompt_ids for prompts that may hold images: (ids, lens, images).  A list / tuple prompt is segmented as generate_for_images_and_texts
+    does it (models.py:600-631): strings are tokenised, <bos> on the first one only (always_add_bos: on every one), and image number j of the
+    batch takes n_visual_tokens slots with the ids -(j * n_visual_tokens + t + 1): rows of the table img_hidden_states takes as extra_rows.
+    images: per prompt the list of its images, None when no prompt is a list (then ids and lens are _prompt_ids' own)."""
+    if isinstance(prompts, torch.Tensor) or not any(isinstance(p, (list, tuple)) for p in prompts):
+      ids, lens = self._prompt_ids(prompts)
+      return ids, lens, None
+    tok = self.model.tokenizer
+    nv = self.model.args.n_visual_tokens
+    rows, images, n_img = [], [], 0
+    for p in prompts:
+      if not isinstance(p, (str, list, tuple)):
+        raise ValueError(f'A prompt should be a str or a list of PIL.Image.Image and str, got {type(p)} instead.')
+      add_bos = True
+      parts, imgs = [], []
+      for seg in ([p] if isinstance(p, str) else p):
+        if type(seg) == str:
+          parts.append(tok(seg, add_special_tokens=add_bos, return_tensors="pt").input_ids[0].to(torch.int64))
+          if not always_add_bos:
+            add_bos = False
+        elif self._is_image(seg):
+          parts.append(-(n_img * nv + torch.arange(nv, dtype=torch.int64) + 1))
+          imgs.append(seg)
+          n_img += 1
+        else:
+          raise ValueError(f'Input prompts should be either PIL.Image.Image or str types, got {type(seg)} instead.')
+      if not parts:
+        raise ValueError('Input prompts should be either PIL.Image.Image or str types, got an empty prompt instead.')
+      rows.append(torch.cat(parts))
+      images.append(imgs)
+    if n_img:
+      self.model._require_vision()
+    lens = torch.tensor([len(r) for r in rows], dtype=torch.int64)
+    pad = tok.pad_token_id
+    ids = torch.full((len(rows), int(lens.max())), pad if pad is not None else 1, dtype=torch.int64)
+    for i, r in enumerate(rows):
+      ids[i, :len(r)] = r
+    return ids, lens, images
+
+  clip_chunk = 16     # images per CLIP forward of _visual_rows when the tower's handle has to grow
+
+  def _visual_rows(self, images) -> Tensor:
+    """The images of a shard -> (len(images) * n_visual_tokens, D) bf16: ops.clip_preprocess, then get_visual_embs(mode='captioning') in chunks
+    of the CLIP handle's capacity, cast as generate_for_images_and_texts casts them on their way into the LM."""
+    from . import ops
+    m = self.model
+    dev = m.logit_scale.device
+    px = ops.clip_preprocess(images, m.feature_extractor.size, dev)
+    chunk = max(m._clip_cap if m._clip_handle is not None else 0, min(len(images), self.clip_chunk))
+    rows = [m.get_visual_embs(px[i:i + chunk], mode='captioning').to(torch.bfloat16) for i in range(0, len(images), chunk)]
+    return torch.cat(rows, dim=0).reshape(-1, m.opt_cfg.hidden_size)
+
+  def _shard_prompts(self, ids: Tensor, lens: Tensor, images, lo: int, hi: int):
+    """The rows lo .. hi - 1 of _interleaved_ids' result for this rank: (ids, lens, keyword arguments of img_hidden_states).  Only the shard's own
+    images are preprocessed and embedded; its negative ids are renumbered from the shard's first image."""
+    ids, lens = ids[lo:hi], lens[lo:hi]
+    if images is None:
+      return ids, lens, {}
+    mine = [im for row in images[lo:hi] for im in row]
+    if not mine:
+      return ids, lens, {}
+    first = sum(len(row) for row in images[:lo]) * self.model.args.n_visual_tokens
+    ids = torch.where(ids < 0, ids + first, ids)
+    return ids, lens, {'extra_rows': self._visual_rows(mine)}
 
 
 def load_gill(model_dir: str, load_ret_embs: bool = True, decision_model_fn: str = 'decision_model.pth.tar', ret_index: bool = False) -> GILL:

@@ -720,3 +720,69 @@ def skinny_gemm(x: torch.Tensor, w: torch.Tensor):
   buf, out = _guarded((M, Nn), torch.float32, x.device)
   N.check(N.lib().gill_op_skinny_gemm(N.ptr(x), N.ptr(w), N.ptr(buf), M, Nn, K, N.current_stream()))
   return out, _guard_ok(buf)
+
+
+def _as_hwc_u8(img):
+  """One image of clip_preprocess -> an (H,W,3) uint8 numpy array (host) or torch tensor (host or device)."""
+  import numpy as np
+  if type(img).__module__.startswith('PIL'):
+    return np.asarray(img.convert('RGB'), dtype=np.uint8)
+  if isinstance(img, (np.ndarray, torch.Tensor)):
+    if img.dtype not in (np.uint8, torch.uint8) or img.ndim != 3 or img.shape[2] != 3:
+      raise ValueError(f'clip_preprocess takes (H,W,3) uint8 images, got {tuple(img.shape)} {img.dtype}')
+    return img
+  raise ValueError(f'clip_preprocess takes PIL images, uint8 arrays or uint8 tensors, got {type(img)}')
+
+
+def clip_preprocess(images, size: int, device, return_u8: bool = False):
+  """The CLIP image preprocessing of utils.ClipImageProcessor(size, size) on the device (gill_clip_preprocess): Pillow's BICUBIC resize of the
+  shortest edge to `size`, centre crop, x / 255, (x - mean) / std.  images: a list of PIL images (convert('RGB')), (H,W,3) uint8 arrays or uint8
+  tensors on the host or the device, of any sizes, or one (B,H,W,3) uint8 tensor — on the device (decode_latents' output) it goes through without
+  touching the host.  Host images are packed into one buffer and uploaded in one copy.  Returns (n,3,size,size) fp32 and, with return_u8, the
+  cropped (n,size,size,3) uint8 pixels before normalisation, equal to Pillow's."""
+  import numpy as np
+  device = torch.device(device)
+  if isinstance(images, torch.Tensor) and images.dim() == 4:
+    if images.dtype != torch.uint8 or images.shape[3] != 3:
+      raise ValueError(f'clip_preprocess takes (B,H,W,3) uint8 tensors, got {tuple(images.shape)} {images.dtype}')
+    n, H, W = int(images.shape[0]), int(images.shape[1]), int(images.shape[2])
+    shapes = [(H, W)] * n
+    offs = {i: i * H * W * 3 for i in range(n)}
+    packed = images.to(device).contiguous().reshape(-1)
+  else:
+    items = [_as_hwc_u8(im) for im in images]
+    shapes = [(int(a.shape[0]), int(a.shape[1])) for a in items]
+    on_dev = [isinstance(a, torch.Tensor) and a.is_cuda for a in items]
+    # host images first, in one staging buffer and one upload; images already on the device are copied there behind them
+    order = [i for i, d in enumerate(on_dev) if not d] + [i for i, d in enumerate(on_dev) if d]
+    offs, total = {}, 0
+    for i in order:
+      offs[i] = total
+      total += shapes[i][0] * shapes[i][1] * 3
+    host_bytes = sum(shapes[i][0] * shapes[i][1] * 3 for i, d in enumerate(on_dev) if not d)
+    packed = torch.empty(max(total, 1), device=device, dtype=torch.uint8)
+    if host_bytes:
+      stage = np.empty(host_bytes, dtype=np.uint8)
+      for i in order:
+        if not on_dev[i]:
+          a = items[i].numpy() if isinstance(items[i], torch.Tensor) else items[i]
+          stage[offs[i]:offs[i] + a.size] = a.reshape(-1)
+      packed[:host_bytes].copy_(torch.from_numpy(stage))
+    for i in order:
+      if on_dev[i]:
+        packed[offs[i]:offs[i] + items[i].numel()].copy_(items[i].reshape(-1))
+    n = len(items)
+  if n == 0:
+    raise ValueError('clip_preprocess: no images')
+  meta = (ctypes.c_int64 * (3 * n))()
+  for i in range(n):
+    meta[3 * i], meta[3 * i + 1], meta[3 * i + 2] = offs[i], shapes[i][0], shapes[i][1]
+  need = ctypes.c_int64(0)
+  N.check(N.lib().gill_clip_preprocess_workspace(meta, n, int(size), ctypes.byref(need)))
+  ws = torch.empty(need.value, device=device, dtype=torch.uint8)
+  out = torch.empty((n, 3, size, size), device=device, dtype=torch.float32)
+  u8 = torch.empty((n, size, size, 3), device=device, dtype=torch.uint8) if return_u8 else None
+  with torch.cuda.device(device):
+    N.check(N.lib().gill_clip_preprocess(N.ptr(packed), packed.numel(), meta, n, int(size), int(size), N.ptr(out), N.ptr(u8), N.ptr(ws), need.value,
+                                         N.current_stream()))
+  return (out, u8) if return_u8 else out

@@ -81,6 +81,14 @@ int gill_opt_forward_cached(gill_opt* h, const void* inputs_embeds_bf16, int B, 
 int gill_opt_img_hidden(gill_opt* h, const int64_t* ids, const int32_t* last_idx_host, int B, int T, int num_tokens,
                         void* raw_out_bf16, void* emb_out_bf16, void* stream);
 
+/* gill_opt_img_hidden for interleaved image + text prompts (gill/models.py:606-613, 625: the visual embeddings of an image take
+ * the place of token embeddings in inputs_embeds).  extra_rows (n_extra, D) bf16 holds those rows; an id < 0 selects row
+ * -(id + 1) of it instead of an embed_tokens row, both for the emb_out gather and for the position-added fp32 stream.  The ids
+ * live on the device, so the range is the caller's to check: an id below -n_extra reads row n_extra - 1 (clamped, like ids past
+ * the vocabulary).  n_extra == 0 (extra_rows may be NULL) is gill_opt_img_hidden itself, bit for bit. */
+int gill_opt_img_hidden_ex(gill_opt* h, const int64_t* ids, const int32_t* last_idx_host, int B, int T, int num_tokens,
+                           const void* extra_rows_bf16, int n_extra, void* raw_out_bf16, void* emb_out_bf16, void* stream);
+
 /* logits[:, -1, :] of the tied lm_head for the generate loop (models.py:470):
  *   hidden (B,T,D) fp32 from gill_opt_forward -> logits_out (B, vocab) fp32.  Any B >= 1: the rows go through the GEMV
  *   8 at a time, each row's arithmetic independent of the others (a row's logits do not depend on B). */
@@ -149,6 +157,27 @@ void gill_clip_destroy(gill_clip* h);
 
 /* pixel_values (B,3,S,S) fp32 (already resized / normalised)  ->  pooler_output (B, hidden) fp32. */
 int gill_clip_forward(gill_clip* h, const float* pixel_values, int B, float* pooled_out, void* stream);
+
+/* The image preprocessing in front of the tower (gill/utils.py:111-119: the CLIP feature extractor, called at gill/models.py:606-613):
+ * bicubic resize of the shortest edge to `size` (the long edge becomes int(size * long / short)), centre crop to crop_size, x / 255,
+ * (x - mean) / std with the CLIP constants.  The resize is Pillow's 8-bit BICUBIC resampler, integer for integer: 22-bit fixed-point
+ * taps, the horizontal pass rounded and clipped to uint8 before the vertical one.
+ *   packed     device, packed_bytes of uint8: n RGB images, HWC, of any sizes, anywhere in the buffer
+ *   meta_host  HOST, n x 3 int64: byte offset, H, W of each image (edges 1 .. 32768)
+ *   out        (n, 3, size, size) fp32;  out_u8 (n, size, size, 3) uint8 or NULL: the cropped pixels before normalisation
+ *   workspace  device, 8-byte aligned, at least gill_clip_preprocess_workspace() bytes: tap tables and the uint8 intermediate
+ * Only size == crop_size is built.  Two launches on `stream`; the tables are uploaded from a call-lifetime host buffer, so the call
+ * waits for that copy (and for the work queued on the stream before it).  Nothing is allocated on the device. */
+int gill_clip_preprocess_workspace(const int64_t* meta_host, int n, int size, int64_t* bytes_out);
+int gill_clip_preprocess(const uint8_t* packed, int64_t packed_bytes, const int64_t* meta_host, int n, int size, int crop_size,
+                         float* out, uint8_t* out_u8, void* workspace, int64_t workspace_bytes, void* stream);
+
+/* HOST only: the tap tables of that resampler for the outputs first .. first + count - 1 of one axis resized in_size -> out_size:
+ * xmin_out[i] the first input index, n_out[i] the tap count, k_out[i * k_stride + x] the fixed-point coefficients (zero past n_out[i]).
+ * k_stride >= gill_clip_resize_ksize(in_size, out_size) = 2 ceil(2 max(in / out, 1)) + 1 (0 for sizes out of range). */
+int gill_clip_resize_ksize(int in_size, int out_size);
+int gill_clip_resize_taps(int in_size, int out_size, int first, int count, int32_t* xmin_out, int32_t* n_out, int32_t* k_out,
+                          int k_stride);
 
 /* ------------------------------------------------------------------------------------------
  * Text prompts — the CLIP text tower of the Stable Diffusion pipeline (transformers CLIPTextModel, `self.text_encoder` of
