@@ -534,3 +534,28 @@ extern "C" int gill_op_skinny_gemm(const void* x_bf16, const void* W_bf16, float
   GILL_CHECK_HIP(hipStreamSynchronize(s));
   return 0;
 }
+
+// The fused LM-head loss on its own (lmloss.hip).  One grow-only workspace, like the split-K one above.
+extern "C" int gill_op_lm_head_loss(const void* X_bf16, const void* W_bf16, const int64_t* target, int M, int V, int D, float* lse, float* tgt,
+                                    int32_t* rank, float* summary, void* stream) {
+  hipStream_t s = (hipStream_t)stream;
+  GILL_REQUIRE(M >= 1 && V >= 1, "lm_head_loss: M, V >= 1");
+  static void* ws = nullptr;
+  static size_t cap = 0;
+  const size_t need = lm_loss_workspace_bytes(M, V);
+  if (need > cap) {
+    if (ws) { GILL_CHECK_HIP(hipDeviceSynchronize()); (void)hipFree(ws); }
+    ws = nullptr; cap = 0;
+    GILL_CHECK_HIP(hipMalloc(&ws, need + (need >> 2)));
+    cap = need + (need >> 2);
+  }
+  for (int r = 0; r < op_repeat(); ++r)
+    GILL_TRY(lm_loss_launch((const bf16_t*)X_bf16, (const bf16_t*)W_bf16, target, M, V, D, lse, tgt, (int*)rank, summary, ws, s));
+  return 0;
+}
+
+extern "C" int gill_lm_loss_geometry(int M, int V, int D, int* row_tile, int* col_tile, int* n_slabs, int* cols_per_slab) {
+  GILL_REQUIRE(M >= 1 && V >= 1 && D >= 32 && D % 32 == 0, "lm_loss_geometry: M, V >= 1 and D a positive multiple of 32");
+  lm_loss_geometry(M, V, D, row_tile, col_tile, n_slabs, cols_per_slab);
+  return 0;
+}

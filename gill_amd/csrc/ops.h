@@ -273,6 +273,15 @@ int conv_out_launch(const bf16_t* x, const bf16_t* w /*[Cout][9][Cin]*/, const f
                     int Cout, float* y, hipStream_t s, int force_general = 0, int* path = nullptr);
 // skinny GEMV-ish: out[M][N] (f32) = x[M][K] (bf16) . W[N][K]^T ; M <= 8, any N (lm_head)
 int skinny_gemm_launch(const bf16_t* x, const bf16_t* W, int M, int N, int K, float* out, hipStream_t s);
+// ---- LM-head loss without a logits tensor (lmloss.hip; HF CrossEntropyLoss over lm_head(hidden_states[-1]) + utils.accuracy's topk) ----
+// Per row of X (M, D) bf16 against W (V, D) bf16 row-major and target (M) int64 (-100: ignored; other values clamped into [0, V)):
+// lse = log sum_c exp(logit[c]), tgt = logit[target], rank = #{c != target: logit[c] > tgt or (logit[c] == tgt and c < target)}; an ignored row
+// gets rank -1 and lse = tgt = 0.  summary (nullable) [4] = {mean of lse - tgt over valid rows (NaN when none), n_valid, #rank < 1, #rank < 5}.
+// workspace: lm_loss_workspace_bytes(M, V) bytes of device memory (partials; nothing to zero).  D % 32 == 0.  No (M, V) buffer anywhere.
+void lm_loss_geometry(int M, int V, int D, int* row_tile, int* col_tile, int* n_slabs, int* cols_per_slab);   // host only; any output may be null
+size_t lm_loss_workspace_bytes(int M, int V);
+int lm_loss_launch(const bf16_t* X, const bf16_t* W, const int64_t* target, int M, int V, int D, float* lse, float* tgt, int* rank, float* summary,
+                   void* workspace, hipStream_t s);
 // ---- decode decision of the generate loop (decode.hip; models.py:471-520) ----
 constexpr int kDecodeMaxIds = 16;
 struct DecodeRuleDev {          // gill_decode_rule resolved on the host: ids in [0, vocab), conditions evaluated

@@ -26,6 +26,14 @@ struct gill_opt {
   int32_t* idx_dev = nullptr; // [B*8 + B*8]
   // KV cache of gill_opt_forward_cached (allocated at its first call): per layer K [B][H][Tcap][dp], Vt [B][H][dpv][Tcap]
   std::vector<TfmKv> cache;
+  // scoring workspace of gill_opt_forward_loss (allocated at its first call): the final LayerNorm of every row, the shifted targets, the
+  // per-row results and the partials of lmloss.hip
+  bf16_t* xn_bf = nullptr;      // [B*T][D]
+  int64_t* loss_tgt = nullptr;  // [B*T]
+  float *loss_lse = nullptr, *loss_tl = nullptr;   // [B*T]
+  int* loss_rank = nullptr;     // [B*T]
+  void* loss_ws = nullptr;
+  float* ll_f32 = nullptr;      // [B][D]: the rows of last_logit_out after the final LayerNorm
   // layers over the fp32 stream h (B*T rows): ReLU, causal.  past < 0: plain forward over T tokens.  past >= 0: the T rows are
   // the tokens past .. past+T-1 of each sequence; their K/V are appended to the cache and they attend to it.
   int run_layers(int B, int T, hipStream_t s, int past = -1) const {
@@ -232,6 +240,94 @@ extern "C" int gill_opt_last_logits(gill_opt* m, const float* hidden, int B, int
       GILL_TRY(cast_f32_to_bf16_launch(hidden + ((size_t)(b0 + b) * T + (T - 1)) * D, m->last_bf + (size_t)b * D, D, s));
     GILL_TRY(skinny_gemm_launch(m->last_bf, m->lm_head, nb, V, D, logits_out + (size_t)b0 * V, s));
   }
+  return 0;
+}
+
+// target[b][t] = labels[b][t + 1] for t < T - 1, -100 for the last position (HF shifts the labels; no labels: nothing is scored)
+__global__ __launch_bounds__(256) void opt_shift_labels_kernel(const int64_t* __restrict__ labels, int n, int T, int64_t* __restrict__ target) {
+  const int i = blockIdx.x * 256 + threadIdx.x;
+  if (i >= n) return;
+  target[i] = (labels && (i % T) < T - 1) ? labels[i + 1] : (int64_t)-100;
+}
+
+// (B, T) per-row results -> (B, T - 1) token_loss = lse - tgt (0 where ignored) and token_rank
+__global__ __launch_bounds__(256) void opt_token_loss_kernel(const float* __restrict__ lse, const float* __restrict__ tgt, const int* __restrict__ rank,
+                                                             int B, int T, float* __restrict__ token_loss, int32_t* __restrict__ token_rank) {
+  const int i = blockIdx.x * 256 + threadIdx.x;
+  if (i >= B * (T - 1)) return;
+  const int b = i / (T - 1), t = i - b * (T - 1);
+  const int r = b * T + t;
+  token_loss[i] = lse[r] - tgt[r];
+  token_rank[i] = rank[r];
+}
+
+extern "C" int gill_opt_forward_loss(gill_opt* m, const int64_t* ids, const int32_t* last_idx_host, int B, int T, int num_tokens,
+                                     const void* extra_rows_bf16, int n_extra, const int64_t* labels, void* raw_out_bf16, void* emb_out_bf16,
+                                     float* token_loss, int32_t* token_rank, float* summary, float* last_logit_out, float* hidden_out,
+                                     void* stream) {
+  GILL_REQUIRE(m && ids && token_loss && token_rank && summary, "null argument");
+  GILL_REQUIRE(B >= 1 && B <= m->cfg.max_batch && T >= 2 && T <= m->cfg.max_seq, "B/T exceed the handle's workspace (T >= 2)");
+  GILL_REQUIRE(n_extra >= 0 && (n_extra == 0 || extra_rows_bf16), "n_extra rows need a table");
+  const bool rows = raw_out_bf16 || emb_out_bf16;
+  GILL_REQUIRE(last_idx_host || !(rows || last_logit_out), "raw_out / emb_out / last_logit_out need last_idx");
+  GILL_REQUIRE(!rows || (num_tokens >= 1 && num_tokens <= 64), "num_tokens out of range");
+  hipStream_t s = (hipStream_t)stream;
+  const int D = m->cfg.hidden_size, V = m->cfg.vocab_size;
+  const bf16_t* extra = (const bf16_t*)extra_rows_bf16;
+  const int ll_base = m->cfg.max_batch * 64;      // idx_dev: [0, B * num_tokens) the gathered rows, [ll_base, ll_base + B) the last-logit rows
+  if (last_idx_host && (rows || last_logit_out)) {
+    std::vector<int32_t> idx((size_t)ll_base + B, 0);
+    for (int b = 0; b < B; ++b) {
+      if (rows) {
+        GILL_REQUIRE(last_idx_host[b] - num_tokens + 1 >= 0 && last_idx_host[b] < T, "last_idx out of range");
+        for (int j = 0; j < num_tokens; ++j) idx[(size_t)b * num_tokens + j] = b * T + last_idx_host[b] - num_tokens + 1 + j;
+      }
+      if (last_logit_out) {
+        GILL_REQUIRE(last_idx_host[b] - 1 >= 0 && last_idx_host[b] - 1 < T, "last_idx - 1 out of range");
+        idx[(size_t)ll_base + b] = b * T + last_idx_host[b] - 1;
+      }
+    }
+    GILL_CHECK_HIP(hipMemcpyAsync(m->idx_dev, idx.data(), sizeof(int32_t) * idx.size(), hipMemcpyHostToDevice, s));
+    GILL_CHECK_HIP(hipStreamSynchronize(s));  // idx is a stack-lifetime host buffer
+  }
+  if (!m->xn_bf) {
+    const size_t R = (size_t)m->cfg.max_batch * m->cfg.max_seq;
+    GILL_TRY(m->pool.alloc(&m->xn_bf, R * D));
+    GILL_TRY(m->pool.alloc(&m->loss_tgt, R));
+    GILL_TRY(m->pool.alloc(&m->loss_lse, R));
+    GILL_TRY(m->pool.alloc(&m->loss_tl, R));
+    GILL_TRY(m->pool.alloc(&m->loss_rank, R));
+    GILL_TRY(m->pool.alloc(&m->ll_f32, (size_t)m->cfg.max_batch * D));
+    unsigned char* ws = nullptr;
+    GILL_TRY(m->pool.alloc(&ws, lm_loss_workspace_bytes((int)R, V), false));
+    m->loss_ws = ws;
+  }
+  // the pass of gill_opt_img_hidden_ex, launch for launch
+  GILL_TRY(img_hidden_embed(m, ids, extra, n_extra, nullptr, B, T, s));
+  GILL_TRY(cast_f32_to_bf16_launch(m->h, m->emb_tmp, (int64_t)B * T * D, s));
+  if (emb_out_bf16) GILL_TRY(gather_rows_launch(m->emb_tmp, 0, m->idx_dev, B * num_tokens, D, emb_out_bf16, 0, s));
+  GILL_TRY(img_hidden_embed(m, ids, extra, n_extra, m->pos, B, T, s));
+  GILL_TRY(m->run_layers(B, T, s));
+  if (raw_out_bf16) {
+    GILL_TRY(gather_rows_launch(m->h, 1, m->idx_dev, B * num_tokens, D, m->gath, 1, s));
+    GILL_TRY(layernorm_launch(m->gath, 1, m->lnfg, m->lnfb, (bf16_t*)raw_out_bf16, B * num_tokens, D, 1e-5f, s));
+  }
+  // here the final LayerNorm runs on every row
+  GILL_TRY(layernorm_launch(m->h, 1, m->lnfg, m->lnfb, m->xn_bf, B * T, D, 1e-5f, s));
+  if (hidden_out) GILL_TRY(layernorm_f32out_launch(m->h, 1, m->lnfg, m->lnfb, hidden_out, B * T, D, 1e-5f, s));
+  if (last_logit_out) {
+    // gill_opt_last_logits on the rows last_idx - 1: fp32 LayerNorm rows -> bf16 -> the GEMV, 8 rows at a time
+    GILL_TRY(gather_rows_launch(m->h, 1, m->idx_dev + ll_base, B, D, m->gath, 1, s));
+    GILL_TRY(layernorm_f32out_launch(m->gath, 1, m->lnfg, m->lnfb, m->ll_f32, B, D, 1e-5f, s));
+    GILL_TRY(gill_opt_last_logits(m, m->ll_f32, B, 1, last_logit_out, stream));
+  }
+  const int n = B * T;
+  hipLaunchKernelGGL(opt_shift_labels_kernel, dim3(cdiv(n, 256)), dim3(256), 0, s, labels, n, T, m->loss_tgt);
+  GILL_CHECK_HIP(hipGetLastError());
+  GILL_TRY(lm_loss_launch(m->xn_bf, m->lm_head, m->loss_tgt, n, V, D, m->loss_lse, m->loss_tl, m->loss_rank, summary, m->loss_ws, s));
+  hipLaunchKernelGGL(opt_token_loss_kernel, dim3(cdiv(B * (T - 1), 256)), dim3(256), 0, s, m->loss_lse, m->loss_tl, m->loss_rank, B, T, token_loss,
+                     token_rank);
+  GILL_CHECK_HIP(hipGetLastError());
   return 0;
 }
 

@@ -109,7 +109,8 @@ class TextFcLayer(nn.Module):
       # ret_text_fc_mode: one Linear over every token (layers.py:44-49), then the first num_output_tokens tokens
       from . import ops
       Bn, T, D = x.shape
-      y = ops.gemm(x.reshape(Bn * T, D), self.model.weight, bias=self.model.bias, out_f32=True).reshape(Bn, T, self.out_dim)
+      y = ops.gemm(x.reshape(Bn * T, D).to(torch.bfloat16), self.model.weight.to(torch.bfloat16), bias=self.model.bias,
+                   out_f32=True).reshape(Bn, T, self.out_dim)
       if y.shape[1] != self.num_output_tokens:
         y = y[:, :self.num_output_tokens, :]
       outputs = y.to(x.dtype) if x.dtype != torch.float32 else y

@@ -4,7 +4,7 @@ image-generation hot path, with every FLOP in libgill_amd (hand-written HIP for 
 Reference map (file:line in /root/reference/gill/models.py):
   GILLArgs                                   :21-36
   GILLModel.__init__ / get_visual_embs       :40-126 / :129-152
-  GILLModel.forward(mode='generation')       :164-441  (relevant: :173-193, :276-299, :357-365, :374-387, :416-419)
+  GILLModel.forward (three modes)            :164-441  (label loops :202-227 / :277-298, :358-362; rows :374-387, :416-435)
   GILLModel.generate                         :443-532
   GILL.__init__ / __call__                   :536-561 / :563-580
   GILL.generate_for_images_and_texts         :582-762  ('gen' branch: :600-662, :706-731, :754-762)
@@ -14,8 +14,9 @@ per-prompt semantics are the 'gen' branch of generate_for_images_and_texts([p], 
 
 Also built: image prompts through the native CLIP vision tower (get_visual_embs), KV-cached decoding in
 generate(), the retrieval / decision / CLIP-rerank branches of generate_for_images_and_texts, load_gill with the cc3m*.npy
-retrieval embeddings.  Out of scope (raise NotImplementedError): the captioning / retrieval TRAINING modes of
-GILLModel.forward.
+retrieval embeddings; the captioning / retrieval / generation scoring modes of GILLModel.forward as gill/validate.py:66-120 calls
+them (loss, token accuracy and the retrieval features, through the fused LM-head loss kernel: DESIGN.md section 7).  Out of scope
+(raise NotImplementedError): concat_captions, an augmentation of main.py's training step; gradients.
 """
 from __future__ import annotations
 
@@ -381,35 +382,156 @@ class GILLModel(nn.Module):
                                                N.ptr(raw), N.ptr(emb), N.current_stream()))
     return raw, emb
 
+  def _full_labels(self, labels: Tensor, mode: str, n_front: int) -> Tensor:
+    """full_labels of the reference's label loops, vectorised: n_front columns of -100 (visual rows and / or prefix), then `labels` with
+    everything from the first stop token on set to -100.  The two regimes stop at different tokens and are kept apart:
+      captioning (models.py:202-227): pad, or ANY retrieval / generation token id;
+      retrieval / generation (:277-298, :358-362): pad, or a retrieval / generation token id other than the first of its list."""
+    front = torch.full((labels.shape[0], n_front), -100, dtype=torch.int64, device=labels.device)
+    full = torch.cat([front, labels.to(torch.int64)], dim=1)
+    if mode == 'captioning':
+      stops = [self.tokenizer.pad_token_id] + list(self.retrieval_token_idx) + list(self.gen_token_idx)
+    else:
+      stops = [self.tokenizer.pad_token_id] + list(self.retrieval_token_idx[1:]) + list(self.gen_token_idx[1:])
+    stop = torch.zeros_like(full, dtype=torch.bool)
+    for tok in stops:
+      stop |= (full == tok)
+    return torch.where(stop.cumsum(dim=1) > 0, torch.full_like(full, -100), full)
+
+  def _lm_head_weight(self) -> Tensor:
+    sd = self.lm.state_dict()
+    return sd['lm_head.weight'] if 'lm_head.weight' in sd else sd['model.decoder.embed_tokens.weight']
+
+  def lm_forward_loss(self, ids: Tensor, full_labels: Tensor, last_embedding_idx: Optional[Tensor] = None,
+                      extra_rows: Optional[Tensor] = None, want_rows: bool = False, want_last_logit: bool = False,
+                      want_hidden: bool = False):
+    """One scoring pass of the LM (gill_opt_forward_loss): ids (B,T) with negative ids naming rows of extra_rows (n,D) bf16, full_labels
+    (B,T) with -100 ignored; row (b,t) is scored against full_labels[b,t+1] by the fused LM-head loss kernel: no (B,T,vocab) tensor.
+    Returns a namespace: token_loss / token_rank (B,T-1), summary (4) = [mean loss, n_valid, #top-1, #top-5], and on request raw / emb
+    (B,num_tokens,D) bf16 (the rows img_hidden_states returns), last_logit (B,vocab) fp32 (logits row last_embedding_idx - 1),
+    hidden (B,T,D) fp32."""
+    B, T = ids.shape
+    dev = self.logit_scale.device
+    D, V = self.opt_cfg.hidden_size, self.opt_cfg.vocab_size
+    if T < 2:
+      raise ValueError('scoring needs at least two positions (the labels are shifted by one)')
+    n_extra = 0
+    if extra_rows is not None:
+      extra_rows = extra_rows.to(dev, torch.bfloat16).contiguous()
+      n_extra = extra_rows.shape[0]
+      assert extra_rows.dim() == 2 and extra_rows.shape[1] == D, extra_rows.shape
+    ids = ids.to(dev, torch.int64).contiguous()
+    full_labels = full_labels.to(dev, torch.int64).contiguous()
+    # the library clamps what it cannot check (ids and labels live on the device): refuse here, with one host read
+    lo, hi = int(ids.min()), int(ids.max())
+    if lo < -n_extra or hi >= V:
+      raise ValueError(f'ids span [{lo}, {hi}]: outside the vocabulary of {V} and the {n_extra} extra rows')
+    bad = (full_labels != -100) & ((full_labels < 0) | (full_labels >= V))
+    if bool(bad.any()):
+      raise ValueError(f'label {int(full_labels[bad][0])} is neither -100 nor a token of [0, {V})')
+    h = self._opt_native(B, T)
+    arr = None
+    if want_rows or want_last_logit:
+      arr = (C.c_int32 * B)(*[int(v) for v in last_embedding_idx.reshape(-1).tolist()])
+    out = SimpleNamespace(raw=None, emb=None, last_logit=None, hidden=None)
+    if want_rows:
+      out.raw = torch.empty((B, self.num_tokens, D), device=dev, dtype=torch.bfloat16)
+      out.emb = torch.empty((B, self.num_tokens, D), device=dev, dtype=torch.bfloat16)
+    if want_last_logit:
+      out.last_logit = torch.empty((B, V), device=dev, dtype=torch.float32)
+    if want_hidden:
+      out.hidden = torch.empty((B, T, D), device=dev, dtype=torch.float32)
+    out.token_loss = torch.empty((B, T - 1), device=dev, dtype=torch.float32)
+    out.token_rank = torch.empty((B, T - 1), device=dev, dtype=torch.int32)
+    out.summary = torch.empty((4,), device=dev, dtype=torch.float32)
+    with torch.cuda.device(dev):
+      N.check(N.lib().gill_opt_forward_loss(h, N.ptr(ids), arr, B, T, self.num_tokens, N.ptr(extra_rows) if n_extra else None, n_extra,
+                                            N.ptr(full_labels), N.ptr(out.raw), N.ptr(out.emb), N.ptr(out.token_loss), N.ptr(out.token_rank),
+                                            N.ptr(out.summary), N.ptr(out.last_logit), N.ptr(out.hidden), N.current_stream()))
+    return out
+
   def forward(self, pixel_values: torch.FloatTensor, labels: Optional[torch.LongTensor] = None,
               caption_len: Optional[torch.LongTensor] = None, mode: str = 'captioning', concat_captions: bool = False,
-              input_prefix: Optional[str] = None):
-    if mode != 'generation' or concat_captions or input_prefix is not None:
-      raise NotImplementedError("only mode='generation' without concat_captions/input_prefix is on the inference hot path; "
-                                "captioning / retrieval are training-time modes of the reference")
+              input_prefix: Optional[str] = None, lm_loss: Optional[bool] = None, return_logits: bool = False):
+    """The reference's forward (models.py:164-441) in its three modes.  lm_loss (default: True for captioning / retrieval, False for
+    generation) scores the sequence: output.loss is HF's mean shifted cross-entropy over the valid tokens of the batch, a 0-d fp32 device
+    tensor, with output.token_loss / output.token_rank (B, T-1) and output.n_tokens beside it, all from the fused LM-head loss kernel;
+    output.logits stays None unless return_logits, which materialises (B, T, vocab) fp32 through ops.gemm.  mode='generation' with the
+    defaults runs the hidden-rows-only pass and leaves loss / logits / last_output_logit / input_embs_norm None, as it always has."""
+    if concat_captions:
+      raise NotImplementedError("concat_captions is an augmentation of the reference's training step (main.py); not built")
+    if mode not in ('captioning', 'retrieval', 'generation'):
+      raise ValueError(f"mode should be one of ['captioning', 'retrieval', 'generation'], got {mode} instead.")
+    if lm_loss is None:
+      lm_loss = mode != 'generation'
+    if mode != 'generation' and not lm_loss:
+      raise ValueError(f"mode={mode!r} exists to score the sequence: lm_loss=False is only meaningful for mode='generation'")
+    score = lm_loss or return_logits
     visual_embs = self.get_visual_embs(pixel_values, mode)
-    batch_size = visual_embs.shape[0]
+    batch_size, vis_seq_len = visual_embs.shape[0], visual_embs.shape[1]
     assert labels.shape[0] == batch_size, (visual_embs.shape, labels.shape)
     visual_embs_norm = ((visual_embs ** 2).sum(dim=-1) ** 0.5).mean()
-    last_embedding_idx = caption_len - 1   # models.py:183
+    dev = self.logit_scale.device
+    labels = labels.to(dev)
+    last_embedding_idx = caption_len.to(dev) - 1 if caption_len is not None else None   # models.py:183
 
-    # models.py:277-298, 358-362: label masking (loss bookkeeping only; vectorised, no effect on the embeddings)
-    full_labels = torch.clone(labels)
-    pad = self.tokenizer.pad_token_id
-    stop = torch.zeros_like(full_labels, dtype=torch.bool)
-    stop |= (full_labels == pad)
-    for tok in (self.retrieval_token_idx[1:] + self.gen_token_idx[1:]):
-      stop |= (full_labels == tok)
-    full_labels = torch.where(stop.cumsum(dim=1) > 0, torch.full_like(full_labels, -100), full_labels)
+    # the id matrix of inputs_embeds: [visual rows (captioning) | prefix | labels]; a visual row is the id -(row + 1) of extra_rows
+    front = []
+    extra_rows = None
+    if mode == 'captioning':
+      n_vis = batch_size * vis_seq_len
+      front.append(-(torch.arange(n_vis, device=dev, dtype=torch.int64).reshape(batch_size, vis_seq_len) + 1))
+      extra_rows = visual_embs.reshape(n_vis, -1).to(torch.bfloat16)
+    if input_prefix is not None:
+      prompt_ids = self.tokenizer(input_prefix, add_special_tokens=False, return_tensors="pt").input_ids.to(dev)   # models.py:186
+      front.append(prompt_ids.to(torch.int64).reshape(1, -1).repeat(batch_size, 1))
+    n_front = sum(f.shape[1] for f in front)
+    ids = torch.cat(front + [labels.to(torch.int64)], dim=1) if front else labels
+    if last_embedding_idx is not None:
+      last_embedding_idx = last_embedding_idx + n_front          # models.py:200, :209, :283
+    full_labels = self._full_labels(labels, mode, n_front)
 
-    raw, emb = self.img_hidden_states(labels, last_embedding_idx)      # models.py:363-365, 384-385
     dt = self.logit_scale.dtype
-    llm_hidden_states = [raw.to(dt)]
-    hidden = [fc(raw.to(dt), emb.to(dt)) for fc in self.gen_text_hidden_fcs]   # models.py:387
-    last_embedding = torch.stack(hidden, dim=-1).sum(dim=-1)                   # models.py:418
-    input_embs_norm = None      # diagnostics of the training loop; not produced by the fast path
-    output = SimpleNamespace(loss=None, logits=None, hidden_states=None)       # LM loss/logits are training-time outputs
+    input_embs_norm = None
+    if score:
+      input_embs = self.input_embeddings(labels)                 # models.py:180-181
+      input_embs_norm = ((input_embs ** 2).sum(dim=-1) ** 0.5).mean()
+
+    last_embedding = None
     last_output_logit = None
+    llm_hidden_states = []
+    want_rows = mode in ('retrieval', 'generation')
+    if not score:
+      raw, emb = self.img_hidden_states(ids, last_embedding_idx)      # models.py:363-365, 384-385
+      output = SimpleNamespace(loss=None, logits=None, hidden_states=None)       # LM loss/logits were not asked for
+    else:
+      r = self.lm_forward_loss(ids, full_labels, last_embedding_idx, extra_rows, want_rows=want_rows, want_last_logit=want_rows,
+                               want_hidden=return_logits)
+      raw, emb, last_output_logit = r.raw, r.emb, r.last_logit
+      logits = None
+      if return_logits:
+        from . import ops
+        B, T, D = r.hidden.shape
+        head = self._lm_head_weight().to(dev, torch.bfloat16)
+        V = head.shape[0]
+        if V % 4:      # ops.gemm takes N % 4 == 0 (GILL's 50274 is not): zero rows behind the head, cut off again
+          head = torch.cat([head, head.new_zeros((4 - V % 4, D))], dim=0)
+        logits = ops.gemm(r.hidden.reshape(B * T, D).to(torch.bfloat16), head, out_f32=True).reshape(B, T, -1)[..., :V]
+      output = SimpleNamespace(loss=r.summary[0], logits=logits, hidden_states=None, token_loss=r.token_loss, token_rank=r.token_rank,
+                               n_tokens=r.summary[1], summary=r.summary)
+    if want_rows:
+      text_hidden_fcs = self.ret_text_hidden_fcs if mode == 'retrieval' else self.gen_text_hidden_fcs
+      llm_hidden_states = [raw.to(dt)]
+      hidden = [fc(raw.to(dt), emb.to(dt)) for fc in text_hidden_fcs]            # models.py:387
+      last_embedding = torch.stack(hidden, dim=-1).sum(dim=-1)                   # models.py:418
+      if mode == 'retrieval':                                                    # models.py:425-435
+        assert visual_embs.shape[1] == 1, visual_embs.shape
+        assert last_embedding.shape[1] == 1, last_embedding.shape
+        visual_embs = visual_embs[:, 0, :]
+        visual_embs = visual_embs / visual_embs.norm(dim=1, keepdim=True)
+        last_embedding = last_embedding[:, 0, :]
+        last_embedding = last_embedding / last_embedding.norm(dim=1, keepdim=True)
+        visual_embs = self.logit_scale.exp() * visual_embs
     return output, full_labels, last_embedding, last_output_logit, visual_embs, visual_embs_norm, input_embs_norm, llm_hidden_states
 
   # The decision of the generate loop (:471-520) runs on the device: the [IMG] logit rule, the greedy pick, the [IMG] forcing and

@@ -786,3 +786,33 @@ def clip_preprocess(images, size: int, device, return_u8: bool = False):
     N.check(N.lib().gill_clip_preprocess(N.ptr(packed), packed.numel(), meta, n, int(size), int(size), N.ptr(out), N.ptr(u8), N.ptr(ws), need.value,
                                          N.current_stream()))
   return (out, u8) if return_u8 else out
+
+
+def lm_loss_geometry(M: int, V: int, D: int):
+  """(row_tile, col_tile, n_slabs, cols_per_slab) of lm_head_loss at this shape (host only: gill_lm_loss_geometry)."""
+  out = [ctypes.c_int() for _ in range(4)]
+  N.check(N.lib().gill_lm_loss_geometry(int(M), int(V), int(D), *[ctypes.byref(o) for o in out]))
+  return tuple(o.value for o in out)
+
+
+def lm_head_loss(x: torch.Tensor, w: torch.Tensor, target: torch.Tensor, check: bool = True):
+  """The LM-head loss without a logits tensor (gill_op_lm_head_loss): x (M,D) bf16, w (V,D) bf16, target (M) int64 with -100 = ignore ->
+  (lse (M) fp32, tgt (M) fp32, rank (M) int32, summary (4) fp32 = [mean of lse - tgt over valid rows, n_valid, #rank < 1, #rank < 5]).
+  rank counts the columns in front of the target (larger logit first, lower index on a tie); ignored rows: rank -1, lse = tgt = 0.
+  check: refuse targets outside [0, V) other than -100 here (one host read); the library can only clamp them."""
+  x, w = _bf(x), _bf(w)
+  M, D = x.shape
+  V = w.shape[0]
+  assert w.shape[1] == D and target.shape == (M,)
+  target = target.to(x.device, torch.int64).contiguous()
+  if check and M:
+    bad = (target != -100) & ((target < 0) | (target >= V))
+    if bool(bad.any()):
+      raise ValueError(f'target {int(target[bad][0])} is neither -100 nor a column of [0, {V})')
+  lse = torch.empty((M,), device=x.device, dtype=torch.float32)
+  tgt = torch.empty((M,), device=x.device, dtype=torch.float32)
+  rank = torch.empty((M,), device=x.device, dtype=torch.int32)
+  summary = torch.empty((4,), device=x.device, dtype=torch.float32)
+  N.check(N.lib().gill_op_lm_head_loss(N.ptr(x), N.ptr(w), N.ptr(target), M, V, D, N.ptr(lse), N.ptr(tgt), N.ptr(rank), N.ptr(summary),
+                                       N.current_stream()))
+  return lse, tgt, rank, summary

@@ -1,5 +1,6 @@
 """The helpers of gill/utils.py that the generation path touches: truncate_caption (gill/models.py:658, :759) and the image
-pre-processing of PIL prompts (gill/utils.py:111-119, gill/models.py:606-613)."""
+pre-processing of PIL prompts (gill/utils.py:111-119, gill/models.py:606-613); and the two accuracy helpers of the scoring modes of
+GILLModel.forward (gill/validate.py:89: accuracy on logits; accuracy_from_ranks on the fused loss kernel's token ranks)."""
 from __future__ import annotations
 
 import os
@@ -80,3 +81,28 @@ def get_image_from_url(url: str):
   img = img.resize((224, 224))
   img = img.convert('RGB')
   return img
+
+
+def accuracy(output, target, padding, topk=(1,)):
+  """Top-k token accuracy in percent over the positions whose target is not `padding`: the signature and the result of the reference's
+  gill/utils.py:128 (a list of one-element tensors, one per k).  output (..., C) scores, target (...) class ids.  Used with
+  forward(return_logits=True) and for the retrieval recall of gill/validate.py, where `output` is a similarity matrix."""
+  with torch.no_grad():
+    n_pred = min(max(topk), output.shape[-1])
+    if n_pred < max(topk):
+      print(f"[WARNING] Less than {max(topk)} predictions available. Using {n_pred} for topk.")
+    best = output.topk(n_pred, dim=-1, largest=True, sorted=True).indices
+    valid = target != padding
+    hit = (best == target.unsqueeze(-1)) & valid.unsqueeze(-1)
+    n_valid = valid.sum().to(target.dtype)
+    return [hit[..., :k].reshape(-1).float().sum(0, keepdim=True) * (100.0 / n_valid) for k in topk]
+
+
+def accuracy_from_ranks(token_rank, topk=(1, 5)):
+  """What accuracy(output.logits[:, :-1], full_labels[:, 1:], -100, topk) returns (gill/validate.py:89), from output.token_rank of
+  GILLModel.forward: rank (B, T-1) int32 = the number of vocabulary entries in front of the target (-1 where the label is -100), so the
+  target is among the k best exactly when 0 <= rank < k.  A list of one-element fp32 tensors: percentages over the valid tokens."""
+  with torch.no_grad():
+    valid = token_rank >= 0
+    n_valid = valid.sum()
+    return [((token_rank < k) & valid).reshape(-1).float().sum(0, keepdim=True) * (100.0 / n_valid) for k in topk]

@@ -649,6 +649,42 @@ int gill_op_linear_reduce_ln(const void* A_bf16, const void* W_bf16, const float
 /* The tied lm_head: out (M,N) fp32 = x (M,K) bf16 . W (N,K)^T, 1 <= M <= 8, K a multiple of 8 (an error otherwise). */
 int gill_op_skinny_gemm(const void* x_bf16, const void* W_bf16, float* out_f32, int M, int N, int K, void* stream);
 
+/* ------------------------------------------------------------------------------------------
+ * LM-head loss (csrc/lmloss.hip).  What HF's CrossEntropyLoss over lm_head(hidden_states[-1]) and utils.accuracy's topk
+ * (gill/models.py:273-275, :363-365; gill/validate.py:89) read off a (B, T, vocab) logits tensor, without that tensor: the
+ * rows are multiplied by the head on the matrix cores and only three numbers per row leave the kernel.
+ *
+ * X (M,D) bf16, W (V,D) bf16 row-major (the head as it lies in memory), target (M) int64 on the device: -100 = ignore, any
+ * other value outside [0, V) is clamped (it lives on the device; the caller checks what it can see).  D % 32 == 0.  Per row:
+ *   lse  = log sum_c exp(logit[c])                      (fp32 on the fp32-accumulated logits)
+ *   tgt  = logit[target]
+ *   rank = #{c != target : logit[c] > tgt or (logit[c] == tgt and c < target)}      (0 = top-1; rank < 5 = top-5)
+ * and the row's loss is lse - tgt.  An ignored row gets rank -1 and lse = tgt = 0.  summary (nullable, 4 floats on the device)
+ * = {mean loss over valid rows (NaN when none), n_valid, #rank < 1, #rank < 5}.  Five launches on `stream`, no host wait, no
+ * float atomics, fixed summation orders: two calls give equal bits, and a row's results do not depend on the other rows.
+ * Honours GILL_OP_REPEAT. */
+int gill_op_lm_head_loss(const void* X_bf16, const void* W_bf16, const int64_t* target, int M, int V, int D, float* lse, float* tgt,
+                         int32_t* rank, float* summary, void* stream);
+/* How gill_op_lm_head_loss splits the work (host only, for tests): row tiles of *row_tile valid rows, MFMA column tiles of
+ * *col_tile columns, *n_slabs vocabulary slabs of *cols_per_slab columns (the last one ragged) whose per-row partials a second
+ * launch merges in ascending order.  The slabs cover [0, V) exactly once.  Any output may be NULL. */
+int gill_lm_loss_geometry(int M, int V, int D, int* row_tile, int* col_tile, int* n_slabs, int* cols_per_slab);
+
+/* Scoring pass of the OPT engine: gill_opt_img_hidden_ex (same embedding, same negative ids, same gathered rows; raw_out / emb_out
+ * bit-equal to its outputs, either may be NULL) with the final LayerNorm on EVERY row, and row (b, t) scored against
+ * labels[b][t + 1] by the fused loss above (HF's shifted CrossEntropyLoss).  labels (B,T) int64 on the device, -100 ignored; NULL
+ * scores nothing (summary[0] is then NaN).
+ *   token_loss (B, T-1) fp32, token_rank (B, T-1) int32: lse - tgt and the rank of every predicting position (0 / -1 where ignored)
+ *   summary [4] fp32: {mean loss over the valid tokens of the whole batch, n_valid, #rank < 1, #rank < 5}
+ *   last_logit_out (B, vocab) fp32, nullable: the logits row last_idx[b] - 1 (gill/models.py:419), through the GEMV of
+ *     gill_opt_last_logits: bit-equal to that call fed the row of hidden_out
+ *   hidden_out (B,T,D) fp32, nullable: hidden_states[-1]
+ * last_idx_host may be NULL when raw_out, emb_out and last_logit_out are. */
+int gill_opt_forward_loss(gill_opt* h, const int64_t* ids, const int32_t* last_idx_host, int B, int T, int num_tokens,
+                          const void* extra_rows_bf16, int n_extra, const int64_t* labels, void* raw_out_bf16, void* emb_out_bf16,
+                          float* token_loss, int32_t* token_rank, float* summary, float* last_logit_out, float* hidden_out, void* stream);
+
+
 #ifdef __cplusplus
 }
 #endif
