@@ -326,6 +326,76 @@ extern "C" int gill_op_conv3x3_fp8(const void* x_bf16, const float* w_oihw, cons
   return 0;
 }
 
+// ---- the fp8 path's launchers one by one, on QUANTISED operands in and out (tests/test_fp8_ops_gpu.py): each entry launches exactly the launcher
+// the engine launches and synchronises; nothing is quantised behind the caller's back, so the bytes a test reads back are the bytes the next
+// kernel multiplies.
+extern "C" int gill_conv_fp8_kpad(int Cin) { return Cin > 0 && Cin % 64 == 0 ? conv_fp8_kpad(Cin) : -1; }
+
+extern "C" int gill_op_quant_fp8(const void* x_bf16, float scale, int64_t n, void* y8, void* stream) {
+  hipStream_t s = (hipStream_t)stream;
+  GILL_REQUIRE(x_bf16 && y8 && n > 0, "quant_fp8: null argument");
+  GILL_TRY(quant_bf16_fp8_launch((const bf16_t*)x_bf16, scale, n, (unsigned char*)y8, s));
+  GILL_CHECK_HIP(hipStreamSynchronize(s));
+  return 0;
+}
+
+extern "C" int gill_op_conv_weight_quant_fp8(const void* w_oihw, int dtype, int Cout, int Cin, float act_scale, void* w8, float* colscale,
+                                             void* stream) {
+  hipStream_t s = (hipStream_t)stream;
+  GILL_REQUIRE(w_oihw && w8 && colscale && Cout > 0 && Cin > 0 && act_scale > 0.f, "conv_weight_quant_fp8: bad argument");
+  GILL_TRY(conv_weight_quant_fp8_launch(w_oihw, dtype, Cout, Cin, act_scale, (unsigned char*)w8, colscale, s));
+  GILL_CHECK_HIP(hipStreamSynchronize(s));
+  return 0;
+}
+
+// UNetRun::conv8 on caller bytes: unsplit, bias / row vector / residual / GroupNorm partials (bins of stats_bin channels) in the kernel's own epilogue;
+// split (ws [splitk][M][N] fp32 from the caller), the partials and — unless partials_only — the bf16 path's reducer with the same operands.
+extern "C" int gill_op_conv3x3_fp8_q(const void* x8, const void* w8, const float* colscale, const float* bias, const float* rowvec,
+                                     const void* resid_bf16, void* y_bf16, float* gn_stats, int stats_bin, float* ws, int partials_only, int B, int H,
+                                     int W, int Cin, int Cout, int splitk, void* stream) {
+  hipStream_t s = (hipStream_t)stream;
+  GILL_REQUIRE(x8 && w8 && colscale && B > 0 && H > 0 && W > 0 && Cin > 0 && Cin % 64 == 0 && Cout > 0, "conv3x3_fp8_q: bad argument");
+  GILL_REQUIRE(splitk >= 1 && (splitk > 1) == (ws != nullptr), "conv3x3_fp8_q: the workspace comes with splitk > 1, and only then");
+  GILL_REQUIRE(y_bf16 || (partials_only && splitk > 1), "conv3x3_fp8_q: output missing");
+  GILL_REQUIRE((gn_stats != nullptr) == (stats_bin > 0) && (!gn_stats || (splitk == 1 && Cout % stats_bin == 0)),
+               "conv3x3_fp8_q: statistics need a bin that divides Cout, and an unsplit launch");
+  ConvF8Args a;
+  a.B = B; a.H = H; a.W = W; a.Cin = Cin; a.M = B * H * W; a.N = Cout; a.Kpad = conv_fp8_kpad(Cin);
+  a.A8 = (const unsigned char*)x8; a.W8 = (const unsigned char*)w8; a.colscale = colscale; a.C = (bf16_t*)y_bf16;
+  a.rows_per_batch = H * W;
+  a.splitk = splitk;
+  if (splitk > 1) {
+    a.ws = ws;
+    GemmArgs g;
+    g.M = a.M; g.N = a.N; g.K = 9 * Cin; g.splitk = splitk; g.ws = ws;
+    g.bias = bias; g.rowvec = rowvec; g.rows_per_batch = a.rows_per_batch; g.rowvec_bstride = Cout;
+    g.resid = resid_bf16; g.ldr = Cout; g.C = y_bf16; g.ldc = Cout;
+    for (int r = 0; r < op_repeat(); ++r) {
+      GILL_TRY(conv3x3_fp8_launch(a, s));
+      if (!partials_only) GILL_TRY(gemm_splitk_reduce_launch(g, s));
+    }
+  } else {
+    a.bias = bias; a.rowvec = rowvec; a.rowvec_bstride = Cout; a.resid = (const bf16_t*)resid_bf16;
+    if (gn_stats) { a.gn_stats = gn_stats; a.gn_groups = Cout / stats_bin; a.gn_cg = stats_bin; }
+    for (int r = 0; r < op_repeat(); ++r) GILL_TRY(conv3x3_fp8_launch(a, s));
+  }
+  GILL_CHECK_HIP(hipStreamSynchronize(s));
+  return 0;
+}
+
+// groupnorm_launch(..., out8_scale): y8 [B][HW][C1 + C2] e4m3 = fp8(scale * [silu](GroupNorm(x1 ++ x2)))
+extern "C" int gill_op_groupnorm_fp8(const void* x1, int C1, const void* x2, int C2, int B, int HW, int groups, const float* gamma,
+                                     const float* beta, float eps, int silu, float scale, void* y8, void* stream) {
+  hipStream_t s = (hipStream_t)stream;
+  GILL_REQUIRE(x1 && gamma && beta && y8 && scale > 0.f && B > 0 && HW > 0 && C1 > 0 && C2 >= 0 && groups > 0, "groupnorm_fp8: bad argument");
+  DevBuf stats;
+  GILL_TRY(stats.alloc(sizeof(float) * groupnorm_stats_floats(B, HW, groups)));
+  GILL_TRY(groupnorm_launch((const bf16_t*)x1, C1, (const bf16_t*)x2, C2, B, HW, groups, gamma, beta, eps, silu, (bf16_t*)y8, (float*)stats.p, s,
+                            scale));
+  GILL_CHECK_HIP(hipStreamSynchronize(s));
+  return 0;
+}
+
 // ---- fused GroupNorm statistics on their own (tests/test_gn_stats_gpu.py): the producers' raw partials, and the consumer on caller-made partials.
 // Launches `g` with GemmArgs::gn_stats set the way ConvRun::fuse_stats() sets it (bins of `bin` channels, rows_per_batch = output rows per sample),
 // forced `splitk` ways (<= 1: unsplit), and reports the slab geometry the launcher used.
@@ -395,16 +465,18 @@ extern "C" int gill_op_gemm_gn_stats(const void* A, const void* W, const float* 
 
 extern "C" int gill_op_groupnorm_from_stats(const void* x1, int C1, const void* x2, int C2, int B, int HW, int groups, const float* gamma,
                                             const float* beta, float eps, int silu, const float* stats1, int bin1, int nslab1,
-                                            const float* stats2, int bin2, int nslab2, void* y, float* ss_out, void* stream) {
+                                            const float* stats2, int bin2, int nslab2, void* y, float* ss_out, float out8_scale,
+                                            void* stream) {
   hipStream_t s = (hipStream_t)stream;
   GILL_REQUIRE(x1 && gamma && beta && stats1 && (y || ss_out) && C1 > 0 && C2 >= 0 && bin1 > 0 && C1 % bin1 == 0, "bad argument");
+  GILL_REQUIRE(out8_scale >= 0.f && (out8_scale == 0.f || (y && !ss_out)), "groupnorm_from_stats: the e4m3 output takes y and no table");
   GILL_REQUIRE((C2 == 0) == (stats2 == nullptr) && (C2 == 0 || (x2 && bin2 > 0 && C2 % bin2 == 0)), "groupnorm_from_stats: second source and its statistics come together");
   GILL_REQUIRE(ss_out == nullptr || C2 == 0, "groupnorm_from_stats: the scale | shift table is for single-source inputs");
   DevBuf tot;      // always passed, as ConvRun::gnorm() does
   GILL_TRY(tot.alloc(sizeof(float) * groupnorm_totals_floats(B, C1 / bin1, C2 ? C2 / bin2 : 0)));
   for (int r = 0; r < op_repeat(); ++r)
     GILL_TRY(groupnorm_apply_launch((const bf16_t*)x1, C1, (const bf16_t*)x2, C2, B, HW, groups, gamma, beta, eps, silu, (bf16_t*)y, stats1, bin1, C1,
-                                    nslab1, stats2, C2 ? bin2 : 0, C2 ? nslab2 : 0, s, 0.f, (float*)tot.p, ss_out));
+                                    nslab1, stats2, C2 ? bin2 : 0, C2 ? nslab2 : 0, s, out8_scale, (float*)tot.p, ss_out));
   GILL_CHECK_HIP(hipStreamSynchronize(s));
   return 0;
 }

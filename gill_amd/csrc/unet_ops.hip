@@ -152,6 +152,38 @@ extern "C" int gill_op_geglu_fp8(const void* t, const float* ln_g, const float* 
   return 0;
 }
 
+// The fp8 GEGLU's three launchers one by one on caller operands (tests/test_fp8_ops_gpu.py; the convolution's are in capi.hip): what goes in and
+// comes out is what the engine's kernels read and write, quantised bytes included.  Each synchronises.
+extern "C" int gill_op_linear_weight_quant_fp8(const void* w_bf16, int N, int K, float act_scale, void* w8, float* colscale, void* stream) {
+  hipStream_t s = (hipStream_t)stream;
+  GILL_REQUIRE(w_bf16 && w8 && colscale && N > 0 && K > 0 && act_scale > 0.f, "linear_weight_quant_fp8: bad argument");
+  GILL_TRY(linear_weight_quant_fp8_launch((const bf16_t*)w_bf16, N, K, act_scale, (unsigned char*)w8, colscale, s));
+  GILL_CHECK_HIP(hipStreamSynchronize(s));
+  return 0;
+}
+// stats [planes][R][2] fp32 {sum, sum of squares}, R = ln_rows ? ln_rows : M (GemmArgs::row_stats layout)
+extern "C" int gill_op_ln_quant_fp8(const void* t_bf16, int M, int C, const float* stats, int planes, int ln_rows, float eps, float act_scale,
+                                    void* y8, void* stream) {
+  hipStream_t s = (hipStream_t)stream;
+  GILL_REQUIRE(t_bf16 && stats && y8 && M > 0 && C > 0 && ln_rows >= 0 && ln_rows <= M && (ln_rows == 0 || M <= 2 * ln_rows) && act_scale > 0.f,
+               "ln_quant_fp8: bad argument (rows m >= ln_rows read row m - ln_rows: M <= 2 ln_rows)");
+  GILL_TRY(ln_quant_fp8_launch((const bf16_t*)t_bf16, M, C, stats, planes, ln_rows, eps, act_scale, (unsigned char*)y8, s));
+  GILL_CHECK_HIP(hipStreamSynchronize(s));
+  return 0;
+}
+// x8 [M][K], w8 [N][K] in the PHYSICAL row order ([16 value | 16 gate] per 16 outputs), colscale / bias [N] in that order -> out [M][N / 2] bf16
+extern "C" int gill_op_geglu_fp8_q(const void* x8, const void* w8, const float* colscale, const float* bias, void* out_bf16, int M, int N, int K,
+                                   void* stream) {
+  hipStream_t s = (hipStream_t)stream;
+  GILL_REQUIRE(x8 && w8 && colscale && out_bf16, "geglu_fp8_q: null argument");
+  LinF8Args a;
+  a.M = M; a.N = N; a.K = K; a.A8 = (const unsigned char*)x8; a.W8 = (const unsigned char*)w8; a.colscale = colscale; a.bias = bias;
+  a.C = (bf16_t*)out_bf16;
+  for (int r = 0, rep = op_repeat(); r < rep; ++r) GILL_TRY(geglu_fp8_launch(a, s));
+  GILL_CHECK_HIP(hipStreamSynchronize(s));
+  return 0;
+}
+
 // Operator-level entry for the fused projection pairs around norm1 / norm2 of a level-0 block (lnproj.hip) on NATURAL operands
 // (unpadded heads, plain LayerNorm parameters): the loader's QKV recipe pads / folds / permutes them, then the kernel.
 //   mode 0: t = W1 . x + b1;  [q | k | v] = W2 . LN(t)            x [M][320], W2 [3 * 320][320] = to_q | to_k | to_v rows

@@ -249,10 +249,12 @@ def gemm_gn_stats(a: torch.Tensor, w: torch.Tensor, bin: int, rows_per_batch: in
 
 def groupnorm_from_stats(x1: torch.Tensor, stats1: torch.Tensor, bin1: int, gamma: torch.Tensor, beta: torch.Tensor, groups: int = 32,
                          eps: float = 1e-5, silu: bool = False, x2: Optional[torch.Tensor] = None, stats2: Optional[torch.Tensor] = None,
-                         bin2: int = 0, want_table: bool = False):
+                         bin2: int = 0, want_table: bool = False, out8_scale: float = 0.0):
   """GroupNorm(+SiLU) of x1 (B,HW,C1) [++ x2 (B,HW,C2)] bf16 from caller-supplied partial sums (gill_op_groupnorm_from_stats): stats1
   (B,nslab1,C1 // bin1,2), stats2 (B,nslab2,C2 // bin2,2) fp32.  want_table (single source): the scale | shift table (B,2,C1) instead of y.
-  Returns (y or None, table or None, stats1, stats2): outputs NaN-prefilled, the statistics tensors as they are after the call."""
+  out8_scale > 0: y is uint8 — the e4m3 bytes of fp8(out8_scale * value), as the fp8 convolutions read them — in a guarded buffer.
+  Returns (y or None, table or None, stats1, stats2[, guard_ok when out8_scale > 0]): outputs NaN-prefilled, the statistics tensors as they
+  are after the call."""
   x1 = _bf(x1)
   B, HW, C1 = x1.shape
   C2 = 0
@@ -264,10 +266,16 @@ def groupnorm_from_stats(x1: torch.Tensor, stats1: torch.Tensor, bin1: int, gamm
   g, b = gamma.float().contiguous(), beta.float().contiguous()
   nan = float("nan")
   y = None if want_table else torch.full((B, HW, C1 + C2), nan, device=x1.device, dtype=torch.bfloat16)
+  buf = None
+  if out8_scale > 0:
+    assert not want_table
+    buf, y = _guarded((B, HW, C1 + C2), torch.uint8, x1.device)
   table = torch.full((B, 2, C1 + C2), nan, device=x1.device, dtype=torch.float32) if want_table else None
   N.check(N.lib().gill_op_groupnorm_from_stats(N.ptr(x1), C1, N.ptr(x2), C2, B, HW, groups, N.ptr(g), N.ptr(b), float(eps), int(silu), N.ptr(stats1),
-                                               bin1, stats1.shape[1], N.ptr(stats2), bin2, 0 if stats2 is None else stats2.shape[1], N.ptr(y),
-                                               N.ptr(table), N.current_stream()))
+                                               bin1, stats1.shape[1], N.ptr(stats2), bin2, 0 if stats2 is None else stats2.shape[1],
+                                               N.ptr(y if buf is None else buf), N.ptr(table), float(out8_scale), N.current_stream()))
+  if buf is not None:
+    return y, table, stats1, stats2, _guard_ok(buf)
   return y, table, stats1, stats2
 
 
@@ -620,17 +628,143 @@ GUARD_WORDS = 256
 _GUARD_VALUE = -12352.0      # exact in bf16
 
 
+_GUARD_BYTE = 0xA5           # uint8 (e4m3) buffers: pre-filled with the NaN code 0x7f, guarded by this byte
+
+
 def _guarded(shape, dtype, device):
   n = 1
   for d in shape:
     n *= int(d)
-  buf = torch.full((n + GUARD_WORDS,), float("nan"), device=device, dtype=dtype)
-  buf[n:] = _GUARD_VALUE
+  if dtype == torch.uint8:
+    buf = torch.full((n + GUARD_WORDS,), 0x7F, device=device, dtype=dtype)
+    buf[n:] = _GUARD_BYTE
+  else:
+    buf = torch.full((n + GUARD_WORDS,), float("nan"), device=device, dtype=dtype)
+    buf[n:] = _GUARD_VALUE
   return buf, buf[:n].view(*shape)
 
 
 def _guard_ok(buf: torch.Tensor) -> bool:
-  return bool((buf[-GUARD_WORDS:] == _GUARD_VALUE).all())
+  return bool((buf[-GUARD_WORDS:] == (_GUARD_BYTE if buf.dtype == torch.uint8 else _GUARD_VALUE)).all())
+
+
+# ---- the fp8 mode's launchers on quantised operands (tests/test_fp8_ops_gpu.py).  e4m3 tensors travel as uint8; every output sits in a
+# guarded buffer and each wrapper returns, last, whether the guard still holds.
+def _u8(t: torch.Tensor) -> torch.Tensor:
+  assert t.dtype == torch.uint8 and t.is_cuda
+  return t.contiguous()
+
+
+def conv_fp8_kpad(cin: int) -> int:
+  """Bytes per weight row of the fp8 convolution (gill_conv_fp8_kpad): 9 * cin rounded up to whole 128-byte K steps."""
+  k = N.lib().gill_conv_fp8_kpad(int(cin))
+  assert k > 0, "Cin must be a positive multiple of 64"
+  return k
+
+
+def quant_fp8(x: torch.Tensor, scale: float):
+  """fp8(scale * x) of a bf16 tensor (gill_op_quant_fp8; numel % 8 == 0) -> (uint8 tensor of x's shape, guard_ok)."""
+  x = _bf(x)
+  buf, y = _guarded(tuple(x.shape), torch.uint8, x.device)
+  N.check(N.lib().gill_op_quant_fp8(N.ptr(x), float(scale), x.numel(), N.ptr(buf), N.current_stream()))
+  return y, _guard_ok(buf)
+
+
+def conv_weight_quant_fp8(w_oihw: torch.Tensor, act_scale: float):
+  """The fp8 convolution's weight quantiser (gill_op_conv_weight_quant_fp8): w (Cout,Cin,3,3) fp32 | bf16 | fp16 ->
+  (w8 (Cout,Kpad) uint8, colscale (Cout) fp32, guard_ok)."""
+  assert w_oihw.is_cuda and w_oihw.dtype in N._DTYPES and w_oihw.dim() == 4 and tuple(w_oihw.shape[2:]) == (3, 3)
+  w = w_oihw.contiguous()
+  Cout, Cin = w.shape[:2]
+  wbuf, w8 = _guarded((Cout, conv_fp8_kpad(Cin)), torch.uint8, w.device)
+  sbuf, sc = _guarded((Cout,), torch.float32, w.device)
+  N.check(N.lib().gill_op_conv_weight_quant_fp8(N.ptr(w), N._DTYPES[w.dtype], Cout, Cin, float(act_scale), N.ptr(wbuf), N.ptr(sbuf),
+                                                N.current_stream()))
+  return w8, sc, _guard_ok(wbuf) and _guard_ok(sbuf)
+
+
+def conv3x3_fp8_q(x8: torch.Tensor, w8: torch.Tensor, colscale: torch.Tensor, bias: Optional[torch.Tensor] = None,
+                  rowvec: Optional[torch.Tensor] = None, resid: Optional[torch.Tensor] = None, splitk: int = 1, stats_bin: int = 0,
+                  partials: bool = False):
+  """The fp8 convolution on quantised operands, launched as UNetRun::conv8 launches it (gill_op_conv3x3_fp8_q): x8 (B,H,W,Cin) uint8, w8
+  (Cout,Kpad) uint8 and colscale (Cout) from conv_weight_quant_fp8, bias (Cout), rowvec (B,Cout), resid (B,H,W,Cout) bf16.
+  Returns (y (B,H,W,Cout) bf16, guard_ok); with stats_bin > 0 (y, stats, guard_ok), stats the whole NaN-prefilled buffer of
+  _gn_stats_buffer of which the launch files [B][H W / 64][Cout / stats_bin][2]; with partials=True (splitk > 1) (the fp32 partials
+  (splitk,M,Cout), guard_ok) and no reducer launch."""
+  x8, w8 = _u8(x8), _u8(w8)
+  B, H, W, Cin = x8.shape
+  Cout = w8.shape[0]
+  assert w8.shape[1] == conv_fp8_kpad(Cin) and colscale.dtype == torch.float32 and colscale.numel() == Cout
+  f = lambda t: None if t is None else t.float().contiguous()   # noqa: E731
+  colscale, bias, rowvec = colscale.contiguous(), f(bias), f(rowvec)
+  assert rowvec is None or tuple(rowvec.shape) == (B, Cout)
+  resid = None if resid is None else _bf(resid)
+  assert (not partials or splitk > 1) and (stats_bin == 0 or splitk == 1)
+  M = B * H * W
+  ybuf, y = _guarded((B, H, W, Cout), torch.bfloat16, x8.device)
+  wsbuf = ws = stats = None
+  if splitk > 1:
+    wsbuf, ws = _guarded((splitk, M, Cout), torch.float32, x8.device)
+  if stats_bin > 0:
+    stats = _gn_stats_buffer(B, H * W, Cout // stats_bin, x8.device)
+  N.check(N.lib().gill_op_conv3x3_fp8_q(N.ptr(x8), N.ptr(w8), N.ptr(colscale), N.ptr(bias), N.ptr(rowvec), N.ptr(resid), N.ptr(ybuf), N.ptr(stats),
+                                        int(stats_bin), N.ptr(wsbuf), int(partials), B, H, W, Cin, Cout, int(splitk), N.current_stream()))
+  ok = _guard_ok(ybuf) and (wsbuf is None or _guard_ok(wsbuf))
+  if partials:
+    return ws, ok
+  return (y, stats, ok) if stats_bin > 0 else (y, ok)
+
+
+def groupnorm_fp8(x1: torch.Tensor, gamma: torch.Tensor, beta: torch.Tensor, groups: int, silu: bool, scale: float,
+                  x2: Optional[torch.Tensor] = None, eps: float = 1e-5):
+  """fp8(scale * [silu](GroupNorm(x1 ++ x2))) with the statistics taken from the tensors (gill_op_groupnorm_fp8): x1 (B,HW,C1) bf16 ->
+  (uint8 (B,HW,C1+C2), guard_ok)."""
+  x1 = _bf(x1)
+  B, HW, C1 = x1.shape
+  x2 = None if x2 is None else _bf(x2)
+  C2 = 0 if x2 is None else x2.shape[-1]
+  g, b = gamma.float().contiguous(), beta.float().contiguous()
+  buf, y = _guarded((B, HW, C1 + C2), torch.uint8, x1.device)
+  N.check(N.lib().gill_op_groupnorm_fp8(N.ptr(x1), C1, N.ptr(x2), C2, B, HW, int(groups), N.ptr(g), N.ptr(b), float(eps), int(silu), float(scale),
+                                        N.ptr(buf), N.current_stream()))
+  return y, _guard_ok(buf)
+
+
+def linear_weight_quant_fp8(w: torch.Tensor, act_scale: float):
+  """Per-row e4m3 quantisation of bf16 rows (gill_op_linear_weight_quant_fp8): w (N,K) -> (w8 (N,K) uint8, colscale (N) fp32, guard_ok)."""
+  w = _bf(w)
+  Nn, K = w.shape
+  wbuf, w8 = _guarded((Nn, K), torch.uint8, w.device)
+  sbuf, sc = _guarded((Nn,), torch.float32, w.device)
+  N.check(N.lib().gill_op_linear_weight_quant_fp8(N.ptr(w), Nn, K, float(act_scale), N.ptr(wbuf), N.ptr(sbuf), N.current_stream()))
+  return w8, sc, _guard_ok(wbuf) and _guard_ok(sbuf)
+
+
+def ln_quant_fp8(t: torch.Tensor, stats: torch.Tensor, ln_rows: int, eps: float, act_scale: float):
+  """fp8(act_scale * LayerNorm-without-affine(t)) from row-sum planes (gill_op_ln_quant_fp8): t (M,C) bf16, stats (planes,R,2) fp32 with
+  R = ln_rows or M -> (uint8 (M,C), guard_ok)."""
+  t = _bf(t)
+  M, Cc = t.shape
+  assert stats.is_cuda and stats.dtype == torch.float32 and stats.is_contiguous() and stats.dim() == 3
+  assert tuple(stats.shape[1:]) == (ln_rows if ln_rows else M, 2)
+  buf, y = _guarded((M, Cc), torch.uint8, t.device)
+  N.check(N.lib().gill_op_ln_quant_fp8(N.ptr(t), M, Cc, N.ptr(stats), stats.shape[0], int(ln_rows), float(eps), float(act_scale), N.ptr(buf),
+                                       N.current_stream()))
+  return y, _guard_ok(buf)
+
+
+def geglu_fp8_q(x8: torch.Tensor, w8: torch.Tensor, colscale: torch.Tensor, bias: Optional[torch.Tensor]):
+  """The fp8 GEGLU projection on quantised operands (gill_op_geglu_fp8_q): x8 (M,K), w8 (N,K) uint8 with rows, colscale (N) and bias (N) in
+  the physical [16 value | 16 gate] order -> (out (M,N/2) bf16, guard_ok)."""
+  x8, w8 = _u8(x8), _u8(w8)
+  M, K = x8.shape
+  Nn = w8.shape[0]
+  assert w8.shape[1] == K and colscale.dtype == torch.float32 and colscale.numel() == Nn
+  colscale = colscale.contiguous()
+  bias = None if bias is None else bias.float().contiguous()
+  buf, out = _guarded((M, Nn // 2), torch.bfloat16, x8.device)
+  N.check(N.lib().gill_op_geglu_fp8_q(N.ptr(x8), N.ptr(w8), N.ptr(colscale), N.ptr(bias), N.ptr(buf), M, Nn, K, N.current_stream()))
+  return out, _guard_ok(buf)
 
 
 def conv_out(x: torch.Tensor, w_oihw: torch.Tensor, bias: Optional[torch.Tensor] = None, force_general: bool = False):

@@ -521,10 +521,11 @@ int gill_op_gemm_gn_stats(const void* A_bf16, const void* W_bf16, const float* b
  * statistics.  stats1 [B][nslab1][C1 / bin1][2] covers the channels of x1, stats2 [B][nslab2][C2 / bin2][2] those of x2 (NULL when C2 == 0);
  * group boundaries must fall on bin boundaries of the block that holds them (an error otherwise); at most 128 bins per block; any partial
  * counts (more than 64 go through an out-of-place totals pass; the partials themselves are never modified).  y (B,HW,C1+C2) bf16; ss_out
- * (optional, single-source only): the scale | shift table [B][2][C1] fp32 (y = x * scale + shift) is written INSTEAD of y.  Synchronises. */
+ * (optional, single-source only): the scale | shift table [B][2][C1] fp32 (y = x * scale + shift) is written INSTEAD of y.  out8_scale > 0: y is
+ * (B,HW,C1+C2) e4m3 bytes holding fp8(out8_scale * value), the A operand of the fp8 convolution (0: bf16).  Synchronises. */
 int gill_op_groupnorm_from_stats(const void* x1, int C1, const void* x2, int C2, int B, int HW, int groups, const float* gamma, const float* beta,
                                  float eps, int silu, const float* stats1, int bin1, int nslab1, const float* stats2, int bin2, int nslab2,
-                                 void* y, float* ss_out, void* stream);
+                                 void* y, float* ss_out, float out8_scale, void* stream);
 
 /* The VAE mid block's single-head attention behind its GroupNorm, launched as the engine launches it (diffusers AutoencoderKL
  * mid_block.attentions.0 without group_norm): out (B*HW, C) bf16 = to_out(softmax(to_q(n) to_k(n)^T / sqrt(C)) to_v(n)) + resid.  n (B*HW, C)
@@ -601,6 +602,39 @@ int gill_op_ln_gemm(int mode, const void* T_bf16, const float* planes, int P, in
  * (activations x 8 per tensor, weights per output channel).  splitk 0 = heuristic. */
 int gill_op_conv3x3_fp8(const void* x_bf16, const float* w_oihw, const float* bias, const void* resid_bf16, void* y_bf16,
                         int B, int H, int W, int Cin, int Cout, int splitk, void* stream);
+
+/* The fp8 mode's launchers one by one on QUANTISED operands (no reference counterpart; for the operator tests): every entry launches the
+ * launcher the UNet engine launches and synchronises.  e4m3 tensors are plain bytes.
+ * gill_conv_fp8_kpad: bytes per weight row of the fp8 convolution for Cin input channels (9 Cin rounded up to whole 128-byte K steps); -1
+ *   unless Cin is a positive multiple of 64.  Host only.
+ * gill_op_quant_fp8: y8[i] = fp8(scale * x[i]), saturating at +-448, NaN kept; n % 8 == 0.
+ * gill_op_conv_weight_quant_fp8: w (Cout,Cin,3,3) of dtype GILL_DTYPE_* -> w8 [Cout][Kpad] in the kernel's K order (64-channel half
+ *   q = tap * Cin / 64 + chunk, zero padding behind), colscale[o] = max|w_o| / 448 / act_scale (1 / act_scale for an all-zero row).
+ * gill_op_conv3x3_fp8_q: y (B,H,W,Cout) bf16 = colscale[n] * (x8 (*) w8) + bias[n] + rowvec[b][n] + resid; x8 (B,H,W,Cin) e4m3.  splitk == 1:
+ *   one launch; gn_stats (optional, with stats_bin > 0 dividing Cout): the GroupNorm partials of the output,
+ *   [(b * (H W / 64) + slab) * (Cout / stats_bin) + bin][2] = {sum, sum of squares} over 64-row slabs, summed BEFORE the bf16 rounding.
+ *   splitk > 1: ws [splitk][M][Cout] fp32 from the caller receives every slice's partial (accumulator times colscale; slices beyond the K
+ *   steps hold zeros); then, unless partials_only, the split-K reducer adds them in slice order with bias, rowvec and residual.
+ * gill_op_groupnorm_fp8: y8 (B,HW,C1+C2) = fp8(scale * [silu](GroupNorm(x1 ++ x2))), statistics from the tensors.
+ * gill_op_linear_weight_quant_fp8: w (N,K) bf16 -> w8 [N][K], colscale[n] = max|w_n| / 448 / act_scale; K even.
+ * gill_op_ln_quant_fp8: y8 (M,C) = fp8(act_scale * (t - mean) * rstd), mean / rstd of row m from stats [planes][R][2] fp32 {sum, sum of
+ *   squares} added in plane order, R = ln_rows ? ln_rows : M; rows m >= ln_rows read row m - ln_rows.  C % 8 == 0.
+ * gill_op_geglu_fp8_q: out (M, N/2) bf16 = (x8 . wv^T * sv + bv) * gelu(x8 . wg^T * sg + bg) with w8 [N][K], colscale, bias [N] in the
+ *   PHYSICAL row order: rows 32 j .. 32 j + 15 are the value rows of outputs 16 j .. 16 j + 15, rows 32 j + 16 .. 32 j + 31 their gate rows.
+ *   K % 128 == 0, N % 32 == 0. */
+int gill_conv_fp8_kpad(int Cin);
+int gill_op_quant_fp8(const void* x_bf16, float scale, int64_t n, void* y8, void* stream);
+int gill_op_conv_weight_quant_fp8(const void* w_oihw, int dtype, int Cout, int Cin, float act_scale, void* w8, float* colscale, void* stream);
+int gill_op_conv3x3_fp8_q(const void* x8, const void* w8, const float* colscale, const float* bias, const float* rowvec, const void* resid_bf16,
+                          void* y_bf16, float* gn_stats, int stats_bin, float* ws, int partials_only, int B, int H, int W, int Cin, int Cout,
+                          int splitk, void* stream);
+int gill_op_groupnorm_fp8(const void* x1, int C1, const void* x2, int C2, int B, int HW, int groups, const float* gamma, const float* beta,
+                          float eps, int silu, float scale, void* y8, void* stream);
+int gill_op_linear_weight_quant_fp8(const void* w_bf16, int N, int K, float act_scale, void* w8, float* colscale, void* stream);
+int gill_op_ln_quant_fp8(const void* t_bf16, int M, int C, const float* stats, int planes, int ln_rows, float eps, float act_scale, void* y8,
+                         void* stream);
+int gill_op_geglu_fp8_q(const void* x8, const void* w8, const float* colscale, const float* bias, void* out_bf16, int M, int N, int K,
+                        void* stream);
 
 /* The denoise loop's own kernels under a teacher: gill_sd_denoise_ex's table, stage kernel, step kernel and device step counter, with the UNet
  * replaced by "read this call's model output".  latents0 (B,n) fp32 (any n), model_out (ncalls,Bx,n) fp32 with Bx = 2B (uncond rows, then cond
