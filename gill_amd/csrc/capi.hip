@@ -138,9 +138,8 @@ extern "C" int gill_op_conv3x3_ex(const void* x1, int C1, const void* x2, int C2
 
 // 3x3 convolution + the GroupNorm (+ SiLU) that consumes its output, without a GroupNorm launch of its own where the geometry allows:
 // y_raw (optional) = conv(x) + bias + rowvec[b] + resid, y_norm = [silu](GroupNorm(y_raw; groups, gamma, beta, eps)).
-//   splitk >= 2: the split-K reduction also normalises (H * W in {64, 256}, Cout / groups a multiple of 4 dividing 80) — coop = 0: in the reducer launch
-//                (gemm.hip "REDUCE + GROUPNORM"); coop = 1: inside the convolution's own launch (gemm.hip "COOP", EPI 7) when gemm_coop_ok() takes it
-//                (B * H * W / 128 x Cout / 160 x splitk workgroups <= the device's CUs, Cout % 160 == 0), else as coop = 0;
+//   splitk >= 2: the split-K reducer launch also normalises (gemm_reduce.hip "REDUCE + GROUPNORM": H * W in {64, 256}, Cout / groups a multiple of 4
+//                dividing 80); coop is ignored;
 //   splitk == 1: coop = 1: in the convolution's epilogue (COOP, EPI 6: H * W a multiple of the 128- / 256-row tile, <= 4096 pixels per sample,
 //                grid <= CUs) — an error where the geometry does not allow it; coop = 0: the reference dataflow, conv with fused statistics +
 //                groupnorm_apply_launch.
@@ -176,7 +175,7 @@ extern "C" int gill_op_conv3x3_gn(const void* x, const float* w_oihw, const floa
     GILL_TRY(st.alloc(sizeof(float) * (size_t)B * (H * W / GN_SLAB_ROWS_MIN) * (Cout / sbin) * 2));
     g.gn_stats = (float*)st.p; g.gn_groups = Cout / sbin; g.gn_cg = sbin;
   }
-  if (coop) { g.coop_ctr = (unsigned*)ctr.p; g.coop_splitk = 1; }
+  if (coop && splitk == 1) g.coop_ctr = (unsigned*)ctr.p;
   if (splitk == 1 && !coop) {
     // reference dataflow: the convolution files its statistics, a GroupNorm-apply launch normalises the rounded tensor
     g.fn_Y = nullptr; g.fn_ss = nullptr;
@@ -190,7 +189,7 @@ extern "C" int gill_op_conv3x3_gn(const void* x, const float* w_oihw, const floa
     return 0;
   }
   if (splitk == 1) GILL_REQUIRE(gemm_coop_ok(g), "conv3x3_gn: splitk == 1 with coop needs the in-kernel finish's geometry (gemm_coop_ok)");
-  else GILL_REQUIRE(gemm_coop_ok(g) || gemm_fused_norm_ok(g), "conv3x3_gn: unsupported geometry (H * W in {64, 256}, Cout % 80 == 0, group width | 80)");
+  else GILL_REQUIRE(gemm_fused_norm_ok(g), "conv3x3_gn: unsupported geometry (H * W in {64, 256}, Cout % 80 == 0, group width | 80)");
   for (int r = 0; r < op_repeat(); ++r) {
     GILL_CHECK_HIP(hipMemsetAsync(ctr.p, 0, sizeof(unsigned) * (size_t)ncnt, s));
     GILL_TRY(gemm_launch(g, s));

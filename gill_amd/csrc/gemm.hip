@@ -21,13 +21,12 @@
 // Workgroup -> tile mapping is XCD-aware: the dispatcher places workgroup b on XCD b % 8, so ids are
 // remapped (bijectively) to give every XCD a contiguous range of tiles — the N tiles of one M range
 // and the 3x3 halo rows of neighbouring M ranges then hit the same 4 MiB L2.
-#include "ops.h"
+#include "gemm_dev.h"
 #include <stdlib.h>
 
 #define BM_HOST 128       // rows of the 4-wave tile, for the host-side split-K heuristic; the kernel's BM is 32 * NWV
 #define BK 64
 #define GEMM_THREADS 256
-#define LN_MAX_PLANES 20   // row-sum planes a folded-LayerNorm consumer can add: 2 per N tile of the producer, or one per 64 columns of a split-K reducer (C <= 1280)
 
 // zeros read by padding taps; a row's pointer advances 128 B per K step within a (tap, source) segment, so the page
 // covers the longest segment (ZERO_PAGE_STEPS K steps) plus one 128-B row
@@ -62,219 +61,12 @@ struct GemmDev {
   int xb_m, xb_n;    // > 0: XCD BLOCK MAP — XCD x owns an xb_m x xb_n block of the (M tile, N group) grid (see xcd_block_pick()); 0: the range map above
 };
 
-__device__ __noinline__ float gelu_erf_call(float v) { return gelu_erf(v); }  // keeps erff out of the unrolled epilogue
-
-__device__ __forceinline__ float apply_act(float v, int act) {
-  if (act == ACT_RELU) return fmaxf(v, 0.f);
-  if (act == ACT_SILU) return silu_f(v);
-  if (act == ACT_GELU) return gelu_erf_call(v);
-  if (act == ACT_QUICK_GELU) return v * __builtin_amdgcn_rcpf(1.0f + __builtin_amdgcn_exp2f(-1.702f * 1.4426950408889634f * v));
-  return v;
-}
-
-// Generic epilogue for 4 consecutive columns n..n+3 of row m (n % 4 == 0, n + 3 < N): used by the split-K reducer.
-// (Loading bias / row vector / residual up front, in flight with the partials, measured SLOWER: loop 518.3 -> 520.1 ms.)
-__device__ __forceinline__ void store4(const GemmArgs& p, int m, int n, float v0, float v1, float v2, float v3,
-                                       float* fin = nullptr) {
-  float v[4] = {v0 * p.alpha, v1 * p.alpha, v2 * p.alpha, v3 * p.alpha};
-  if (p.bias) {
-    const float4 b = *reinterpret_cast<const float4*>(p.bias + n);
-    v[0] += b.x; v[1] += b.y; v[2] += b.z; v[3] += b.w;
-  }
-  if (p.rowvec) {
-    const float4 b = *reinterpret_cast<const float4*>(p.rowvec + (size_t)(m / p.rows_per_batch) * p.rowvec_bstride + n);
-    v[0] += b.x; v[1] += b.y; v[2] += b.z; v[3] += b.w;
-  }
-  if (p.resid) {
-    if (p.resid_f32) {
-      const float4 r = *reinterpret_cast<const float4*>((const float*)p.resid + (size_t)m * p.ldr + n);
-      v[0] += r.x; v[1] += r.y; v[2] += r.z; v[3] += r.w;
-    } else {
-      const uint2 r = *reinterpret_cast<const uint2*>((const bf16_t*)p.resid + (size_t)m * p.ldr + n);
-      v[0] += bf2f((bf16_t)(r.x & 0xffff)); v[1] += bf2f((bf16_t)(r.x >> 16));
-      v[2] += bf2f((bf16_t)(r.y & 0xffff)); v[3] += bf2f((bf16_t)(r.y >> 16));
-    }
-  }
-  if (p.act != ACT_NONE) {
-#pragma unroll
-    for (int i = 0; i < 4; ++i) v[i] = apply_act(v[i], p.act);
-  }
-  if (fin) { fin[0] = v[0]; fin[1] = v[1]; fin[2] = v[2]; fin[3] = v[3]; }
-  if (p.out_mode == OUT_BF16) {
-    uint2 o; o.x = pack_bf2(v[0], v[1]); o.y = pack_bf2(v[2], v[3]);
-    *reinterpret_cast<uint2*>((bf16_t*)p.C + (size_t)m * p.ldc + n) = o;
-  } else if (p.out_mode == OUT_F32) {
-    *reinterpret_cast<float4*>((float*)p.C + (size_t)m * p.ldc + n) = make_float4(v[0], v[1], v[2], v[3]);
-  } else {  // OUT_QKV
-    const int hd = p.heads * p.dp;
-    const int seg = p.seg_base + n / hd;
-    const int within = n % hd;
-    const int h = within / p.dp, dd = within % p.dp;
-    const int b = m / p.ntok, t = m % p.ntok;
-    if (seg == 0) {
-      uint2 o; o.x = pack_bf2(v[0] * p.qscale, v[1] * p.qscale); o.y = pack_bf2(v[2] * p.qscale, v[3] * p.qscale);
-      *reinterpret_cast<uint2*>(p.Cq + ((size_t)(b * p.heads + h) * p.ntok_pad_q + t) * p.dp + dd) = o;
-    } else if (seg == 1) {
-      uint2 o; o.x = pack_bf2(v[0], v[1]); o.y = pack_bf2(v[2], v[3]);
-      *reinterpret_cast<uint2*>(p.Ck + ((size_t)(b * p.heads + h) * p.ntok_pad_kv + t + p.kv_tok_offset) * p.dp + dd) = o;
-    } else {
-      bf16_t* base = p.Cvt + ((size_t)(b * p.heads + h) * p.dpv + dd) * p.ntok_pad_kv + t + p.kv_tok_offset;
-#pragma unroll
-      for (int i = 0; i < 4; ++i) base[(size_t)i * p.ntok_pad_kv] = f2bf(v[i]);
-      if (dd + 4 == p.dp && p.dpv > p.dp) base[(size_t)4 * p.ntok_pad_kv] = (bf16_t)0x3F80;
-    }
-  }
-}
-
-// REDUCE + GROUPNORM.  Where a split-K GEMM's output feeds a single-source GroupNorm (every 3x3 convolution of UNet levels 2-3 at
-// the 8-sample batch: conv1 -> norm2 inside a ResnetBlock2D, and a block's last GEMM -> the next block's first norm), the reducer is
-// the first place that holds complete output values — and a unit that owns ALL rows of one sample for a run of whole groups holds
-// complete GroupNorm statistics too.  Unit = (sample b, W output columns from col0 = whole groups of fn_cg channels): sums the split slices
-// in slice order, applies the GEMM epilogue (bias, per-sample row vector, bf16 residual), optionally stores the raw tensor, totals
-// {sum, sum of squares} per group in a fixed order (thread -> 16 row lanes -> the group's column quads), and writes the normalised
-// (+ SiLU) tensor: the GroupNorm-apply launch of that norm (5.5-7.5 us each, 24 per forward) and its read of the raw tensor disappear.
-// Also files the fused-statistics partials of the raw output (gn_stats: one slab = the whole sample) for a later two-source consumer.
-// fn_Y == nullptr: the plain finish (raw tensor + partials only).
-// RPT rows per thread: rows_per_batch = 16 * RPT (256 -> 16, 64 -> 4).  W columns (80 | 40): W / 4 column quads x 16 row lanes = 4 W threads
-// do the work; a caller with more threads (the COOP finish inside gemm_kernel: 512) passes them all — they only take part in the barriers.
-// Two callers, one body: the stand-alone reducer kernel below (one unit per block) and gemm_kernel's EPI 7 (one unit per workgroup, after the
-// arrival counter of its group has filled) — so the in-kernel finish is bit-identical to the reducer launch it replaces.
-// poison: the caller gave up waiting for its group (COOP_SPIN_LIMIT): every output of the unit becomes NaN.
-template <int RPT, int W>
-__device__ __forceinline__ void splitk_finish_unit(const GemmArgs& p, const int b, const int col0, const int tidx, float2 (*part)[W / 4], float2* quad,
-                                                   float2* mr, const bool poison) {
-  constexpr int QW = W / 4, ROWS = 16 * RPT;
-  const bool act = tidx < 4 * W;
-  const int tx = tidx % QW, ty = act ? tidx / QW : 0;
-  const int n = col0 + tx * 4;
-  const int mbase = b * ROWS;
-  const bool norm = p.fn_Y != nullptr;
-  // every global load of the unit goes out before the first use: the partials of the first slices, the epilogue's vectors, the
-  // residual rows, the norm's parameters — one memory round trip in front of the reduction, not four
-  float4 v[RPT];
-  auto row_of = [&](int r) -> int { return mbase + ty + 16 * r; };     // row of the thread's r-th value
-  float ps = 0.f, pq = 0.f;
-  uint2 raw[RPT];
-  float4 gam = make_float4(0, 0, 0, 0), bet = make_float4(0, 0, 0, 0);
-  if (act) {
-  float4 add = p.bias ? *reinterpret_cast<const float4*>(p.bias + n) : make_float4(0, 0, 0, 0);
-  const float4 rv = p.rowvec ? *reinterpret_cast<const float4*>(p.rowvec + (size_t)b * p.rowvec_bstride + n) : make_float4(0, 0, 0, 0);
-  if (norm) { gam = *reinterpret_cast<const float4*>(p.fn_gamma + n); bet = *reinterpret_cast<const float4*>(p.fn_beta + n); }
-  uint2 rr[RPT];
-#pragma unroll
-  for (int r = 0; r < RPT; ++r)
-    rr[r] = p.resid ? *reinterpret_cast<const uint2*>((const bf16_t*)p.resid + (size_t)row_of(r) * p.ldr + n) : make_uint2(0u, 0u);
-  const float* src = p.ws + (size_t)(mbase + ty) * p.N + n;
-  const size_t zstride = (size_t)p.M * p.N, rstride = (size_t)16 * p.N;
-  // slices are ADDED in slice order whatever the order their loads go out in.  Few rows per thread (RPT = 4: the 64-row samples of UNet level 3,
-  // split up to eight ways): the first eight slices' loads all at once — 32 independent 16-B loads per thread, ONE memory round trip — where a loop
-  // over the slices is one round trip per slice (round 6: inside gemm_kernel's COOP finish one workgroup per CU has no neighbour to hide them: the
-  // level-3 finish took 21 us that way; clamped slice index + predicated add, so absent slices cost a redundant load and nothing else).
-  constexpr int CH = (RPT <= 4) ? 8 : 2;
-  {
-    float4 t[CH][RPT];
-#pragma unroll
-    for (int u = 0; u < CH; ++u) {
-      const int zz = (u < p.splitk) ? u : p.splitk - 1;
-#pragma unroll
-      for (int r = 0; r < RPT; ++r) t[u][r] = *reinterpret_cast<const float4*>(src + (size_t)zz * zstride + (size_t)r * rstride);
-    }
-#pragma unroll
-    for (int r = 0; r < RPT; ++r) v[r] = t[0][r];
-#pragma unroll
-    for (int u = 1; u < CH; ++u) {
-      if (u < p.splitk) {      // (uniform; splitk >= 2)
-#pragma unroll
-        for (int r = 0; r < RPT; ++r) { v[r].x += t[u][r].x; v[r].y += t[u][r].y; v[r].z += t[u][r].z; v[r].w += t[u][r].w; }
-      }
-    }
-  }
-  for (int z = CH; z < p.splitk; ++z) {
-    float4 t[RPT];
-#pragma unroll
-    for (int r = 0; r < RPT; ++r) t[r] = *reinterpret_cast<const float4*>(src + (size_t)z * zstride + (size_t)r * rstride);
-#pragma unroll
-    for (int r = 0; r < RPT; ++r) { v[r].x += t[r].x; v[r].y += t[r].y; v[r].z += t[r].z; v[r].w += t[r].w; }
-  }
-  add.x += rv.x; add.y += rv.y; add.z += rv.z; add.w += rv.w;
-  if (poison) add.x = add.y = add.z = add.w = __builtin_nanf("");
-  // STATISTICS SOURCE.  The producers that file RAW partials for a later GroupNorm-apply launch — the in-kernel epilogue (gs / gq) and the plain reducer
-  // (store4()'s `fin`) — sum the values AS STORED, i.e. after their rounding to bf16: their partials are the sums of the tensor the consumer reads
-  // (tests/test_gn_stats_gpu.py holds them to that within fp32 summation error).  This unit, which normalises in the same breath, sums the fp32 values
-  // BEFORE their rounding and normalises the ROUNDED tensor (below: raw[r], what a stand-alone apply pass would read); its one-slab
-  // partials for a later two-source consumer are those same sums.  The fused and unfused forms of one layer differ by that rounding noise (~1e-4 of a
-  // sum) and by the (fixed) order of the fp32 additions, which is why they are held to closeness, not equality.  Variance: E[x^2] - E[x]^2 in fp32 over a
-  // (sample, group) slab of <= 256 x 80 values of O(1): cancellation costs ~1e-6 relative at |mean| ~ sigma, far below the bf16 output step.
-#pragma unroll
-  for (int r = 0; r < RPT; ++r) {
-    const int m = row_of(r);
-    v[r].x += add.x; v[r].y += add.y; v[r].z += add.z; v[r].w += add.w;
-    v[r].x += bf2f((bf16_t)(rr[r].x & 0xffff)); v[r].y += bf2f((bf16_t)(rr[r].x >> 16));        // (zeros without a residual)
-    v[r].z += bf2f((bf16_t)(rr[r].y & 0xffff)); v[r].w += bf2f((bf16_t)(rr[r].y >> 16));
-    ps += (v[r].x + v[r].y) + (v[r].z + v[r].w);
-    pq += (v[r].x * v[r].x + v[r].y * v[r].y) + (v[r].z * v[r].z + v[r].w * v[r].w);
-    raw[r].x = pack_bf2(v[r].x, v[r].y); raw[r].y = pack_bf2(v[r].z, v[r].w);
-    if (p.C) *reinterpret_cast<uint2*>((bf16_t*)p.C + (size_t)m * p.ldc + n) = raw[r];
-  }
-  part[ty][tx] = make_float2(ps, pq);
-  }
-  __syncthreads();
-  if (tidx < QW) {
-    float a = 0.f, q = 0.f;
-#pragma unroll
-    for (int r = 0; r < 16; ++r) { const float2 t = part[r][tidx]; a += t.x; q += t.y; }
-    quad[tidx] = make_float2(a, q);
-  }
-  __syncthreads();
-  if (norm) {
-    const int qpg = p.fn_cg / 4;             // column quads per group
-    const int ngrp = W / p.fn_cg;
-    if (tidx < ngrp) {
-      float a = 0.f, q = 0.f;
-      for (int t = 0; t < qpg; ++t) { const float2 u = quad[tidx * qpg + t]; a += u.x; q += u.y; }
-      const float inv_n = 1.f / ((float)p.fn_cg * (float)ROWS);
-      const float sm = a * inv_n, sq = q * inv_n;
-      const float var = fmaxf(sq - sm * sm, 0.f);
-      mr[tidx] = make_float2(sm, rsqrtf(var + p.fn_eps));
-    }
-  }
-  if (p.gn_stats) {      // partials of the raw output for a later (two-source) GroupNorm: bins of gn_cg channels, one slab per sample
-    const int qpb = p.gn_cg / 4, nbin = W / p.gn_cg;
-    const int t2 = tidx - 32;
-    if (t2 >= 0 && t2 < 2 * nbin) {
-      const int which = t2 & 1, lb = t2 >> 1;
-      float a = 0.f;
-      for (int t = 0; t < qpb; ++t) { const float2 u = quad[lb * qpb + t]; a += which ? u.y : u.x; }
-      p.gn_stats[((size_t)b * p.gn_groups + col0 / p.gn_cg + lb) * 2 + which] = a;
-    }
-  }
-  __syncthreads();
-  if (norm && act) {
-    const float2 g = mr[(tx * 4) / p.fn_cg];
-    const float s0 = g.y * gam.x, s1 = g.y * gam.y, s2 = g.y * gam.z, s3 = g.y * gam.w;
-    const float h0 = bet.x - g.x * s0, h1 = bet.y - g.x * s1, h2 = bet.z - g.x * s2, h3 = bet.w - g.x * s3;
-#pragma unroll
-    for (int r = 0; r < RPT; ++r) {
-      const int m = row_of(r);
-      // (the consumer of the unfused path reads the bf16 tensor: normalise the rounded values)
-      float o0 = fmaf(bf2f((bf16_t)(raw[r].x & 0xffff)), s0, h0), o1 = fmaf(bf2f((bf16_t)(raw[r].x >> 16)), s1, h1);
-      float o2 = fmaf(bf2f((bf16_t)(raw[r].y & 0xffff)), s2, h2), o3 = fmaf(bf2f((bf16_t)(raw[r].y >> 16)), s3, h3);
-      if (p.fn_silu) { o0 = silu_f(o0); o1 = silu_f(o1); o2 = silu_f(o2); o3 = silu_f(o3); }
-      uint2 o; o.x = pack_bf2(o0, o1); o.y = pack_bf2(o2, o3);
-      *reinterpret_cast<uint2*>(p.fn_Y + (size_t)m * p.N + n) = o;
-    }
-  }
-}
-
 // ---- COOP: hand-offs between the co-resident workgroups of ONE launch (cdna_hip_programming.md Guideline 16, recipe R1; prices in
-// MI355X_MICROARCH.md "publish-large" / "splitk-seam").  Payload goes out WRITE-THROUGH (sc1: nothing left dirty, no release fence), every storing
+// MI355X_MICROARCH.md "publish-large").  Payload (the GroupNorm partials) goes out WRITE-THROUGH (sc1: nothing left dirty, no release fence), every storing
 // wave drains its own stores (s_waitcnt vmcnt(0)), the workgroup meets at a barrier, ONE lane arrives on the group's counter (agent-scope atomic)
-// and polls it relaxed with s_sleep; readers then take ONE agent-scope acquire (split-K: bulk plain loads) or read the few words with sc1 loads
-// (GroupNorm partials).  Counters are zeroed once per forward (unet.hip), every slot is used by exactly one launch: the target is the group size.
+// and polls it relaxed with s_sleep; readers then read the few words with sc1 loads.
+// Counters are zeroed once per forward (unet.hip), every slot is used by exactly one launch: the target is the group size.
 // The spin is bounded: a workgroup that gives up poisons its outputs with NaN (every test and bench.py check finiteness) instead of hanging the GPU.
-__device__ __forceinline__ void st_wt_f32x4(float* p, const f32x4 v) {
-  asm volatile("global_store_dwordx4 %0, %1, off sc1\n\ts_nop 1" ::"v"(p), "v"(v) : "memory");
-}
 __device__ __forceinline__ void st_wt_f32(float* p, float v) {
   __hip_atomic_store(reinterpret_cast<unsigned*>(p), __float_as_uint(v), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 }
@@ -294,14 +86,6 @@ __device__ __forceinline__ bool coop_wait(unsigned* ctr, unsigned target) {
     __builtin_amdgcn_s_sleep(2);
   }
 }
-__device__ __forceinline__ bool coop_arrive_wait(unsigned* ctr, unsigned target) {
-  __hip_atomic_fetch_add(ctr, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-  for (unsigned spins = 0;; ++spins) {
-    if (__hip_atomic_load(ctr, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) >= target) return true;
-    if (spins > COOP_SPIN_LIMIT) { coop_note_giveup(); return false; }
-    __builtin_amdgcn_s_sleep(2);
-  }
-}
 
 // CONV: 0 plain GEMM, 1 conv3x3, 2 conv3x3 with fused nearest-2x upsample (9 taps gathered from the source grid),
 //       3 nearest-2x upsample + conv3x3 as FOUR 2x2-tap convolutions of the source grid, one per output parity (see "UPS4")
@@ -309,35 +93,9 @@ __device__ __forceinline__ bool coop_arrive_wait(unsigned* ctr, unsigned target)
 //       4 = 0 without activation / fp32 output / fp32 residual (the UNet's plain GEMMs: half the epilogue's code and branches)
 //       5 folded-LayerNorm scores + softmax over each wave's 80 columns (OUT_SOFTMAX80; BN = 160)
 //       6 = 0 on the ping-pong conv tiles + the consuming GroupNorm finished in-kernel (COOP, splitk == 1: see GemmArgs::coop_ctr)
-//       7 = 2 + the split-K finish in-kernel (COOP): partials published write-through, one (sample, 40-column) unit finished per workgroup
 // STAGES: depth of the LDS ring.  2: two workgroups per CU hide each other's DMA waits.  3: one workgroup per CU,
 //         the DMA of K steps i+1 AND i+2 is in flight while step i is multiplied (counted s_waitcnt vmcnt(N), raw
 //         s_barrier) — for grids of ~one workgroup per CU where co-residency cannot do the hiding.
-// folded LayerNorm: rstd and mean*rstd of A's row m from the producer's {sum, sum of squares}
-__device__ __forceinline__ void ln_row_factors(const GemmArgs& p, int m, float& rr, float& rm) {
-  // the producer's per-plane partial sums of this row, added in plane order (fixed order: bit-reproducible); the loads go out four
-  // planes at a time (predicated), not one L2 round trip per plane — and not LN_MAX_PLANES predicated loads per row: a level-0
-  // consumer reads 4 planes (the prologue of the GEGLU / QKV kernels was 80 load slots per lane for them)
-  const int R = p.ln_rows ? p.ln_rows : p.M;
-  if (m >= R) m -= R;
-  const float* base = p.ln_stats + (size_t)m * 2;
-  const size_t pstride = (size_t)R * 2;
-  float2 st = make_float2(0.f, 0.f);
-  for (int pl = 0; pl < p.ln_planes; pl += 4) {      // (wave-uniform trip count)
-    float2 v[4];
-#pragma unroll
-    for (int u = 0; u < 4; ++u)
-      v[u] = (pl + u < p.ln_planes) ? *reinterpret_cast<const float2*>(base + (size_t)(pl + u) * pstride) : make_float2(0.f, 0.f);
-#pragma unroll
-    for (int u = 0; u < 4; ++u) { st.x += v[u].x; st.y += v[u].y; }
-  }
-  const float invk = 1.f / (float)p.K;
-  const float mean = st.x * invk;
-  const float var = fmaxf(st.y * invk - mean * mean, 0.f);
-  rr = rsqrtf(var + p.ln_eps);
-  rm = mean * rr;
-}
-
 // NWV: waves per workgroup.  4 -> 128-row tile (waves 2 x 2).  2 -> 64-row tile (waves 1 x 2) for problems with so few
 // 128-row tiles that half the CUs would idle (UNet level 2-3 projections: M = 2048 / 512).
 // 8 -> 256-row tile (waves 4 x 2, one workgroup per CU).  BN = 160, STAGES = 3: the convolutions' ping-pong kernel.
@@ -353,18 +111,12 @@ __device__ __forceinline__ void ln_row_factors(const GemmArgs& p, int m, float& 
 // small plain GEMMs: the same 48 KiB of LDS as the 2-wave 64 x 128 tile (three workgroups per CU), twice the waves per CU.
 // (The timing-only ablation guards of round 4 — PP_ABL: no fragment reads / no LDS-DMA / no MFMAs / no bookkeeping / no epilogue / no barriers —
 // are gone from this file; their table is profiles/r04_pingpong_ablations.md, the bare loops live on in tools/ubench/gemm_loop.hip and gemm_ws.hip.)
-// The kernel body is a device function of the workgroup's coordinates (gemm_kernel below passes blockIdx / gridDim), so that a PERSISTENT launch can
-// run several GEMMs back to back in one workgroup (tools/ubench/persist_resnet.hip, round 6: the go / no-go prototype of one launch per ResnetBlock2D).
-// SEAM (prototype only; 0 in every product instantiation — all of it compiles away): the tile is one PHASE of such a launch.  On entry it waits on
-// the arrival counter of the M-tile group whose rows it reads (seam_in) — after issuing the WEIGHT pieces of its first ring stages when
-// `prefetch` is set (weights do not depend on the previous phase: MI355X_MICROARCH "prefetch-credit") — and on exit (EPI 7) it publishes its
-// finished units and arrives on seam_out.
+// The kernel body is a device function of the workgroup's coordinates; gemm_kernel below passes blockIdx / gridDim.  (Reading them in the body itself
+// is the same program and a different instruction schedule in all 63 instantiations — profiles/gemm_prune_isa.md — so the wrapper stays.)
 struct GemmTileCtx {
-  int bx, by, bz, gdx, gdy;
-  unsigned* seam_in = nullptr; unsigned seam_in_target = 0; int seam_in_mtg = 1; int prefetch = 0;
-  unsigned* seam_out = nullptr;
+  int bx, by, bz, gdx;
 };
-template <int NWV, int BN, int CONV, int EPI, int STAGES, int KT, int MI, int SEAM = 0>
+template <int NWV, int BN, int CONV, int EPI, int STAGES, int KT, int MI>
 __device__ __forceinline__ void gemm_tile(const GemmDev& d, const GemmTileCtx cx) {
   constexpr int BM = (NWV / 2) * MI * 16;
   static_assert(MI == 4 || (MI == 2 && NWV == 4 && CONV == 0 && (STAGES == 2 || STAGES == 3) && KT == 64) ||
@@ -421,7 +173,7 @@ __device__ __forceinline__ void gemm_tile(const GemmDev& d, const GemmTileCtx cx
   const int tn_first = gn * d.npw;
   // (convolutions and split-K partials: one N tile per workgroup — gemm_launch_bn() — known at compile time, so that the K walk's
   // state is dead by the epilogue instead of being carried around it for a next tile that never comes)
-  const int ntl = (CONV != 0 || EPI == 2 || EPI == 7) ? 1 : ((d.tiles_n - tn_first < d.npw) ? d.tiles_n - tn_first : d.npw);   // N tiles of this workgroup
+  const int ntl = (CONV != 0 || EPI == 2) ? 1 : ((d.tiles_n - tn_first < d.npw) ? d.tiles_n - tn_first : d.npw);   // N tiles of this workgroup
   int n0 = tn_first * BN;
   const int z = cx.by;
   const int kt_beg = z * d.ksteps_per_split;
@@ -627,23 +379,6 @@ __device__ __forceinline__ void gemm_tile(const GemmDev& d, const GemmTileCtx cx
                                        (__attribute__((address_space(3))) void*)l, 16, 0, WBLK ? 2 : 0);     // (aux 2 = nt)
     }
   };
-  // (SEAM prologue only: the two halves of issue_dma on their own — the W pieces `koff` elements ahead of the walk's current position)
-  auto issue_dma_a = [&](int buf) {
-    bf16_t* As = smem + buf * BUF_ELEMS;
-#pragma unroll
-    for (int i = 0; i < AI; ++i)
-      __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)a_ptr[i],
-                                       (__attribute__((address_space(3))) void*)(As + (i * NWV + w) * RPI * KT), 16, 0, 0);
-  };
-  auto issue_dma_w = [&](int buf, int koff) {
-    bf16_t* Bs = smem + buf * BUF_ELEMS + A_ELEMS;
-#pragma unroll
-    for (int i = 0; i < WI; ++i) {
-      if (i == WI - 1 && !w_last_ok) break;
-      __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(w_ptr[i] + koff),
-                                       (__attribute__((address_space(3))) void*)(Bs + (i * NWV + w) * RPI * KT), 16, 0, 0);
-    }
-  };
   auto issue_post = [&]() {
     ++steps_in_tile;
     --seg_left;
@@ -667,34 +402,9 @@ __device__ __forceinline__ void gemm_tile(const GemmDev& d, const GemmTileCtx cx
 
   static_assert(STAGES >= 2 && STAGES <= 6, "ring depth");
   const int total_steps = ntl * nsteps;
-  if constexpr (SEAM != 0) {
-    static_assert(SEAM == 0 || (PP && !WBLK), "SEAM: the ping-pong tiles");
-    if (cx.seam_in) {
-      if (cx.prefetch) {
-#pragma unroll
-        for (int s = 0; s < STAGES - 1; ++s)
-          if (s < total_steps) issue_dma_w(s, s * KT);
-      }
-      if (tid == 0) {
-        unsigned* c = cx.seam_in + tm / cx.seam_in_mtg;
-        for (unsigned spins = 0; __hip_atomic_load(c, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) < cx.seam_in_target && spins < COOP_SPIN_LIMIT; ++spins)
-          __builtin_amdgcn_s_sleep(2);
-        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
-      }
-      __builtin_amdgcn_s_barrier();      // (raw: a __syncthreads() here would drain the weight pieces in flight)
-#pragma unroll
-      for (int s = 0; s < STAGES - 1; ++s)
-        if (s < total_steps) { issue_prepare(); issue_dma_a(s); if (!cx.prefetch) issue_dma_w(s, 0); issue_post(); }
-    } else {
-#pragma unroll
-      for (int s = 0; s < STAGES - 1; ++s)
-        if (s < total_steps) issue(s);
-    }
-  } else {
 #pragma unroll
   for (int s = 0; s < STAGES - 1; ++s)
     if (s < total_steps) issue(s);
-  }
   // folded LayerNorm (GEGLU / QKV epilogues): the row factors are loaded here, under the first tile's DMA latency
   float ln_rr[4] = {1.f, 1.f, 1.f, 1.f}, ln_rm[4] = {0.f, 0.f, 0.f, 0.f};   // (first MI entries used)
   if constexpr (EPI == 1 || EPI == 3 || EPI == 5) {
@@ -734,10 +444,6 @@ __device__ __forceinline__ void gemm_tile(const GemmDev& d, const GemmTileCtx cx
     // two-way test — wait_vm()'s general switch is a chain of ~13 compare-and-branch pairs, twice per K step, at the END of group A's MMA phase
     auto landed = [&](int k) {
       if (k >= nsteps) return;
-      if constexpr (SEAM != 0) {
-        // prefetched prologue: the pieces went out as [W0 W1 | A0 A1] — stage 0 is complete once only A1's pieces are in flight
-        if (cx.seam_in && cx.prefetch && k == 0 && issued == STAGES - 1) { asm volatile("s_waitcnt vmcnt(%0)" ::"n"(AI) : "memory"); return; }
-      }
       if (issued - 1 - k <= 0) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
       else if (w_last_ok) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(AI + WI) : "memory");
       else asm volatile("s_waitcnt vmcnt(%0)" ::"n"(AI + WI - 1) : "memory");
@@ -899,7 +605,7 @@ __device__ __forceinline__ void gemm_tile(const GemmDev& d, const GemmTileCtx cx
       return m;
     }
   };
-  if constexpr (EPI == 2 || EPI == 7) {
+  if constexpr (EPI == 2) {
     float* ws = p.ws + (size_t)z * (CONV == 3 ? 4 : 1) * p.M * p.N;
 #pragma unroll
     for (int i = 0; i < MI; ++i) {
@@ -912,57 +618,9 @@ __device__ __forceinline__ void gemm_tile(const GemmDev& d, const GemmTileCtx cx
         const int n = nbase + (pair ? g * 32 + fkc * 8 : (2 * g) * 16 + fkc * 4);
         if (n >= p.N) continue;
         float* dst = ws + (size_t)m * p.N + n;
-        if constexpr (EPI == 7) {      // COOP: write-through, nothing left dirty in this XCD's L2 for a release to flush
-          st_wt_f32x4(dst, acc[i][2 * g]);
-          if (pair && n + 4 < p.N) st_wt_f32x4(dst + 4, acc[i][j1]);
-        } else {
-          *reinterpret_cast<float4*>(dst) = make_float4(acc[i][2 * g][0], acc[i][2 * g][1], acc[i][2 * g][2], acc[i][2 * g][3]);
-          if (pair && n + 4 < p.N)
-            *reinterpret_cast<float4*>(dst + 4) = make_float4(acc[i][j1][0], acc[i][j1][1], acc[i][j1][2], acc[i][j1][3]);
-        }
-      }
-    }
-    if constexpr (EPI == 7) {
-      // ---- COOP split-K finish (GemmArgs::coop_ctr).  Group = the workgroups whose tiles cover whole samples of one N tile, over all splits:
-      // M tiles per group mtg = rows_per_batch / BM (level 2: 2) or 1 with spg = BM / rows_per_batch samples in the tile (level 3: 2); G = mtg x splits
-      // workgroups arrive, then workgroup widx of the group finishes units widx, widx + G, ... of the group's spg x (BN / 40) (sample, 40-column) units.
-      static_assert(EPI != 7 || (PP && BN % 40 == 0), "COOP split-K finish: the ping-pong tiles");
-      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");      // every storing wave drains its own write-through stores ...
-      __syncthreads();                                       // ... before the one arrival of the workgroup
-      const int rpb = p.rows_per_batch;
-      const int mtg = rpb > BM ? rpb / BM : 1, spg = rpb < BM ? BM / rpb : 1;
-      const int G = mtg * cx.gdy;
-      const int tg = tm / mtg;
-      unsigned char* cs = smem_raw + 16384;                  // (the ring is dead; [0, 5 KiB) is the row-major epilogue's `red`, unused here)
-      float2 (*part)[10] = reinterpret_cast<float2 (*)[10]>(cs);
-      float2* quad = reinterpret_cast<float2*>(cs + 2048);
-      float2* mr = reinterpret_cast<float2*>(cs + 2304);
-      unsigned* okf = reinterpret_cast<unsigned*>(cs + 2560);
-      if (tid == 0) {
-        const bool ok = coop_arrive_wait(p.coop_ctr + (size_t)tg * d.tiles_n + n0 / BN, (unsigned)G);
-        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");   // ONE acquire per workgroup: drops this CU's stale L1 lines; the slices are read with plain loads
-        *okf = ok ? 1u : 0u;
-      }
-      __syncthreads();
-      const bool poison = *okf == 0u;
-      constexpr int UPT = BN / 40;                           // units per sample in this N tile
-      const int widx = z * mtg + (tm - tg * mtg);
-      for (int u = widx; u < spg * UPT; u += G) {            // (workgroup-uniform trip count)
-        const int b = tg * spg + u / UPT, col0 = n0 + (u % UPT) * 40;
-        if (rpb == 256) splitk_finish_unit<16, 40>(p, b, col0, tid, part, quad, mr, poison);
-        else splitk_finish_unit<4, 40>(p, b, col0, tid, part, quad, mr, poison);
-        __syncthreads();                                     // (the scratch is reused by the next unit)
-      }
-      if constexpr (SEAM != 0) {
-        if (cx.seam_out) {      // this phase's units are finished: publish them (plain stores -> one agent-scope release) and arrive
-          asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-          __syncthreads();
-          if (tid == 0) {
-            __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
-            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-            __hip_atomic_fetch_add(cx.seam_out + tg, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-          }
-        }
+        *reinterpret_cast<float4*>(dst) = make_float4(acc[i][2 * g][0], acc[i][2 * g][1], acc[i][2 * g][2], acc[i][2 * g][3]);
+        if (pair && n + 4 < p.N)
+          *reinterpret_cast<float4*>(dst + 4) = make_float4(acc[i][j1][0], acc[i][j1][1], acc[i][j1][2], acc[i][j1][3]);
       }
     }
   } else if constexpr (EPI == 1) {
@@ -1475,163 +1133,10 @@ template <int NWV, int BN, int CONV, int EPI, int STAGES, int KT, int MI>
 __global__ __launch_bounds__(NWV * 64, NWV == 8 ? ((BN == 128 && STAGES == 2) ? 2 : 1) : (MI == 2 ? 3 : 2)) void gemm_kernel(const GemmDev d) {
   kernarg_warm<sizeof(GemmDev)>();
   GemmTileCtx cx;
-  cx.bx = blockIdx.x; cx.by = blockIdx.y; cx.bz = blockIdx.z; cx.gdx = gridDim.x; cx.gdy = gridDim.y;
-  gemm_tile<NWV, BN, CONV, EPI, STAGES, KT, MI, 0>(d, cx);
+  cx.bx = blockIdx.x; cx.by = blockIdx.y; cx.bz = blockIdx.z; cx.gdx = gridDim.x;
+  gemm_tile<NWV, BN, CONV, EPI, STAGES, KT, MI>(d, cx);
 }
 
-// split-K reduction + epilogue
-// Block = 64 rows x W columns (W = 80 when the fused GroupNorm bins need it, else 64), 16 row lanes x W/4 column quads:
-// thread = one float4 column quad of rows ty, ty+16, ty+32, ty+48.  The partials of every split are summed in split order.
-// Fused statistics are fixed-order like the in-kernel epilogue's: per-row / per-column cells in LDS written once each, then
-// one thread per output sum adds them in index order (row sums -> plane blockIdx.x of row_stats, bins -> this slab's
-// GroupNorm partial).
-template <int W, int R>
-__global__ __launch_bounds__(4 * W) void gemm_splitk_reduce_kernel(const GemmArgs p) {
-  kernarg_warm<sizeof(GemmArgs)>();
-  constexpr int QW = W / 4;                     // column quads per row
-  constexpr int ROWS = 16 * R;                  // rows per block: 64 for large outputs, 16 when blocks would be too few
-  __shared__ float2 rowp[ROWS][QW];               // per (row, quad) {sum, sum of squares} of the bf16-rounded outputs
-  __shared__ float2 colp[16][W];                // per (row lane, column) {sum, sum of squares} over the lane's 4 rows
-  const int tx = threadIdx.x % QW, ty = threadIdx.x / QW;
-  const int n = blockIdx.x * W + tx * 4;
-  const int mbase = blockIdx.y * ROWS;
-  float gs[4] = {0.f, 0.f, 0.f, 0.f}, gq[4] = {0.f, 0.f, 0.f, 0.f};
-  float rsum[R], rsq[R];
-#pragma unroll
-  for (int r = 0; r < R; ++r) { rsum[r] = 0.f; rsq[r] = 0.f; }
-  // row of the thread's r-th value
-  auto row_of = [&](int r) -> int { return mbase + ty + 16 * r; };
-  if (n < p.N) {
-    // all partial loads of the thread's 4 rows are issued before any epilogue store (a store in between would fence the
-    // next row's loads): 4 rows x 4 splits = 16 independent 16-B loads in flight per pass
-    float4 s[R];
-    const float* src[R];
-#pragma unroll
-    for (int r = 0; r < R; ++r) {
-      int m = mbase + ty + 16 * r;
-      if (m > p.M - 1) m = p.M - 1;
-      s[r] = make_float4(0, 0, 0, 0);
-      src[r] = p.ws + (size_t)m * p.N + n;
-    }
-    const size_t zstride = (size_t)p.M * p.N;
-    constexpr int U = 16 / R;        // slices per pass: 16 independent 16-B loads in flight per thread either way
-    int z = 0;
-    for (; z + U <= p.splitk; z += U) {
-      float4 v[R][U];
-#pragma unroll
-      for (int r = 0; r < R; ++r)
-#pragma unroll
-        for (int u = 0; u < U; ++u) v[r][u] = *reinterpret_cast<const float4*>(src[r] + (size_t)(z + u) * zstride);
-#pragma unroll
-      for (int r = 0; r < R; ++r)
-#pragma unroll
-        for (int u = 0; u < U; ++u) { s[r].x += v[r][u].x; s[r].y += v[r][u].y; s[r].z += v[r][u].z; s[r].w += v[r][u].w; }
-    }
-    for (; z < p.splitk; ++z) {
-      float4 v[R];
-#pragma unroll
-      for (int r = 0; r < R; ++r) v[r] = *reinterpret_cast<const float4*>(src[r] + (size_t)z * zstride);
-#pragma unroll
-      for (int r = 0; r < R; ++r) { s[r].x += v[r].x; s[r].y += v[r].y; s[r].z += v[r].z; s[r].w += v[r].w; }
-    }
-    const float4 cs = p.ln_stats ? *reinterpret_cast<const float4*>(p.ln_colsum + n) : make_float4(0, 0, 0, 0);
-#pragma unroll
-    for (int r = 0; r < R; ++r) {
-      const int m = row_of(r);
-      if (m >= p.M) continue;
-      if (p.ln_stats) {
-        float rr, rm;
-        ln_row_factors(p, m, rr, rm);
-        s[r].x = s[r].x * rr - rm * cs.x; s[r].y = s[r].y * rr - rm * cs.y;
-        s[r].z = s[r].z * rr - rm * cs.z; s[r].w = s[r].w * rr - rm * cs.w;
-      }
-      float fin[4];
-      store4(p, m, n, s[r].x, s[r].y, s[r].z, s[r].w, fin);
-#pragma unroll
-      for (int e = 0; e < 4; ++e) {      // both kinds of statistics are those of the STORED values (the fp32 output: as they are)
-        const float q = bf2f(f2bf(fin[e])), g = (p.out_mode == OUT_F32) ? fin[e] : q;
-        gs[e] += g; gq[e] += g * g;
-        rsum[r] += q; rsq[r] += q * q;
-      }
-    }
-  }
-  if (p.row_stats) {
-#pragma unroll
-    for (int r = 0; r < R; ++r) rowp[ty + 16 * r][tx] = make_float2(rsum[r], rsq[r]);
-    __syncthreads();
-    if ((int)threadIdx.x < ROWS && mbase + (int)threadIdx.x < p.M) {
-      int nq = (p.N - blockIdx.x * W + 3) / 4;
-      if (nq > QW) nq = QW;
-      float a = 0.f, q = 0.f;
-      for (int t = 0; t < nq; ++t) { a += rowp[threadIdx.x][t].x; q += rowp[threadIdx.x][t].y; }
-      *reinterpret_cast<float2*>(p.row_stats + ((size_t)blockIdx.x * p.M + mbase + threadIdx.x) * 2) = make_float2(a, q);
-    }
-  }
-  if (p.gn_stats) {
-#pragma unroll
-    for (int e = 0; e < 4; ++e) colp[ty][tx * 4 + e] = make_float2(gs[e], gq[e]);
-    __syncthreads();
-    // two levels, each in index order: column totals over the 16 row lanes (one thread per column), then the bin's columns — a chain
-    // of 16 + gn_cg additions instead of 16 x gn_cg on the 2 x bins threads that finish the block (640 at 40 channels per group)
-    __shared__ float2 colt[W];
-    if ((int)threadIdx.x < W) {
-      float a = 0.f, q = 0.f;
-#pragma unroll
-      for (int r = 0; r < 16; ++r) { const float2 v = colp[r][threadIdx.x]; a += v.x; q += v.y; }
-      colt[threadIdx.x] = make_float2(a, q);
-    }
-    __syncthreads();
-    const int bins_blk = W / p.gn_cg;            // gemm_fused_gn_ok(): W % gn_cg == 0
-    if ((int)threadIdx.x < 2 * bins_blk && mbase < p.M) {
-      const int which = threadIdx.x & 1, lb = threadIdx.x >> 1;
-      const int bin = blockIdx.x * bins_blk + lb;
-      if (bin < p.gn_groups) {
-        float a = 0.f;
-        for (int c = 0; c < p.gn_cg; ++c) { const float2 v = colt[lb * p.gn_cg + c]; a += which ? v.y : v.x; }
-        const int b = mbase / p.rows_per_batch;
-        const int slab = (mbase - b * p.rows_per_batch) / ROWS;
-        const int nslab = p.rows_per_batch / ROWS;
-        p.gn_stats[(((size_t)b * nslab + slab) * p.gn_groups + bin) * 2 + which] = a;
-      }
-    }
-  }
-}
-
-template <int RPT, int W>
-__global__ __launch_bounds__(4 * W) void gemm_splitk_reduce_gn_kernel(const GemmArgs p) {
-  kernarg_warm<sizeof(GemmArgs)>();
-  __shared__ float2 part[16][W / 4];     // per (row lane, column quad) {sum, sum of squares} over the thread's rows
-  __shared__ float2 quad[W / 4];         // per column quad, over the 16 row lanes
-  __shared__ float2 mr[W / 4];           // per group of the block: {mean, rstd}   (fn_cg >= 4)
-  splitk_finish_unit<RPT, W>(p, blockIdx.y, blockIdx.x * W, threadIdx.x, part, quad, mr, false);
-}
-// blocks of 40 columns where 80-column blocks would leave half the CUs without one and the groups / bins allow it
-static inline int reduce_gn_width(const GemmArgs& a) {
-  const bool ok40 = 40 % a.fn_cg == 0 && (a.gn_stats == nullptr || 40 % a.gn_cg == 0) && a.N % 40 == 0;
-  if (!ok40) return 80;
-  return ((int64_t)(a.N / 80) * (a.M / a.rows_per_batch) < 256) ? 40 : 80;
-}
-// geometries the fused reducer takes: whole samples of 64 or 256 rows, 80-column blocks of whole groups, the plain bf16 epilogue
-bool gemm_fused_norm_ok(const GemmArgs& a) {
-  const int rows = a.rows_per_batch;
-  const int M = (a.conv && a.ups == 2) ? 0 : a.M;      // (not the 4-tap upsample form: its partials are filed per parity class)
-  return (rows == 64 || rows == 256) && M > 0 && M % rows == 0 && a.N % 80 == 0 && a.fn_cg >= 4 && a.fn_cg % 4 == 0 && 80 % a.fn_cg == 0 &&
-         a.out_mode == OUT_BF16 && a.act == ACT_NONE && !a.resid_f32 && !a.row_stats && !a.ln_stats && a.alpha == 1.f && a.ldc == a.N &&
-         (a.gn_stats == nullptr || (a.gn_cg >= 4 && a.gn_cg % 4 == 0 && 80 % a.gn_cg == 0));
-}
-
-// width of the split-K reducer's blocks: 80 when the fused GroupNorm bins do not divide 64 (UNet: 5 / 10 / 20 / 40 channels)
-// (160 where N allows: a block row is then 640 B = five whole 128-B lines of a partial slice; 80-wide blocks read 320-B pieces, every
-// other one straddling a line: loop 568.3 -> 562.5 ms, profiles/r02_big_tile.md)
-static inline int reduce_width(const GemmArgs& a) {
-  if (a.gn_stats && 64 % a.gn_cg != 0) return (a.N % 160 == 0 && 160 % a.gn_cg == 0) ? 160 : 80;
-  return 64;
-}
-// rows per block of the reducer: 64 for large outputs, 16 when there would be too few blocks to pull the partials
-// (32-row blocks where they would still give every CU two blocks: measured equal, 536.2 vs 536.3 ms on the loop — not kept)
-static inline int reduce_rows(const GemmArgs& a) {
-  return ((int64_t)cdiv(a.N, reduce_width(a)) * cdiv(a.M, 64) >= 1024) ? 64 : 16;
-}
 // Long-K plain GEMMs whose width tiles by 160 (the feed-forward output GEMMs of UNet levels 1-3: K = 5 C) run on the convolutions'
 // ping-pong kernel too: their 64 x 160 / 128 x 160 four-wave tiles fetch 22 / 14 KiB per MFLOP through a 64 B/clk L2 port, the 8-wave
 // tiles 14 / 10 (round 4 A/B: 57 -> 43 us at level 1, loop -0.5 %)
@@ -1698,7 +1203,7 @@ int gemm_row_planes(const GemmArgs& a) {
   return 2 * cdiv(a.N, tile_width(a));
 }
 int gemm_gn_slab_rows(const GemmArgs& a) {
-  if (a.splitk > 1 && (a.fn_Y || gemm_coop_ok(a))) return a.rows_per_batch;      // the fused reducer / the in-kernel finish files one partial per (sample, bin)
+  if (a.splitk > 1 && a.fn_Y) return a.rows_per_batch;      // the fused reducer files one partial per (sample, bin)
   return a.splitk > 1 ? reduce_rows(a) : GN_SLAB_ROWS;
 }
 bool gemm_fused_gn_ok(int N, int cg) {
@@ -1727,42 +1232,28 @@ static int device_cus() {
   return n;
 }
 // rows of the ping-pong tile gemm_launch_bn() runs this launch on (0: it is not a ping-pong launch, or a form COOP does not take)
-static int coop_tile_rows(const GemmArgs& a, int sk) {
-  if (a.N % 160 != 0) return 0;
-  const int tiles_n = a.N / 160;
-  if (a.conv) {
-    if (a.ups || !gemm_conv_pingpong(a.M, a.N)) return 0;      // (upsample forms: parity classes in blockIdx.z / a 9-tap gather — their finish stays a launch)
-    return ((int64_t)cdiv(a.M, 256) * tiles_n * sk <= 128 && a.M % 128 == 0) ? 128 : 256;
-  }
-  if (!gemm_plain_pingpong_args(a)) return 0;
-  return ((int64_t)cdiv(a.M, 256) * tiles_n * sk <= 128 || a.M % 256 != 0) ? 128 : 256;
+static int coop_tile_rows(const GemmArgs& a) {
+  // (convolutions only; upsample forms: parity classes in blockIdx.z / a 9-tap gather — their finish stays a launch)
+  if (!a.conv || a.ups || a.N % 160 != 0 || !gemm_conv_pingpong(a.M, a.N)) return 0;
+  return ((int64_t)cdiv(a.M, 256) * (a.N / 160) <= 128 && a.M % 128 == 0) ? 128 : 256;
 }
-// GILL_GEMM_COOP = 0: every finish as its own launch (split-K reducers, GroupNorm-apply), the round-5 dataflow (A/B and the on / off parity test);
-// 1 (default): the GroupNorm finish in the 3x3 convolutions' epilogue (EPI 6: a measured go); 2: also the split-K finish (EPI 7: a measured no-go)
+// GILL_GEMM_COOP = 0: every finish as its own launch (GroupNorm-apply), the round-5 dataflow (A/B and the on / off parity test);
+// anything else (default 1): the GroupNorm finish in the 3x3 convolutions' epilogue (EPI 6).  Split-K GEMMs always finish in the reducer launch
+// (the in-kernel form measured slower: profiles/r06_coop_finish.md).
 int gemm_coop_mode() {
   static const int mode = [] { const char* e = getenv("GILL_GEMM_COOP"); return e ? atoi(e) : 1; }();
   return mode;
 }
 bool gemm_coop_ok(const GemmArgs& a) {
-  if (!a.coop_ctr || gemm_coop_mode() == 0) return false;
-  const int sk = a.splitk > 1 ? a.splitk : 1;
-  if (sk > 1 && !a.coop_splitk) return false;
-  const int bm = coop_tile_rows(a, sk);
+  if (!a.coop_ctr || gemm_coop_mode() == 0 || a.splitk > 1) return false;
+  const int bm = coop_tile_rows(a);
   const int rpb = a.rows_per_batch;
   if (bm == 0 || rpb <= 0 || a.M % bm != 0 || a.M % rpb != 0) return false;
   // co-residency: the waiting workgroups must all be on the chip — one per CU (the ping-pong tiles take a CU's whole LDS), so the grid may not
   // exceed the CU count (MI355X: 256; a device with fewer falls back to the launches)
-  if ((int64_t)(a.M / bm) * (a.N / 160) * sk > device_cus()) return false;
+  if ((int64_t)(a.M / bm) * (a.N / 160) > device_cus()) return false;
   if (a.out_mode != OUT_BF16 || a.act != ACT_NONE || a.resid_f32 || a.row_stats || a.ln_stats || a.alpha != 1.f || a.wb_rows || a.partials_only || a.w_blk64)
     return false;
-  if (sk > 1) {
-    // split-K finish: (whole sample, 40 columns) units on the 128 x 160 tile, the reducer's geometries (64 / 256 rows per sample)
-    if (bm != 128 || !(rpb == 64 || rpb == 256) || a.fn_ss) return false;
-    if (a.fn_Y) { if (a.fn_cg < 4 || a.fn_cg % 4 != 0 || 40 % a.fn_cg != 0 || !a.fn_gamma || !a.fn_beta) return false; }
-    else if (!a.C) return false;
-    if (a.gn_stats && (a.gn_cg < 4 || a.gn_cg % 4 != 0 || 40 % a.gn_cg != 0)) return false;
-    return true;
-  }
   // GroupNorm finish in the convolution's epilogue: whole M tiles per sample, <= 64 slab partials per bin (the apply kernel's own limit),
   // <= 32 bins per N tile, groups made of whole bins inside one N tile
   if (!a.conv || (!a.fn_Y && !a.fn_ss) || !a.fn_gamma || !a.fn_beta) return false;
@@ -1849,30 +1340,6 @@ int gemm_pick_splitk(int M, int N, int K, int act, bool plain, bool generic) {
   return s;
 }
 
-int gemm_splitk_reduce_launch(const GemmArgs& a, hipStream_t s) {
-  GILL_REQUIRE(a.splitk > 1 && a.ws != nullptr, "split-K reducer: no partials");
-  if (a.fn_Y) {
-    GILL_REQUIRE(gemm_fused_norm_ok(a) && a.fn_gamma && a.fn_beta, "split-K reducer: unsupported fused GroupNorm geometry");
-    const int w = reduce_gn_width(a);
-    const dim3 rg(a.N / w, a.M / a.rows_per_batch);
-    if (a.rows_per_batch == 256 && w == 80) hipLaunchKernelGGL((gemm_splitk_reduce_gn_kernel<16, 80>), rg, dim3(320), 0, s, a);
-    else if (a.rows_per_batch == 256) hipLaunchKernelGGL((gemm_splitk_reduce_gn_kernel<16, 40>), rg, dim3(160), 0, s, a);
-    else if (w == 80) hipLaunchKernelGGL((gemm_splitk_reduce_gn_kernel<4, 80>), rg, dim3(320), 0, s, a);
-    else hipLaunchKernelGGL((gemm_splitk_reduce_gn_kernel<4, 40>), rg, dim3(160), 0, s, a);
-    GILL_CHECK_HIP(hipGetLastError());
-    return 0;
-  }
-  const int rw = reduce_width(a), rr = reduce_rows(a);
-  const dim3 rg(cdiv(a.N, rw), cdiv(a.M, rr));
-  if (rw == 160 && rr == 64) hipLaunchKernelGGL((gemm_splitk_reduce_kernel<160, 4>), rg, dim3(640), 0, s, a);
-  else if (rw == 160) hipLaunchKernelGGL((gemm_splitk_reduce_kernel<160, 1>), rg, dim3(640), 0, s, a);
-  else if (rw == 80 && rr == 64) hipLaunchKernelGGL((gemm_splitk_reduce_kernel<80, 4>), rg, dim3(320), 0, s, a);
-  else if (rw == 80) hipLaunchKernelGGL((gemm_splitk_reduce_kernel<80, 1>), rg, dim3(320), 0, s, a);
-  else if (rr == 64) hipLaunchKernelGGL((gemm_splitk_reduce_kernel<64, 4>), rg, dim3(256), 0, s, a);
-  else hipLaunchKernelGGL((gemm_splitk_reduce_kernel<64, 1>), rg, dim3(256), 0, s, a);
-  GILL_CHECK_HIP(hipGetLastError());
-  return 0;
-}
 
 template <int NWV, int BN, int CONV, int EPI, int STAGES, int KT = BK, int MI = 4>
 static int gemm_launch_inst(const GemmDev& d, dim3 grid, hipStream_t s) {
@@ -2056,11 +1523,11 @@ static int gemm_launch_bn(const GemmArgs& a, hipStream_t s) {
   GILL_REQUIRE(a.wb_rows == 0 || (a.wb_rows % ((d.nwv / 2) * d.mi * 16) == 0 && !a.conv), "per-sample weights: tiles must not straddle samples");
   dim3 grid(tiles_m * d.groups_n, sk, ncls);
   if (d.nwv == 8) GILL_REQUIRE(d.npw == 1, "internal: the ping-pong kernel walks one N tile per workgroup");
-  // COOP: the finish inside this launch (EPI 6: GroupNorm in the conv epilogue; EPI 7: the split-K reduction) — no second launch
+  // COOP: the finish inside this launch (EPI 6: GroupNorm in the conv epilogue) — no second launch
   bool coop = false;
   if constexpr (BN == 160) {
     coop = gemm_coop_ok(d.a);
-    if (coop) GILL_REQUIRE(d.nwv == 8 && (d.nwv / 2) * d.mi * 16 == coop_tile_rows(d.a, sk) && (sk == 1 || d.mi == 2) && ncls == 1,
+    if (coop) GILL_REQUIRE(d.nwv == 8 && (d.nwv / 2) * d.mi * 16 == coop_tile_rows(d.a) && ncls == 1,
                            "internal: gemm_coop_ok() and the launcher disagree about the tile");
   }
   GILL_REQUIRE(coop || sk > 1 || (a.fn_Y == nullptr && a.fn_ss == nullptr), "fused GroupNorm output without a split-K reducer or an in-kernel finish");
@@ -2073,8 +1540,7 @@ static int gemm_launch_bn(const GemmArgs& a, hipStream_t s) {
       else GILL_TRY((gemm_launch_stages<BN, 2, 0>(d, grid, s)));
     } else if (coop) {
       if constexpr (BN == 160) {
-        if (sk > 1) GILL_TRY((gemm_launch_inst<8, 160, 1, 7, 3, BK, 2>(d, grid, s)));
-        else if (d.mi == 2) GILL_TRY((gemm_launch_inst<8, 160, 1, 6, 3, BK, 2>(d, grid, s)));
+        if (d.mi == 2) GILL_TRY((gemm_launch_inst<8, 160, 1, 6, 3, BK, 2>(d, grid, s)));
         else GILL_TRY((gemm_launch_inst<8, 160, 1, 6, 3, BK, 4>(d, grid, s)));
       }
     } else {
@@ -2082,10 +1548,7 @@ static int gemm_launch_bn(const GemmArgs& a, hipStream_t s) {
       else GILL_TRY((gemm_launch_stages<BN, 1, 0>(d, grid, s)));
     }
   } else {
-    if (sk > 1 && coop) {
-      if constexpr (BN == 160) GILL_TRY((gemm_launch_inst<8, 160, 0, 7, 3, BK, 2>(d, grid, s)));
-    }
-    else if (sk > 1) GILL_TRY((gemm_launch_stages<BN, 0, 2>(d, grid, s)));
+    if (sk > 1) GILL_TRY((gemm_launch_stages<BN, 0, 2>(d, grid, s)));
     else if (a.act == ACT_GEGLU) {
       if constexpr (BN == 128) GILL_TRY((gemm_launch_stages<BN, 0, 1>(d, grid, s)));
       else GILL_REQUIRE(BN == 128, "internal: GEGLU runs on 128-wide tiles");
@@ -2098,7 +1561,7 @@ static int gemm_launch_bn(const GemmArgs& a, hipStream_t s) {
     else if (a.act == ACT_NONE && a.out_mode == OUT_BF16 && !a.resid_f32) GILL_TRY((gemm_launch_stages<BN, 0, 4>(d, grid, s)));
     else GILL_TRY((gemm_launch_stages<BN, 0, 0>(d, grid, s)));
   }
-  if (sk > 1 && !a.partials_only && !coop) return gemm_splitk_reduce_launch(red, s);
+  if (sk > 1 && !a.partials_only) return gemm_splitk_reduce_launch(red, s);
   return 0;
 }
 

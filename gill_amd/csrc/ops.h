@@ -56,7 +56,7 @@ struct GemmArgs {
   // gemm_gn_slab_rows() (64, or 16 when a split-K reducer with small blocks produces them), nslab = rows_per_batch / that
   // (row-major epilogue only; the tile width must be a multiple of gn_cg: gemm_fused_gn_ok())
   // Statistics source: the in-kernel epilogue and the plain split-K reducer sum the values as stored.  Two producers of this layout still sum the fp32
-  // values BEFORE their rounding to bf16 (~1e-4 of a sum away): the fused-norm reducer / in-kernel split-K finish (gemm.hip splitk_finish_unit, one slab
+  // values BEFORE their rounding to bf16 (~1e-4 of a sum away): the fused-norm reducer (gemm_reduce.hip splitk_finish_unit, one slab
   // per sample) and the fp8 convolution's epilogue (conv_fp8.hip); a two-source consumer may therefore read one block of each kind.
   float* gn_stats = nullptr; int gn_groups = 0; int gn_cg = 0;
   // LayerNorm folded into the NEXT GEMM: LN(x) W^T + b = rstd (x (g*W)^T - mean * colsum(g*W)) + (beta W^T + b).
@@ -75,30 +75,28 @@ struct GemmArgs {
   int wb_rows = 0; int64_t wb_stride = 0; int vb_stride = 0;
   // OUT_SOFTMAX80 (folded-LayerNorm consumer, like OUT_QKV): C[m][80 h .. 80 h + 79] = softmax over the 80 columns of group h of
   // exp2-domain scores rstd (A W^T - mean colsum) + bias; N % 160 == 0; no split-K.  Columns that must not take part carry bias -1e30.
-  // split-K only: the GroupNorm (+ SiLU) that consumes this output, run by the reducer itself (gemm.hip "REDUCE + GROUPNORM"):
+  // split-K only: the GroupNorm (+ SiLU) that consumes this output, run by the reducer itself (gemm_reduce.hip "REDUCE + GROUPNORM"):
   // fn_Y [M][N] bf16 = [silu]((C - mean) * rstd * fn_gamma + fn_beta) with mean / rstd over (rows_per_batch rows, fn_cg channels).
   // C may then be null (the raw tensor has no other reader).  gemm_fused_norm_ok() says which geometries the reducer takes.
   bf16_t* fn_Y = nullptr; const float* fn_gamma = nullptr; const float* fn_beta = nullptr; float fn_eps = 1e-5f; int fn_silu = 0; int fn_cg = 0;
-  // COOP (gemm.hip "COOP"): the finish that used to be a second launch, done by the producing kernel's own workgroups, which wait for each other on
-  // an arrival counter — legal because the grid is at most one workgroup per CU (gemm_coop_ok() checks it against the device), i.e. co-resident.
-  //   splitk > 1: every workgroup publishes its fp32 partial tile (write-through), arrives on the counter of its (sample group, N tile), and once all
-  //     slices have arrived finishes one (sample, 40-column) unit exactly as the stand-alone reducer would (slices summed in slice order, bias / row
-  //     vector / residual, GroupNorm partials, and the consuming GroupNorm when fn_Y is set): no reducer launch;
-  //   splitk == 1 (3x3 convolutions on the ping-pong tiles): the epilogue publishes its per-slab GroupNorm partials (gn_stats), waits for the other
+  // COOP (gemm.hip "COOP"): the GroupNorm finish that used to be a second launch, done by the producing kernel's own workgroups, which wait for each other
+  // on an arrival counter — legal because the grid is at most one workgroup per CU (gemm_coop_ok() checks it against the device), i.e. co-resident.
+  //   splitk == 1 only (3x3 convolutions on the ping-pong tiles): the epilogue publishes its per-slab GroupNorm partials (gn_stats), waits for the other
   //     M tiles of its (sample, N tile), totals them in the consumer's order and writes fn_Y = [silu](GroupNorm(C)) straight from the accumulators
   //     (C itself only when non-null), and / or the per-(sample, channel) scale | shift table fn_ss [B][2][N] (what lnproj.hip applies on load).
+  //   (The same hand-off for the split-K reduction measured slower than the reducer launch — profiles/r06_coop_finish.md — and is not in the product.)
   // coop_ctr: one zeroed 32-bit counter per (sample group, N tile) of THIS launch (gemm_coop_counters() says how many).
   unsigned* coop_ctr = nullptr; float* fn_ss = nullptr;
-  // coop_splitk: also allow the split-K finish (EPI 7).  MEASURED NO-GO (profiles/r06_coop_finish.md: +1 ... +6 us per launch against conv + reducer,
-  // the loop +1.7 %): the engine sets it only under GILL_GEMM_COOP=2, the operator entry sets it on request (the parity tests, tools/coop_bench.py,
-  // tools/ubench/persist_resnet.hip build on it).
-  int coop_splitk = 0;
+  // Unused word (the flag of the removed in-kernel split-K finish lived here).  GemmArgs travels by value in every GEMM kernel's argument block:
+  // without it the struct is 8 bytes shorter, the argument offsets of all 63 gemm_kernel instantiations move and two of them change beyond the offsets
+  // (profiles/gemm_prune_isa.md).  The next field added takes its place.
+  int spare_word = 0;
 };
-// can this launch finish in-kernel (GemmArgs::coop_ctr)?  Geometry of the ping-pong tiles, whole samples per counter group, grid <= CUs of the device.
+// can this launch finish in-kernel (GemmArgs::coop_ctr)?  splitk == 1, geometry of the ping-pong tiles, whole samples per counter group, grid <= CUs of the device.
 bool gemm_coop_ok(const GemmArgs& a);
 int gemm_coop_counters(const GemmArgs& a);
 int gemm_coop_giveups(unsigned* count);      // read + clear the device-side give-up counter of the bounded waits (synchronous)
-int gemm_coop_mode();      // GILL_GEMM_COOP: 0 = every finish a launch of its own, 1 (default) = GroupNorm finish in the conv epilogue, 2 = + the split-K finish
+int gemm_coop_mode();      // GILL_GEMM_COOP: 0 = every finish a launch of its own, anything else (default 1) = GroupNorm finish in the conv epilogue
 bool gemm_fused_norm_ok(const GemmArgs& a);
 int gemm_launch(const GemmArgs& a, hipStream_t s);
 #define GN_SLAB_ROWS 64        // rows per fused GroupNorm-statistics partial of the in-kernel epilogue

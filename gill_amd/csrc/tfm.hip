@@ -4,7 +4,7 @@
 
 // REDUCE + RESIDUAL + LAYERNORM.  The narrow GEMMs of a layer (out_proj, fc2: N = D) run split-K; their reducer is also the natural place
 // for the LayerNorm that follows them (the next sub-block's pre-LN): one workgroup per row adds the row's fp32 partials in split order, the
-// bias and the fp32 residual stream (the order of gemm.hip's reducer epilogue), stores the new stream row, and — the row being complete in its
+// bias and the fp32 residual stream (the order of gemm_reduce.hip's reducer epilogue), stores the new stream row, and — the row being complete in its
 // registers — normalises it (two-pass variance like layernorm_kernel) into the bf16 operand of the next GEMM.  Two launches per layer gone
 // (the LayerNorm passes) and the stream row is not re-read.  Fixed summation order: bit-repeatable.  (tests/test_ends_gpu.py holds the stream row to
 // the bits of that order, and to the bits of the unfused way on the same operands.)

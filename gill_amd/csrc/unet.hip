@@ -437,7 +437,7 @@ struct UNetRun : ConvRun {
     return 0;
   }
   // The GroupNorm (+ SiLU) that consumes a GEMM's output, offered to the producer: a split-K launch of a supported geometry runs it in
-  // its reducer (gemm.hip "REDUCE + GROUPNORM") and sets `done`; otherwise the consumer runs its GroupNorm-apply as before.
+  // its reducer (gemm_reduce.hip "REDUCE + GROUPNORM") and sets `done`; otherwise the consumer runs its GroupNorm-apply as before.
   // raw_needed = false: nobody else reads the raw output (conv1 -> norm2 inside a ResnetBlock2D): it is not even written.
   // ss: (optional) the consumer wants the per-(sample, channel) scale | shift table [Bx][2][C] instead of a normalised copy (the level-0 transformer
   // blocks: lnproj.hip applies it to the rows it loads) — only the in-kernel finish (COOP) writes it; y is then unused.
@@ -478,7 +478,6 @@ struct UNetRun : ConvRun {
     // (split-K partials come from 128-row tiles: not where a sample's rows are fewer — the 8 x 8 maps of the mid block)
     if (g.out_mode == OUT_SOFTMAX80 || (g.wb_rows && g.wb_rows % 128 != 0)) g.splitk = 1;
     g.coop_ctr = ctr;
-    g.coop_splitk = gemm_coop_mode() >= 2;      // (the split-K finish in-kernel: a measured no-go, opt-in — GemmArgs::coop_splitk)
     if (fn) {
       g.rows_per_batch = fn->y.H * fn->y.W;
       g.fn_Y = fn->ss ? nullptr : fn->y.p; g.fn_ss = fn->ss;

@@ -110,7 +110,7 @@ def conv3x3_gn(x: torch.Tensor, w_oihw: torch.Tensor, bias: Optional[torch.Tenso
                groups: int = 32, eps: float = 1e-5, silu: bool = True, resid: Optional[torch.Tensor] = None, splitk: int = 2,
                want_raw: bool = True, coop: bool = True, rowvec: Optional[torch.Tensor] = None, want_table: bool = False, want_norm: bool = True):
   """3x3 convolution + the consuming GroupNorm (+ SiLU) without a GroupNorm launch of its own (include/gill_amd.h gill_op_conv3x3_gn):
-  splitk >= 2 in the split-K reducer (coop=False) or inside the convolution's launch (coop=True, where the geometry allows); splitk == 1 in the
+  splitk >= 2 in the split-K reducer launch (coop is ignored); splitk == 1 in the
   convolution's epilogue (coop=True) or as conv + GroupNorm-apply (coop=False, the reference dataflow).  x (B,H,W,Cin) bf16 NHWC, rowvec (B,Cout).
   Returns (y_raw or None, y_norm or None[, table (B,2,Cout) fp32 when want_table]) — outputs NaN-prefilled, so an unwritten element shows."""
   x = _bf(x)

@@ -473,8 +473,7 @@ int gill_op_conv3x3_ex(const void* x1, int C1, const void* x2, int C2, const flo
  * y_raw (optional, may be NULL) = conv(x) + bias + rowvec[b] + resid, y_norm = [silu](GroupNorm(y_raw)).
  * x (B,H,W,Cin) bf16 NHWC, w (Cout,Cin,3,3) fp32, rowvec (B,Cout) fp32 optional, gamma / beta (Cout) fp32.
  * splitk >= 2: H * W in {64, 256}, Cout % 80 == 0, Cout / groups a multiple of 4 that divides 80; the normalisation runs in the split-K reducer
- *   launch (coop = 0) or inside the convolution's own launch by its co-resident workgroups (coop = 1, where the grid fits the device's CUs and
- *   Cout % 160 == 0; otherwise as coop = 0).
+ *   launch; coop is ignored.
  * splitk == 1: coop = 1: in the convolution's epilogue (rows per sample a multiple of the 128- / 256-row tile, B * H * W % 256 == 0, Cout % 160 == 0,
  *   grid <= CUs; an error elsewhere); coop = 0: convolution with fused statistics + a GroupNorm-apply launch (the reference dataflow).
  * ss_out (optional; splitk == 1 && coop only): the scale | shift table [B][2][Cout] fp32 (y = x * scale + shift); y_norm may then be NULL.

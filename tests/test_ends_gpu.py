@@ -184,7 +184,7 @@ def test_reduce_ln_refuses_widths_off_the_vector_or_past_8192(cuda, D):
 # ---------------------------------------------------------------------------------------------------------------- fused against unfused linear
 @pytest.mark.parametrize("case", U.LINEAR_CASES, ids=str)
 def test_fused_reducer_gives_the_bits_of_the_gemm_reducer(cuda, case):
-  """tfm.hip's claim: opt_reduce_ln_kernel adds in the order of gemm.hip's reducer epilogue (slices in split order, bias, fp32 residual), so the
+  """tfm.hip's claim: opt_reduce_ln_kernel adds in the order of gemm_reduce.hip's reducer epilogue (slices in split order, bias, fp32 residual), so the
   stream is the same bit for bit whichever way TfmRun::linear runs; the two LayerNorms (one fused, one layernorm_kernel) agree to a bf16 ulp."""
   from gill_amd import ops
   M, N, K, sk = case

@@ -1,7 +1,7 @@
 #!/usr/bin/env python
-"""Operator-level timing of the round-6 in-kernel finishes (gemm.hip "COOP") against the launches they replace, on the UNet's shapes at the CFG
-batch 8: per shape the per-call time of gill_op_conv3x3_gn with coop=0 (split-K: conv + reducer that normalises; splitk 1: conv + GroupNorm-apply)
-and coop=1 (one launch).  Per-call time = (call at R2 repeats - call at R1 repeats) / (R2 - R1), HIP events (the wrapper's own work cancels).
+"""Operator-level timing of the round-6 in-kernel GroupNorm finish (gemm.hip "COOP") against the launches it replaces, on the UNet's non-split
+shapes at the CFG batch 8: per shape the per-call time of gill_op_conv3x3_gn with coop=0 (conv + GroupNorm-apply) and coop=1 (one launch).
+(Split-K shapes always finish in the reducer launch; their in-kernel numbers are in profiles/r06_coop_finish.md.)  Per-call time = (call at R2 repeats - call at R1 repeats) / (R2 - R1), HIP events (the wrapper's own work cancels).
   python tools/coop_bench.py            (GILL_XMAP=0 in the environment: the XCD range map instead of the block map)"""
 import os
 import sys
@@ -29,11 +29,6 @@ def per_call(fn):
 
 
 shapes = [   # B, H, W, Cin, Cout, splitk, note
-  (8, 8, 8, 1280, 1280, 8, "level 3 conv (mid / down3 resnets)"),
-  (8, 8, 8, 2560, 1280, 8, "level 3 up-block conv1 (concat input)"),
-  (8, 16, 16, 1280, 1280, 2, "level 2 conv"),
-  (8, 16, 16, 2560, 1280, 2, "level 2 up-block conv1 (concat input)"),
-  (8, 16, 16, 640, 1280, 2, "level 2 down-block conv1"),
   (8, 32, 32, 640, 640, 1, "level 1 conv"),
   (8, 32, 32, 1280, 640, 1, "level 1 up-block conv1"),
   (8, 64, 64, 320, 320, 1, "level 0 conv"),
