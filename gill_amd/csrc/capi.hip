@@ -6,6 +6,7 @@
 #include "convnet.h"
 #include "tfm.h"
 #include "xf_weights.h"
+#include "gemm_plan.h"
 #include <vector>
 
 static thread_local std::string g_last_error;
@@ -628,5 +629,58 @@ extern "C" int gill_op_lm_head_loss(const void* X_bf16, const void* W_bf16, cons
 extern "C" int gill_lm_loss_geometry(int M, int V, int D, int* row_tile, int* col_tile, int* n_slabs, int* cols_per_slab) {
   GILL_REQUIRE(M >= 1 && V >= 1 && D >= 32 && D % 32 == 0, "lm_loss_geometry: M, V >= 1 and D a positive multiple of 32");
   lm_loss_geometry(M, V, D, row_tile, col_tile, n_slabs, cols_per_slab);
+  return 0;
+}
+
+// ---- the GEMM launcher's plan, host only (gemm_plan.h; tests/test_gemm_plan_host.py)
+// case descriptor of gill_gemm_plan (include/gill_amd.h GILL_GEMM_PLAN_CASE_INTS): the GemmArgs fields a plan reads, pointers as 0 / 1 flags
+static void gemm_args_from_desc(const int32_t* c, GemmArgs* out) {
+  GemmArgs a;
+  int i = 0;
+  a.M = c[i++]; a.N = c[i++]; a.K = c[i++]; a.lda = c[i++]; a.ldc = c[i++]; a.ldr = c[i++]; a.K1 = c[i++]; a.conv = c[i++];
+  a.IH = c[i++]; a.IW = c[i++]; a.OH = c[i++]; a.OW = c[i++]; a.Cin = c[i++]; a.stride = c[i++]; a.ups = c[i++]; a.pad_shift = c[i++];
+  a.KX = c[i++]; a.KX1 = c[i++]; a.k_chunked = c[i++]; a.alpha = c[i++] ? 1.f : 0.5f; a.rows_per_batch = c[i++]; a.resid_f32 = c[i++];
+  a.act = c[i++]; a.out_mode = c[i++]; a.heads = c[i++]; a.dp = c[i++]; a.ntok = c[i++]; a.splitk = c[i++]; a.w_blk64 = c[i++];
+  a.partials_only = c[i++]; a.gn_groups = c[i++]; a.gn_cg = c[i++]; a.ln_planes = c[i++]; a.wb_rows = c[i++]; a.fn_cg = c[i++];
+  static float dummy[4];      // never dereferenced: a plan reads pointers as present / absent
+  auto flag = [&](int v) -> void* { return v ? (void*)dummy : nullptr; };
+  a.A = (const bf16_t*)flag(c[i++]); a.A2 = (const bf16_t*)flag(c[i++]); a.X1 = (const bf16_t*)flag(c[i++]); a.X2 = (const bf16_t*)flag(c[i++]);
+  a.W = (const bf16_t*)flag(c[i++]); a.bias = (const float*)flag(c[i++]); a.rowvec = (const float*)flag(c[i++]); a.resid = flag(c[i++]);
+  a.C = flag(c[i++]); a.ws = (float*)flag(c[i++]); a.gn_stats = (float*)flag(c[i++]); a.row_stats = (float*)flag(c[i++]);
+  a.ln_stats = (const float*)flag(c[i++]); a.ln_colsum = (const float*)flag(c[i++]); a.fn_Y = (bf16_t*)flag(c[i++]);
+  a.fn_gamma = (const float*)flag(c[i++]); a.fn_beta = (const float*)flag(c[i++]); a.coop_ctr = (unsigned*)flag(c[i++]); a.fn_ss = (float*)flag(c[i++]);
+  *out = a;
+}
+
+static_assert(GILL_GEMM_PLAN_ROW_INTS == 1 + GEMM_PLAN_INTS, "a row = the return code + the plan");
+extern "C" int gill_gemm_plan(const int32_t* cases, int n, int pp, int coop, int cus, int32_t* rows) {
+  GILL_REQUIRE(n >= 0 && (n == 0 || (cases != nullptr && rows != nullptr)), "gemm_plan: null case list or output");
+  const GemmEnv env = {pp, coop, cus};
+  for (int i = 0; i < n; ++i) {
+    GemmArgs a;
+    gemm_args_from_desc(cases + (size_t)i * GILL_GEMM_PLAN_CASE_INTS, &a);
+    GemmPlan p;
+    int32_t* r = rows + (size_t)i * GILL_GEMM_PLAN_ROW_INTS;
+    r[0] = gemm_plan(a, env, &p);      // (a refusal leaves the zero plan)
+    const int* v = reinterpret_cast<const int*>(&p);      // (GemmPlan is GEMM_PLAN_INTS ints, in the row's order)
+    for (int k = 0; k < GEMM_PLAN_INTS; ++k) r[1 + k] = v[k];
+  }
+  return 0;
+}
+extern "C" int gill_gemm_query(const int32_t* queries, int n, int pp, int coop, int cus, int32_t* answers) {
+  GILL_REQUIRE(n >= 0 && (n == 0 || (queries != nullptr && answers != nullptr)), "gemm_query: null query list or output");
+  const GemmEnv env = {pp, coop, cus};
+  for (int i = 0; i < n; ++i) {
+    const int32_t* q = queries + (size_t)i * 7;
+    switch (q[0]) {
+      case 0: answers[i] = gemm_pick_splitk_env(env, q[1], q[2], q[3], q[4], q[5] != 0, q[6] != 0); break;
+      case 1: answers[i] = gemm_pick_splitk_blk64_env(env, q[1], q[2], q[3]); break;
+      case 2: answers[i] = gemm_fused_gn_ok(q[1], q[2]) ? 1 : 0; break;
+      case 3: answers[i] = gemm_conv_pingpong_env(env, q[1], q[2]) ? 1 : 0; break;
+      case 4: answers[i] = conv_k_chunked_env(env, q[1], q[2], q[3]) ? 1 : 0; break;
+      case 5: answers[i] = gemm_stream64_weights(q[1], q[2]) ? 1 : 0; break;
+      default: GILL_REQUIRE(false, "gemm_query: unknown question");
+    }
+  }
   return 0;
 }

@@ -22,15 +22,15 @@
 // remapped (bijectively) to give every XCD a contiguous range of tiles — the N tiles of one M range
 // and the 3x3 halo rows of neighbouring M ranges then hit the same 4 MiB L2.
 #include "gemm_dev.h"
+#include "gemm_plan.h"
 #include <stdlib.h>
 
-#define BM_HOST 128       // rows of the 4-wave tile, for the host-side split-K heuristic; the kernel's BM is 32 * NWV
-#define BK 64
+#define BK GEMM_BK
 #define GEMM_THREADS 256
 
 // zeros read by padding taps; a row's pointer advances 128 B per K step within a (tap, source) segment, so the page
 // covers the longest segment (ZERO_PAGE_STEPS K steps) plus one 128-B row
-#define ZERO_PAGE_STEPS 127
+#define ZERO_PAGE_STEPS GEMM_ZERO_PAGE_STEPS
 __device__ __attribute__((aligned(256))) uint32_t g_zero_page_storage[(ZERO_PAGE_STEPS + 1) * 32];
 
 const bf16_t* gill_zero_page() {
@@ -99,14 +99,13 @@ __device__ __forceinline__ bool coop_wait(unsigned* ctr, unsigned target) {
 // NWV: waves per workgroup.  4 -> 128-row tile (waves 2 x 2).  2 -> 64-row tile (waves 1 x 2) for problems with so few
 // 128-row tiles that half the CUs would idle (UNet level 2-3 projections: M = 2048 / 512).
 // 8 -> 256-row tile (waves 4 x 2, one workgroup per CU).  BN = 160, STAGES = 3: the convolutions' ping-pong kernel.
-// BN = 256 (GILL_GEMM_BIG only): a K step fetches 64 KiB for 8.4 MFLOP — half the
-// bytes per FLOP of the 128 x 160 tile, whose 36.8 KiB per 2.6 MFLOP is 89 % of the 64 B/clk a CU can pull from L2 at the
-// MFMA peak — for the wide plain GEMMs (GEGLU, QKV) with enough 256 x 256 tiles to fill the chip.
-// KT: K elements per ring stage (64 | 32).  With a 2-deep ring the loads of stage t+1 can only be issued after the barrier of
-// stage t (their buffer is free from there): prefetch distance = one stage.  KT = 32 cuts the SAME 73.7 KiB of LDS into a
-// 4-deep ring of half-size stages: loads are issued three stages (1.5 K steps of 64) ahead and waited for with counted
-// s_waitcnt vmcnt(N), at the price of a barrier per 32-wide stage.  Measured: that price is higher than the gain (the
-// launcher keeps KT = 64 unless GILL_GEMM_KT = 32).
+// BN: 128 | 160 (general and ping-pong tiles), 64 (STREAM64).  (A 256 x 256 eight-wave tile for the wide plain GEMMs — half the bytes per FLOP of the
+// 128 x 160 tile, whose 36.8 KiB per 2.6 MFLOP is 89 % of the 64 B/clk a CU can pull from L2 at the MFMA peak — measured slower and is gone with
+// its switch: profiles/r02_big_tile.md.)
+// KT: K elements per ring stage.  Every instantiation has KT = 64 and the plan never asks for another (GemmPlan::k_kt, GemmDev::kt).  The
+// parameter is what is left of a 4-deep ring of 32-wide stages in the SAME 73.7 KiB of LDS — loads issued three stages ahead and waited for with
+// counted s_waitcnt vmcnt(N), at the price of a barrier per 32-wide stage; that price measured higher than the gain (+7 % on the loop) and the
+// switch that selected it is gone.  It stays a parameter because removing it renames and re-lays-out every kernel.
 // MI: 16-row M sub-tiles per wave (4 | 2).  MI = 2 with NWV = 4 is a 64-row tile on FOUR waves (2 x 2, wave tile 32 x BN/2) for the
 // small plain GEMMs: the same 48 KiB of LDS as the 2-wave 64 x 128 tile (three workgroups per CU), twice the waves per CU.
 // (The timing-only ablation guards of round 4 — PP_ABL: no fragment reads / no LDS-DMA / no MFMAs / no bookkeeping / no epilogue / no barriers —
@@ -171,7 +170,7 @@ __device__ __forceinline__ void gemm_tile(const GemmDev& d, const GemmTileCtx cx
   }
   const int m0 = tm * BM;
   const int tn_first = gn * d.npw;
-  // (convolutions and split-K partials: one N tile per workgroup — gemm_launch_bn() — known at compile time, so that the K walk's
+  // (convolutions and split-K partials: one N tile per workgroup — gemm_plan.hip plan_general() — known at compile time, so that the K walk's
   // state is dead by the epilogue instead of being carried around it for a next tile that never comes)
   const int ntl = (CONV != 0 || EPI == 2) ? 1 : ((d.tiles_n - tn_first < d.npw) ? d.tiles_n - tn_first : d.npw);   // N tiles of this workgroup
   int n0 = tn_first * BN;
@@ -1137,92 +1136,14 @@ __global__ __launch_bounds__(NWV * 64, NWV == 8 ? ((BN == 128 && STAGES == 2) ? 
   gemm_tile<NWV, BN, CONV, EPI, STAGES, KT, MI>(d, cx);
 }
 
-// Long-K plain GEMMs whose width tiles by 160 (the feed-forward output GEMMs of UNet levels 1-3: K = 5 C) run on the convolutions'
-// ping-pong kernel too: their 64 x 160 / 128 x 160 four-wave tiles fetch 22 / 14 KiB per MFLOP through a 64 B/clk L2 port, the 8-wave
-// tiles 14 / 10 (round 4 A/B: 57 -> 43 us at level 1, loop -0.5 %)
-// (round 6: ... and, from K = 640 up, the plain GEMMs whose ping-pong tiling is ONE full round of workgroups — proj_in / attn1.to_out of level 1 at the CFG batch 8,
-// 8192 x 640 x 640: 256 ping-pong workgroups, one per CU, instead of 320 four-wave 128 x 128 tiles of which 64 CUs get two; 17.4 -> 14.3 us stand-alone,
-// tools/pp_shortk_probe.py.  Fewer tiles than CUs (2048 x 1280 x 1280: 16.4 -> 18.3 us) and K = 320 (level 0: +-0) stay on the general tiles.)
+// ---- host half: the launcher.  Every decision about a launch is made in gemm_plan.hip (gemm_plan.h); this file supplies the process-wide environment,
+// fills GemmDev from the plan and maps the plan's template tuple to its instantiation.
+
 // GILL_GEMM_PP = 0 (A/B switch, read once): no ping-pong tiles for the convolutions, the short-K plain GEMMs and the QKV GEMMs (the long-K plain GEMMs keep them)
 static bool gemm_pp_switch() {
   static const int pp_env = [] { const char* v = getenv("GILL_GEMM_PP"); return v ? atoi(v) : 1; }();
   return pp_env != 0;
 }
-static bool gemm_plain_pingpong(int M, int N, int K) {
-  if (N % 160 != 0 || M % 128 != 0 || K % 64 != 0) return false;
-  if (K >= 2560) return true;
-  // workgroups the launcher will make of it (gemm_launch_bn: 128-row tiles when 256-row ones give at most 128): ONE balanced round only — with
-  // ten K steps a second, partial round costs more than the tile gains
-  const int64_t wg256 = (int64_t)cdiv(M, 256) * (N / 160);
-  const int64_t wg = (wg256 <= 128 || M % 256 != 0) ? (int64_t)(M / 128) * (N / 160) : wg256;
-  return gemm_pp_switch() && K >= 640 && wg >= 200 && wg <= 256;
-}
-
-// ... and the launch's other conditions (tile_width() and gemm_launch_bn() used to test different things): the 8-wave plain kernel has
-// the lean bf16 row-major epilogue only
-// (per-sample weights — GemmArgs::wb_rows, the cross-attention values GEMM — where samples are whole 256-row tiles: round 6, loop 441.8 -> 440.0 ms)
-static bool gemm_plain_pingpong_args(const GemmArgs& a) {
-  return !a.conv && gemm_plain_pingpong(a.M, a.N, a.K) && a.act == ACT_NONE && a.out_mode == OUT_BF16 && !a.resid_f32 && a.wb_rows % 256 == 0 && !a.ln_stats;
-}
-
-// QKV GEMMs (head-major scatter epilogue, folded LayerNorm) on the 256 x 160 ping-pong tiles where those give a balanced round of one workgroup per CU
-// (round 6): the workgroups fill >= 75 % of their last round of 256, and 128-row tiles would not fill theirs better.  Level 2 at the CFG batch 8
-// (2048 x 3840 x 1280: 192 workgroups) 52.5 -> 38.5 us per launch, loop -0.9 %.  Returns the wave M sub-tile count (4) or 0.
-// (Measured with it and not kept: the 128-row tiles where THEY are the balanced choice — level 1, 8192 x 1920 x 640, 768 workgroups = three rounds:
-// 46.9 -> 42.7 us per launch, and the loop gains nothing because the card then clocks 15 MHz lower, three boxes, profiles/r06_skeleton_ab.log.
-// Round 4 had these GEMMs on 128-wide ping-pong tiles at every level and lost 0.6-1 %: K = 320 at level 0 and the 1.5-round grids were in it.)
-static int gemm_qkv_pingpong_mi(const GemmArgs& a) {
-  if (!gemm_pp_switch() || a.conv || a.out_mode != OUT_QKV || a.N % 160 != 0 || a.M % 256 != 0 || a.K % 64 != 0 || a.K < 640 || a.splitk > 1 || a.wb_rows || a.w_blk64) return 0;
-  auto fill = [](int64_t wg) { return (double)wg / (double)(((wg + 255) / 256) * 256); };
-  const double f128 = fill((int64_t)(a.M / 128) * (a.N / 160)), f256 = fill((int64_t)(a.M / 256) * (a.N / 160));
-  // ONE round only: several rounds of these tiles (level 1 at UNet batch 16: 768 workgroups) make the kernel faster and the card clock lower, like the
-  // 128-row form at batch 8 — loop 764.6 ms without, 767.3 ms with, 15-35 MHz apart (profiles/r06_skeleton_ab.log, session r06_s33)
-  if ((int64_t)(a.M / 256) * (a.N / 160) > 256) return 0;
-  return (f256 >= 0.75 && f256 >= f128) ? 4 : 0;
-}
-
-// Tile width.  Tried and removed (numbers in profiles/r02_big_tile.md, profiles/r01_sweep_gemm_tiles.md): a 256 x 256 8-wave tile for
-// the wide plain GEMMs (GEGLU 94 -> 100 us, QKV 46.6 -> 48.3 us: those kernels are bound by their epilogues), a 4-deep ring of
-// 32-wide K stages (+7 % on the loop), a 3-deep ring on the 4-wave tiles.
-static inline int tile_width(const GemmArgs& a) {
-  if (a.act == ACT_GEGLU) return 128;
-  // measured on MI355X (profiles/r01_sweep_gemm_tiles.md): the 128x160 tile (5 N sub-tiles per wave: more MFMAs per LDS
-  // byte) beats 128x128 by 15-40 % on every UNet width, all of which are multiples of 160
-  int bn = (a.N % 160 == 0) ? 160 : 128;
-  // ... and except for the head-major scatter epilogue (QKV / to_q), whose columns fall into 48..160-wide heads: 128-wide tiles
-  // measured 579.3 -> 576.3 ms on the loop
-  if (!a.conv && a.out_mode == OUT_QKV && a.N % 128 == 0 && !gemm_qkv_pingpong_mi(a)) bn = 128;
-  // ... except on the 64-row tile (plain GEMMs with few tiles, see gemm_launch_bn): 64 x 128 needs 48 KiB of LDS, i.e. three
-  // workgroups (six waves) per CU instead of two (four) — loop 587.3 -> 584.7 ms
-  if (!a.conv && a.splitk <= 1 && a.N % 128 == 0 && !a.gn_stats && (int64_t)cdiv(a.M, 128) * cdiv(a.N, 160) < 300 && a.M > 64 && a.out_mode != OUT_SOFTMAX80 &&
-      !gemm_plain_pingpong_args(a)) bn = 128;
-  return bn;
-}
-int gemm_row_planes(const GemmArgs& a) {
-  if (a.splitk > 1) return cdiv(a.N, reduce_width(a));
-  return 2 * cdiv(a.N, tile_width(a));
-}
-int gemm_gn_slab_rows(const GemmArgs& a) {
-  if (a.splitk > 1 && a.fn_Y) return a.rows_per_batch;      // the fused reducer files one partial per (sample, bin)
-  return a.splitk > 1 ? reduce_rows(a) : GN_SLAB_ROWS;
-}
-bool gemm_fused_gn_ok(int N, int cg) {
-  if (cg < 1 || N % cg != 0 || N / cg > 64) return false;
-  const int bn = (N % 160 == 0) ? 160 : 128;
-  // in-kernel epilogue: bins must not straddle N tiles; split-K reducer: nor its 64- or 80-column blocks
-  return bn % cg == 0 && (64 % cg == 0 || (80 % cg == 0 && N % 80 == 0));
-}
-
-
-// 3x3 convolutions whose row count is a multiple of 256 and whose width tiles by 160 run on the 256 x 160 ping-pong kernel
-// (GILL_GEMM_PP = 0: two co-resident 128 x 160 workgroups instead, the round-1 structure)
-// (round 4: 256 x 128 ping-pong tiles for the widths 160 does not divide — the VAE decoder's 128 / 256 / 512-channel convolutions: 484.8 /
-// 403.2 / 303.9 us against 464.8 / 406.1 / 301.0 us on the four-wave 128 x 128 tiles, VAE decode 12.74 vs 12.69 ms.  Not kept.)
-bool gemm_conv_pingpong(int rows_multiple_of, int Cout) {
-  return gemm_pp_switch() && rows_multiple_of % 256 == 0 && Cout % 160 == 0;
-}
-
-// ---- COOP (GemmArgs::coop_ctr): which launches may finish in-kernel.
 static int device_cus() {
   static const int n = [] {
     int dev = 0, v = 0;
@@ -1231,38 +1152,17 @@ static int device_cus() {
   }();
   return n;
 }
-// rows of the ping-pong tile gemm_launch_bn() runs this launch on (0: it is not a ping-pong launch, or a form COOP does not take)
-static int coop_tile_rows(const GemmArgs& a) {
-  // (convolutions only; upsample forms: parity classes in blockIdx.z / a 9-tap gather — their finish stays a launch)
-  if (!a.conv || a.ups || a.N % 160 != 0 || !gemm_conv_pingpong(a.M, a.N)) return 0;
-  return ((int64_t)cdiv(a.M, 256) * (a.N / 160) <= 128 && a.M % 128 == 0) ? 128 : 256;
-}
 // GILL_GEMM_COOP = 0: every finish as its own launch (GroupNorm-apply), the round-5 dataflow (A/B and the on / off parity test);
-// anything else (default 1): the GroupNorm finish in the 3x3 convolutions' epilogue (EPI 6).  Split-K GEMMs always finish in the reducer launch
-// (the in-kernel form measured slower: profiles/r06_coop_finish.md).
+// anything else (default 1): the GroupNorm finish in the 3x3 convolutions' epilogue (EPI 6) — gemm_plan.hip plan_coop()
 int gemm_coop_mode() {
   static const int mode = [] { const char* e = getenv("GILL_GEMM_COOP"); return e ? atoi(e) : 1; }();
   return mode;
 }
-bool gemm_coop_ok(const GemmArgs& a) {
-  if (!a.coop_ctr || gemm_coop_mode() == 0 || a.splitk > 1) return false;
-  const int bm = coop_tile_rows(a);
-  const int rpb = a.rows_per_batch;
-  if (bm == 0 || rpb <= 0 || a.M % bm != 0 || a.M % rpb != 0) return false;
-  // co-residency: the waiting workgroups must all be on the chip — one per CU (the ping-pong tiles take a CU's whole LDS), so the grid may not
-  // exceed the CU count (MI355X: 256; a device with fewer falls back to the launches)
-  if ((int64_t)(a.M / bm) * (a.N / 160) > device_cus()) return false;
-  if (a.out_mode != OUT_BF16 || a.act != ACT_NONE || a.resid_f32 || a.row_stats || a.ln_stats || a.alpha != 1.f || a.wb_rows || a.partials_only || a.w_blk64)
-    return false;
-  // GroupNorm finish in the convolution's epilogue: whole M tiles per sample, <= 64 slab partials per bin (the apply kernel's own limit),
-  // <= 32 bins per N tile, groups made of whole bins inside one N tile
-  if (!a.conv || (!a.fn_Y && !a.fn_ss) || !a.fn_gamma || !a.fn_beta) return false;
-  if (!a.gn_stats || a.gn_cg <= 0 || 160 % a.gn_cg != 0 || 160 / a.gn_cg > 32 || a.gn_cg * a.gn_groups != a.N) return false;
-  if (a.fn_cg <= 0 || a.fn_cg % a.gn_cg != 0 || 160 % a.fn_cg != 0) return false;
-  if (rpb % bm != 0 || rpb % GN_SLAB_ROWS != 0 || rpb / GN_SLAB_ROWS > 64) return false;
-  return true;
+GemmEnv gemm_env_default() {
+  GemmEnv e;
+  e.pp = gemm_pp_switch() ? 1 : 0; e.coop = gemm_coop_mode(); e.cus = device_cus();
+  return e;
 }
-int gemm_coop_counters(const GemmArgs& a) { return cdiv(a.M, 128) * cdiv(a.N, 160); }     // (an upper bound: one per 128-row tile)
 // Reads and clears the give-up count of the in-kernel finishes (a small synchronous copy: call it where the host waits anyway).  Non-zero means
 // outputs of an earlier launch were NaN-poisoned because waiting workgroups were not co-resident: this process shared the GPU with another stream
 // or process that ALSO ran waiting workgroups (two of them can starve each other for CUs).  The contract is exclusive use of the device by ONE
@@ -1280,68 +1180,7 @@ int gemm_coop_giveups(unsigned* count) {
   return 0;
 }
 
-bool conv_k_chunked(int HW, int Cin, int Cout) {
-  return HW >= 4096 && (int64_t)HW * Cin * 2 > (int64_t)4 << 20 && !gemm_conv_pingpong(HW, Cout);
-}
-
-// STREAM64.  Weight-streaming GEMMs (a few hundred rows against 33-134 MB matrices: OPT-6.7b at <= 8 prompts) ran at 2.2-3 TB/s of weights on
-// the general tiles, whatever the ring depth (profiles/r05_opt_stream64.md: 128 x 64 tiles with a 6-deep ring streamed no faster than 64 x 128
-// tiles with a 3-deep one): a K step fetched 64-128 weight ROWS of 128 B each at a stride of 2 K bytes, i.e. one DRAM page activation per 128 B.
-// STREAM64 changes the layout, not only the tile: the matrix is stored at load time as [N / 64][K / 64][64][64] (gemm_stream64_weights() says
-// which matrices; convert_to_bf16_blk64_launch() writes them), so the 128 x 64 tile's weight stage is one contiguous 8 KiB run, a workgroup's
-// whole K walk one contiguous K * 128 B stream, fetched with the non-temporal policy (MI355X_MICROARCH "nt-weights") into a 6-deep ring
-// (144 KiB, one workgroup of eight waves per CU, 40 KiB of weights + 80 KiB of L2-resident activations in flight per CU).  All rows of a <= 128-row problem
-// sit in the one M tile (every weight is read once); more rows = more M tiles next to each other on one XCD (n_major), sharing the L2.
-// No split for >= 160 workgroups; narrower matrices split K to ~256 workgroups.  (The A/B switch of round 5 is gone: row-major weights on the general
-// tiles measured 5.95-6.08 ms for the OPT stage against 4.31 ms, profiles/r05_opt_stream64.md.)
-bool gemm_stream64_weights(int N, int K) {
-  return N % 64 == 0 && K % 64 == 0 && K >= 1024 && (int64_t)N * K >= ((int64_t)4 << 20);
-}
-int gemm_pick_splitk_blk64(int M, int N, int K) {
-  if (M > GEMM_STREAM64_MAX_ROWS) return gemm_pick_splitk(M, N, K, ACT_NONE);     // (runs on the general tiles: gemm_launch())
-  const int tiles = cdiv(M, 128) * (N / 64), ksteps = K / BK;
-  if (tiles >= 160) return 1;
-  int s = (256 + tiles / 2) / tiles;
-  while (s > 1 && ksteps / s < 8) --s;
-  if (s > 16) s = 16;
-  // no empty trailing split (ksteps = 129, s = 16 -> 9 steps per split, split 15 would start past the end and write a zero plane)
-  return cdiv(ksteps, cdiv(ksteps, s));
-}
-
-int gemm_pick_splitk(int M, int N, int K, int act, bool plain, bool generic) {
-  if (act == ACT_GEGLU) return 1;
-  const int bn = (N % 160 == 0) ? 160 : 128;
-  const int tiles = cdiv(M, BM_HOST) * cdiv(N, bn);
-  const int ksteps = K / BK;
-  if (tiles >= 384 || ksteps < 8) return 1;
-  {   // convs that gemm_launch_bn puts on 128 x 160 ping-pong tiles: one workgroup per CU, 256 slots
-    if (!generic && (plain ? gemm_plain_pingpong(M, N, K) : gemm_conv_pingpong(M, N)) && tiles <= 256 && M % 128 == 0) {
-      int s = (256 + tiles / 2) / tiles;
-      const int min_steps = (M <= 256 || tiles < 64) ? 4 : 24;
-      if (s > ksteps / min_steps) s = ksteps / min_steps;
-      if (s > 16) s = 16;
-      return s < 1 ? 1 : s;
-    }
-  }
-  // (round 5, first session: an M-dependent rule for skinny weight-streaming GEMMs lived here.  The OPT matrices now take gemm_pick_splitk_blk64();
-  // for everything else it made the split factor — the fp32 summation order — depend on the batch, and the tiny UNet's batch-invariance check went
-  // from bit-identical to 2.4e-2 after 11 recurrent calls.  Removed.)
-  // plain GEMMs with 150..383 128-row tiles run on 64-row tiles instead (gemm_launch: >= 300 workgroups, no partials):
-  // measured 8192 x 640 x 3200 unsplit 49.1 us, two-way split + reducer 54.6 us
-  if (plain && !generic && tiles >= 150 && tiles < 300 && M > 64) return 1;
-  int s = (512 + tiles / 2) / tiles;   // aim for ~2 workgroups per CU (512 resident slots)
-  // each split pays an fp32 partial write + a reduce pass: keep >= 24 K steps per split (measured: K = 1280 GEMMs lose
-  // from any split, K >= 5120 convs win up to 4-8 ways), except for skinny weight-streaming GEMMs (OPT, M <= 256)
-  // where filling every CU with HBM requests matters more than the tiny partials
-  const int min_steps = (M <= 256 || tiles < 64) ? 4 : 24;
-  if (s > ksteps / min_steps) s = ksteps / min_steps;
-  if (s > 16) s = 16;
-  if (s < 1) s = 1;
-  return s;
-}
-
-
-template <int NWV, int BN, int CONV, int EPI, int STAGES, int KT = BK, int MI = 4>
+template <int NWV, int BN, int CONV, int EPI, int STAGES, int KT, int MI>
 static int gemm_launch_inst(const GemmDev& d, dim3 grid, hipStream_t s) {
   static bool attr_set = false;
   constexpr int smem = STAGES * ((NWV / 2) * MI * 16 * KT + BN * KT) * (int)sizeof(bf16_t);
@@ -1355,314 +1194,56 @@ static int gemm_launch_inst(const GemmDev& d, dim3 grid, hipStream_t s) {
   return 0;
 }
 
-// d.nwv = 2 selects the 64-row tile (plain GEMMs, 2-deep ring, no split-K)
-template <int BN, int CONV, int EPI>
-static int gemm_launch_stages(const GemmDev& d, dim3 grid, hipStream_t s) {
-  if constexpr (BN == 64) {
-    // STREAM64 (see gemm_stream64()): 128 x 64 tile, 6-deep ring = 144 KiB, one workgroup per CU
-    static_assert(CONV == 0 && (EPI == 0 || EPI == 2 || EPI == 3), "the 64-wide streaming tile: plain GEMMs, row-major / partial / QKV epilogues");
-    return gemm_launch_inst<8, 64, 0, EPI, 6, BK, 2>(d, grid, s);     // eight waves of 32 x 32: see gemm_launch_stream64()
-  } else {
-  if constexpr (CONV == 0 && EPI != 2) {
-    if (d.nwv == 2) return gemm_launch_inst<2, BN, CONV, EPI, 2>(d, grid, s);
-  }
-  if constexpr (CONV == 0 && (EPI == 0 || EPI == 4) && BN == 160) {
-    if (d.nwv == 4 && d.mi == 2) {
-      // (2-deep ring: 56 KB, two workgroups per CU; 3-deep = 84 KB = one per CU measured slower: 495.7 vs 489.4 ms)
-      return gemm_launch_inst<4, BN, CONV, EPI, 2, BK, 2>(d, grid, s);
-    }
-  }
-  if constexpr (CONV == 0 && EPI == 5) {
-    if (d.nwv == 8) return gemm_launch_inst<8, BN, CONV, EPI, 3, BK, 2>(d, grid, s);     // ping-pong 128 x 160 tile
-    // 64 x 160 tile on four waves of 32 x 80.  Measured on the three UNet shapes of the 8-sample batch back to back (tools/xalg_bench.py, 20
-    // launches each, operands warm): two waves of 64 x 80 1177 us, this with a 2-deep ring 1003-1013 us, 3-deep 1212 us, 3-deep only on
-    // the <= 256-workgroup grids 1051 us.  In the UNet forward the per-sample weights are cold (13 MB per layer, read once per call) and
-    // a workgroup's K walk is a chain of HBM round trips: there the 3-deep ring on the one-workgroup-per-CU grids (levels 2-3) wins,
-    // loop 446.7 -> 444.1 ms (4-deep: 444.7).
-    if (d.nwv == 4 && d.mi == 2) {
-      if ((int)(grid.x * grid.y) <= 256) return gemm_launch_inst<4, BN, CONV, EPI, 3, BK, 2>(d, grid, s);
-      return gemm_launch_inst<4, BN, CONV, EPI, 2, BK, 2>(d, grid, s);
-    }
-  }
-  if constexpr (CONV == 0 && (EPI == 0 || EPI == 3 || EPI == 4) && BN == 128) {
-    if (d.nwv == 4 && d.mi == 2) {
-      // 64-row tile on four waves, 3-deep ring (72 KB: two workgroups per CU).  These grids are 1-2 workgroups per CU, so the ring depth IS
-      // the number of K stages in flight on a CU, and a K step of these short-K GEMMs is one L2 round trip: 2-deep 487.3 ms, 3-deep
-      // 483.4 ms, 4-deep (one workgroup per CU) 496.1 ms on the loop.
-      return gemm_launch_inst<4, BN, CONV, EPI, 3, BK, 2>(d, grid, s);
-    }
-  }
-  if constexpr (BN == 160 && (CONV != 0 || EPI == 2 || EPI == 4 || (CONV == 0 && EPI == 3))) {
-    if (d.nwv == 8 && d.mi == 2) return gemm_launch_inst<8, BN, CONV, EPI, 3, BK, 2>(d, grid, s);   // ping-pong 128 x 160 tile
-    if (d.nwv == 8) return gemm_launch_inst<8, BN, CONV, EPI, 3>(d, grid, s);     // ping-pong 256 x 160 tile
-  }
-  if constexpr (CONV == 0 && BN == 128 && (EPI == 1 || EPI == 3)) {
-    // round 5: the 128 x 128 tile of the GEGLU / QKV GEMMs on eight waves of 32 x 64 (two workgroups = 16 waves per CU, 116 registers) instead of four of
-    // 64 x 64: half the LDS-DMA pieces, fragment reads and MFMAs per wave and step, twice the waves to overlap them.  Loop 447.4 -> 445.8 ms (A/B x3,
-    // profiles/r05_linears.md); level-1 GEGLU 82.1 -> 79.7 us stand-alone
-    if (d.nwv == 4 && d.mi == 4) return gemm_launch_inst<8, BN, CONV, EPI, 2, BK, 2>(d, grid, s);
-  }
-  // (the same for the UNet's plain 128-row GEMMs — the lean row-major epilogue, EPI 4 — measured slower: loop 451.3 -> 456.0 ms, profiles/r05_linears.md)
-  return gemm_launch_inst<4, BN, CONV, EPI, 2>(d, grid, s);
-  }
-}
+// The gemm_kernel instantiations that exist: (NWV, BN, CONV, EPI, STAGES, KT, MI).  A plan names one of them or the launch is refused.
+#define GEMM_KERNELS(X) \
+  /* STREAM64: 128 x 64, 6-deep ring */ \
+  X(8, 64, 0, 0, 6, 64, 2) X(8, 64, 0, 2, 6, 64, 2) X(8, 64, 0, 3, 6, 64, 2) \
+  /* plain, 128 wide: 64-row two-wave, 128-row four-wave, 64-row four-wave (3-deep), 128-row eight-wave (GEGLU / QKV) */ \
+  X(2, 128, 0, 0, 2, 64, 4) X(4, 128, 0, 0, 2, 64, 4) X(4, 128, 0, 0, 3, 64, 2) \
+  X(2, 128, 0, 1, 2, 64, 4) X(4, 128, 0, 1, 2, 64, 4) X(8, 128, 0, 1, 2, 64, 2) \
+  X(4, 128, 0, 2, 2, 64, 4) \
+  X(2, 128, 0, 3, 2, 64, 4) X(4, 128, 0, 3, 2, 64, 4) X(4, 128, 0, 3, 3, 64, 2) X(8, 128, 0, 3, 2, 64, 2) \
+  X(2, 128, 0, 4, 2, 64, 4) X(4, 128, 0, 4, 2, 64, 4) X(4, 128, 0, 4, 3, 64, 2) \
+  /* convolutions, 128 wide */ \
+  X(4, 128, 1, 0, 2, 64, 4) X(4, 128, 1, 2, 2, 64, 4) X(4, 128, 2, 0, 2, 64, 4) X(4, 128, 2, 2, 2, 64, 4) X(4, 128, 3, 0, 2, 64, 4) X(4, 128, 3, 2, 2, 64, 4) \
+  /* plain, 160 wide: the same tiles + the ping-pong ones (eight waves, 3-deep: 128 / 256 rows) */ \
+  X(2, 160, 0, 0, 2, 64, 4) X(4, 160, 0, 0, 2, 64, 2) X(4, 160, 0, 0, 2, 64, 4) \
+  X(4, 160, 0, 2, 2, 64, 4) X(8, 160, 0, 2, 3, 64, 2) X(8, 160, 0, 2, 3, 64, 4) \
+  X(2, 160, 0, 3, 2, 64, 4) X(4, 160, 0, 3, 2, 64, 4) X(8, 160, 0, 3, 3, 64, 2) X(8, 160, 0, 3, 3, 64, 4) \
+  X(2, 160, 0, 4, 2, 64, 4) X(4, 160, 0, 4, 2, 64, 2) X(4, 160, 0, 4, 2, 64, 4) X(8, 160, 0, 4, 3, 64, 2) X(8, 160, 0, 4, 3, 64, 4) \
+  X(2, 160, 0, 5, 2, 64, 4) X(4, 160, 0, 5, 2, 64, 2) X(4, 160, 0, 5, 2, 64, 4) X(4, 160, 0, 5, 3, 64, 2) X(8, 160, 0, 5, 3, 64, 2) \
+  /* convolutions, 160 wide: four-wave and ping-pong, + the in-kernel GroupNorm finish (EPI 6) */ \
+  X(4, 160, 1, 0, 2, 64, 4) X(8, 160, 1, 0, 3, 64, 2) X(8, 160, 1, 0, 3, 64, 4) X(4, 160, 1, 2, 2, 64, 4) X(8, 160, 1, 2, 3, 64, 2) X(8, 160, 1, 2, 3, 64, 4) \
+  X(8, 160, 1, 6, 3, 64, 2) X(8, 160, 1, 6, 3, 64, 4) \
+  X(4, 160, 2, 0, 2, 64, 4) X(8, 160, 2, 0, 3, 64, 2) X(8, 160, 2, 0, 3, 64, 4) X(4, 160, 2, 2, 2, 64, 4) X(8, 160, 2, 2, 3, 64, 2) X(8, 160, 2, 2, 3, 64, 4) \
+  X(4, 160, 3, 0, 2, 64, 4) X(8, 160, 3, 0, 3, 64, 2) X(8, 160, 3, 0, 3, 64, 4) X(4, 160, 3, 2, 2, 64, 4) X(8, 160, 3, 2, 3, 64, 2) X(8, 160, 3, 2, 3, 64, 4)
 
-// XCD BLOCK MAP.  Model of the fabric traffic of one launch under a map that gives every XCD an xm x xn block of the (M tile, N group) grid (all
-// K splits of a tile sit on its XCD: blockIdx.y does not move the XCD when gridDim.x % 8 == 0):
-//   activations: the block's rows x the channels a K walk reads, once if they fit next to the streaming weights in the 4 MiB L2 (budget 2 MiB),
-//                else once per re-read (a tap-major 3x3 convolution re-reads its input rows 9 times, a plain GEMM once per N tile a workgroup walks);
-//   weights:     the block's N columns x K, once (the block's M tiles walk K in step and share the stream).
-// Picks the block with the least modelled traffic; the two range maps (n_major / m-major) are candidates like any other, and the block map is only
-// used where it beats the range map in force by 15 % (profiles/r06_xcd_block_map.md: level-2 convolutions 417 -> ... MB per dispatch).
-static void xcd_block_pick(const GemmArgs& a, GemmDev& d, int bm_rows, int bn_cols, int ncls) {
-  d.xb_m = d.xb_n = 0;
-  const int nwg = d.tiles_m * d.groups_n;
-  // (the ping-pong tiles only — the 3x3 convolutions and the long-K plain GEMMs of levels 1-3, one workgroup per CU: the launches whose fetch
-  // profiles/r05_fetch_by_kernel.md flagged; the model is not trusted on the multi-N-tile walks of the GEGLU / QKV kernels)
-  if (ncls != 1 || nwg % 8 != 0 || nwg < 16 || a.wb_rows || d.nwv != 8 || bn_cols != 160) return;
-  const double l2_budget = 2.0 * 1024 * 1024;
-  const int taps = a.conv ? 9 : 1;
-  const double row_bytes = 2.0 * (a.conv ? (double)(a.Cin + a.KX) * (a.stride == 2 ? 4 : 1) : (double)a.K);     // input bytes behind one output row
-  const double col_bytes = 2.0 * (double)a.K * bn_cols * d.npw;                                                   // weight bytes of one N group
-  auto cost = [&](double xm, double xn) {
-    const double A = xm * bm_rows * row_bytes, W = xn * col_bytes;
-    // (a plain GEMM's N groups of one M tile run side by side on the XCD and share the activation stream; only a workgroup's own walk over npw N
-    // tiles comes back to the same rows later)
-    const double rereads = (A <= l2_budget) ? 1.0 : (a.conv ? (a.k_chunked ? 1.0 : (double)taps) : (double)d.npw);
-    return A * rereads + W;
-  };
-  double best = 1e30; int bxm = 0, bxn = 0;
-  for (int blocks_m = 1; blocks_m <= 8; blocks_m *= 2) {
-    const int blocks_n = 8 / blocks_m;
-    if (d.tiles_m % blocks_m != 0 || d.groups_n % blocks_n != 0) continue;
-    const int xm = d.tiles_m / blocks_m, xn = d.groups_n / blocks_n;
-    const double c = cost(xm, xn);
-    if (c < best) { best = c; bxm = xm; bxn = xn; }
-  }
-  if (bxm == 0) return;
-  // the range map in force: n_major = (all of M, 1/8 of N) per XCD, else (1/8 of M, all of N) — priced with the same model
-  const double cur = d.n_major ? cost(d.tiles_m, d.groups_n / 8.0) : cost(d.tiles_m / 8.0, d.groups_n);
-  if (best <= 0.85 * cur) { d.xb_m = bxm; d.xb_n = bxn; }
-}
-
-template <int BN>
-static int gemm_launch_bn(const GemmArgs& a, hipStream_t s) {
-  GemmDev d;
-  d.a = a;
-  d.zero = gill_zero_page();
-  GILL_REQUIRE(d.zero != nullptr, "zero page unavailable");
-  const int sk = a.splitk > 1 ? a.splitk : 1;
-  d.a.splitk = sk;
-  GemmArgs red = d.a;       // what the split-K reducer sees: the output tensor, whatever the conv kernel's row space is
-  // UPS4 (a.ups == 2): the kernel's rows are the SOURCE pixels of one parity class, blockIdx.z the class
-  const int ncls = (a.conv && a.ups == 2) ? 4 : 1;
-  const int Mk = a.M / ncls;
-  d.a.M = Mk;
-  d.a.rows_per_batch = a.rows_per_batch / ncls;
-  d.tiles_n = cdiv(a.N, BN);
-  // 64-row tiles for plain GEMMs whose 128-row tiling leaves CUs without a tile
-  d.nwv = 4;
-  // (tile_width() counts 128 x 160 tiles when it hands these GEMMs BN = 128, this rule counts 128 x 128 tiles: an 8192 x 640 GEMM
-  // — 256 vs 320 — therefore lands on the 4-wave 128 x 128 tile, not the 64-row one; measured better that way: 567.8 vs 575.5 ms)
-  // (re-measured with the 3-deep ring below: < 300 493.8 ms, < 400 495.6, < 520 496.3, < 700 496.5)
-  if (!a.conv && sk == 1 && (int64_t)cdiv(a.M, 128) * d.tiles_n < 300 && a.M > 64) d.nwv = 2;   // measured: < 300 +0.3 %, < 520 -3 % end to end
-  if (a.wb_rows % 128 != 0 && !a.conv && sk == 1) d.nwv = 2;      // per-sample weights on samples of 64 rows (GemmArgs::wb_rows): 64-row tiles
-  d.mi = 4;
-  // the 64-row tile on FOUR waves (2 x 2, wave tile 32 x 64) where its width is 128: same LDS, twice the waves per CU —
-  // loop 580.4 -> 576.3 ms, 2048 x 1280 x 1280 19.8 -> 17.3 us
-  if (d.nwv == 2 && BN == 128 && a.act != ACT_GEGLU && !a.gn_stats) { d.nwv = 4; d.mi = 2; }
-  // ... and where it is 160 (the feed-forward output GEMMs of levels 1-3 with their fused GroupNorm partials: bins of 20 / 40 channels
-  // need the 160-wide tile): loop 492.4 -> 489.4 ms against the two-wave tile.
-  if (d.nwv == 2 && BN == 160 && a.act == ACT_NONE && a.out_mode == OUT_BF16) { d.nwv = 4; d.mi = 2; }
-  if (a.out_mode == OUT_SOFTMAX80) { d.nwv = 4; d.mi = 2; }      // (see gemm_launch_stages)
-  // ... or, where 128-row ping-pong tiles are exactly one balanced round (level 1 at the CFG batch 8: 8192 x 640 x 640 = 256 workgroups instead of 512
-  // four-wave ones), those (round 6, like the plain GEMMs of that shape)
-  if (BN == 160 && a.out_mode == OUT_SOFTMAX80 && gemm_pp_switch() && sk == 1 && a.M % 128 == 0 && a.wb_rows % 128 == 0 && a.K >= 640 &&
-      (int64_t)(a.M / 128) * d.tiles_n >= 200 && (int64_t)(a.M / 128) * d.tiles_n <= 256) { d.nwv = 8; d.mi = 2; }
-  // (round 4: the 64-row four-wave tile with its 3-deep ring — 96 instead of 64 KB in flight per CU — on ALL GEGLU / QKV / 128-wide plain
-  // GEMMs, not only the few-tile ones: loop 460.4 -> 469.4 / 464.8 / 460.7 ms.  Not kept.)
-  // 3x3 convolutions: 256 x 160 tile with the ping-pong main loop, one workgroup per CU (GILL_GEMM_PP = 0 keeps the two
-  // co-resident 128 x 160 workgroups)
-  if (BN == 160 && a.conv && gemm_conv_pingpong(Mk, a.N)) {
-    d.nwv = 8;
-    // Where the 256-row tiling x split-K gives at most 128 workgroups (UNet levels 1-3 at the 8-sample batch), run
-    // 128 x 160 ping-pong tiles (eight waves of 32 x 80); gemm_pick_splitk() then aims at 256 workgroups of those, i.e. half the
-    // split factor: half the fp32 partials (none at level 1)
-    // (loop 561.1 -> 558.0 ms; GILL_GEMM_PP128 = 0 keeps the 256-row tile with twice the split)
-    if ((int64_t)cdiv(Mk, 256) * ncls * d.tiles_n * sk <= 128 && Mk % 128 == 0) d.mi = 2;
-  }
-  if (BN == 160 && gemm_plain_pingpong_args(a)) {
-    d.nwv = 8; d.mi = 4;
-    if (((int64_t)cdiv(Mk, 256) * d.tiles_n * sk <= 128) || Mk % 256 != 0) d.mi = 2;
-  }
-  if (BN == 160 && gemm_qkv_pingpong_mi(a)) { d.nwv = 8; d.mi = gemm_qkv_pingpong_mi(a); }
-  // (round 4: the short-K GEGLU / QKV GEMMs on 256 x 128 / 128 x 128 ping-pong tiles, one N tile per workgroup: loop 464.0 -> 478.0 / 480.4 ms
-  // (GEGLU), 467.0 / 468.8 ms (QKV) — ten K steps do not amortise a prologue and an epilogue that no second workgroup covers.  Not kept.)
-  d.kt = 64;
-  d.ksteps = a.K / d.kt;
-  d.ksteps_per_split = cdiv(d.ksteps, sk);
-  const int tiles_m = cdiv(Mk, (d.nwv / 2) * d.mi * 16);
-  // Short-K GEMMs with many N tiles (GEGLU, QKV: K = 320..1280, 6..80 N tiles) spend most of a tile's life in the first-load
-  // latency and the epilogue.  Let one workgroup walk `npw` N tiles back to back instead: the ring is staged across tile
-  // boundaries, so the loads of tile t+1 fly during the epilogue of tile t.  Keep ~2 workgroups per CU.
-  d.npw = 1;
-  if (!a.conv && sk == 1 && d.nwv != 8 && !a.gn_stats && d.tiles_n >= 2) {
-    int groups = cdiv(512, tiles_m);   // ~2 workgroups per CU
-    if (groups < 1) groups = 1;
-    if (groups > d.tiles_n) groups = d.tiles_n;
-    d.npw = cdiv(d.tiles_n, groups);
-  }
-  d.groups_n = cdiv(d.tiles_n, d.npw);
-  d.tiles_m = tiles_m;
-  {
-    const int64_t wel = (int64_t)a.N * a.K;
-    const int64_t ael = (int64_t)a.M * (a.conv ? a.Cin + a.KX : a.K);
-    d.n_major = (wel > ael && d.groups_n >= 8) ? 1 : 0;
-  }
-  xcd_block_pick(a, d, (d.nwv / 2) * d.mi * 16, BN, ncls);
-  GILL_REQUIRE(a.wb_rows == 0 || (a.wb_rows % ((d.nwv / 2) * d.mi * 16) == 0 && !a.conv), "per-sample weights: tiles must not straddle samples");
-  dim3 grid(tiles_m * d.groups_n, sk, ncls);
-  if (d.nwv == 8) GILL_REQUIRE(d.npw == 1, "internal: the ping-pong kernel walks one N tile per workgroup");
-  // COOP: the finish inside this launch (EPI 6: GroupNorm in the conv epilogue) — no second launch
-  bool coop = false;
-  if constexpr (BN == 160) {
-    coop = gemm_coop_ok(d.a);
-    if (coop) GILL_REQUIRE(d.nwv == 8 && (d.nwv / 2) * d.mi * 16 == coop_tile_rows(d.a) && ncls == 1,
-                           "internal: gemm_coop_ok() and the launcher disagree about the tile");
-  }
-  GILL_REQUIRE(coop || sk > 1 || (a.fn_Y == nullptr && a.fn_ss == nullptr), "fused GroupNorm output without a split-K reducer or an in-kernel finish");
-  if (a.conv) {
-    if (a.ups == 2) {
-      if (sk > 1) GILL_TRY((gemm_launch_stages<BN, 3, 2>(d, grid, s)));
-      else GILL_TRY((gemm_launch_stages<BN, 3, 0>(d, grid, s)));
-    } else if (a.ups) {
-      if (sk > 1) GILL_TRY((gemm_launch_stages<BN, 2, 2>(d, grid, s)));
-      else GILL_TRY((gemm_launch_stages<BN, 2, 0>(d, grid, s)));
-    } else if (coop) {
-      if constexpr (BN == 160) {
-        if (d.mi == 2) GILL_TRY((gemm_launch_inst<8, 160, 1, 6, 3, BK, 2>(d, grid, s)));
-        else GILL_TRY((gemm_launch_inst<8, 160, 1, 6, 3, BK, 4>(d, grid, s)));
-      }
-    } else {
-      if (sk > 1) GILL_TRY((gemm_launch_stages<BN, 1, 2>(d, grid, s)));
-      else GILL_TRY((gemm_launch_stages<BN, 1, 0>(d, grid, s)));
-    }
-  } else {
-    if (sk > 1) GILL_TRY((gemm_launch_stages<BN, 0, 2>(d, grid, s)));
-    else if (a.act == ACT_GEGLU) {
-      if constexpr (BN == 128) GILL_TRY((gemm_launch_stages<BN, 0, 1>(d, grid, s)));
-      else GILL_REQUIRE(BN == 128, "internal: GEGLU runs on 128-wide tiles");
-    }
-    else if (a.out_mode == OUT_SOFTMAX80) {
-      if constexpr (BN == 160) GILL_TRY((gemm_launch_stages<BN, 0, 5>(d, grid, s)));
-      else GILL_REQUIRE(BN == 160, "internal: the softmax epilogue runs on 160-wide tiles");
-    }
-    else if (a.out_mode == OUT_QKV) GILL_TRY((gemm_launch_stages<BN, 0, 3>(d, grid, s)));
-    else if (a.act == ACT_NONE && a.out_mode == OUT_BF16 && !a.resid_f32) GILL_TRY((gemm_launch_stages<BN, 0, 4>(d, grid, s)));
-    else GILL_TRY((gemm_launch_stages<BN, 0, 0>(d, grid, s)));
-  }
-  if (sk > 1 && !a.partials_only) return gemm_splitk_reduce_launch(red, s);
-  return 0;
-}
-
-static int gemm_launch_stream64(const GemmArgs& a, hipStream_t s) {
-  GemmDev d;
-  d.a = a;
-  d.zero = gill_zero_page();
-  GILL_REQUIRE(d.zero != nullptr, "zero page unavailable");
-  const int sk = a.splitk > 1 ? a.splitk : 1;
-  d.a.splitk = sk;
-  d.tiles_n = a.N / 64; d.tiles_m = cdiv(a.M, 128); d.npw = 1; d.groups_n = d.tiles_n; d.n_major = 1; d.xb_m = d.xb_n = 0;
-  d.kt = 64;
-  d.ksteps = a.K / 64;
-  d.ksteps_per_split = cdiv(d.ksteps, sk);
-  // (round 5: every workgroup starting its K walk (t * 5 | 13 | 29) % steps into its slice, against HBM-channel camping of 256 lockstep streams
-  // whose bases are K * 128 B apart: OPT stage 5.18 -> 5.24 ms, profiles/r05_opt_stream64.md.  Not that; removed.)
-  // eight waves of 32 x 32 (three LDS-DMA pieces per wave and stage) rather than four of 64 x 32 (six): OPT stage 5.03 -> 4.70 ms — a wave issues its
-  // pieces, fragment reads and MFMAs one after the other, and with one workgroup per CU only more waves overlap them
-  d.nwv = 8; d.mi = 2;
-  const dim3 grid(d.tiles_n * d.tiles_m, sk, 1);
-  if (sk > 1) GILL_TRY((gemm_launch_stages<64, 0, 2>(d, grid, s)));
-  else if (a.out_mode == OUT_QKV) GILL_TRY((gemm_launch_stages<64, 0, 3>(d, grid, s)));
-  else GILL_TRY((gemm_launch_stages<64, 0, 0>(d, grid, s)));
-  if (sk > 1 && !a.partials_only) return gemm_splitk_reduce_launch(d.a, s);
-  return 0;
+static int gemm_dispatch(const GemmPlan& p, const GemmDev& d, dim3 grid, hipStream_t s) {
+#define GEMM_KERNEL_CASE(NWV, BN, CONV, EPI, STAGES, KT, MI)                                                                                    \
+  if (p.k_nwv == NWV && p.k_bn == BN && p.k_conv == CONV && p.k_epi == EPI && p.k_stages == STAGES && p.k_kt == KT && p.k_mi == MI)             \
+    return gemm_launch_inst<NWV, BN, CONV, EPI, STAGES, KT, MI>(d, grid, s);
+  GEMM_KERNELS(GEMM_KERNEL_CASE)
+#undef GEMM_KERNEL_CASE
+  GILL_REQUIRE(false, "internal: no kernel for this plan");
+  return -2;
 }
 
 int gemm_launch(const GemmArgs& a, hipStream_t s) {
-  GILL_REQUIRE(a.M > 0 && a.N > 0 && a.K > 0, "empty GEMM");
-  GILL_REQUIRE((int64_t)a.M * (a.lda > a.N ? a.lda : a.N) < (int64_t)1 << 31, "GEMM operand too large for 32-bit offsets");
-  GILL_REQUIRE((int64_t)a.M * (a.ldc > a.ldr ? a.ldc : a.ldr) < (int64_t)1 << 31, "GEMM output / residual too large for 32-bit offsets");
-  GILL_REQUIRE(a.K % BK == 0, "K must be a multiple of 64");
-  GILL_REQUIRE(a.N % 4 == 0, "N must be a multiple of 4");
-  GILL_REQUIRE(a.A != nullptr && a.W != nullptr, "null operand");
-  if (a.conv) {
-    if (a.ups == 2) {
-      GILL_REQUIRE(a.Cin % BK == 0 && a.K == 4 * a.Cin && a.KX == 0, "upsample conv (4-tap form): Cin must be a multiple of 64 and K == 4*Cin");
-      GILL_REQUIRE(!a.k_chunked && !a.resid && !a.rowvec && a.M % 4 == 0 && a.OH == 2 * a.IH && a.OW == 2 * a.IW,
-                   "upsample conv (4-tap form): tap-major weights, no residual / row vector, output = 2x the source grid");
-      GILL_REQUIRE(!a.gn_stats || a.rows_per_batch % 256 == 0, "upsample conv (4-tap form): fused GroupNorm statistics need whole 64-row slabs per class");
-    } else {
-      GILL_REQUIRE(a.Cin % BK == 0 && a.K == 9 * a.Cin + a.KX, "conv: Cin must be a multiple of 64 and K == 9*Cin + KX");
-    }
-    if (a.KX) {
-      GILL_REQUIRE(a.stride == 1 && !a.ups && a.X1 != nullptr, "conv: the fused 1x1 segment needs stride 1, no upsample");
-      GILL_REQUIRE(a.KX % BK == 0 && a.KX1 % BK == 0 && a.KX1 <= a.KX && (a.KX1 == a.KX || a.X2 != nullptr),
-                   "conv: fused 1x1 segment channel counts must be multiples of 64");
-    }
-    GILL_REQUIRE(a.K1 % BK == 0 && a.K1 <= a.Cin, "conv: source split must be a multiple of 64");
-    GILL_REQUIRE(a.Cin / BK <= ZERO_PAGE_STEPS, "conv: Cin too large for the zero page");
-    GILL_REQUIRE(a.K1 == a.Cin || a.A2 != nullptr, "conv: second source missing");
-    GILL_REQUIRE(!(a.ups && a.stride != 1), "conv: upsample needs stride 1");
-    if (a.pad_shift) {
-      GILL_REQUIRE(a.pad_shift == 1 && a.stride == 2 && !a.ups && a.KX == 0, "conv: pad_shift is 0 or 1 and needs stride 2, no upsample, no fused 1x1 segment");
-      GILL_REQUIRE(a.IH % 2 == 0 && a.IW % 2 == 0 && a.OH == a.IH / 2 && a.OW == a.IW / 2, "conv: pad_shift needs even IH and IW and an output of half the size");
-    }
-    GILL_REQUIRE(a.out_mode == OUT_BF16 && a.act == ACT_NONE && !a.resid_f32 && !a.row_stats,
-                 "conv: bf16 row-major epilogue without activation / fp32 residual / row statistics only");
-    GILL_REQUIRE((int64_t)(a.M / (a.OH * a.OW)) * a.IH * a.IW * a.Cin < (int64_t)1 << 31, "conv input too large for 32-bit offsets");
-  } else {
-    GILL_REQUIRE(a.K1 % BK == 0 && a.K1 <= a.K, "K split must be a multiple of 64");
-    GILL_REQUIRE(a.K1 == a.K || a.A2 != nullptr, "second A source missing");
-  }
-  if (a.gn_stats) {
-    GILL_REQUIRE(a.out_mode != OUT_QKV && a.act != ACT_GEGLU, "fused GroupNorm statistics need the row-major epilogue");
-    GILL_REQUIRE(a.rows_per_batch % 64 == 0 && a.gn_groups > 0 && a.gn_groups <= 64 && a.gn_cg * a.gn_groups == a.N,
-                 "fused GroupNorm statistics: rows per sample must be a multiple of 64 and bins must tile N");
-    GILL_REQUIRE(gemm_fused_gn_ok(a.N, a.gn_cg) && tile_width(a) % a.gn_cg == 0,
-                 "fused GroupNorm statistics: bins must not straddle output tiles");
-  }
-  if (a.row_stats)
-    GILL_REQUIRE(a.out_mode == OUT_BF16 && a.act != ACT_GEGLU, "row statistics need the bf16 row-major epilogue");
-  if (a.ln_stats) {
-    GILL_REQUIRE(a.ln_planes >= 1 && a.ln_planes <= LN_MAX_PLANES, "folded LayerNorm: 1 <= ln_planes <= 20");
-    GILL_REQUIRE(a.ln_colsum != nullptr && !a.conv && a.K1 == a.K, "folded LayerNorm: column sums missing / single-source plain GEMM only");
-    GILL_REQUIRE(a.act == ACT_GEGLU || a.out_mode == OUT_QKV || a.out_mode == OUT_SOFTMAX80, "folded LayerNorm is implemented in the GEGLU, QKV and softmax epilogues");
-    GILL_REQUIRE(a.alpha == 1.f, "folded LayerNorm: alpha must be 1");
-  }
-  GILL_REQUIRE((a.fn_Y == nullptr && a.fn_ss == nullptr) || gemm_coop_ok(a) || (a.fn_ss == nullptr && a.splitk > 1 && gemm_fused_norm_ok(a)),
-               "fused GroupNorm output: split-K GEMMs of a supported geometry, or an in-kernel finish (gemm_coop_ok), only");
-  GILL_REQUIRE(a.C != nullptr || a.fn_Y != nullptr || a.out_mode == OUT_QKV, "no output tensor");
-  if (a.splitk > 1) {
-    GILL_REQUIRE(a.ws != nullptr, "split-K workspace missing");
-    GILL_REQUIRE(a.act != ACT_GEGLU, "split-K cannot be combined with GEGLU");
-  }
-  if (a.act == ACT_GEGLU) {
-    GILL_REQUIRE(a.N % 128 == 0 && a.out_mode == OUT_BF16, "GEGLU needs N % 128 == 0 and bf16 row-major output");
-    return gemm_launch_bn<128>(a, s);
-  }
-  if (a.out_mode == OUT_SOFTMAX80)
-    GILL_REQUIRE(a.N % 160 == 0 && a.splitk <= 1 && a.ln_stats && a.ln_colsum && a.bias && !a.conv && !a.gn_stats && !a.row_stats && a.C,
-                 "softmax epilogue: N % 160 == 0, no split-K, folded-LayerNorm operands and a bias vector required");
-  if (a.out_mode == OUT_QKV) GILL_REQUIRE(a.dp % 8 == 0 && a.heads > 0 && a.ntok > 0, "bad QKV scatter geometry (padded head dim must be a multiple of 8)");
-  if (a.w_blk64) {
-    GILL_REQUIRE(!a.conv && a.N % 64 == 0 && a.K1 == a.K && !a.gn_stats && !a.row_stats && !a.ln_stats && !a.wb_rows && !a.fn_Y &&
-                     a.act != ACT_GEGLU && a.out_mode != OUT_SOFTMAX80,
-                 "64 x 64-blocked weights (STREAM64): plain GEMMs with the row-major, QKV or split-K epilogue only");
-    if (a.M <= GEMM_STREAM64_MAX_ROWS) return gemm_launch_stream64(a, s);
-    // more rows than that: the general tiles read the blocked layout (the 128 x 64 tile is CU-bound per M tile: profiles/r05_opt_stream64.md)
-  }
-  const int bn = tile_width(a);
-  if (bn == 160) return gemm_launch_bn<160>(a, s);
-  return gemm_launch_bn<128>(a, s);
+  GemmPlan p;
+  GILL_TRY(gemm_plan(a, gemm_env_default(), &p));
+  GemmDev d;
+  d.a = a;
+  d.zero = gill_zero_page();
+  GILL_REQUIRE(d.zero != nullptr, "zero page unavailable");
+  d.a.splitk = p.splitk;
+  const GemmArgs red = d.a;       // what the split-K reducer sees: the output tensor, whatever the conv kernel's row space is
+  d.a.M = p.M;
+  d.a.rows_per_batch = p.rows_per_batch;
+  d.ksteps = p.ksteps; d.ksteps_per_split = p.ksteps_per_split;
+  d.tiles_n = p.tiles_n; d.npw = p.npw; d.groups_n = p.groups_n;
+  d.nwv = p.nwv; d.mi = p.mi; d.kt = p.kt;
+  d.n_major = p.n_major; d.tiles_m = p.tiles_m; d.xb_m = p.xb_m; d.xb_n = p.xb_n;
+  GILL_TRY(gemm_dispatch(p, d, dim3(p.grid_x, p.grid_y, p.grid_z), s));
+  if (p.reduce) return gemm_splitk_reduce_launch(red, s);
+  return 0;
 }

@@ -92,6 +92,8 @@ struct GemmArgs {
   // (profiles/gemm_prune_isa.md).  The next field added takes its place.
   int spare_word = 0;
 };
+// gemm_coop_ok(), gemm_coop_counters(), gemm_gn_slab_rows() and gemm_row_planes() read the launch's plan (gemm_plan.h: the host-side decisions of
+// gemm_launch(), made in one place) for callers that need the answer before the launch.
 // can this launch finish in-kernel (GemmArgs::coop_ctr)?  splitk == 1, geometry of the ping-pong tiles, whole samples per counter group, grid <= CUs of the device.
 bool gemm_coop_ok(const GemmArgs& a);
 int gemm_coop_counters(const GemmArgs& a);
@@ -379,7 +381,7 @@ int conv_weight_relayout_launch(const void* w, int dtype, int Cout, int Cin, bf1
 // (not for convolutions that run on the ping-pong 256 x 160 tile — gemm_conv_pingpong(): there a new (tap, chunk) segment every K
 // step lengthens the memory phase, measured 155 us chunk-major against 126 us tap-major for 64 x 64 x 640 -> 320)
 bool gemm_conv_pingpong(int rows_multiple_of, int Cout);     // true: gemm_launch runs this conv's 3x3 GEMM on the ping-pong kernel
-bool conv_k_chunked(int HW, int Cin, int Cout);   // (GILL_CONV_KORDER = 0 | 1 forces tap-major / chunk-major: tests and tools)
+bool conv_k_chunked(int HW, int Cin, int Cout);   // chunk-major K order for this conv?  Decided by the shape alone: a large input (>= 4096 pixels, > 4 MiB per sample) off the ping-pong tile
 int conv_weight_relayout_ups4_launch(const void* w, int dtype, int Cout, int Cin, bf16_t* out /*[4][Cout][4][Cin]*/, hipStream_t s);   // GemmArgs::ups == 2
 int conv_weight_relayout_chunked_launch(const void* w, int dtype, int Cout, int Cin, bf16_t* out /*[Cout][Cin/64][9][64]*/, hipStream_t s);   // GemmArgs::conv
 int convert_to_bf16_launch(const void* src, int dtype, int64_t n, bf16_t* dst, hipStream_t s);

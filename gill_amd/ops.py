@@ -929,6 +929,25 @@ def lm_loss_geometry(M: int, V: int, D: int):
   return tuple(o.value for o in out)
 
 
+def gemm_plan(cases, pp: int = 1, coop: int = 1, cus: int = 256):
+  """What the GEMM launcher decides for each case (host only: gill_gemm_plan).  cases (n, 54) int32 descriptors -> (n, 34) int32 rows; the
+  field orders are in include/gill_amd.h.  pp / coop / cus: GILL_GEMM_PP, GILL_GEMM_COOP and the CU count the plan is made for."""
+  import numpy as np
+  cases = np.ascontiguousarray(cases, dtype=np.int32).reshape(-1, 54)
+  rows = np.zeros((cases.shape[0], 34), dtype=np.int32)
+  N.check(N.lib().gill_gemm_plan(cases.ctypes.data, cases.shape[0], int(pp), int(coop), int(cus), rows.ctypes.data))
+  return rows
+
+
+def gemm_query(queries, pp: int = 1, coop: int = 1, cus: int = 256):
+  """The engines' pre-launch GEMM choices (host only: gill_gemm_query).  queries (n, 7) int32 = [what, six arguments] -> (n,) int32."""
+  import numpy as np
+  queries = np.ascontiguousarray(queries, dtype=np.int32).reshape(-1, 7)
+  out = np.zeros(queries.shape[0], dtype=np.int32)
+  N.check(N.lib().gill_gemm_query(queries.ctypes.data, queries.shape[0], int(pp), int(coop), int(cus), out.ctypes.data))
+  return out
+
+
 def lm_head_loss(x: torch.Tensor, w: torch.Tensor, target: torch.Tensor, check: bool = True):
   """The LM-head loss without a logits tensor (gill_op_lm_head_loss): x (M,D) bf16, w (V,D) bf16, target (M) int64 with -100 = ignore ->
   (lse (M) fp32, tgt (M) fp32, rank (M) int32, summary (4) fp32 = [mean of lse - tgt over valid rows, n_valid, #rank < 1, #rank < 5]).

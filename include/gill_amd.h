@@ -703,6 +703,28 @@ int gill_op_lm_head_loss(const void* X_bf16, const void* W_bf16, const int64_t* 
  * launch merges in ascending order.  The slabs cover [0, V) exactly once.  Any output may be NULL. */
 int gill_lm_loss_geometry(int M, int V, int D, int* row_tile, int* col_tile, int* n_slabs, int* cols_per_slab);
 
+/* What the GEMM / convolution launcher decides for a launch (host only, for tests; no GPU is touched).  Every decision of a launch — kernel
+ * instantiation, grid, tile -> workgroup map, in-kernel finish, reducer — is made once, by a pure function of the arguments and of an environment
+ * (pp = GILL_GEMM_PP, coop = GILL_GEMM_COOP, cus = compute units of the device), given explicitly here.
+ * cases: n descriptors of GILL_GEMM_PLAN_CASE_INTS int32, in this order (pointers as 0 / 1 = absent / present):
+ *   M N K lda ldc ldr K1 conv IH IW OH OW Cin stride ups pad_shift KX KX1 k_chunked alpha_is_one rows_per_batch resid_f32 act out_mode
+ *   heads dp ntok splitk w_blk64 partials_only gn_groups gn_cg ln_planes wb_rows fn_cg
+ *   A A2 X1 X2 W bias rowvec resid C ws gn_stats row_stats ln_stats ln_colsum fn_Y fn_gamma fn_beta coop_ctr fn_ss
+ * rows: n rows of GILL_GEMM_PLAN_ROW_INTS int32:
+ *   rc (0, or the error the launch would return: the rest of the row is then 0)
+ *   k_nwv k_bn k_conv k_epi k_stages k_kt k_mi        the gemm_kernel template arguments
+ *   grid_x grid_y grid_z
+ *   ksteps ksteps_per_split tiles_m tiles_n npw groups_n nwv mi kt n_major xb_m xb_n M rows_per_batch     the kernel argument block's integers
+ *   tile_rows ncls splitk coop reduce reduce_M        rows per M tile, parity classes, effective split, finish in-kernel, reducer launch follows (over reduce_M rows)
+ *   row_planes gn_slab_rows coop_counters             what the engines ask before the launch */
+#define GILL_GEMM_PLAN_CASE_INTS 54
+#define GILL_GEMM_PLAN_ROW_INTS 34
+int gill_gemm_plan(const int32_t* cases, int n, int pp, int coop, int cus, int32_t* rows);
+/* The engines' pre-launch choices under the same explicit environment (host only).  queries: n rows of 7 int32 = {what, six arguments}:
+ *   0 split factor (M, N, K, act, plain, generic)    1 split factor on 64 x 64-blocked weights (M, N, K)    2 fused GroupNorm bins possible (N, cg)
+ *   3 convolution on the ping-pong tile (rows, Cout)  4 chunk-major K order (HW, Cin, Cout)                  5 weights stored 64 x 64-blocked (N, K) */
+int gill_gemm_query(const int32_t* queries, int n, int pp, int coop, int cus, int32_t* answers);
+
 /* Scoring pass of the OPT engine: gill_opt_img_hidden_ex (same embedding, same negative ids, same gathered rows; raw_out / emb_out
  * bit-equal to its outputs, either may be NULL) with the final LayerNorm on EVERY row, and row (b, t) scored against
  * labels[b][t + 1] by the fused loss above (HF's shifted CrossEntropyLoss).  labels (B,T) int64 on the device, -100 ignored; NULL

@@ -388,7 +388,7 @@ def producer_defect_applies(defect, name):
 
 
 def expected_slab_rows(name):
-  """csrc/gemm.hip gemm_gn_slab_rows(): 64 from the epilogue; from the split-K reducer 64 where its grid (blocks of 64 rows and 160, 80 or
+  """csrc/gemm_plan.hip gemm_gn_slab_rows(): 64 from the epilogue; from the split-K reducer 64 where its grid (blocks of 64 rows and 160, 80 or
   64 columns) has 1024 blocks or more, else 16."""
   form, B, H, W, C1, C2, Cout, bin, CS, sk, _, _ = PRODUCER_CASES[name]
   if sk <= 1:

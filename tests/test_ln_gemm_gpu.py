@@ -15,7 +15,7 @@ Measured on an MI355X (worst case of each kind): residual stream 3.5e-3 of 6e-3;
 the whole tensor; GEGLU 5.4e-3 per row (the chain at C = 640, both producers), 3.9e-3 over the whole tensor; plane sums within 1.2e-2 of sums of squares
 of 6e4 (2e-7 relative).  No case needed a fix in gemm.hip.
 
-Which kernel a case lands on follows gemm.hip's tile_width() / gemm_launch_bn() / gemm_launch_stages() (kernel = gemm_kernel<waves, BN, conv, EPI,
+Which kernel a case lands on follows gemm_plan.hip's plan_tile_width() / plan_waves() / plan_kernel() (kernel = gemm_kernel<waves, BN, conv, EPI,
 ring depth, KT, MI>, rows per tile = waves / 2 * MI * 16); each case says so next to its parameters."""
 import functools
 
@@ -57,7 +57,7 @@ def _check_producer(cuda, M, N, K, sk, want_planes, a2=False, inplace=False):
 @pytest.mark.parametrize("M,N,want_planes", [
   (64, 320, 4), (64, 640, 8), (64, 1280, 16),        # one 128-row tile, half of it beyond M: gemm_kernel<4, 160, 0, 4, 2> (M <= 64 keeps the 160-wide tile)
   (128, 320, 4), (200, 320, 4), (512, 320, 4),       # 64-row tiles, 320 % 128 != 0: gemm_kernel<4, 160, 0, 4, 2, 64, 2>, 2 N tiles x 2 wave columns
-  (128, 640, 10), (200, 640, 10), (512, 640, 10),    # few tiles, N % 128 == 0: tile_width() = 128, gemm_kernel<4, 128, 0, 4, 3, 64, 2>, 5 N tiles
+  (128, 640, 10), (200, 640, 10), (512, 640, 10),    # few tiles, N % 128 == 0: plan_tile_width() = 128, gemm_kernel<4, 128, 0, 4, 3, 64, 2>, 5 N tiles
   (128, 1280, 20), (200, 1280, 20), (512, 1280, 20),       # the same kernel, 10 N tiles: LN_MAX_PLANES
   (3900, 1280, 20),                                  # 31 x 10 = 310 tiles of 128 x 128, the last M tile ragged: the 128-row four-wave tile gemm_kernel<4, 128, 0, 4, 2>
   (4096, 1280, 16),                                  # 32 x 8 = 256 ping-pong workgroups, one round: gemm_plain_pingpong(), gemm_kernel<8, 160, 0, 4, 3, 64, 2>
@@ -151,21 +151,21 @@ def _run_qkv(cuda, C, heads, d, nseg, B, ntok, P, splitk=1, ln_rows=0):
 @pytest.mark.parametrize("C,heads,d,P", [(320, 8, 40, 4), (640, 8, 80, 10), (1280, 8, 160, 20), (640, 10, 64, 1)])
 def test_ln_gemm_qkv(cuda, C, heads, d, P, nseg, ntok):
   """norm1 -> attn1.to_q / to_k / to_v (nseg 3) and norm2 -> attn2.to_q (nseg 1) as xf() launches them, B = 2: M = 128, or M = 200 with ntok = 100 padded to
-  128 token rows and tiles that straddle the two samples.  N = nseg * heads * dp is a multiple of 128 in every geometry, so tile_width() = 128 and the few
+  128 token rows and tiles that straddle the two samples.  N = nseg * heads * dp is a multiple of 128 in every geometry, so plan_tile_width() = 128 and the few
   tiles run gemm_kernel<4, 128, 0, 3, 3, 64, 2> (64-row four-wave tile, scatter epilogue EPI 3).  Padded head dims: 40 -> 48 and 80 -> 80 with a spare V^T row
   (dpv 64 / 96), 160 and 64 without (dpv == dp).  Planes: 4, 10 (the predicated tail of the 4-at-a-time reader), 20 (LN_MAX_PLANES) and 1."""
   _run_qkv(cuda, C, heads, d, nseg, 2, ntok, P)
 
 
 def test_ln_gemm_qkv_one_128_row_tile(cuda):
-  """M = 64: gemm_launch_bn() keeps nwv = 4, mi = 4 and gemm_launch_stages() puts the scatter epilogue on the eight-wave 128 x 128 tile
+  """M = 64: plan_waves() keeps nwv = 4, mi = 4 and plan_kernel() puts the scatter epilogue on the eight-wave 128 x 128 tile
   gemm_kernel<8, 128, 0, 3, 2, 64, 2>; rows 64 .. 127 of the tile are beyond M."""
   _run_qkv(cuda, 640, 8, 80, 3, 1, 64, 10)
 
 
 def test_ln_gemm_qkv_pingpong_256_row_tile(cuda):
   """M = 4096, C = 640, N = 1920: gemm_qkv_pingpong_mi() = 4 (16 x 12 = 192 workgroups of 256 x 160: 75 % of a round, no worse than 128-row tiles), so
-  tile_width() stays 160 and the scatter epilogue runs on the ping-pong kernel gemm_kernel<8, 160, 0, 3, 3> — level 1 at UNet batch 4."""
+  plan_tile_width() stays 160 and the scatter epilogue runs on the ping-pong kernel gemm_kernel<8, 160, 0, 3, 3> — level 1 at UNet batch 4."""
   _run_qkv(cuda, 640, 8, 80, 3, 4, 1024, 8)
 
 
