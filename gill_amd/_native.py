@@ -170,6 +170,7 @@ SYMBOLS: Dict[str, Tuple[object, List[object]]] = {
   "gill_op_lm_head_loss": (_i, [_vp, _vp, _vp, _i, _i, _i, _vp, _vp, _vp, _vp, _vp]),
   "gill_lm_loss_geometry": (_i, [_i, _i, _i, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int)]),
   "gill_gemm_plan": (_i, [_vp, _i, _i, _i, _i, _vp]),
+  "gill_unet_xf_plan": (_i, [_vp, _i, _i, _i, _i, _vp]),
   "gill_gemm_query": (_i, [_vp, _i, _i, _i, _i, _vp]),
   "gill_opt_forward_loss": (_i, [_vp, _vp, C.POINTER(C.c_int32), _i, _i, _i, _vp, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
 }

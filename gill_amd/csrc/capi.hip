@@ -7,6 +7,7 @@
 #include "tfm.h"
 #include "xf_weights.h"
 #include "gemm_plan.h"
+#include "xf_plan.h"
 #include <vector>
 
 static thread_local std::string g_last_error;
@@ -681,6 +682,28 @@ extern "C" int gill_gemm_query(const int32_t* queries, int n, int pp, int coop, 
       case 5: answers[i] = gemm_stream64_weights(q[1], q[2]) ? 1 : 0; break;
       default: GILL_REQUIRE(false, "gemm_query: unknown question");
     }
+  }
+  return 0;
+}
+
+// ---- which kernels a UNet transformer block runs, host only (xf_plan.h; tests/test_xf_plan_host.py)
+static_assert(sizeof(XfForms) + sizeof(XfPlan) == GILL_UNET_XF_PLAN_ROW_INTS * sizeof(int), "a row = the forms + the plan, all int");
+extern "C" int gill_unet_xf_plan(const int32_t* cases, int n, int lnproj, int xalg, int ffn_fused, int32_t* rows) {
+  GILL_REQUIRE(n >= 0 && (n == 0 || (cases != nullptr && rows != nullptr)), "unet_xf_plan: null case list or output");
+  const XfEnv env = {lnproj != 0, xalg != 0, ffn_fused != 0};
+  for (int i = 0; i < n; ++i) {
+    const int32_t* c = cases + (size_t)i * GILL_UNET_XF_PLAN_CASE_INTS;
+    const int C = c[0], heads = c[1], Bx = c[6];
+    GILL_REQUIRE(C > 0 && heads > 0 && C % heads == 0 && attn_padded_dim(C / heads) > 0 && c[4] > 0 && Bx > 0 && (c[7] == 0 || Bx % 2 == 0),
+                 "unet_xf_plan: heads must divide C into a supported head dim; hw and Bx positive; a shared block has an even Bx");
+    const XfGeom g = {C, heads, attn_padded_dim(C / heads), c[2], c[3], c[4], c[5] != 0};
+    const XfForms f = xf_forms(g, env);
+    GILL_REQUIRE(xf_forms_consistent(f), "internal: transformer block forms that exclude each other");
+    const XfPlan p = xf_plan(f, g, Bx, c[4], c[7] != 0);
+    int32_t* r = rows + (size_t)i * GILL_UNET_XF_PLAN_ROW_INTS;
+    const int nf = sizeof f / sizeof(int), np = sizeof p / sizeof(int);      // (both are rows of ints, in the row's order)
+    for (int k = 0; k < nf; ++k) r[k] = reinterpret_cast<const int*>(&f)[k];
+    for (int k = 0; k < np; ++k) r[nf + k] = reinterpret_cast<const int*>(&p)[k];
   }
   return 0;
 }

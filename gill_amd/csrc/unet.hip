@@ -21,6 +21,8 @@
 #include "convnet.h"
 #include "sd_schedule.h"
 #include "xf_weights.h"
+#include "xf_plan.h"
+#include "xf_args.h"
 #include <math.h>
 #include <map>
 #include <set>
@@ -36,6 +38,8 @@ struct ResnetW : ResW {
 
 struct XfW {  // Transformer2DModel with one BasicTransformerBlock
   int C = 0, heads = 0, d = 0, dp = 0, dpv = 0, layer_id = 0;
+  XfGeom geom{};              // what the forms and every call's plan are decided from (xf_plan.h)
+  XfForms forms{};            // the layouts this layer was loaded with: the optional weights below exist exactly where their form is set
   NormW gn;
   LinW proj_in, proj_out;
   NormW ln1, ln2, ln3;
@@ -47,12 +51,11 @@ struct XfW {  // Transformer2DModel with one BasicTransformerBlock
   bf16_t* wff1 = nullptr; float* bff1 = nullptr;   // GEGLU-permuted [8C][C]
   unsigned char* wff1_8 = nullptr; float* cs_ff1 = nullptr;   // gill_unet_config.fp8_convs: the same (LayerNorm-folded) rows in e4m3 + per-row de-quantisation scale (linear_fp8.hip)
   bf16_t* w1c = nullptr; float* b1c = nullptr; bf16_t* w2p = nullptr;   // the same weights as the fused feed-forward kernel reads them (ffn.hip; C = 320 only)
-  bf16_t* wpp = nullptr;        // proj_out's weight in the permuted k order: set when the fused feed-forward kernel also runs attn2.to_out (ffn.hip PRE)
-  bool w1c_kperm = false;       // the layout w1c was written in: the PRE kernel's permuted k order (ffn_relayout_launch with Wpp) — the kernel form run in xf() must match it
+  bf16_t* wpp = nullptr;        // proj_out's weight in the permuted k order, and w1c written in that order: the fused feed-forward kernel also runs attn2.to_out (ffn.hip PRE)
   bf16_t *wqkv1p = nullptr, *wq2p = nullptr;   // wqkv1 / wq2 (LayerNorm-folded) with the K order of the fused projection pairs (lnproj.hip; C = 320 only)
   // norm1/2/3 are folded into wqkv1 / wq2 / wff1 at load (GemmArgs::ln_stats): column sums of g*W and beta.W^T (+ bias)
   float *s_qkv1 = nullptr, *c_qkv1 = nullptr, *s_q2 = nullptr, *c_q2 = nullptr, *s_ff1 = nullptr;
-  bf16_t* xg = nullptr; float* xgb = nullptr;   // XALG (xf_weights.hip): [2 H C][ctx_dim] = G | G2, and gb [H][ctx_dim]; null = attention-kernel form
+  bf16_t* xg = nullptr; float* xgb = nullptr;   // XALG (xf_weights.hip): [2 H C][ctx_dim] = G | G2, and gb [H][ctx_dim]
   LinW ff2;                   // [C][4C]
   bf16_t* wfo = nullptr; float* bfo = nullptr;   // ff2 and proj_out as one map: [C][4C + C] = [Wp W2 | Wp], bias Wp b2 + bp
 };
@@ -139,23 +142,6 @@ struct gill_unet : ConvWorkspace {
   }
 };
 
-// The feed-forward sub-blocks at C = 320 (level 0) run as one kernel (ffn.hip) instead of GEGLU + the two-source ffo GEMM: loop
-// 528.9 -> 522.8 ms.  GILL_UNET_FFN_FUSED = 0 restores the two GEMMs.
-// GILL_UNET_LNPROJ=0: proj_in / QKV and attn1.to_out / attn2.to_q of the level-0 blocks as the separate GEMMs
-static bool lnproj_on() {
-  static const bool on = [] { const char* e = getenv("GILL_UNET_LNPROJ"); return !(e && e[0] == '0'); }();
-  return on;
-}
-// GILL_UNET_XALG=0: attn2 of levels 1-3 as to_q + attention kernel + to_out instead of the two per-sample GEMMs ("XALG": xf_weights.hip)
-static bool xalg_on() {
-  static const bool on = [] { const char* e = getenv("GILL_UNET_XALG"); return !(e && e[0] == '0'); }();
-  return on;
-}
-static bool ffn_fused_on() {
-  static const bool on = [] { const char* e = getenv("GILL_UNET_FFN_FUSED"); return !(e && e[0] == '0'); }();
-  return on;
-}
-
 namespace {
 
 struct Loader {
@@ -202,6 +188,9 @@ struct Loader {
     GILL_REQUIRE(x->dp > 0, "unsupported attention head dim");
     const int hdp = H * x->dp;
     GILL_REQUIRE(hdp % 64 == 0, "padded attention width must be a multiple of 64");
+    x->geom = XfGeom{C, H, x->dp, ctx_len, ctx_dim, hw, f8};
+    const XfForms forms = x->forms = xf_forms(x->geom, xf_env_default());
+    GILL_REQUIRE(xf_forms_consistent(forms), "internal: transformer block forms that exclude each other");
     GILL_TRY(norm(p + ".norm", C, &x->gn));
     GILL_TRY(lin(p + ".proj_in", C, C, &x->proj_in));
     GILL_TRY(lin(p + ".proj_out", C, C, &x->proj_out));
@@ -255,30 +244,26 @@ struct Loader {
     GILL_TRY(xf_qkv_weights(hr, 3, nullptr, H, x->d, x->dp, C, x->ln1.g, x->ln1.b, x->wqkv1, x->s_qkv1, x->c_qkv1, x->wqkv1p, s, XF_FOLD));
     GILL_TRY(xf_qkv_weights(hr + 3, 1, nullptr, H, x->d, x->dp, C, x->ln2.g, x->ln2.b, x->wq2, x->s_q2, x->c_q2, x->wq2p, s, XF_FOLD));
     GILL_TRY(xf_geglu_weights(tmpw, tmpb, inner, C, x->ln3.g, x->ln3.b, idx, x->wff1, x->bff1, x->s_ff1, s, XF_FOLD));
-    // fp8 mode (BASELINE configs[4]): the GEGLU projection of the blocks that run it as a GEMM (levels 1-3; level 0 has the fused feed-forward
-    // kernel) on the fp8 matrix instruction — the folded rows quantised per output row
-    if (f8 && C % 128 == 0 && !(ffn_fused_on() && ffn_fused_supported(C, 128))) {
+    // the optional layouts (xf_plan.h has the rules).  fp8 GEGLU: the folded rows quantised per output row
+    if (forms.geglu_fp8) {
       GILL_TRY(pool.alloc(&x->wff1_8, (size_t)8 * C * C, false));
       GILL_TRY(pool.alloc(&x->cs_ff1, (size_t)8 * C, false));
       GILL_TRY(linear_weight_quant_fp8_launch(x->wff1, 8 * C, C, F8_LIN_ACT_SCALE, x->wff1_8, x->cs_ff1, s));
     }
-    // cross-attention as two GEMMs: where the 80 key slots per head are no wider than the head itself (d >= 80: SD-1.5 levels 1-3)
-    // ... and a sample is whole 64-row tiles (per-sample weights: a tile must not straddle samples — sample_size 32 / 96 have 16- / 144-token
-    // mid blocks); otherwise the layer keeps its K / V caches and the attention-kernel form
-    if (xalg_on() && H % 2 == 0 && ctx_len <= 80 && 80 * H <= hdp && x->dp <= 160 && C % 64 == 0 && ctx_dim % 64 == 0 && hw % 64 == 0) {
+    // cross-attention as two GEMMs; otherwise the layer keeps its K / V caches and the attention-kernel form
+    if (forms.xalg) {
       GILL_TRY(pool.alloc(&x->xg, (size_t)2 * H * C * ctx_dim, false));
       GILL_TRY(pool.alloc(&x->xgb, (size_t)H * ctx_dim));
       GILL_TRY(xalg_fold_launch(x->wq2, x->c_q2, x->wkv2, x->out2.w, H, C, x->d, x->dp, ctx_dim, x->xg, x->xgb, s));
     }
-    if (ffn_fused_on() && ffn_fused_supported(C, 128)) {
+    if (forms.ffn_fused) {
       GILL_TRY(pool.alloc(&x->w1c, (size_t)8 * C * C, false));
       GILL_TRY(pool.alloc(&x->b1c, (size_t)8 * C, false));
       GILL_TRY(pool.alloc(&x->w2p, (size_t)4 * C * C, false));
-      if (hdp == 384) GILL_TRY(pool.alloc(&x->wpp, (size_t)C * C, false));
+      if (forms.ffn_pre) GILL_TRY(pool.alloc(&x->wpp, (size_t)C * C, false));
       GILL_TRY(ffn_relayout_launch(x->wff1, x->bff1, x->wfo, x->w1c, x->b1c, x->w2p, x->wpp, s));
-      x->w1c_kperm = x->wpp != nullptr;
     }
-    if (lnproj_on() && lnproj_supported(C, 128, H, x->dp)) {
+    if (forms.lnproj) {
       GILL_TRY(pool.alloc(&x->wqkv1p, (size_t)3 * hdp * C, false));
       GILL_TRY(pool.alloc(&x->wq2p, (size_t)hdp * C, false));
       GILL_TRY(xf_qkv_weights(hr, 3, nullptr, H, x->d, x->dp, C, x->ln1.g, x->ln1.b, x->wqkv1, x->s_qkv1, x->c_qkv1, x->wqkv1p, s, XF_KPERM));
@@ -604,156 +589,148 @@ struct UNetRun : ConvRun {
     return attention_launch(a, s);
   }
 
-  // does xf() take its GroupNorm as a table (the fused projection kernel applies it on load)?  Mirrors the conditions inside xf().
-  bool xf_wants_table(const XfW& w, int HW, bool shared) const {
-    return w.wqkv1p != nullptr && !shared && lnproj_supported(w.C, Bx * HW, w.heads, w.dp) && HW % 128 == 0;
-  }
-
-  // shared: `x` (and Bx on entry) cover only the first half of a CFG pair; the block runs at that half batch up to the end of
-  // the self-attention, then the residual stream is duplicated and the rest runs on the full pair (Bx restored on return)
-  // pre: x already normalised (this block's GroupNorm, no SiLU) by its producer's reducer; next: see resnet()
-  // pre_ss: this block's GroupNorm as a scale | shift table already written by its producer's in-kernel finish (FusedNorm::ss; only where
-  // xf_wants_table() said so)
-  int xf(const Tensor& x, const XfW& w, Tensor* out, bool out_stats, bool shared = false, const Tensor* pre = nullptr,
-         FusedNorm* next = nullptr, const float* pre_ss = nullptr) {
-    const int Bpre = Bx, Bfull = shared ? 2 * Bx : Bx;
-    Bx = Bfull;                    // every buffer is sized for the full batch
-    const int H = x.H, Wd = x.W, C = w.C, HW = H * Wd, M = Bfull * HW, M1 = Bpre * HW;
-    const int nh = w.heads, hdp = nh * w.dp;
-    const bool ffn_fused = w.w1c != nullptr && ffn_fused_supported(C, M) && HW % 128 == 0;
-    // proj_in + norm1 + QKV, and attn1.to_out + residual + norm2 + attn2.to_q, as one kernel each (lnproj.hip).  Not on the shared-prefix
-    // block: its M1 = M / 2 rows are 128 tiles for 256 CUs — one tile per CU takes as long as at full size, the two GEMMs take half.
-    const bool lnproj = w.wqkv1p != nullptr && !shared && lnproj_supported(C, M, nh, w.dp) && HW % 32 == 0;
-    *out = talloc(H, Wd, C, out_stats);
-    const size_t mk = m->arena.mark();
-    Tensor n = talloc(H, Wd, C);
-    Tensor xd = x;                 // the outer residual at full batch
-    if (shared) xd = talloc(H, Wd, C);
-    Bx = Bpre;
-    // the fused projection kernel applies this GroupNorm itself to the rows it loads (lnproj.hip: gn_ss) where the producer filed the
-    // statistics: the stand-alone pass (13 us, 21 MB read + 21 MB written per level-0 block) becomes a 640-float table per sample
-    float* gn_ss = nullptr;
-    bool gn_folded = false;
-    if (lnproj && HW % 128 == 0) gn_ss = (float*)m->arena.alloc(sizeof(float) * (size_t)Bx * 2 * C);
-    if (pre_ss && gn_ss) { gn_ss = const_cast<float*>(pre_ss); gn_folded = true; }
-    else if (pre) n = *pre;
-    else GILL_TRY(gnorm(x, nullptr, w.gn, 1e-6f, 0, n, 0.f, gn_ss, &gn_folded));
-    Bx = Bfull;
-    Tensor t = talloc(H, Wd, C);   // transformer residual stream
+  // Bx for a scope: xf() sizes its buffers for the full batch of a CFG pair and runs its GroupNorm and self-attention kernel at the half batch
+  struct BatchScope {
+    int& Bx; const int saved;
+    BatchScope(int& Bx, int b) : Bx(Bx), saved(Bx) { Bx = b; }
+    ~BatchScope() { Bx = saved; }
+  };
+  // what one call of the block runs (xf_plan.h); Bx is the batch of the block's input: half of a CFG pair where `shared`
+  XfPlan xf_plan_of(const XfW& w, int HW, bool shared) const { return xf_plan(w.forms, w.geom, shared ? 2 * Bx : Bx, HW, shared); }
+  // one block's tensors on their way through the three stages of xf()
+  struct XfBlock {
+    const XfW& w; const XfPlan p; const int HW, hw_pad, Bpre; const bool shared;
+    Tensor t;                            // transformer residual stream
+    Tensor xd;                           // the outer residual at full batch
+    bf16_t *q, *k, *vt, *o;              // attention operands (attn1's, then attn2's query) and output
     // norm1/2/3 never materialise: the GEMM that writes the residual stream also accumulates each row's sum and sum of
     // squares, and the projection that follows applies mean / rstd in its epilogue on weights pre-multiplied by the LN gain
-    RowStats st1 = ln_slot(M, C), st2 = ln_slot(M, C), st3 = ln_slot(M, C);
-    if (!lnproj) GILL_TRY(linear(n.p, C, nullptr, 0, C, M1, w.proj_in.w, w.proj_in.b, C, C, nullptr, ACT_NONE, t.p, C, nullptr, &st1));
-    const int hw_pad = round_up(HW, 32);   // kv tiles are 32 wide; pad rows hold finite stale data and are masked
-    bf16_t* q = (bf16_t*)m->arena.alloc(sizeof(bf16_t) * (size_t)Bx * nh * hw_pad * w.dp);
-    bf16_t* k = (bf16_t*)m->arena.alloc(sizeof(bf16_t) * (size_t)Bx * nh * hw_pad * w.dp);
-    bf16_t* vt = (bf16_t*)m->arena.alloc(sizeof(bf16_t) * (size_t)Bx * nh * w.dpv * hw_pad);
-    bf16_t* o = (bf16_t*)m->arena.alloc(sizeof(bf16_t) * (size_t)M * hdp);
-    // --- self attention
-    LnProjArgs lp;
-    lp.M = M; lp.T = t.p; lp.heads = nh; lp.dp = w.dp; lp.dpv = w.dpv; lp.ntok = HW; lp.ntok_pad = hw_pad;
-    lp.Cq = q; lp.Ck = k; lp.Cvt = vt; lp.qscale = 1.4426950408889634f / sqrtf((float)w.d);
-    if (lnproj) {
-      lp.mode = 0; lp.X = gn_folded ? x.p : n.p; lp.gn_ss = gn_folded ? gn_ss : nullptr; lp.W1 = w.proj_in.w; lp.b1 = w.proj_in.b; lp.W2p = w.wqkv1p; lp.c2 = w.c_qkv1;
+    RowStats st1, st2, st3;
+    XfHeads heads() const { return xf_heads(w.heads, w.d); }
+    // proj_in + norm1 + QKV, and attn1.to_out + residual + norm2 + attn2.to_q, as one kernel each (lnproj.hip): what both modes share
+    LnProjArgs lnproj_args() const {
+      LnProjArgs lp;
+      lp.M = p.M; lp.T = t.p; lp.heads = w.heads; lp.dp = w.dp; lp.dpv = w.dpv; lp.ntok = HW; lp.ntok_pad = hw_pad;
+      lp.Cq = q; lp.Ck = k; lp.Cvt = vt; lp.qscale = heads().qscale;
+      return lp;
+    }
+  };
+
+  // n: the block's input after its GroupNorm; or (gn_ss) x itself and the scale | shift table the projection kernel applies to the rows it loads
+  int xf_self_attention(XfBlock& b, const bf16_t* n, const float* gn_ss) {
+    const XfW& w = b.w; const int C = w.C;
+    if (b.p.lnproj) {
+      LnProjArgs lp = b.lnproj_args();
+      lp.mode = 0; lp.X = n; lp.gn_ss = gn_ss; lp.W1 = w.proj_in.w; lp.b1 = w.proj_in.b; lp.W2p = w.wqkv1p; lp.c2 = w.c_qkv1;
       if (!dry) GILL_TRY(lnproj_launch(lp, s));
     } else {
-      GemmArgs g;
-      g.M = M1; g.N = 3 * hdp; g.K = C; g.K1 = C; g.A = t.p; g.lda = C; g.W = w.wqkv1;
-      g.ln_stats = st1.p; g.ln_planes = st1.planes; g.ln_colsum = w.s_qkv1; g.bias = w.c_qkv1;
-      g.out_mode = OUT_QKV; g.Cq = q; g.Ck = k; g.Cvt = vt; g.heads = nh; g.dp = w.dp; g.dpv = w.dpv;
-      g.ntok = HW; g.ntok_pad_q = hw_pad; g.ntok_pad_kv = hw_pad; g.seg_base = 0;
-      g.qscale = 1.4426950408889634f / sqrtf((float)w.d);
+      GILL_TRY(linear(n, C, nullptr, 0, C, b.p.M1, w.proj_in.w, w.proj_in.b, C, C, nullptr, ACT_NONE, b.t.p, C, nullptr, &b.st1));
+      GemmArgs g = xf_qkv_args(b.t.p, b.p.M1, C, {b.st1.p, b.st1.planes, 0}, w.wqkv1, w.s_qkv1, w.c_qkv1, 3, b.heads(), b.HW, b.q, b.k, b.vt);
       GILL_TRY(gemm(g));
     }
-    Bx = Bpre;
-    GILL_TRY(attend(q, k, vt, o, HW, HW, hw_pad, hw_pad, w));
-    Bx = Bfull;
-    const bf16_t* tres = t.p;         // the residual stream after the two attention sub-blocks
-    bool ffn_pre = false;             // ... or, PRE: before attn2.to_out, which the feed-forward kernel then runs itself
-    bool xalg_done = false;
-    {
-    if (lnproj) {
-      GILL_REQUIRE(!w.xg, "internal: the fused projection pairs and the two-GEMM cross-attention are alternatives");
-      lp.mode = 1; lp.X = o; lp.gn_ss = nullptr; lp.W1 = w.out1.w; lp.b1 = w.out1.b; lp.W2p = w.wq2p; lp.c2 = w.c_q2;
+    BatchScope half(Bx, b.Bpre);
+    return attend(b.q, b.k, b.vt, b.o, b.HW, b.HW, b.hw_pad, b.hw_pad, w);
+  }
+
+  // x: the block's input (the shared prefix's half batch is duplicated into b.xd here, with the residual stream)
+  int xf_cross_attention(XfBlock& b, const Tensor& x) {
+    const XfW& w = b.w; const XfPlan& p = b.p; const int C = w.C, hdp = w.heads * w.dp;
+    if (p.lnproj) {
+      LnProjArgs lp = b.lnproj_args();
+      lp.mode = 1; lp.X = b.o; lp.W1 = w.out1.w; lp.b1 = w.out1.b; lp.W2p = w.wq2p; lp.c2 = w.c_q2;
       if (!dry) GILL_TRY(lnproj_launch(lp, s));
     } else {
-    GILL_TRY(linear(o, hdp, nullptr, 0, hdp, M1, w.out1.w, w.out1.b, C, hdp, t.p, ACT_NONE, t.p, C, nullptr, &st2));
-    if (shared && !dry) {
+      GILL_TRY(linear(b.o, hdp, nullptr, 0, hdp, p.M1, w.out1.w, w.out1.b, C, hdp, b.t.p, ACT_NONE, b.t.p, C, nullptr, &b.st2));
       // second half of the pair := first half (residual stream, its LayerNorm row sums, the block input)
-      // (out1 ran on M1 rows: its row-sum planes are [planes][M1][2]; the consumer below wraps rows >= M1 onto them)
-      GILL_TRY(dup_pair_launch(t.p, x.p, xd.p, sizeof(bf16_t) * (size_t)M1 * C, s));
-    }
-    // --- cross attention (K/V cached per prompt)
-    if (w.xg) {
-      // ... as P = softmax80(LN(t) Mq_b^T), t += P Wo_b^T + bias on per-sample weights (xf_weights.hip)
-      const int n80 = 80 * nh, id = w.layer_id;
-      GemmArgs g;
-      g.M = M; g.N = n80; g.K = C; g.K1 = C; g.A = t.p; g.lda = C; g.W = m->xq_w[id];
-      g.wb_rows = HW; g.wb_stride = (int64_t)n80 * C; g.vb_stride = n80;
-      g.ln_stats = st2.p; g.ln_planes = st2.planes; g.ln_rows = M1; g.ln_colsum = m->xq_cs[id]; g.bias = m->xq_b[id];
-      g.out_mode = OUT_SOFTMAX80; g.C = o; g.ldc = n80;
-      GILL_TRY(gemm(g));
-      GemmArgs g2;
-      g2.M = M; g2.N = C; g2.K = n80; g2.K1 = n80; g2.A = o; g2.lda = n80; g2.W = m->xo_w[id]; g2.bias = w.out2.b;
-      g2.wb_rows = HW; g2.wb_stride = (int64_t)n80 * C;
-      g2.resid = t.p; g2.ldr = C; g2.C = t.p; g2.ldc = C;
-      GILL_TRY(gemm(g2, &st3));
-      xalg_done = true;
-    } else {
-      GemmArgs g;
-      g.M = M; g.N = hdp; g.K = C; g.K1 = C; g.A = t.p; g.lda = C; g.W = w.wq2;
-      g.ln_stats = st2.p; g.ln_planes = st2.planes; g.ln_rows = M1; g.ln_colsum = w.s_q2; g.bias = w.c_q2;
-      g.out_mode = OUT_QKV; g.Cq = q; g.Ck = k; g.Cvt = vt; g.heads = nh; g.dp = w.dp; g.dpv = w.dpv;
-      g.ntok = HW; g.ntok_pad_q = hw_pad; g.ntok_pad_kv = hw_pad; g.seg_base = 0;
-      g.qscale = 1.4426950408889634f / sqrtf((float)w.d);
-      GILL_TRY(gemm(g));
-    }
-    }
-    if (!xalg_done) {
-    GILL_REQUIRE(m->kcache[w.layer_id] != nullptr || dry, "internal: cross-attention K/V cache missing");
-    GILL_TRY(attend(q, m->kcache[w.layer_id], m->vcache[w.layer_id], o, HW, m->cfg.ctx_len, hw_pad, m->ctx_pad, w));
-    // (with the fused feed-forward kernel's PRE form, attn2.to_out + residual run inside it: ffn.hip)
-    ffn_pre = ffn_fused && w.wpp != nullptr;
-    GILL_REQUIRE(!ffn_fused || ffn_pre == w.w1c_kperm, "internal: fused feed-forward kernel form does not match the layout its weights were written in");
-    if (!ffn_pre) GILL_TRY(linear(o, hdp, nullptr, 0, hdp, M, w.out2.w, w.out2.b, C, hdp, t.p, ACT_NONE, t.p, C, nullptr, &st3));
-    }
-    }
-    if (ffn_fused) {
-      // --- GEGLU feed-forward, its residual, proj_out and the outer residual as ONE kernel (ffn.hip)
-      if (!dry) {
-        FfnArgs fa;
-        fa.M = M; fa.T = tres; fa.ln_stats = st3.p; fa.ln_planes = st3.planes;
-        fa.W1c = w.w1c; fa.b1c = w.b1c; fa.W2p = w.w2p; fa.Wfo = w.wfo; fa.bo = w.bfo; fa.resid = xd.p; fa.out = out->p;
-        if (ffn_pre) { fa.X = o; fa.Wo = w.out2.w; fa.bo2 = w.out2.b; fa.Wpp = w.wpp; }
-        if (out->stats && out->sbin == 5) { fa.gn_stats = out->stats; fa.rows_per_batch = HW; out->nslab = HW / GN_SLAB_ROWS; }
-        else out->stats = nullptr;        // (no partials from this producer: the consumer runs its own statistics pass)
-        GILL_TRY(ffn_fused_launch(fa, s));
+      // (out1 ran on M1 rows: its row-sum planes are [planes][M1][2]; the consumers below wrap rows >= M1 onto them)
+      if (b.shared && !dry) GILL_TRY(dup_pair_launch(b.t.p, x.p, b.xd.p, sizeof(bf16_t) * (size_t)p.M1 * C, s));
+      const XfLnRows ln2 = {b.st2.p, b.st2.planes, p.M1};
+      if (p.cross == XF_CROSS_XALG) {
+        // P = softmax80(LN(t) Mq_b^T), t += P Wo_b^T + bias on per-sample weights (xf_weights.hip)
+        const int id = w.layer_id;
+        GemmArgs g, g2;
+        xf_xalg_args(b.t.p, p.M, b.HW, C, w.heads, ln2, m->xq_w[id], m->xq_cs[id], m->xq_b[id], m->xo_w[id], w.out2.b, b.o, b.t.p, b.t.p, &g, &g2);
+        GILL_TRY(gemm(g));
+        return gemm(g2, &b.st3);
       }
-      m->arena.release(mk);
-      return 0;
+      GemmArgs g = xf_qkv_args(b.t.p, p.M, C, ln2, w.wq2, w.s_q2, w.c_q2, 1, b.heads(), b.HW, b.q, b.k, b.vt);
+      GILL_TRY(gemm(g));
     }
-    // --- GEGLU feed-forward
+    // the attention kernel over the K / V cached per prompt
+    GILL_REQUIRE(m->kcache[w.layer_id] != nullptr || dry, "internal: cross-attention K/V cache missing");
+    GILL_TRY(attend(b.q, m->kcache[w.layer_id], m->vcache[w.layer_id], b.o, b.HW, m->cfg.ctx_len, b.hw_pad, m->ctx_pad, w));
+    // (with the fused feed-forward kernel's PRE form, attn2.to_out + residual run inside it: ffn.hip)
+    if (p.ffn == XF_FFN_FUSED_PRE) return 0;
+    return linear(b.o, hdp, nullptr, 0, hdp, p.M, w.out2.w, w.out2.b, C, hdp, b.t.p, ACT_NONE, b.t.p, C, nullptr, &b.st3);
+  }
+
+  int xf_feed_forward(XfBlock& b, Tensor* out, FusedNorm* next) {
+    const XfW& w = b.w; const XfPlan& p = b.p; const int C = w.C, M = p.M;
+    if (p.ffn == XF_FFN_FUSED || p.ffn == XF_FFN_FUSED_PRE) {
+      // GEGLU feed-forward, its residual, proj_out and the outer residual as ONE kernel (ffn.hip)
+      if (dry) return 0;
+      FfnArgs fa;
+      fa.M = M; fa.T = b.t.p; fa.ln_stats = b.st3.p; fa.ln_planes = b.st3.planes;
+      fa.W1c = w.w1c; fa.b1c = w.b1c; fa.W2p = w.w2p; fa.Wfo = w.wfo; fa.bo = w.bfo; fa.resid = b.xd.p; fa.out = out->p;
+      if (p.ffn == XF_FFN_FUSED_PRE) { fa.X = b.o; fa.Wo = w.out2.w; fa.bo2 = w.out2.b; fa.Wpp = w.wpp; }
+      if (out->stats && out->sbin == 5) { fa.gn_stats = out->stats; fa.rows_per_batch = b.HW; out->nslab = b.HW / GN_SLAB_ROWS; }
+      else out->stats = nullptr;        // (no partials from this producer: the consumer runs its own statistics pass)
+      return ffn_fused_launch(fa, s);
+    }
     bf16_t* ffh = (bf16_t*)m->arena.alloc(sizeof(bf16_t) * (size_t)M * 4 * C);
-    unsigned char* t8 = w.wff1_8 ? (unsigned char*)m->arena.alloc((size_t)M * C) : nullptr;
-    if (w.wff1_8) {
+    if (p.ffn == XF_FFN_GEMM_FP8) {
       // fp8 mode: norm3 applied explicitly into an e4m3 copy of t (one pass: 3 bytes per element), then the GEGLU GEMM on the fp8 matrix instruction
+      unsigned char* t8 = (unsigned char*)m->arena.alloc((size_t)M * C);
       if (!dry) {
-        GILL_TRY(ln_quant_fp8_launch(tres, M, C, st3.p, st3.planes, 0, 1e-5f, F8_LIN_ACT_SCALE, t8, s));
+        GILL_TRY(ln_quant_fp8_launch(b.t.p, M, C, b.st3.p, b.st3.planes, 0, 1e-5f, F8_LIN_ACT_SCALE, t8, s));
         LinF8Args a;
         a.M = M; a.N = 8 * C; a.K = C; a.A8 = t8; a.W8 = w.wff1_8; a.colscale = w.cs_ff1; a.bias = w.bff1; a.C = ffh;
         GILL_TRY(geglu_fp8_launch(a, s));
         GILL_TRY(dbg_sync("geglu fp8", M, 8 * C, C));
       }
     } else {
-      GemmArgs g;
-      g.M = M; g.N = 8 * C; g.K = C; g.K1 = C; g.A = tres; g.lda = C; g.W = w.wff1; g.bias = w.bff1;
-      g.ln_stats = st3.p; g.ln_planes = st3.planes; g.ln_colsum = w.s_ff1;
-      g.act = ACT_GEGLU; g.C = ffh; g.ldc = 4 * C;
+      GemmArgs g = xf_geglu_args(b.t.p, M, C, 4 * C, {b.st3.p, b.st3.planes, 0}, w.wff1, w.s_ff1, w.bff1, ffh);
       GILL_TRY(gemm(g));
     }
-    // --- feed-forward output, its residual, proj_out and the outer residual: one GEMM over K = [h | t] (see ffo_fuse_kernel in xf_weights.hip; the
+    // feed-forward output, its residual, proj_out and the outer residual: one GEMM over K = [h | t] (see ffo_fuse_kernel in xf_weights.hip; the
     // reference graph's two GEMMs measured 604.3 -> 588.9 ms against it, profiles/HISTORY.md)
-    GILL_TRY(linear(ffh, 4 * C, tres, C, 4 * C, M, w.wfo, w.bfo, C, 5 * C, xd.p, ACT_NONE, out->p, C, out, nullptr, next));
+    return linear(ffh, 4 * C, b.t.p, C, 4 * C, M, w.wfo, w.bfo, C, 5 * C, b.xd.p, ACT_NONE, out->p, C, out, nullptr, next);
+  }
+
+  // shared: `x` (and Bx) cover only the first half of a CFG pair; the block runs at that half batch up to the end of the self-attention, then
+  // the residual stream is duplicated and the rest runs on the full pair
+  // pre: x already normalised (this block's GroupNorm, no SiLU) by its producer's reducer; next: see resnet()
+  // pre_ss: this block's GroupNorm as a scale | shift table already written by its producer's in-kernel finish (FusedNorm::ss; only where
+  // the plan has gn_table)
+  int xf(const Tensor& x, const XfW& w, Tensor* out, bool out_stats, bool shared = false, const Tensor* pre = nullptr,
+         FusedNorm* next = nullptr, const float* pre_ss = nullptr) {
+    const int H = x.H, Wd = x.W, C = w.C, HW = H * Wd;
+    XfBlock b{w, xf_plan_of(w, HW, shared), HW, round_up(HW, 32), Bx, shared};
+    BatchScope full(Bx, shared ? 2 * Bx : Bx);     // every buffer is sized for the full batch
+    *out = talloc(H, Wd, C, out_stats);
+    const size_t mk = m->arena.mark();
+    Tensor n = talloc(H, Wd, C);
+    b.xd = shared ? talloc(H, Wd, C) : x;
+    // the fused projection kernel applies this GroupNorm itself to the rows it loads (lnproj.hip: gn_ss) where the producer filed the
+    // statistics: the stand-alone pass (13 us, 21 MB read + 21 MB written per level-0 block) becomes a 640-float table per sample
+    float* gn_ss = nullptr;
+    bool gn_folded = false;
+    {
+      BatchScope half(Bx, b.Bpre);
+      if (b.p.gn_table) gn_ss = (float*)m->arena.alloc(sizeof(float) * (size_t)Bx * 2 * C);
+      if (pre_ss && gn_ss) { gn_ss = const_cast<float*>(pre_ss); gn_folded = true; }
+      else if (pre) n = *pre;
+      else GILL_TRY(gnorm(x, nullptr, w.gn, 1e-6f, 0, n, 0.f, gn_ss, &gn_folded));
+    }
+    b.t = talloc(H, Wd, C);
+    b.st1 = ln_slot(b.p.M, C); b.st2 = ln_slot(b.p.M, C); b.st3 = ln_slot(b.p.M, C);
+    b.q = (bf16_t*)m->arena.alloc(sizeof(bf16_t) * (size_t)Bx * w.heads * b.hw_pad * w.dp);      // (kv tiles are 32 wide; pad rows hold finite stale data and are masked)
+    b.k = (bf16_t*)m->arena.alloc(sizeof(bf16_t) * (size_t)Bx * w.heads * b.hw_pad * w.dp);
+    b.vt = (bf16_t*)m->arena.alloc(sizeof(bf16_t) * (size_t)Bx * w.heads * w.dpv * b.hw_pad);
+    b.o = (bf16_t*)m->arena.alloc(sizeof(bf16_t) * (size_t)b.p.M * w.heads * w.dp);
+    GILL_TRY(xf_self_attention(b, gn_folded ? x.p : n.p, gn_folded ? gn_ss : nullptr));
+    GILL_TRY(xf_cross_attention(b, x));
+    GILL_TRY(xf_feed_forward(b, out, next));
     m->arena.release(mk);
     return 0;
   }
@@ -791,13 +768,13 @@ struct UNetRun : ConvRun {
       for (int j = 0; j < 2; ++j) {
         Tensor y;
         // CFG pair: the first resnet and the first transformer block up to its self-attention see identical inputs in
-        // both halves of the batch -> run them on the first half only (xf() widens back to the full batch)
+        // both halves of the batch -> run them on the first half only (xf() widens to the full pair inside)
         const bool share = cfg_pair && i == 0 && j == 0 && Bx % 2 == 0 && temb_bstride == 0;
-        if (share) Bx /= 2;
+        BatchScope prefix(Bx, share ? Bx / 2 : Bx);     // (to the end of this iteration)
         const Handoff::Taken pre = pn.take();
         // this resnet's consumer: the transformer block's GroupNorm (i < 3), else the next resnet's / the mid block's norm1
         FusedNorm* nx = nullptr;
-        if (i < 3) nx = pn.offer(m->down_xf[i][j].gn, 1e-6f, 0, x.H, x.W, ch[i], xf_wants_table(m->down_xf[i][j], x.H * x.W, share));
+        if (i < 3) nx = pn.offer(m->down_xf[i][j].gn, 1e-6f, 0, x.H, x.W, ch[i], xf_plan_of(m->down_xf[i][j], x.H * x.W, share).gn_table);
         else nx = pn.offer(j == 0 ? m->down_res[3][1].n1 : m->mid_res[0].n1, 1e-5f, 1, x.H, x.W, ch[i]);
         GILL_TRY(resnet(x, nullptr, m->down_res[i][j], &y, true, pre.copy(), nx));
         x = y;
@@ -832,7 +809,7 @@ struct UNetRun : ConvRun {
         Tensor skip = skips.back(); skips.pop_back();
         Tensor y;
         // (norm1 of an up-block resnet is two-source: never offered; its conv2 feeds the transformer block's GroupNorm)
-        FusedNorm* nx = (i >= 1) ? pn.offer(m->up_xf[i][j].gn, 1e-6f, 0, x.H, x.W, ch[3 - i], xf_wants_table(m->up_xf[i][j], x.H * x.W, false)) : nullptr;
+        FusedNorm* nx = (i >= 1) ? pn.offer(m->up_xf[i][j].gn, 1e-6f, 0, x.H, x.W, ch[3 - i], xf_plan_of(m->up_xf[i][j], x.H * x.W, false).gn_table) : nullptr;
         GILL_TRY(resnet(x, &skip, m->up_res[i][j], &y, true, nullptr, nx));
         x = y;
         if (i > 0) {
@@ -895,7 +872,7 @@ static int unet_plan_and_alloc(gill_unet* m) {
   GILL_TRY(m->pool.alloc(&m->splitk_ws, m->splitk_ws_floats, false));
   // cross-attention K/V caches
   auto alloc_cache = [&](const XfW& w) -> int {
-    if (w.xg) {
+    if (w.forms.xalg) {
       const size_t n80 = (size_t)80 * w.heads;
       GILL_TRY(m->pool.alloc(&m->xq_w[w.layer_id], (size_t)Bx * n80 * w.C, false));
       GILL_TRY(m->pool.alloc(&m->xo_w[w.layer_id], (size_t)Bx * n80 * w.C, false));
@@ -972,7 +949,7 @@ static int unet_time_table(gill_unet* m, const float* t_host, int rows, hipStrea
 static int unet_ctx_cache(gill_unet* m, const bf16_t* ctx, int Bx, hipStream_t s) {
   const gill_unet_config& c = m->cfg;
   auto one = [&](const XfW& w) -> int {
-    if (w.xg) {
+    if (w.forms.xalg) {
       const int H = w.heads, C = w.C, E = c.cross_attention_dim, id = w.layer_id;
       return xalg_operands_launch(ctx, w.xg, w.xgb, Bx, H, C, E, c.ctx_len, (bf16_t*)m->arena.base, m->xq_w[id], m->xq_cs[id], m->xq_b[id], m->xo_w[id], s);
     }

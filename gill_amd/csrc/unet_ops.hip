@@ -1,6 +1,7 @@
 // The UNet's operator-level entry points (gill_op_*), for tests and tools; their operands come from the engine's own code: sd_schedule.h, xf_weights.h.
 #include "sd_schedule.h"
 #include "xf_weights.h"
+#include "xf_args.h"
 
 // Operator-level entry for the loop's sampler arithmetic: the schedule, the stage and step kernels and the device-side step counter exactly as
 // sd_denoise_on (unet.hip) drives them, the UNet replaced by the caller's model outputs.  For tests/test_samplers_gpu.py; synchronises.
@@ -91,7 +92,8 @@ extern "C" int gill_op_ffn_fused(const void* t, const float* ln_g, const float* 
                                  const float* b2, const void* Wp, const float* bp, const void* resid, void* out, float* gn_stats,
                                  int M, int rows_per_batch, const void* o2, const void* Wo, const float* bo2, void* stream) {
   hipStream_t s = (hipStream_t)stream;
-  const int C = 320, inner = 4 * C, heads = 8, d = 40, dp = attn_padded_dim(d), hdp = heads * dp;
+  const XfHeads hd = xf_heads(8, 40);
+  const int C = 320, inner = 4 * C, heads = hd.heads, d = hd.d, dp = hd.dp, hdp = hd.hdp;
   GILL_REQUIRE(t && ln_g && ln_b && W1 && b1 && W2 && b2 && Wp && bp && resid && out, "null argument");
   GILL_REQUIRE((o2 != nullptr) == (Wo != nullptr) && (o2 != nullptr) == (bo2 != nullptr), "o2 / Wo / bo2: all or none");
   GILL_REQUIRE(ffn_fused_supported(C, M), "ffn_fused: M must be a multiple of 128");
@@ -192,7 +194,8 @@ extern "C" int gill_op_geglu_fp8_q(const void* x8, const void* w8, const float* 
 extern "C" int gill_op_lnproj(int mode, const void* x, void* t, const void* W1, const float* b1, const float* ln_g, const float* ln_b,
                               const void* W2, void* q, void* k, void* vt, int B, int HW, void* stream) {
   hipStream_t s = (hipStream_t)stream;
-  const int C = 320, heads = 8, d = 40, dp = attn_padded_dim(d), dpv = round_up(dp, 32), hdp = heads * dp, M = B * HW;
+  const XfHeads hd = xf_heads(8, 40);
+  const int C = 320, heads = hd.heads, d = hd.d, dp = hd.dp, dpv = hd.dpv, hdp = hd.hdp, M = B * HW;
   const int nseg = mode == 0 ? 3 : 1;
   GILL_REQUIRE(mode == 0 || mode == 1, "mode must be 0 or 1");
   GILL_REQUIRE(x && t && W1 && b1 && ln_g && ln_b && W2 && q && (mode == 1 || (k && vt)), "null argument");
@@ -207,7 +210,7 @@ extern "C" int gill_op_lnproj(int mode, const void* x, void* t, const void* W1, 
   LnProjArgs a;
   a.mode = mode; a.M = M; a.T = (bf16_t*)t; a.b1 = b1; a.W2p = (const bf16_t*)w2p.p; a.c2 = (const float*)cb.p;
   a.Cq = (bf16_t*)q; a.Ck = (bf16_t*)k; a.Cvt = (bf16_t*)vt; a.heads = heads; a.dp = dp; a.dpv = dpv; a.ntok = HW; a.ntok_pad = round_up(HW, 32);
-  a.qscale = 1.4426950408889634f / sqrtf((float)d);
+  a.qscale = hd.qscale;
   if (mode == 0) {
     a.X = (const bf16_t*)x; a.W1 = (const bf16_t*)W1;
   } else {
@@ -252,15 +255,9 @@ extern "C" int gill_op_cross_attention_folded(const void* t, const float* ln_g, 
   GILL_TRY(row_sums_launch((const bf16_t*)t, M, C, (float*)st.p, s));
   void* pp = P;
   if (!pp) { GILL_TRY(p.alloc(sizeof(bf16_t) * (size_t)M * n80)); pp = p.p; }
-  GemmArgs g;
-  g.M = M; g.N = n80; g.K = C; g.K1 = C; g.A = (const bf16_t*)t; g.lda = C; g.W = (const bf16_t*)mq.p;
-  g.wb_rows = HW; g.wb_stride = (int64_t)n80 * C; g.vb_stride = n80;
-  g.ln_stats = (const float*)st.p; g.ln_planes = 1; g.ln_colsum = (const float*)mcs.p; g.bias = (const float*)mb.p;
-  g.out_mode = OUT_SOFTMAX80; g.C = pp; g.ldc = n80;
-  GemmArgs g2;
-  g2.M = M; g2.N = C; g2.K = n80; g2.K1 = n80; g2.A = (const bf16_t*)pp; g2.lda = n80; g2.W = (const bf16_t*)wo.p; g2.bias = bo;
-  g2.wb_rows = HW; g2.wb_stride = (int64_t)n80 * C;
-  g2.resid = t; g2.ldr = C; g2.C = out; g2.ldc = C;
+  GemmArgs g, g2;
+  xf_xalg_args((const bf16_t*)t, M, HW, C, H, {(const float*)st.p, 1, 0}, (const bf16_t*)mq.p, (const float*)mcs.p, (const float*)mb.p, (const bf16_t*)wo.p,
+               bo, pp, t, out, &g, &g2);
   for (int r = 0, rep = op_repeat(); r < rep; ++r) { GILL_TRY(gemm_launch(g, s)); GILL_TRY(gemm_launch(g2, s)); }
   GILL_CHECK_HIP(hipStreamSynchronize(s));
   return 0;
@@ -268,7 +265,8 @@ extern "C" int gill_op_cross_attention_folded(const void* t, const float* ln_g, 
 
 // Operator-level entries for the folded-LayerNorm chain of UNet levels 1-3 (unet.hip xf()): the GEMM that writes the residual stream and files
 // its row-sum planes (GemmArgs::row_stats), and the GEMM that reads them back (GemmArgs::ln_stats) in its GEGLU / QKV epilogue or its split-K
-// reducer.  Both build their GemmArgs as UNetRun::linear() / xf() do and synchronise.  For tests/test_ln_gemm_gpu.py and tools.
+// reducer.  The producer builds its GemmArgs as UNetRun::linear() does, the consumer with xf()'s own builders (xf_args.h); both synchronise.  For
+// tests/test_ln_gemm_gpu.py and tools.
 // splitk: 0 = the engine's heuristic (UNetRun::pick_sk), 1 = unsplit, n > 1 = forced.
 static int op_ln_splitk(GemmArgs& g, int splitk, DevBuf& ws) {
   g.splitk = splitk > 0 ? splitk : gemm_pick_splitk(g.M, g.N, g.K, g.act, true, false);
@@ -314,32 +312,28 @@ extern "C" int gill_op_ln_gemm(int mode, const void* T, const float* planes, int
   GILL_REQUIRE(ln_rows >= 0 && ln_rows <= M && (ln_rows == 0 || 2 * ln_rows >= M), "ln_gemm: ln_rows must cover at least half the rows");
   DevBuf idx, wf, cs, cb, ws;
   GemmArgs g;
-  g.M = M; g.K = C; g.K1 = C; g.A = (const bf16_t*)T; g.lda = C;
-  g.ln_stats = planes; g.ln_planes = P; g.ln_rows = ln_rows;
+  const XfLnRows ln = {planes, P, ln_rows};
   if (mode == 0) {
     GILL_REQUIRE(out && b && inner > 0 && inner % 64 == 0, "ln_gemm (GEGLU): output / bias missing, or inner not a multiple of 64");
     const int N = 2 * inner;
     GILL_TRY(idx.alloc(sizeof(int32_t) * N));
     GILL_TRY(wf.alloc(sizeof(bf16_t) * (size_t)N * C)); GILL_TRY(cb.alloc(sizeof(float) * N)); GILL_TRY(cs.alloc(sizeof(float) * N));
     GILL_TRY(xf_geglu_weights((const bf16_t*)W, b, inner, C, ln_g, ln_b, (int32_t*)idx.p, (bf16_t*)wf.p, (float*)cb.p, (float*)cs.p, s));
-    g.N = N; g.act = ACT_GEGLU; g.C = out; g.ldc = inner;
+    g = xf_geglu_args((const bf16_t*)T, M, C, inner, ln, (const bf16_t*)wf.p, (const float*)cs.p, (const float*)cb.p, out);
   } else {
     GILL_REQUIRE((nseg == 1 || nseg == 3) && heads > 0 && d > 0 && heads * d == C && ntok > 0 && M % ntok == 0,
                  "ln_gemm (QKV): nseg 1 or 3, heads * d == C, M a multiple of ntok");
     GILL_REQUIRE(q && (nseg == 1 || (k && vt)), "ln_gemm (QKV): output missing");
-    const int dp = attn_padded_dim(d);
-    GILL_REQUIRE(dp > 0, "ln_gemm (QKV): unsupported head dim");
-    const int dpv = round_up(dp, 32), hdp = heads * dp, N = nseg * hdp, ntok_pad = round_up(ntok, 32);
+    const XfHeads hd = xf_heads(heads, d);
+    GILL_REQUIRE(hd.dp > 0, "ln_gemm (QKV): unsupported head dim");
+    const int dp = hd.dp, N = nseg * hd.hdp;
     GILL_TRY(wf.alloc_zero(sizeof(bf16_t) * (size_t)N * C, s));
     GILL_TRY(cs.alloc_zero(sizeof(float) * N, s)); GILL_TRY(cb.alloc_zero(sizeof(float) * N, s));
     HeadRows seg[3];
     for (int sg = 0; sg < nseg; ++sg) seg[sg] = HeadRows{(const bf16_t*)W + (size_t)sg * C * C, 0};
     GILL_TRY(xf_qkv_weights(seg, nseg, b, heads, d, dp, C, ln_g, ln_b, (bf16_t*)wf.p, (float*)cs.p, (float*)cb.p, nullptr, s));
-    g.N = N; g.out_mode = OUT_QKV; g.Cq = (bf16_t*)q; g.Ck = (bf16_t*)k; g.Cvt = (bf16_t*)vt; g.heads = heads; g.dp = dp; g.dpv = dpv;
-    g.ntok = ntok; g.ntok_pad_q = ntok_pad; g.ntok_pad_kv = ntok_pad; g.seg_base = 0;
-    g.qscale = 1.4426950408889634f / sqrtf((float)d);
+    g = xf_qkv_args((const bf16_t*)T, M, C, ln, (const bf16_t*)wf.p, (const float*)cs.p, (const float*)cb.p, nseg, hd, ntok, (bf16_t*)q, (bf16_t*)k, (bf16_t*)vt);
   }
-  g.W = (const bf16_t*)wf.p; g.ln_colsum = (const float*)cs.p; g.bias = (const float*)cb.p;
   GILL_TRY(op_ln_splitk(g, splitk, ws));
   for (int r = 0, rep = op_repeat(); r < rep; ++r) GILL_TRY(gemm_launch(g, s));
   GILL_CHECK_HIP(hipStreamSynchronize(s));

@@ -939,6 +939,17 @@ def gemm_plan(cases, pp: int = 1, coop: int = 1, cus: int = 256):
   return rows
 
 
+def unet_xf_plan(cases, lnproj: int = 1, xalg: int = 1, ffn_fused: int = 1):
+  """Which kernels a UNet transformer block runs (host only: gill_unet_xf_plan).  cases (n, 8) int32 = [C, heads, ctx_len, ctx_dim, hw, fp8, Bx,
+  shared] -> (n, 11) int32 rows = the load-time forms [lnproj, xalg, ffn_fused, ffn_pre, geglu_fp8] + the call's plan [lnproj, gn_table, cross, ffn,
+  M, M1]; include/gill_amd.h has the codes.  lnproj / xalg / ffn_fused: GILL_UNET_LNPROJ, GILL_UNET_XALG, GILL_UNET_FFN_FUSED."""
+  import numpy as np
+  cases = np.ascontiguousarray(cases, dtype=np.int32).reshape(-1, 8)
+  rows = np.zeros((cases.shape[0], 11), dtype=np.int32)
+  N.check(N.lib().gill_unet_xf_plan(cases.ctypes.data, cases.shape[0], int(lnproj), int(xalg), int(ffn_fused), rows.ctypes.data))
+  return rows
+
+
 def gemm_query(queries, pp: int = 1, coop: int = 1, cus: int = 256):
   """The engines' pre-launch GEMM choices (host only: gill_gemm_query).  queries (n, 7) int32 = [what, six arguments] -> (n,) int32."""
   import numpy as np

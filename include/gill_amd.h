@@ -725,6 +725,22 @@ int gill_gemm_plan(const int32_t* cases, int n, int pp, int coop, int cus, int32
  *   3 convolution on the ping-pong tile (rows, Cout)  4 chunk-major K order (HW, Cin, Cout)                  5 weights stored 64 x 64-blocked (N, K) */
 int gill_gemm_query(const int32_t* queries, int n, int pp, int coop, int cus, int32_t* answers);
 
+/* Which kernels a UNet transformer block (Transformer2DModel with one BasicTransformerBlock) runs (host only, for tests; no GPU is touched).  The
+ * engine decides it in two pure steps: the weight layouts a layer is loaded with ("forms"), then what one call launches ("plan").  lnproj / xalg /
+ * ffn_fused: the switches GILL_UNET_LNPROJ, GILL_UNET_XALG, GILL_UNET_FFN_FUSED (0 = off), given explicitly here.
+ * cases: n descriptors of GILL_UNET_XF_PLAN_CASE_INTS int32:
+ *   C heads ctx_len ctx_dim hw fp8 Bx shared      channels and heads of the layer, context tokens and width, tokens per sample at its level,
+ *                                                 gill_unet_config.fp8_convs == 1, samples of the call, 1 = the shared prefix of a CFG pair (Bx counts the pair)
+ * rows: n rows of GILL_UNET_XF_PLAN_ROW_INTS int32:
+ *   lnproj xalg ffn_fused ffn_pre geglu_fp8       forms: fused projection pairs, two-GEMM cross-attention, fused feed-forward (PRE: it also runs
+ *                                                 attn2.to_out), GEGLU projection in fp8
+ *   lnproj gn_table cross ffn M M1                plan: fused projection pairs run, the block's GroupNorm arrives as a scale | shift table,
+ *                                                 cross-attention 0 attention kernel / 1 two GEMMs, feed-forward 0 GEMMs / 1 GEMMs with the fp8 GEGLU /
+ *                                                 2 fused / 3 fused PRE, rows of the call, rows up to the end of the self-attention */
+#define GILL_UNET_XF_PLAN_CASE_INTS 8
+#define GILL_UNET_XF_PLAN_ROW_INTS 11
+int gill_unet_xf_plan(const int32_t* cases, int n, int lnproj, int xalg, int ffn_fused, int32_t* rows);
+
 /* Scoring pass of the OPT engine: gill_opt_img_hidden_ex (same embedding, same negative ids, same gathered rows; raw_out / emb_out
  * bit-equal to its outputs, either may be NULL) with the final LayerNorm on EVERY row, and row (b, t) scored against
  * labels[b][t + 1] by the fused loss above (HF's shifted CrossEntropyLoss).  labels (B,T) int64 on the device, -100 ignored; NULL
