@@ -49,6 +49,10 @@ class gill_decode_rule(C.Structure):
               ("ret_scale", C.c_double), ("gen_scale", C.c_double), ("filter_value", C.c_double)]
 
 
+class gill_decode_sampler(C.Structure):
+  _fields_ = [("seed", C.c_uint64), ("draw", C.c_int32), ("row0", C.c_int32), ("temperature", C.c_double), ("top_p", C.c_double)]
+
+
 class gill_clip_config(C.Structure):
   _fields_ = [(n, C.c_int32) for n in ("image_size", "patch_size", "hidden_size", "num_layers", "num_heads", "intermediate_size",
                                        "max_batch")]
@@ -89,6 +93,10 @@ SYMBOLS: Dict[str, Tuple[object, List[object]]] = {
   "gill_opt_pick_token": (_i, [_vp, _vp, _i, C.POINTER(gill_decode_rule), _vp, _i, _i, _vp, _vp, _vp]),
   "gill_opt_decode_logits": (_i, [_vp, _vp, _i, _i, C.POINTER(gill_decode_rule), _vp, _vp]),
   "gill_opt_filter_logits": (_i, [_vp, _vp, _vp, _i, C.c_double, C.c_double, C.c_double, _i, _vp]),
+  "gill_opt_sample_token": (_i, [_vp, _vp, _i, _i, C.POINTER(gill_decode_rule), C.POINTER(gill_decode_sampler), _vp, _vp, _i, _i, _vp,
+                                 _vp, _vp]),
+  "gill_opt_draw_token": (_i, [_vp, _vp, _i, C.POINTER(gill_decode_rule), C.POINTER(gill_decode_sampler), _vp, _i, _i, _vp, _vp, _vp]),
+  "gill_decode_uniforms": (_i, [C.c_uint64, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.POINTER(C.c_float)]),
   "gill_clip_create": (_i, [C.POINTER(_vp), C.POINTER(gill_clip_config), C.POINTER(gill_tensor), _i]),
   "gill_clip_destroy": (None, [_vp]),
   "gill_clip_forward": (_i, [_vp, _vp, _i, _vp, _vp]),

@@ -301,6 +301,18 @@ struct DecodeRuleDev {          // gill_decode_rule resolved on the host: ids in
 int decode_rule_pick_launch(float* logits, int B, int V, const DecodeRuleDev& r, const bf16_t* table, int D, int64_t* tokens,
                             int ld, int col, int32_t* n_out, bf16_t* next_embeds, hipStream_t s);
 int decode_rule_launch(float* logits, int B, int V, const DecodeRuleDev& r, hipStream_t s);   // the rule only, in place
+// The seeded draw in the place of the argmax (gill_decode_sampler, checked by the launcher): rule in place, then per row the token
+// argmax_c exp(y_c - max) / -log(u_c) over the top-p filter's kept set, y = x / temperature, u_c the Philox4x32-10 uniform of
+// (seed; c >> 2, row0 + b, draw, 0) word c & 3 (philox.h); rows with no finite maximum take torch.argmax's pick.  The rest as
+// decode_rule_pick_launch.  vocab <= 65536.
+struct DecodeSampler {
+  uint64_t seed;
+  int draw, row0;
+  double temperature, top_p;
+};
+int decode_sample_check(int B, int V, const DecodeRuleDev& r, const DecodeSampler& sm, int D, int ld, int col);   // host: arguments only
+int decode_sample_launch(float* logits, int B, int V, const DecodeRuleDev& r, const DecodeSampler& sm, const bf16_t* table, int D,
+                         int64_t* tokens, int ld, int col, int32_t* n_out, bf16_t* next_embeds, hipStream_t s);
 // out = in / temperature (reciprocal: in * fp32(1 / temperature)), then the top-p filter when top_p < 1
 int decode_filter_launch(const float* in, float* out, int B, int V, double temperature, int reciprocal, double top_p,
                          double filter_value, hipStream_t s);

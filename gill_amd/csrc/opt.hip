@@ -8,6 +8,7 @@
 // skinny (M = B*T) weight-streaming GEMMs cover all 256 CUs; attention is the shared flash kernel.
 // The layer loop is the shared block of tfm.h; here: embeddings and positions, the KV cache, img_hidden, logits and the decode entry points.
 #include "tfm.h"
+#include "philox.h"
 
 struct gill_opt {
   gill_opt_config cfg;
@@ -383,6 +384,44 @@ extern "C" int gill_opt_next_token(gill_opt* m, const float* hidden, int B, int 
   GILL_TRY(gill_opt_last_logits(m, hidden, B, T, logits_out, stream));
   return decode_rule_pick_launch(logits_out, B, m->cfg.vocab_size, r, m->embed, m->cfg.hidden_size, tokens, ld, col, n_out,
                                  (bf16_t*)next_embeds_bf16, (hipStream_t)stream);
+}
+
+static int resolve_sampler(const gill_decode_sampler* sm, DecodeSampler* o) {
+  GILL_REQUIRE(sm, "null sampler");
+  *o = DecodeSampler{sm->seed, sm->draw, sm->row0, sm->temperature, sm->top_p};
+  return 0;
+}
+
+extern "C" int gill_opt_draw_token(gill_opt* m, float* logits, int B, const gill_decode_rule* rule, const gill_decode_sampler* sampler,
+                                   int64_t* tokens, int ld, int col, int32_t* n_out, void* next_embeds_bf16, void* stream) {
+  GILL_REQUIRE(m && logits && tokens && n_out && next_embeds_bf16, "null argument");
+  DecodeRuleDev r;
+  DecodeSampler sm;
+  GILL_TRY(resolve_rule(m, rule, &r));
+  GILL_TRY(resolve_sampler(sampler, &sm));
+  return decode_sample_launch(logits, B, m->cfg.vocab_size, r, sm, m->embed, m->cfg.hidden_size, tokens, ld, col, n_out,
+                              (bf16_t*)next_embeds_bf16, (hipStream_t)stream);
+}
+
+extern "C" int gill_opt_sample_token(gill_opt* m, const float* hidden, int B, int T, const gill_decode_rule* rule,
+                                     const gill_decode_sampler* sampler, float* logits_out, int64_t* tokens, int ld, int col,
+                                     int32_t* n_out, void* next_embeds_bf16, void* stream) {
+  GILL_REQUIRE(m && hidden && logits_out && tokens && n_out && next_embeds_bf16, "null argument");
+  DecodeRuleDev r;
+  DecodeSampler sm;
+  GILL_TRY(resolve_rule(m, rule, &r));   // argument errors before anything is enqueued
+  GILL_TRY(resolve_sampler(sampler, &sm));
+  GILL_TRY(decode_sample_check(B, m->cfg.vocab_size, r, sm, m->cfg.hidden_size, ld, col));
+  GILL_TRY(gill_opt_last_logits(m, hidden, B, T, logits_out, stream));
+  return decode_sample_launch(logits_out, B, m->cfg.vocab_size, r, sm, m->embed, m->cfg.hidden_size, tokens, ld, col, n_out,
+                              (bf16_t*)next_embeds_bf16, (hipStream_t)stream);
+}
+
+extern "C" int gill_decode_uniforms(uint64_t seed, int32_t row, int32_t draw, int32_t first, int32_t count, float* u_out) {
+  GILL_REQUIRE(u_out && row >= 0 && draw >= 0 && first >= 0 && count >= 0, "decode uniforms: bad argument");
+  GILL_REQUIRE((int64_t)first + count <= 65536, "decode uniforms: columns are below 65536");
+  for (int32_t j = 0; j < count; ++j) u_out[j] = decode_uniform(seed, (uint32_t)row, (uint32_t)draw, (uint32_t)(first + j));
+  return 0;
 }
 
 extern "C" int gill_opt_decode_logits(gill_opt* m, const float* hidden, int B, int T, const gill_decode_rule* rule, float* logits_out,

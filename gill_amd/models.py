@@ -26,7 +26,7 @@ import json
 import os
 from collections import namedtuple
 from types import SimpleNamespace
-from typing import Dict, List, Optional
+from typing import Dict, List, Optional, Tuple
 
 import numpy as np
 import torch
@@ -536,7 +536,8 @@ class GILLModel(nn.Module):
 
   # The decision of the generate loop (:471-520) runs on the device: the [IMG] logit rule, the greedy pick, the [IMG] forcing and
   # the next step's embeddings (gill_opt_next_token), and the rule, the temperature and the top-p filter of the sampled path
-  # (gill_opt_decode_logits / gill_opt_filter_logits).  False runs the reference's host decision instead (A/B and test arm).
+  # (gill_opt_decode_logits / gill_opt_filter_logits); with generate(seed=...) the sampled path's draw runs there too
+  # (gill_opt_sample_token).  False runs the reference's host decision instead (A/B and test arm).
   decode_on_device = True
   _decode_host_waits = 0      # instrumentation: host waits inside the loop of the last generate() call
 
@@ -558,7 +559,7 @@ class GILLModel(nn.Module):
 
   def generate(self, embeddings=torch.FloatTensor, max_len: int = 32, temperature: float = 0.0, top_p: float = 1.0,
                min_word_tokens: int = 0, ret_scale_factor: float = 1.0, gen_scale_factor: float = 1.0,
-               filter_value: float = -float('Inf'), use_kv_cache: bool = True):
+               filter_value: float = -float('Inf'), use_kv_cache: bool = True, seed: Optional[int] = None):
     """Greedy / top-p decoding, same loop and outputs as the reference (models.py:443-532).  The reference re-runs the
     whole sequence through the LM at every step; with use_kv_cache (default) only the tokens appended since the last
     step go through the layers, against keys/values cached in the native handle — causal attention makes the hidden
@@ -566,11 +567,27 @@ class GILLModel(nn.Module):
     With decode_on_device (default) the logit rule and the pick run in libgill_amd: greedy decoding at batch > 1 never
     waits for the device inside the loop, at batch 1 it reads one 4-byte count per step (the [IMG] forcing decides how
     many tokens the next forward takes).  Outputs: out (N,T) token ids, output_embeddings list of hidden_states[-1],
-    output_logits list (N, vocab) — CPU tensors when top_p == 1 (:471-472), device tensors otherwise."""
+    output_logits list (N, vocab) — CPU tensors when top_p == 1 (:471-472), device tensors otherwise.
+    seed (an integer; None, the default, is the reference's torch.multinomial draw from torch's generator): with a temperature
+    above 0 the draw runs in libgill_amd too (gill_opt_sample_token: an exponential race on Philox uniforms keyed by (seed, row,
+    step), over exp(logit / temperature - max) and the top-p filter's kept set).  It is repeatable bit for bit, a row's tokens do
+    not depend on the other rows of the batch, no temperature overflows, torch's generators are not touched, and the loop waits
+    for the device as the greedy one does: never at batch > 1, one 4-byte count per step at batch 1."""
     self._decode_host_waits = 0
+    if seed is not None:
+      if not self.decode_on_device:
+        raise ValueError('seed needs decode_on_device: the seeded draw runs in libgill_amd only.')
+      seed = int(seed)
+      if not 0 <= seed < 2 ** 64:
+        raise ValueError(f'seed should be in [0, 2**64), got {seed} instead.')
     if self.decode_on_device and temperature == 0.0 and top_p == 1.0:
-      return self._generate_greedy_device(embeddings, max_len, min_word_tokens, ret_scale_factor, gen_scale_factor,
-                                          filter_value, use_kv_cache)
+      return self._generate_device(embeddings, max_len, min_word_tokens, ret_scale_factor, gen_scale_factor, filter_value,
+                                   use_kv_cache)
+    if seed is not None and temperature != 0.0:
+      if top_p < 1.0:
+        assert top_p > 0, f'top_p should be above 0, got {top_p} instead.'
+      return self._generate_device(embeddings, max_len, min_word_tokens, ret_scale_factor, gen_scale_factor, filter_value,
+                                   use_kv_cache, sample=(float(temperature), float(top_p), seed))
     with torch.no_grad():
       out = None
       output_embeddings = []
@@ -669,12 +686,14 @@ class GILLModel(nn.Module):
     grow = max(1, len(self.retrieval_token_idx))
     self._opt_native(embeddings.shape[0], min(embeddings.shape[1] + max_len * grow, self.opt_cfg.max_positions))
 
-  def _generate_greedy_device(self, embeddings: Tensor, max_len: int, min_word_tokens: int, ret_scale_factor: float,
-                              gen_scale_factor: float, filter_value: float, use_kv_cache: bool):
-    """generate() at temperature 0 with the decision in libgill_amd (gill_opt_next_token).  The picked ids go to a device
-    token buffer, their embeddings to the next step's input; the post-rule logits go to pinned host memory by asynchronous
-    copies, and the one synchronisation is at the end.  At batch 1 the count of emitted ids (1, or the 8 forced [IMG] ids)
-    is read back each step: the next forward's length depends on it."""
+  def _generate_device(self, embeddings: Tensor, max_len: int, min_word_tokens: int, ret_scale_factor: float,
+                       gen_scale_factor: float, filter_value: float, use_kv_cache: bool,
+                       sample: Optional[Tuple[float, float, int]] = None):
+    """generate() with the decision in libgill_amd: the greedy pick (gill_opt_next_token), or with sample = (temperature, top_p,
+    seed) the seeded draw (gill_opt_sample_token; draw = the step, row0 = 0).  The picked ids go to a device token buffer, their
+    embeddings to the next step's input; the post-rule logits go to pinned host memory by asynchronous copies, and the one
+    synchronisation is at the end — except at top_p < 1, where the reference keeps them on the device (:471-472).  At batch 1
+    the count of emitted ids (1, or the 8 forced [IMG] ids) is read back each step: the next forward's length depends on it."""
     with torch.no_grad():
       output_embeddings = []
       output_logits = []
@@ -686,7 +705,13 @@ class GILLModel(nn.Module):
       nxt = torch.empty((B0, grow, D), device=dev, dtype=torch.bfloat16)
       n_dev = torch.empty(1, device=dev, dtype=torch.int32)
       n_host = torch.empty(1, dtype=torch.int32, pin_memory=True)
-      host_logits = torch.empty((max_len, B0, vocab), dtype=torch.float32, pin_memory=True) if max_len > 0 else None
+      logits_to_host = sample is None or sample[1] == 1.0
+      host_logits = torch.empty((max_len, B0, vocab), dtype=torch.float32, pin_memory=True) \
+        if max_len > 0 and logits_to_host else None
+      if sample is not None:
+        sampler = N.gill_decode_sampler()
+        # top_p above 1 filters nothing, as in the reference (:502 tests top_p < 1.0 only)
+        sampler.temperature, sampler.top_p, sampler.seed, sampler.row0 = sample[0], min(sample[1], 1.0), sample[2], 0
       ev = torch.cuda.Event()
       col = 0
       hidden = None
@@ -706,10 +731,19 @@ class GILLModel(nn.Module):
         logits = torch.empty((B, vocab), device=dev, dtype=torch.float32)
         rule = self._decode_rule(i, min_word_tokens, ret_scale_factor, gen_scale_factor, filter_value)
         with torch.cuda.device(dev):
-          N.check(N.lib().gill_opt_next_token(self._opt_handle, N.ptr(hidden), B, T, C.byref(rule), N.ptr(logits), N.ptr(tokens),
-                                              tokens.shape[1], col, N.ptr(n_dev), N.ptr(nxt), N.current_stream()))
-          host_logits[i].copy_(logits, non_blocking=True)                      # :471-472, the post-rule values (:476-489)
-          output_logits.append(host_logits[i])
+          if sample is None:
+            N.check(N.lib().gill_opt_next_token(self._opt_handle, N.ptr(hidden), B, T, C.byref(rule), N.ptr(logits), N.ptr(tokens),
+                                                tokens.shape[1], col, N.ptr(n_dev), N.ptr(nxt), N.current_stream()))
+          else:
+            sampler.draw = i
+            N.check(N.lib().gill_opt_sample_token(self._opt_handle, N.ptr(hidden), B, T, C.byref(rule), C.byref(sampler),
+                                                  N.ptr(logits), N.ptr(tokens), tokens.shape[1], col, N.ptr(n_dev), N.ptr(nxt),
+                                                  N.current_stream()))
+          if logits_to_host:
+            host_logits[i].copy_(logits, non_blocking=True)                    # :471-472, the post-rule values (:476-489)
+            output_logits.append(host_logits[i])
+          else:
+            output_logits.append(logits)
           if B == 1:
             n_host.copy_(n_dev, non_blocking=True)
             ev.record()
@@ -724,7 +758,7 @@ class GILLModel(nn.Module):
         new_embeds = nxt[:, :n].to(embeddings.dtype)
         if not use_kv_cache:
           embeddings = torch.cat([embeddings, new_embeds], dim=1)
-      if max_len > 0:
+      if max_len > 0 and logits_to_host:
         torch.cuda.current_stream(dev).synchronize()                           # the pinned logits are complete
     out = tokens[:, :col].clone() if max_len > 0 else None
     return out, output_embeddings, output_logits
@@ -780,8 +814,10 @@ class GILL(nn.Module):
   def generate_for_images_and_texts(self, prompts: List, num_words: int = 0, min_word_tokens: int = 0,
                                     ret_scale_factor: float = 1.0, gen_scale_factor: float = 1.0, top_p: float = 1.0,
                                     temperature: float = 0.0, max_num_rets: int = 1, generator=None,
-                                    always_add_bos: bool = False, guidance_scale: float = 7.5, num_inference_steps: int = 50):
-    """Encode prompts into embeddings, and generates text and image outputs accordingly (models.py:582-762)."""
+                                    always_add_bos: bool = False, guidance_scale: float = 7.5, num_inference_steps: int = 50,
+                                    seed: Optional[int] = None):
+    """Encode prompts into embeddings, and generates text and image outputs accordingly (models.py:582-762).  seed: the seeded
+    on-device draw of GILLModel.generate for the text (temperature > 0); None draws as the reference does."""
     input_embs = []
     input_ids = []
     add_bos = True
@@ -816,7 +852,7 @@ class GILL(nn.Module):
       elif num_words > 0:
         generated_ids, generated_embeddings, _ = self.model.generate(
           input_embs, num_words, min_word_tokens=min_word_tokens, temperature=temperature, top_p=top_p,
-          ret_scale_factor=ret_scale_factor, gen_scale_factor=gen_scale_factor)
+          ret_scale_factor=ret_scale_factor, gen_scale_factor=gen_scale_factor, seed=seed)
         embeddings = generated_embeddings[-1][:, input_embs.shape[1]:]
         newline_token_id = self.model.tokenizer('\n', add_special_tokens=False).input_ids[0]
         trunc_idx = 0

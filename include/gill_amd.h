@@ -135,6 +135,43 @@ int gill_opt_decode_logits(gill_opt* h, const float* hidden, int B, int T, const
 int gill_opt_filter_logits(gill_opt* h, const float* in, float* out, int B, double temperature, double top_p,
                            double filter_value, int reciprocal, void* stream);
 
+/* The seeded draw: temperature / top-p sampling decided on the device, in the place of torch.multinomial (:514).  For row b of a
+ * call, with x the post-rule logits, T = temperature > 0 and 0 < top_p <= 1:
+ *   y_c = x_c / T (correctly rounded fp32: the reciprocal = 0 arm of gill_opt_filter_logits); mx = max_c y_c;
+ *   e_c = exp(y_c - mx), 0 where y_c = -inf: the values gill_opt_filter_logits forms, to the bit.  With top_p < 1 the kept set is
+ *   that entry's (one device function serves both); with top_p == 1 every token is kept.
+ *   u_c = (2 * (w >> 9) + 1) * 2^-24 with w the output word c & 3 of Philox4x32-10 (multipliers D2511F53 / CD9E8D57, key
+ *   increments 9E3779B9 / BB67AE85) at key (seed & 0xffffffff, seed >> 32) and counter (c >> 2, row0 + b, draw, 0): exact in
+ *   fp32 and strictly inside (0, 1).
+ *   key_c = e_c / -logf(u_c) (accurate logf, correctly rounded division); the token is the argmax of key_c over the kept columns,
+ *   larger key first, then lower index: the exponential race, P(token = c) = e_c / sum of the kept e.
+ * A row's token is a function of (seed, row0 + b, draw, that row's logits) alone: repeatable bit for bit, independent of the batch
+ * it runs in, and safe at any temperature.  A row with no finite maximum (it holds a NaN or +inf, or is all -inf) draws nothing: its
+ * token is torch.argmax's pick on y (first NaN, else larger value, else lower index).  What follows the pick is gill_opt_next_token's
+ * to the byte: the [IMG] forcing at B == 1, -1 in *n_out when ret_eq_gen == 0, tokens, *n_out and the bf16 embedding rows.
+ * temperature <= 0, top_p outside (0, 1], vocab > 65536, draw or row0 < 0, a null pointer or a token buffer that is too short are
+ * errors, reported before anything is enqueued. */
+typedef struct gill_decode_sampler {
+  uint64_t seed;
+  int32_t draw;    /* the loop step */
+  int32_t row0;    /* id of row 0 */
+  double temperature;
+  double top_p;
+} gill_decode_sampler;
+
+/* Twin of gill_opt_next_token: lm_head -> logits_out, the rule in place (logits_out keeps the post-rule, pre-temperature values,
+ * what output_logits holds), then the draw.  No host wait. */
+int gill_opt_sample_token(gill_opt* h, const float* hidden, int B, int T, const gill_decode_rule* rule,
+                          const gill_decode_sampler* sampler, float* logits_out, int64_t* tokens, int ld, int col, int32_t* n_out,
+                          void* next_embeds_bf16, void* stream);
+
+/* Twin of gill_opt_pick_token: the caller's logits (B, vocab) fp32, modified by the rule only. */
+int gill_opt_draw_token(gill_opt* h, float* logits, int B, const gill_decode_rule* rule, const gill_decode_sampler* sampler,
+                        int64_t* tokens, int ld, int col, int32_t* n_out, void* next_embeds_bf16, void* stream);
+
+/* Host only, no GPU: u_c of the draw above for c in [first, first + count), first + count <= 65536, from the code the kernel runs. */
+int gill_decode_uniforms(uint64_t seed, int32_t row, int32_t draw, int32_t first, int32_t count, float* u_out);
+
 /* ------------------------------------------------------------------------------------------
  * Image prompts — the frozen CLIP vision tower (transformers CLIPVisionModel built at gill/models.py:78-96 and called by
  * GILLModel.get_visual_embs, gill/models.py:129-145: `self.visual_model(pixel_values).pooler_output`).

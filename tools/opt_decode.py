@@ -1,8 +1,10 @@
 #!/usr/bin/env python3
-"""KV-cached greedy decoding on the OPT-6.7b shapes (GILLModel.generate, 8-token prompt, N new tokens): ms per decoded token.
-  python tools/opt_decode.py [new_tokens] [--batch B[,B2..]] [--host] [--alternate R]
+"""KV-cached decoding on the OPT-6.7b shapes (GILLModel.generate, 8-token prompt, N new tokens): ms per decoded token.
+  python tools/opt_decode.py [new_tokens] [--batch B[,B2..]] [--host] [--alternate R] [--sample T,P [--seed S]]
 --host runs the host decision (GILLModel.decode_on_device = False: logits copied to the host, rule + argmax there);
---alternate R times the device and the host decision R times each, alternating, with the mean sclk of each run."""
+--alternate R times the device and the host decision R times each, alternating, with the mean sclk of each run;
+--sample T,P decodes at temperature T and top_p P instead of greedily: the seeded draw on the device (generate(seed=S)) beside
+the torch.multinomial draw (seed=None), alternating under --alternate; each line prints the host waits of its loop."""
 import argparse
 import os
 import sys
@@ -21,6 +23,8 @@ ap.add_argument("new_tokens", nargs="?", type=int, default=24)
 ap.add_argument("--batch", default="1", help="batch size, or a comma list (one model build for all)")
 ap.add_argument("--host", action="store_true", help="host decision (decode_on_device = False)")
 ap.add_argument("--alternate", type=int, default=0, help="R rounds of device / host, alternating")
+ap.add_argument("--sample", default=None, help="T,P: temperature and top_p of the sampled path (seeded draw beside the torch draw)")
+ap.add_argument("--seed", type=int, default=1234, help="seed of the seeded draw")
 a = ap.parse_args()
 n = a.new_tokens
 dev = torch.device("cuda:0")
@@ -33,31 +37,53 @@ args = SimpleNamespace(freeze_lm=True, freeze_vm=True, opt_version="facebook/opt
 g = GILL(synth.HashTokenizer(), args, load_sd=False).eval().bfloat16().cuda()
 del osd
 kw = dict(min_word_tokens=n, temperature=0.0)          # [IMG] suppressed: n ordinary greedy steps
+if a.sample:
+  t_, p_ = (float(v) for v in a.sample.split(","))
+  kw = dict(min_word_tokens=n, temperature=t_, top_p=p_)
 
 
-def run(emb, on_device):
+peak = 0.0      # largest logit / temperature the last run saw (sampled runs only)
+
+
+def run(emb, on_device, seed=None):
+  global peak
   B = emb.shape[0]
   g.model.decode_on_device = on_device
-  g.model.generate(emb, 4, use_kv_cache=True, **kw)
+  kw_run = dict(kw, seed=seed) if seed is not None else kw
+  what = "seeded draw" if seed is not None else "torch draw" if a.sample else "device decision" if on_device else "host decision"
+  g.model.generate(emb, 4, use_kv_cache=True, **kw_run)
   torch.cuda.synchronize()
   clk = bench.ClockSampler(dev)
   clk.start()
   t0 = time.time()
-  out, _, _ = g.model.generate(emb, n, use_kv_cache=True, **kw)
+  out, _, logits = g.model.generate(emb, n, use_kv_cache=True, **kw_run)
   torch.cuda.synchronize()
   dt = time.time() - t0
   c = clk.stop()
   waits = g.model._decode_host_waits
   sclk = c["sclk_mhz_mean"]
-  print(f"OPT-6.7b KV-cached decode, batch {B}, {'device' if on_device else 'host'} decision: {n} tokens in {dt * 1e3:.1f} ms = "
+  print(f"OPT-6.7b KV-cached decode, batch {B}, {what}: {n} tokens in {dt * 1e3:.1f} ms = "
         f"{dt / n * 1e3:.2f} ms per token, {waits} host waits, sclk {'%.0f MHz' % sclk if sclk else 'n/a'}", flush=True)
+  if a.sample:
+    peak = max(float(l.max()) for l in logits) / kw["temperature"]
   return out
 
 
 for B in [int(b) for b in a.batch.split(",")]:
   ids = synth.synthetic_prompt_ids(B, 8, seed=1)[:, :8].to(dev)
   emb = g.model.input_embeddings(ids)
-  if a.alternate:
+  if a.sample:
+    seeded = []
+    for _ in range(max(1, a.alternate)):
+      seeded.append(run(emb, True, seed=a.seed))
+      # the torch draw takes exp(logit / T) with no maximum subtracted and refuses an inf: it is timed only where the seeded run's
+      # logits stay well below fp32's exp limit (88.7)
+      if peak < 80.0:
+        run(emb, True)
+      else:
+        print(f"OPT-6.7b KV-cached decode, batch {B}, torch draw: not run, logit / T reaches {peak:.1f} and exp() would overflow", flush=True)
+    assert all(torch.equal(o, seeded[0]) for o in seeded), "the seeded draw is not repeatable"
+  elif a.alternate:
     outs = []
     for _ in range(a.alternate):
       outs.append(run(emb, True))
