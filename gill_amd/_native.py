@@ -97,6 +97,12 @@ SYMBOLS: Dict[str, Tuple[object, List[object]]] = {
                                  _vp, _vp]),
   "gill_opt_draw_token": (_i, [_vp, _vp, _i, C.POINTER(gill_decode_rule), C.POINTER(gill_decode_sampler), _vp, _i, _i, _vp, _vp, _vp]),
   "gill_decode_uniforms": (_i, [C.c_uint64, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.POINTER(C.c_float)]),
+  "gill_attention_decode": (_i, [_vp, _vp, _vp, _i, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp, _vp]),
+  "gill_opt_decode_step": (_i, [_vp, _vp, _vp, _i, _i, _vp, _vp]),
+  "gill_opt_prefill_ids": (_i, [_vp, _vp, _i, _i, _vp, _i, _vp, _vp]),
+  "gill_opt_next_token_ragged": (_i, [_vp, _vp, _i, C.POINTER(gill_decode_rule), _i, C.POINTER(gill_decode_sampler), _vp, _vp, _vp, _i, _vp,
+                                      _vp]),
+  "gill_opt_pick_token_ragged": (_i, [_vp, _vp, _i, C.POINTER(gill_decode_rule), _i, C.POINTER(gill_decode_sampler), _vp, _vp, _i, _vp, _vp]),
   "gill_clip_create": (_i, [C.POINTER(_vp), C.POINTER(gill_clip_config), C.POINTER(gill_tensor), _i]),
   "gill_clip_destroy": (None, [_vp]),
   "gill_clip_forward": (_i, [_vp, _vp, _i, _vp, _vp]),

@@ -296,7 +296,163 @@ __global__ __launch_bounds__(kFilterThreads) void decode_sample_kernel(float* __
   emit_pick(bi, row, r, table, D, tokens, ld, col, n_out, force, next_embeds, emit, &n_emit);
 }
 
+// ---- ragged decision: every row its own step count, length and [IMG] forcing state (the layout of `st` is in include/gill_amd.h) ----
+
+// The draw of decode_sample_kernel on one row, as a device function for the ragged kernel (decode_sample_kernel keeps its own copy so that its
+// code stays what it was): rule already applied; on return (bv, bi) is this thread's best key, to be joined by block_argmax.
+__device__ __forceinline__ void draw_row(const float* __restrict__ x, int V, float t, int do_top_p, float top_p, uint64_t seed, uint32_t prow,
+                                         uint32_t draw, float* red, float& bv, int& bi) {
+  const int tid = threadIdx.x;
+  int parity = 0;
+  float e[kFilterPerThread];
+#pragma unroll
+  for (int i = 0; i < kFilterPerThread; ++i) {
+    const int c = tid + i * kFilterThreads;
+    e[i] = c < V ? divide<false>(x[c], t, 0.f) : -INFINITY;
+  }
+  float mx;
+  const uint32_t lo = softmax_keep_threshold(e, mx, do_top_p, top_p, red, parity);
+  int has_nan = 0;
+#pragma unroll
+  for (int i = 0; i < kFilterPerThread; ++i) has_nan |= e[i] != e[i];
+  const int no_draw = __syncthreads_or(has_nan) || !(fabsf(mx) < INFINITY);    // uniform over the workgroup
+  bv = -INFINITY;
+  bi = 0x7fffffff;
+  if (no_draw) {
+    for (int c = tid; c < V; c += kFilterThreads) {
+      const float v = divide<false>(x[c], t, 0.f);
+      if (argmax_better(v, c, bv, bi)) { bv = v; bi = c; }
+    }
+    return;
+  }
+  const uint32_t k0 = (uint32_t)seed, k1 = (uint32_t)(seed >> 32);
+#pragma unroll 1
+  for (int q = tid; 4 * q < V; q += kFilterThreads) {
+    float ev[4];
+    bool kept = false;
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      const int c = 4 * q + j;
+      ev[j] = -1.f;
+      if (c < V) {
+        const float v = divide<false>(x[c], t, 0.f);
+        const float e1 = v == -INFINITY ? 0.f : __expf(v - mx);
+        if (__float_as_uint(e1) >= lo) { ev[j] = e1; kept = true; }
+      }
+    }
+    if (!kept) continue;
+    const Philox4 p = philox4x32_10((uint32_t)q, prow, draw, 0u, k0, k1);
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      if (ev[j] >= 0.f) {
+        const float key = __fdiv_rn(ev[j], -logf(philox_uniform(p.w[j])));
+        if (argmax_better(key, 4 * q + j, bv, bi)) { bv = key; bi = 4 * q + j; }
+      }
+    }
+  }
+}
+
+// One workgroup per row, one launch per iteration of the ragged loop.  A row in a forced [IMG] block emits the block's next id and touches no
+// logit; a finished row (step >= max_steps, no block pending) changes nothing; every other row takes a decision: the rule with suppress =
+// (its own step < min_word_tokens), the argmax or the seeded draw keyed (seed, row_id, draw = step), then step + 1.  A pick of ret[0] with
+// n_ret > 1 opens a forced block (or, with ret != gen, sets the row's error flag: the reference's assert).  An emitting row appends its id to
+// tokens[row][n_tok++], copies the id's embedding row to next_embeds[row] and advances len.  The active-row count goes down by one (an integer
+// atomic: exact in any order) when a row emits its last id.  Rows never read each other's state: a row's tokens do not depend on the batch.
+template <bool SAMPLE>
+__global__ __launch_bounds__(kPickThreads) void decode_ragged_kernel(float* __restrict__ logits, int V, DecodeRuleDev r, DecodeRuleDev rs, int min_word_tokens,
+                                                                     int max_steps, float t, int do_top_p, float top_p, uint64_t seed,
+                                                                     int32_t* __restrict__ st, int B, int32_t* __restrict__ clamp_flags,
+                                                                     const bf16_t* __restrict__ table, int D, int64_t* __restrict__ tokens,
+                                                                     int ld, bf16_t* __restrict__ next_embeds) {
+  static_assert(kFilterThreads == kPickThreads, "block_argmax strides by kPickThreads");
+  const int row = blockIdx.x, tid = threadIdx.x;
+  __shared__ float red[2 * (kFilterThreads / 64)];
+  __shared__ float wv[kPickThreads / 64];
+  __shared__ int wi[kPickThreads / 64];
+  __shared__ int64_t emit_id;
+  const int step = st[DEC_STEP * B + row], forced = st[DEC_FORCED * B + row];
+  __syncthreads();      // every thread holds the row's state before thread 0 rewrites it
+  if (tid == 0 && clamp_flags && clamp_flags[row]) {      // a length clamp of the step's attention: reported through the row's flags
+    st[DEC_FLAGS * B + row] |= DEC_FLAG_CLAMP;
+    clamp_flags[row] = 0;
+  }
+  if (forced == 0 && step >= max_steps) return;           // finished (uniform over the workgroup)
+  int bi = 0;
+  if (forced == 0) {
+    float* x = logits + (size_t)row * V;
+    if (tid == 0) {       // r with suppress = 0, rs with suppress = 1: the row's own step chooses
+      if (step < min_word_tokens) apply_rule_row(x, rs);
+      else apply_rule_row(x, r);
+    }
+    __syncthreads();
+    float bv = -INFINITY;
+    bi = 0x7fffffff;
+    if (SAMPLE) {
+      draw_row(x, V, t, do_top_p, top_p, seed, (uint32_t)st[DEC_ROW_ID * B + row], (uint32_t)step, red, bv, bi);
+    } else {
+      for (int c = tid; c < V; c += kPickThreads) {
+        const float v = x[c];
+        if (argmax_better(v, c, bv, bi)) { bv = v; bi = c; }
+      }
+    }
+    block_argmax(bv, bi, wv, wi);
+  }
+  if (tid == 0) {
+    int64_t id;
+    int nforced = 0, nstep = step, flags = 0;
+    if (forced > 0) {
+      id = r.ret_raw[forced];
+      nforced = forced + 1 < r.n_ret ? forced + 1 : 0;
+    } else {
+      id = bi;
+      nstep = step + 1;
+      if (bi == r.ret0_raw && r.n_ret > 1) {
+        if (r.ret_eq_gen) { id = r.ret_raw[0]; nforced = 1; }
+        else flags |= DEC_FLAG_ASSERT;
+      }
+    }
+    const int nt = st[DEC_NTOK * B + row];
+    if (nt < ld) tokens[(size_t)row * ld + nt] = id;
+    else flags |= DEC_FLAG_FULL;
+    st[DEC_NTOK * B + row] = nt + 1;
+    st[DEC_LEN * B + row] += 1;
+    st[DEC_STEP * B + row] = nstep;
+    st[DEC_FORCED * B + row] = nforced;
+    if (flags) st[DEC_FLAGS * B + row] |= flags;
+    if (nforced == 0 && nstep >= max_steps) atomicSub(&st[DEC_FIELDS * B], 1);
+    emit_id = id;
+  }
+  __syncthreads();
+  int64_t id = emit_id;
+  if (id < 0) id = 0;
+  if (id >= r.vocab) id = r.vocab - 1;
+  const uint32_t* e = reinterpret_cast<const uint32_t*>(table + (size_t)id * D);
+  uint32_t* o = reinterpret_cast<uint32_t*>(next_embeds + (size_t)row * D);
+  for (int c = tid; c < D / 2; c += kPickThreads) o[c] = e[c];
+}
+
 }  // namespace
+
+int decode_ragged_launch(float* logits, int B, int V, const DecodeRuleDev& r_in, int min_word_tokens, int max_steps, const DecodeSampler* sm,
+                         int32_t* state, int32_t* clamp_flags, const bf16_t* table, int D, int64_t* tokens, int ld, bf16_t* next_embeds,
+                         hipStream_t s) {
+  GILL_REQUIRE(B >= 1 && V >= 1 && D % 2 == 0 && ld >= 1 && max_steps >= 0, "ragged decode: bad shape");
+  GILL_REQUIRE(logits && state && tokens && next_embeds && table, "ragged decode: null argument");
+  DecodeRuleDev r = r_in, rs = r_in;
+  r.suppress = 0;
+  rs.suppress = 1;
+  if (sm) {
+    GILL_TRY(decode_sample_check(B, V, r, *sm, D, kDecodeMaxIds + 1, 0));
+    hipLaunchKernelGGL(decode_ragged_kernel<true>, dim3(B), dim3(kPickThreads), 0, s, logits, V, r, rs, min_word_tokens, max_steps,
+                       (float)sm->temperature, (int)(sm->top_p < 1.0), (float)sm->top_p, sm->seed, state, B, clamp_flags, table, D, tokens, ld,
+                       next_embeds);
+  } else {
+    hipLaunchKernelGGL(decode_ragged_kernel<false>, dim3(B), dim3(kPickThreads), 0, s, logits, V, r, rs, min_word_tokens, max_steps, 1.f, 0, 1.f,
+                       (uint64_t)0, state, B, clamp_flags, table, D, tokens, ld, next_embeds);
+  }
+  GILL_CHECK_HIP(hipGetLastError());
+  return 0;
+}
 
 int decode_rule_pick_launch(float* logits, int B, int V, const DecodeRuleDev& r, const bf16_t* table, int D, int64_t* tokens,
                             int ld, int col, int32_t* n_out, bf16_t* next_embeds, hipStream_t s) {

@@ -174,6 +174,22 @@ struct AttnArgs {
 };
 int attention_launch(const AttnArgs& a, hipStream_t s);
 
+// Decode attention with append (attention_decode.hip): ONE new token per sequence against that sequence's own cache length.  For (b, h) with
+// n = lens[b] read on the device (clamped into [0, pitch - 1]; a clamp sets flags[b] = 1 when flags is given):
+//   K[b][h][n][:] = k[b][h dp ..], Vt[b][h][:][n] = v[b][h dp ..] (row dp := 1.0 where dpv > dp, as the QKV epilogue writes it), and
+//   O[b][h dp ..] = softmax(qscale * q . [K[0 .. n - 1] ; k]) . [V[0 .. n - 1] ; v]   — the new key and value from the input rows, slots > n never read as data.
+// q / k / v: rows of ld elements, head h at column h * dp (the three thirds of a plain (B, 3 D) projection).  dp 64 | 80 | 128.
+struct AttnDecodeArgs {
+  const bf16_t* q = nullptr; const bf16_t* k = nullptr; const bf16_t* v = nullptr; int ld = 0;
+  bf16_t* K = nullptr; bf16_t* Vt = nullptr;     // [B][H][pitch][dp], [B][H][dpv][pitch]
+  const int32_t* lens = nullptr;                 // [B] device
+  bf16_t* O = nullptr; int ldo = 0;              // [B][ldo], token-major
+  int32_t* flags = nullptr;                      // [B] device, nullable
+  int B = 0, H = 0, dp = 0, dpv = 0, pitch = 0;
+  float qscale = 1.f;                            // log2(e) / sqrt(head dim): the kernel works in the log2 domain
+};
+int attention_decode_launch(const AttnDecodeArgs& a, hipStream_t s);
+
 
 // The feed-forward sub-block + proj_out + outer residual of a level-0 transformer block (C = 320) as one kernel (ffn.hip):
 //   out = [Wp.W2 | Wp] . [ value * gelu(gate) | t ] + bo + resid,  [value | gate] = W1' . LN(t) + b1'  (LN from the row-sum planes).
@@ -313,6 +329,14 @@ struct DecodeSampler {
 int decode_sample_check(int B, int V, const DecodeRuleDev& r, const DecodeSampler& sm, int D, int ld, int col);   // host: arguments only
 int decode_sample_launch(float* logits, int B, int V, const DecodeRuleDev& r, const DecodeSampler& sm, const bf16_t* table, int D,
                          int64_t* tokens, int ld, int col, int32_t* n_out, bf16_t* next_embeds, hipStream_t s);
+// Ragged decision (one launch per iteration; include/gill_amd.h "ragged decode state"): state int32 [DEC_FIELDS][B] then the active-row count.
+enum { DEC_LEN = 0, DEC_STEP = 1, DEC_FORCED = 2, DEC_NTOK = 3, DEC_ROW_ID = 4, DEC_FLAGS = 5, DEC_FIELDS = 6 };
+enum { DEC_FLAG_ASSERT = 1, DEC_FLAG_CLAMP = 2, DEC_FLAG_FULL = 4 };
+// sm == nullptr: greedy; else the seeded draw keyed (seed, row_id, draw = the row's step); sm->draw / sm->row0 are not read.
+// clamp_flags (nullable): [B] words set by attention_decode_launch, folded into the rows' flags and cleared
+int decode_ragged_launch(float* logits, int B, int V, const DecodeRuleDev& r, int min_word_tokens, int max_steps, const DecodeSampler* sm,
+                         int32_t* state, int32_t* clamp_flags, const bf16_t* table, int D, int64_t* tokens, int ld, bf16_t* next_embeds,
+                         hipStream_t s);
 // out = in / temperature (reciprocal: in * fp32(1 / temperature)), then the top-p filter when top_p < 1
 int decode_filter_launch(const float* in, float* out, int B, int V, double temperature, int reciprocal, double top_p,
                          double filter_value, hipStream_t s);

@@ -27,6 +27,7 @@ struct gill_opt {
   int32_t* idx_dev = nullptr; // [B*8 + B*8]
   // KV cache of gill_opt_forward_cached (allocated at its first call): per layer K [B][H][Tcap][dp], Vt [B][H][dpv][Tcap]
   std::vector<TfmKv> cache;
+  int32_t* dec_flags = nullptr;   // [max_batch]: length clamps of gill_opt_decode_step's attention, folded into the rows' flags by the ragged decision
   // scoring workspace of gill_opt_forward_loss (allocated at its first call): the final LayerNorm of every row, the shifted targets, the
   // per-row results and the partials of lmloss.hip
   bf16_t* xn_bf = nullptr;      // [B*T][D]
@@ -128,6 +129,21 @@ extern "C" int gill_opt_forward(gill_opt* m, const void* inputs_embeds_bf16, int
   return 0;
 }
 
+// the KV cache of the cached entries, allocated at the first call that needs it
+static int opt_ensure_cache(gill_opt* m) {
+  if (!m->cache.empty()) return 0;
+  // zero-filled: rows beyond the valid length are masked in attention, but must stay finite (0 * NaN would poison PV)
+  const int tcap = round_up(m->cfg.max_seq, 32);
+  const size_t kn = (size_t)m->cfg.max_batch * m->cfg.num_heads * tcap * m->tfm.dp;
+  const size_t vn = (size_t)m->cfg.max_batch * m->cfg.num_heads * m->tfm.dpv * tcap;
+  m->cache.assign(m->layers.size(), TfmKv{nullptr, nullptr, tcap});
+  for (TfmKv& c : m->cache) {
+    GILL_TRY(m->pool.alloc(&c.k, kn, true));
+    GILL_TRY(m->pool.alloc(&c.vt, vn, true));
+  }
+  return m->pool.alloc(&m->dec_flags, (size_t)m->cfg.max_batch, true);
+}
+
 extern "C" int gill_opt_forward_cached(gill_opt* m, const void* inputs_embeds_bf16, int B, int T_new, int past_len,
                                        float* hidden_out, void* stream) {
   GILL_REQUIRE(m && inputs_embeds_bf16 && hidden_out, "null argument");
@@ -136,17 +152,7 @@ extern "C" int gill_opt_forward_cached(gill_opt* m, const void* inputs_embeds_bf
   GILL_REQUIRE(past_len + T_new + 2 <= m->cfg.max_positions + 2, "sequence longer than the position table");
   hipStream_t s = (hipStream_t)stream;
   const int D = m->cfg.hidden_size;
-  if (m->cache.empty()) {
-    // zero-filled: rows beyond the valid length are masked in attention, but must stay finite (0 * NaN would poison PV)
-    const int tcap = round_up(m->cfg.max_seq, 32);
-    const size_t kn = (size_t)m->cfg.max_batch * m->cfg.num_heads * tcap * m->tfm.dp;
-    const size_t vn = (size_t)m->cfg.max_batch * m->cfg.num_heads * m->tfm.dpv * tcap;
-    m->cache.assign(m->layers.size(), TfmKv{nullptr, nullptr, tcap});
-    for (TfmKv& c : m->cache) {
-      GILL_TRY(m->pool.alloc(&c.k, kn, true));
-      GILL_TRY(m->pool.alloc(&c.vt, vn, true));
-    }
-  }
+  GILL_TRY(opt_ensure_cache(m));
   hipLaunchKernelGGL(opt_add_pos_kernel, dim3(B * T_new), dim3(256), 0, s, (const bf16_t*)inputs_embeds_bf16, m->pos,
                      2 + past_len, T_new, D, m->h);
   GILL_CHECK_HIP(hipGetLastError());
@@ -438,4 +444,117 @@ extern "C" int gill_opt_filter_logits(gill_opt* m, const float* in, float* out, 
   GILL_REQUIRE(m, "null handle");
   return decode_filter_launch(in, out, B, m->cfg.vocab_size, temperature, reciprocal != 0, top_p, filter_value,
                               (hipStream_t)stream);
+}
+
+// ---- ragged batched decoding: every row at its own length ----
+
+// opt_add_pos_kernel for one token per row at a per-row position: out[b][:] = bf16->f32(emb[b][:]) + pos[2 + lens[b]][:], the length read on
+// the device and clamped into the table (the attention kernel of the same step raises the flag).  16-byte loads, 8 elements per thread.
+__global__ __launch_bounds__(256) void opt_add_pos_rows_kernel(const bf16_t* __restrict__ emb, const bf16_t* __restrict__ pos,
+                                                               const int32_t* __restrict__ lens, int max_positions, int D, float* __restrict__ out) {
+  const int row = blockIdx.x;
+  int n = lens[row];
+  n = n < 0 ? 0 : (n > max_positions - 1 ? max_positions - 1 : n);
+  const bf16_t* e = emb + (size_t)row * D;
+  const bf16_t* pe = pos + (size_t)(2 + n) * D;
+  float* o = out + (size_t)row * D;
+  for (int c = threadIdx.x * 8; c < D; c += blockDim.x * 8) {
+    const uint4 u = *reinterpret_cast<const uint4*>(e + c);
+    const uint4 v = *reinterpret_cast<const uint4*>(pe + c);
+    const uint32_t uu[4] = {u.x, u.y, u.z, u.w}, vv[4] = {v.x, v.y, v.z, v.w};
+    float r[8];
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+      r[2 * i] = bf2f((bf16_t)(uu[i] & 0xffff)) + bf2f((bf16_t)(vv[i] & 0xffff));
+      r[2 * i + 1] = bf2f((bf16_t)(uu[i] >> 16)) + bf2f((bf16_t)(vv[i] >> 16));
+    }
+    *reinterpret_cast<float4*>(o + c) = make_float4(r[0], r[1], r[2], r[3]);
+    *reinterpret_cast<float4*>(o + c + 4) = make_float4(r[4], r[5], r[6], r[7]);
+  }
+}
+
+extern "C" int gill_opt_decode_step(gill_opt* m, const void* new_embeds_bf16, const int32_t* lens_dev, int B, int len_bound, float* hidden_out,
+                                    void* stream) {
+  GILL_REQUIRE(m && new_embeds_bf16 && lens_dev && hidden_out, "null argument");
+  GILL_REQUIRE(B >= 1 && B <= m->cfg.max_batch, "B exceeds the handle's workspace");
+  GILL_REQUIRE(len_bound >= 1 && len_bound <= m->cfg.max_seq, "len_bound exceeds the handle's max_seq");
+  GILL_REQUIRE(len_bound <= m->cfg.max_positions, "sequence longer than the position table");
+  hipStream_t s = (hipStream_t)stream;
+  const int D = m->cfg.hidden_size, n = (int)m->layers.size();
+  GILL_TRY(opt_ensure_cache(m));
+  hipLaunchKernelGGL(opt_add_pos_rows_kernel, dim3(B), dim3(256), 0, s, (const bf16_t*)new_embeds_bf16, m->pos, lens_dev, m->cfg.max_positions, D,
+                     m->h);
+  GILL_CHECK_HIP(hipGetLastError());
+  // TfmRun::layers at T = 1, self-attention as projection -> decode attention with append -> out-projection
+  const Tfm& t = m->tfm;
+  const TfmRun run{t, s};
+  const TfmLayer* L = m->layers.data();
+  if (n > 0) GILL_TRY(layernorm_launch(m->h, 1, L[0].ln1g, L[0].ln1b, t.nbuf, B, D, 1e-5f, s));
+  for (int i = 0; i < n; ++i) {
+    const TfmLayer* next = i + 1 < n ? &L[i + 1] : nullptr;
+    GILL_TRY(run.linear(t.nbuf, B, L[i].wqkv, L[i].blk_qkv, L[i].bqkv, 3 * D, D, nullptr, ACT_NONE, t.q, false));
+    AttnDecodeArgs a;
+    a.q = t.q; a.k = t.q + D; a.v = t.q + 2 * D; a.ld = 3 * D;
+    a.K = m->cache[i].k; a.Vt = m->cache[i].vt; a.lens = lens_dev; a.O = t.o; a.ldo = D; a.flags = m->dec_flags;
+    a.B = B; a.H = t.H; a.dp = t.dp; a.dpv = t.dpv; a.pitch = m->cache[i].pad;
+    a.qscale = 1.4426950408889634f / sqrtf((float)t.dp);
+    GILL_TRY(attention_decode_launch(a, s));
+    GILL_TRY(run.linear(t.o, B, L[i].wo, L[i].blk_o, L[i].bo, D, D, m->h, ACT_NONE, m->h, true, L[i].ln2g, L[i].ln2b, t.nbuf));
+    GILL_TRY(run.ffn(m->h, B, L[i], ACT_RELU, next ? next->ln1g : nullptr, next ? next->ln1b : nullptr));
+  }
+  GILL_TRY(layernorm_f32out_launch(m->h, 1, m->lnfg, m->lnfb, hidden_out, B, D, 1e-5f, s));
+  return 0;
+}
+
+extern "C" int gill_opt_prefill_ids(gill_opt* m, const int64_t* ids, int B, int Tmax, const void* extra_rows_bf16, int n_extra, float* hidden_out,
+                                    void* stream) {
+  GILL_REQUIRE(m && ids && hidden_out, "null argument");
+  GILL_REQUIRE(B >= 1 && B <= m->cfg.max_batch && Tmax >= 1 && Tmax <= m->cfg.max_seq, "B / Tmax exceed the handle's workspace");
+  GILL_REQUIRE(Tmax <= m->cfg.max_positions, "sequence longer than the position table");
+  GILL_REQUIRE(n_extra >= 0 && (n_extra == 0 || extra_rows_bf16), "n_extra rows need a table");
+  hipStream_t s = (hipStream_t)stream;
+  const int D = m->cfg.hidden_size;
+  GILL_TRY(opt_ensure_cache(m));
+  // rows of embed_tokens (id >= 0) or of extra_rows (id < 0) + positions 2 + t -> the fp32 stream, then the cached forward at past_len = 0
+  GILL_TRY(img_hidden_embed(m, ids, (const bf16_t*)extra_rows_bf16, n_extra, m->pos, B, Tmax, s));
+  GILL_TRY(m->run_layers(B, Tmax, s, 0));
+  GILL_TRY(layernorm_f32out_launch(m->h, 1, m->lnfg, m->lnfb, hidden_out, B * Tmax, D, 1e-5f, s));
+  return 0;
+}
+
+// the arguments both ragged decisions share, checked before anything is enqueued
+static int ragged_args(const gill_opt* m, int B, const gill_decode_rule* rule, const gill_decode_sampler* sampler, int max_steps, DecodeRuleDev* r,
+                       DecodeSampler* sm) {
+  GILL_REQUIRE(B >= 1 && max_steps >= 0, "ragged decode: bad shape");
+  GILL_TRY(resolve_rule(m, rule, r));
+  if (sampler) {
+    GILL_TRY(resolve_sampler(sampler, sm));
+    sm->draw = 0; sm->row0 = 0;     // the row's own step and row_id take their place
+  }
+  return 0;
+}
+
+extern "C" int gill_opt_pick_token_ragged(gill_opt* m, float* logits, int B, const gill_decode_rule* rule, int max_steps,
+                                          const gill_decode_sampler* sampler, int32_t* state, int64_t* tokens, int ld, void* next_embeds_bf16,
+                                          void* stream) {
+  GILL_REQUIRE(m && logits && state && tokens && next_embeds_bf16, "null argument");
+  DecodeRuleDev r;
+  DecodeSampler sm;
+  GILL_TRY(ragged_args(m, B, rule, sampler, max_steps, &r, &sm));
+  return decode_ragged_launch(logits, B, m->cfg.vocab_size, r, rule->min_word_tokens, max_steps, sampler ? &sm : nullptr, state, m->dec_flags,
+                              m->embed, m->cfg.hidden_size, tokens, ld, (bf16_t*)next_embeds_bf16, (hipStream_t)stream);
+}
+
+extern "C" int gill_opt_next_token_ragged(gill_opt* m, const float* hidden, int B, const gill_decode_rule* rule, int max_steps,
+                                          const gill_decode_sampler* sampler, float* logits_out, int32_t* state, int64_t* tokens, int ld,
+                                          void* next_embeds_bf16, void* stream) {
+  GILL_REQUIRE(m && hidden && logits_out && state && tokens && next_embeds_bf16, "null argument");
+  DecodeRuleDev r;
+  DecodeSampler sm;
+  GILL_TRY(ragged_args(m, B, rule, sampler, max_steps, &r, &sm));      // argument errors before anything is enqueued
+  if (sampler) GILL_TRY(decode_sample_check(B, m->cfg.vocab_size, r, sm, m->cfg.hidden_size, kDecodeMaxIds + 1, 0));
+  GILL_REQUIRE(ld >= 1 && m->cfg.hidden_size % 2 == 0, "ragged decode: bad shape");
+  GILL_TRY(gill_opt_last_logits(m, hidden, B, 1, logits_out, stream));
+  return decode_ragged_launch(logits_out, B, m->cfg.vocab_size, r, rule->min_word_tokens, max_steps, sampler ? &sm : nullptr, state, m->dec_flags,
+                              m->embed, m->cfg.hidden_size, tokens, ld, (bf16_t*)next_embeds_bf16, (hipStream_t)stream);
 }

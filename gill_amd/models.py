@@ -763,6 +763,125 @@ class GILLModel(nn.Module):
     out = tokens[:, :col].clone() if max_len > 0 else None
     return out, output_embeddings, output_logits
 
+  def generate_batch(self, embeddings: Optional[Tensor] = None, lengths=None, ids: Optional[Tensor] = None,
+                     extra_rows: Optional[Tensor] = None, max_len: int = 32, temperature: float = 0.0, top_p: float = 1.0,
+                     min_word_tokens: int = 0, ret_scale_factor: float = 1.0, gen_scale_factor: float = 1.0,
+                     filter_value: float = -float('Inf'), seed: Optional[int] = None, row_ids=None):
+    """Ragged batched decoding: one dialogue per row, every row at its own length, with the tokens the one-sequence generate()
+    emits for that row alone.  The prompts are right-padded: embeddings (B, Tmax, D), or ids (B, Tmax) int64 (an id < 0 selects
+    row -(id + 1) of extra_rows (n, D) bf16, the visual embeddings of image prompts), with lengths (B,) the real lengths.
+    One prefill, then per iteration one decode step over all rows (gill_opt_decode_step: every row against its own cache length)
+    and one decision (gill_opt_next_token_ragged: every row its own step count and [IMG] forcing state, so an [IMG] block takes
+    len(retrieval_token_idx) iterations of its row while the other rows go on deciding).  max_len counts decisions per row, as in
+    generate().  temperature > 0 needs seed: the draw is the seeded one of generate(seed=), keyed (seed, row_ids[b], the row's
+    decision count), so a row draws the same tokens alone (row_ids=[its id]) as inside any batch; row_ids defaults to 0 .. B - 1.
+    The loop never makes the device wait: it reads the count of active rows of iteration i after it has enqueued iteration i + 1
+    (at most one surplus iteration); _decode_host_waits counts those reads.
+    Returns tokens (B, L) int64 padded with -1, n_tokens (B,), hidden (B, L, D) fp32 and n_hidden (B,): hidden[b, j] is
+    hidden_states[-1] at generated token j's position for j < n_hidden[b] = n_tokens[b] minus what the row's last decision emitted
+    — the rows generated_embeddings[-1][:, T0:] holds in the one-sequence call."""
+    self._decode_host_waits = 0
+    if (embeddings is None) == (ids is None):
+      raise ValueError('generate_batch takes embeddings (B, Tmax, D) or ids (B, Tmax), one of the two.')
+    src = embeddings if embeddings is not None else ids
+    B, Tmax = int(src.shape[0]), int(src.shape[1])
+    if lengths is None:
+      raise ValueError('generate_batch needs lengths (B,): the real length of every right-padded row.')
+    lens = [int(v) for v in torch.as_tensor(lengths).reshape(-1).tolist()]
+    if len(lens) != B:
+      raise ValueError(f'lengths has {len(lens)} entries for a batch of {B}.')
+    if min(lens) < 1 or max(lens) > Tmax:
+      raise ValueError(f'lengths should be in [1, {Tmax}], got {lens}.')
+    if temperature == 0.0 and top_p != 1.0:
+      raise ValueError('top_p cannot be set if temperature is 0 (greedy decoding).')
+    if temperature != 0.0:
+      if seed is None:
+        raise ValueError('generate_batch draws on the device only: temperature > 0 needs seed.')
+      seed = int(seed)
+      if not 0 <= seed < 2 ** 64:
+        raise ValueError(f'seed should be in [0, 2**64), got {seed} instead.')
+      assert top_p > 0, f'top_p should be above 0, got {top_p} instead.'
+    max_len = int(max_len)
+    n_ret = max(1, len(self.retrieval_token_idx))
+    L = max_len * n_ret
+    if max(lens) + L > self.opt_cfg.max_positions:
+      raise ValueError(f'max(lengths) + max_len * {n_ret} = {max(lens) + L} exceeds the position table ({self.opt_cfg.max_positions}).')
+    rows = list(range(B)) if row_ids is None else [int(v) for v in torch.as_tensor(row_ids).reshape(-1).tolist()]
+    if len(rows) != B or min(rows) < 0:
+      raise ValueError(f'row_ids should be {B} integers >= 0.')
+    dev = self.logit_scale.device
+    D, vocab = self.opt_cfg.hidden_size, self.opt_cfg.vocab_size
+    with torch.no_grad():
+      h = self._opt_native(B, max(Tmax, max(lens) + L))       # sized once: the handle is not rebuilt inside the loop
+      lib = N.lib()
+      st = torch.zeros(6 * B + 1, dtype=torch.int32)
+      st[0:B] = torch.tensor(lens, dtype=torch.int32) - 1
+      st[4 * B:5 * B] = torch.tensor(rows, dtype=torch.int32)
+      st[6 * B] = B if max_len > 0 else 0
+      st = st.to(dev)
+      tokens = torch.full((B, max(L, 1)), -1, device=dev, dtype=torch.int64)
+      full = torch.empty((B, Tmax, D), device=dev, dtype=torch.float32)
+      with torch.cuda.device(dev):
+        if ids is not None:
+          idt = ids.to(dev, torch.int64).contiguous()
+          n_extra = 0
+          if extra_rows is not None:
+            if extra_rows.dim() != 2 or extra_rows.shape[1] != D or extra_rows.dtype != torch.bfloat16:
+              raise ValueError(f'extra_rows must be (n, {D}) bfloat16, got {tuple(extra_rows.shape)} {extra_rows.dtype}')
+            extra_rows = extra_rows.to(dev).contiguous()
+            n_extra = extra_rows.shape[0]
+          lowest = int(idt.min())
+          if lowest < -n_extra:
+            raise ValueError(f'id {lowest} selects extra row {-(lowest + 1)} of {n_extra}')
+          N.check(lib.gill_opt_prefill_ids(h, N.ptr(idt), B, Tmax, N.ptr(extra_rows) if n_extra else None, n_extra, N.ptr(full),
+                                           N.current_stream()))
+        else:
+          x = embeddings.to(dev, torch.bfloat16).contiguous()
+          N.check(lib.gill_opt_forward_cached(h, N.ptr(x), B, Tmax, 0, N.ptr(full), N.current_stream()))
+      lens_dev = torch.tensor(lens, device=dev, dtype=torch.int64)
+      hid = full[torch.arange(B, device=dev), lens_dev - 1].contiguous()       # the rows len[b] - 1
+      steps = torch.zeros((max(L, 1), B, D), device=dev, dtype=torch.float32)
+      nxt = torch.zeros((B, D), device=dev, dtype=torch.bfloat16)
+      logits = torch.empty((B, vocab), device=dev, dtype=torch.float32)
+      rule = self._decode_rule(0, min_word_tokens, ret_scale_factor, gen_scale_factor, filter_value)
+      sampler = None
+      if temperature != 0.0:
+        sampler = N.gill_decode_sampler()
+        sampler.temperature, sampler.top_p, sampler.seed = float(temperature), min(float(top_p), 1.0), seed
+      count = torch.zeros(2, dtype=torch.int32, pin_memory=True)
+      evs = [torch.cuda.Event(), torch.cuda.Event()]
+      with torch.cuda.device(dev):
+        for it in range(L):
+          if it > 0:
+            N.check(lib.gill_opt_decode_step(h, N.ptr(nxt), N.ptr(st), B, max(lens) + it, N.ptr(steps[it - 1]), N.current_stream()))
+            hid = steps[it - 1]
+          N.check(lib.gill_opt_next_token_ragged(h, N.ptr(hid), B, C.byref(rule), max_len, C.byref(sampler) if sampler is not None else None,
+                                                 N.ptr(logits), N.ptr(st), N.ptr(tokens), tokens.shape[1], N.ptr(nxt), N.current_stream()))
+          count[it & 1:(it & 1) + 1].copy_(st[6 * B:], non_blocking=True)
+          evs[it & 1].record()
+          if it > 0:                    # one iteration late: the device already has iteration `it` to run
+            evs[(it - 1) & 1].synchronize()
+            self._decode_host_waits += 1
+            if int(count[(it - 1) & 1]) == 0:
+              break
+      state = st.cpu()
+      flags = state[5 * B:6 * B]
+      if bool((flags & 1).any()):
+        raise AssertionError((self.retrieval_token_idx, self.gen_token_idx))   # :519
+      if bool((flags & 6).any()):
+        raise N.GillNativeError(f'ragged decode: a row outgrew the cache or the token buffer (flags {flags.tolist()})')
+      n_tokens = state[3 * B:4 * B].to(torch.int64)
+      toks = tokens.cpu()
+      n_hidden = torch.zeros(B, dtype=torch.int64)
+      for b in range(B):
+        nt = int(n_tokens[b])
+        last = 1
+        if n_ret > 1 and nt >= n_ret and int(toks[b, nt - n_ret]) == int(self.retrieval_token_idx[0]):
+          last = n_ret            # the row's last decision opened an [IMG] block, which ends the row
+        n_hidden[b] = max(nt - last, 0)
+      hidden = steps.transpose(0, 1)[:, :L].contiguous() if L > 0 else steps.new_zeros((B, 0, D))
+    return tokens[:, :L], n_tokens.to(dev), hidden, n_hidden.to(dev)
+
 class _TopScores:
   """The scores of the rows a fused search returned, indexed by row like the reference's full score vector (scores[img_idx].item())."""
 
@@ -970,6 +1089,93 @@ class GILL(nn.Module):
           return_outputs.append(utils.truncate_caption(caption) + f' {gen_prefix}')
           return_outputs.append(image_outputs)
     return return_outputs
+
+  @torch.no_grad()
+  def generate_for_images_and_texts_batch(self, prompt_lists: List, num_words: int = 32, min_word_tokens: int = 0,
+                                          ret_scale_factor: float = 1.0, gen_scale_factor: float = 1.0, top_p: float = 1.0,
+                                          temperature: float = 0.0, max_num_rets: int = 1, generator=None,
+                                          always_add_bos: bool = False, guidance_scale: float = 7.5, num_inference_steps: int = 50,
+                                          seed: Optional[int] = None):
+    """generate_for_images_and_texts for several dialogues at once: prompt_lists[b] is one prompt list (PIL images and strings); returns,
+    per prompt list, the list the one-sequence method returns for it.  The prompts are segmented as the batched entries segment them
+    (_interleaved_ids, _visual_rows), decoded as ONE ragged batch (GILLModel.generate_batch: every row at its own length, an [IMG]
+    block forced per row), then per row the reference's newline truncation, the [IMG] blocks up to max_num_rets and the captions; the
+    raw_emb blocks of ALL rows go through gen_text_hidden_fcs[0] in one call and, with load_sd, through the SD pipeline in chunks of 8.
+    Scope: the 'gen' branch only.  With a retrieval embedding matrix or a decision model attached this raises NotImplementedError:
+    retrieval, the decision MLP and the CLIP rerank stay with generate_for_images_and_texts, one sequence at a time.  Nothing is
+    sharded over ranks.  temperature > 0 needs seed (row b draws with row id b)."""
+    if self.emb_matrix is not None or self.decision_model is not None:
+      raise NotImplementedError('generate_for_images_and_texts_batch covers the generation branch only: with retrieval embeddings or a '
+                                'decision model attached, call generate_for_images_and_texts per prompt list.')
+    prompts = [[p] if isinstance(p, str) else list(p) for p in prompt_lists]
+    for pl in prompts:
+      for p in pl:
+        if type(p) != str and not self._is_image(p):
+          raise ValueError(f'Input prompts should be either PIL.Image.Image or str types, got {type(p)} instead.')
+    if num_words == 0:
+      raise NotImplementedError('Generation not implemented for num_words=0.')
+    if num_words < 0:
+      raise ValueError
+    m = self.model
+    dev = m.logit_scale.device
+    ids, lens, images = self._interleaved_ids(prompts, always_add_bos)
+    flat = [im for row in images for im in row]
+    extra = self._visual_rows(flat) if flat else None
+    tokens, n_tok, hidden, n_hid = m.generate_batch(ids=ids, lengths=lens, extra_rows=extra, max_len=num_words, temperature=temperature,
+                                                    top_p=top_p, min_word_tokens=min_word_tokens, ret_scale_factor=ret_scale_factor,
+                                                    gen_scale_factor=gen_scale_factor, seed=seed)
+    n_tok, n_hid = n_tok.tolist(), n_hid.tolist()
+    newline_token_id = m.tokenizer('\n', add_special_tokens=False).input_ids[0]
+    gen_prefix = ''.join([f'[IMG{i}]' for i in range(m.args.num_tokens)])
+    outputs, blocks = [], []          # blocks: (the image_outputs dict to fill, raw_emb (1, 8, D))
+    for b in range(len(prompts)):
+      generated_ids = tokens[b:b + 1, :n_tok[b]]
+      embeddings = hidden[b:b + 1, :n_hid[b]].to(m.logit_scale.dtype)
+      trunc_idx = 0
+      for j, t in enumerate(generated_ids[0].tolist()):
+        if t == newline_token_id:
+          trunc_idx = j
+          break
+      if trunc_idx > 0:
+        generated_ids = generated_ids[:, :trunc_idx]
+        embeddings = embeddings[:, :trunc_idx]
+      row_out = []
+      all_ret_idx = [i for i, x in enumerate(generated_ids[0, :] == m.retrieval_token_idx[0]) if x][:max_num_rets]
+      last_ret_idx = 0
+      if len(all_ret_idx) == 0:
+        row_out.append(utils.truncate_caption(m.tokenizer.batch_decode(generated_ids, skip_special_tokens=True)[0]))
+      for ret_idx in all_ret_idx:
+        assert generated_ids[0, ret_idx:ret_idx + m.num_tokens].tolist() == m.retrieval_token_idx, \
+          (generated_ids[0, ret_idx:ret_idx + m.num_tokens], m.retrieval_token_idx)
+        assert len(m.args.text_emb_layers) == 1
+        image_outputs = {'gen': [], 'ret': [], 'decision': ['gen', [0, 1]]}
+        blocks.append((image_outputs, embeddings[:, ret_idx:ret_idx + m.num_tokens, :]))
+        caption = m.tokenizer.batch_decode(generated_ids[:, last_ret_idx:ret_idx], skip_special_tokens=True)[0]
+        last_ret_idx = ret_idx + 1
+        row_out.append(utils.truncate_caption(caption) + f' {gen_prefix}')
+        row_out.append(image_outputs)
+      outputs.append(row_out)
+    if blocks:
+      gen_prefx_ids = m.tokenizer(gen_prefix, add_special_tokens=False, return_tensors="pt").input_ids.to(dev)
+      gen_prefix_embs = m.input_embeddings(gen_prefx_ids)                                  # (1, T, D)
+      raw = torch.cat([r for _, r in blocks], dim=0)                                       # (n, 8, D): every row's blocks at once
+      gen_emb = m.gen_text_hidden_fcs[0](raw, gen_prefix_embs)                             # (n, 77, 768)
+      if gen_emb.shape[1] != 77:
+        gen_emb = gen_emb.reshape(gen_emb.shape[0], -1, 768)
+        gen_emb = torch.cat([gen_emb, torch.zeros((gen_emb.shape[0], 77 - gen_emb.shape[1], 768), device=dev, dtype=gen_emb.dtype)], dim=1)
+      gen_emb = gen_emb.repeat_interleave(self.num_gen_images, dim=0)                      # block k: rows k * num_gen_images ..
+      if self.load_sd:
+        gen_images = []
+        for i in range(0, gen_emb.shape[0], 8):
+          gen_images.extend(self.sd_pipe(prompt_embeds=gen_emb[i:i + 8], generator=generator, guidance_scale=guidance_scale,
+                                         num_inference_steps=num_inference_steps,
+                                         output_type="pil" if getattr(self.sd_pipe, "_vae", None) else "latent").images)
+        for k, (image_outputs, _) in enumerate(blocks):
+          image_outputs['gen'] = [(gen_images[k * self.num_gen_images], 0)]
+      else:
+        for k, (image_outputs, _) in enumerate(blocks):
+          image_outputs['gen'] = [gen_emb[k * self.num_gen_images:(k + 1) * self.num_gen_images]]
+    return outputs
 
   @torch.no_grad()
   def get_log_likelihood_scores(self, prompts: List) -> float:

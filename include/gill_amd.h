@@ -172,6 +172,66 @@ int gill_opt_draw_token(gill_opt* h, float* logits, int B, const gill_decode_rul
 /* Host only, no GPU: u_c of the draw above for c in [first, first + count), first + count <= 65536, from the code the kernel runs. */
 int gill_decode_uniforms(uint64_t seed, int32_t row, int32_t draw, int32_t first, int32_t count, float* u_out);
 
+/* ---- Ragged batched decoding: every row of the batch at its own length (one dialogue per row). ----
+ *
+ * Decode attention with append, the operator under gill_opt_decode_step.  One new token per row: q, k_new, v_new are rows of ld bf16
+ * elements with head h at column h * d (d = 64, 80 or 128); K (B,H,pitch,d) and Vt (B,H,round_up(d,32),pitch) are the cache in the
+ * layout of gill_opt_forward_cached; lens (B) int32 on the DEVICE.  With n = lens[b]: the new key / value are stored at slot n and
+ * o (B, H*d) bf16 = softmax(q . [K[0..n-1]; k_new] / sqrt(d)) . [V[0..n-1]; v_new].  Slots beyond n are excluded by selection whatever
+ * they hold.  n outside [0, pitch - 1] is clamped into it and flags[b] (device int32, nullable) is set to 1; nothing outside the
+ * buffers is touched.  A row's output is a fixed function of its own operands and length: the same bits at any B, on any run. */
+int gill_attention_decode(const void* q, const void* k_new, const void* v_new, int ld, void* K, void* Vt, const int32_t* lens,
+                          void* o, int B, int H, int d, int pitch, int32_t* flags, void* stream);
+
+/* One decode step of B rows at B different lengths.  new_embeds (B,1,D) bf16: row b's token sits at position lens_dev[b] (device
+ * int32): it takes position embedding 2 + lens_dev[b], its key / value go to slot lens_dev[b] of row b's cache and it attends to
+ * slots 0 .. lens_dev[b].  len_bound is the host's upper bound on max(lens) + 1, checked against max_seq and the position table
+ * before anything is enqueued.  The layers are those of gill_opt_forward_cached with self-attention as projection ->
+ * gill_attention_decode -> out-projection.  hidden_out (B,1,D) fp32 = hidden_states[-1].  The step neither writes nor advances
+ * lens_dev (the ragged decision below owns it).  A length the device holds beyond the cache is clamped and reported through the
+ * rows' flags by the next ragged decision.  No host wait. */
+int gill_opt_decode_step(gill_opt* h, const void* new_embeds_bf16, const int32_t* lens_dev, int B, int len_bound, float* hidden_out,
+                         void* stream);
+
+/* Prefill for the ragged loop: ids (B,Tmax) int64 on the device, right-padded (an id < 0 selects row -(id + 1) of extra_rows
+ * (n_extra, D) bf16, as in gill_opt_img_hidden_ex), embedded and run through gill_opt_forward_cached's pass at past_len = 0.
+ * hidden_out (B,Tmax,D) fp32; row b's last real row is len[b] - 1.  Pad positions write keys / values at slots >= len[b]: the first
+ * decode step overwrites slot len[b] and nothing beyond a row's length is ever selected. */
+int gill_opt_prefill_ids(gill_opt* h, const int64_t* ids, int B, int Tmax, const void* extra_rows_bf16, int n_extra, float* hidden_out,
+                         void* stream);
+
+/* Ragged decode state: int32 words on the device, field-major, [6][B] followed by one word:
+ *   state[0*B + b] len     position of row b's newest token: the one whose hidden row the next decision reads.  An emitting
+ *                          decision advances it to the emitted token's position, which is where gill_opt_decode_step (lens_dev =
+ *                          state) then stores that token: the row's cache length at that step.  Start: prompt length - 1.
+ *   state[1*B + b] step    decisions taken (the loop index i of the one-sequence generate())
+ *   state[2*B + b] forced  index into ret_ids of the next forced id, 0 = no [IMG] block pending
+ *   state[3*B + b] n_tok   ids emitted into tokens[b][..]
+ *   state[4*B + b] row_id  the row's Philox key (gill_decode_sampler.row0 of the one-sequence draw)
+ *   state[5*B + b] flags   1: [IMG0] picked with ret_eq_gen == 0 (the reference's AssertionError); 2: a length was clamped to the
+ *                          cache; 4: the token buffer was full
+ *   state[6*B]             rows still active (start: B, or the number of rows with max_steps > 0)
+ * One launch per iteration, every row one of three ways:
+ *   forced > 0:  emits ret_ids[forced], forced + 1 (0 after the last id); no decision: step stands, the logits are not touched;
+ *   else step >= max_steps: finished, nothing changes;
+ *   else: the rule with rule->step replaced by the row's step, torch.argmax (sampler == NULL) or the seeded draw of
+ *         gill_opt_sample_token keyed (seed, row_id, draw = step) (sampler->draw and ->row0 are not read); a pick of ret_ids[0]
+ *         with n_ret > 1 sets forced = 1 (ret_eq_gen == 0: flag 1 instead); step + 1.
+ * An emitting row stores its id at tokens[b][n_tok++] (tokens (B, ld) int64), the id's input_embeddings row at next_embeds[b]
+ * ((B,1,D) bf16) and advances len.  The active count drops by one when a row emits its last id.  A row's ids are a function of its
+ * own logits and state: they are those of the one-sequence loop, an [IMG] block taking n_ret iterations.  No host wait.
+ * hidden (B,1,D) fp32: the rows the decision reads (the prefill's rows len[b] - 1 gathered by the caller, then gill_opt_decode_step's
+ * output); lm_head as gill_opt_last_logits (a row's logits do not depend on B) -> logits_out (B, vocab) fp32, the rule in place on
+ * the rows that decide.  max_steps: decisions per row.  Argument errors are reported before anything is enqueued. */
+int gill_opt_next_token_ragged(gill_opt* h, const float* hidden, int B, const gill_decode_rule* rule, int max_steps,
+                               const gill_decode_sampler* sampler, float* logits_out, int32_t* state, int64_t* tokens, int ld,
+                               void* next_embeds_bf16, void* stream);
+
+/* The same decision on caller-supplied logits (B, vocab) fp32, modified by the rule only (rows that take no decision: untouched). */
+int gill_opt_pick_token_ragged(gill_opt* h, float* logits, int B, const gill_decode_rule* rule, int max_steps,
+                               const gill_decode_sampler* sampler, int32_t* state, int64_t* tokens, int ld, void* next_embeds_bf16,
+                               void* stream);
+
 /* ------------------------------------------------------------------------------------------
  * Image prompts — the frozen CLIP vision tower (transformers CLIPVisionModel built at gill/models.py:78-96 and called by
  * GILLModel.get_visual_embs, gill/models.py:129-145: `self.visual_model(pixel_values).pooler_output`).
