@@ -83,6 +83,13 @@ SYMBOLS: Dict[str, Tuple[object, List[object]]] = {
   "gill_version": (_i, []),
   "gill_opt_create": (_i, [C.POINTER(_vp), C.POINTER(gill_opt_config), C.POINTER(gill_tensor), _i]),
   "gill_opt_destroy": (None, [_vp]),
+  "gill_opt_create_ex": (_i, [C.POINTER(_vp), C.POINTER(gill_opt_config), C.POINTER(gill_tensor), _i, _i]),
+  "gill_opt_weight_mode": (_i, [_vp]),
+  "gill_opt_decode_uses_w8": (_i, [_vp, _i]),
+  "gill_w8_max_rows": (_i, []),
+  "gill_op_w8_quant": (_i, [_vp, _i, _i, _vp, _vp, _vp]),
+  "gill_op_w8_dequant": (_i, [_vp, _vp, _i, _i, _i, _vp, _vp]),
+  "gill_op_linear_w8": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp]),
   "gill_opt_embed": (_i, [_vp, _vp, _i, _vp, _vp]),
   "gill_opt_forward": (_i, [_vp, _vp, _i, _i, _vp, _vp]),
   "gill_opt_forward_cached": (_i, [_vp, _vp, _i, _i, _i, _vp, _vp]),

@@ -718,3 +718,37 @@ extern "C" int gill_unet_xf_plan(const int32_t* cases, int n, int lnproj, int xa
   }
   return 0;
 }
+
+// ---- the w8 format and its linear on their own (linear_w8.hip; tests/test_w8_ops_gpu.py)
+extern "C" int gill_op_w8_quant(const void* w_bf16, int N, int K, void* w8, float* scale, void* stream) {
+  hipStream_t s = (hipStream_t)stream;
+  GILL_TRY(w8_quant_launch((const bf16_t*)w_bf16, 0, N, K, (unsigned char*)w8, scale, s));
+  GILL_CHECK_HIP(hipStreamSynchronize(s));
+  return 0;
+}
+
+extern "C" int gill_op_w8_dequant(const void* w8, const float* scale, int N, int K, int blk64, void* out_bf16, void* stream) {
+  hipStream_t s = (hipStream_t)stream;
+  GILL_TRY(w8_dequant_launch((const unsigned char*)w8, scale, N, K, blk64 != 0, (bf16_t*)out_bf16, s));
+  GILL_CHECK_HIP(hipStreamSynchronize(s));
+  return 0;
+}
+
+extern "C" int gill_op_linear_w8(const void* A_bf16, const void* w8, const float* scale, const float* bias, const float* resid_f32, void* out, int M,
+                                 int N, int K, int act, int out_f32, int splitk, const float* ln_g, const float* ln_b, void* ln_out_bf16,
+                                 void* stream) {
+  hipStream_t s = (hipStream_t)stream;
+  GILL_REQUIRE(A_bf16 && w8 && scale && out, "linear_w8: null operand");
+  GILL_REQUIRE(M >= 1 && M <= W8_MAX_ROWS && N > 0 && K > 0 && N % 64 == 0 && K % 64 == 0 && splitk >= 0 && splitk <= K / 64,
+               "linear_w8: 1 <= M <= W8_MAX_ROWS; N and K multiples of 64; at most K / 64 slices");
+  const int sk = splitk > 0 ? splitk : w8_pick_splitk(N, K);
+  const size_t ws_floats = (size_t)sk * M * N;
+  float* ws = op_splitk_ws(ws_floats);
+  GILL_REQUIRE(ws != nullptr, "split-K workspace allocation failed");
+  const bool in_place = resid_f32 == (const float*)out;      // (out is updated in place: no repeat loop)
+  for (int r = 0, rep = in_place ? 1 : op_repeat(); r < rep; ++r)
+    GILL_TRY(tfm_linear_w8_launch((const bf16_t*)A_bf16, M, (const unsigned char*)w8, scale, bias, N, K, resid_f32, act, out, out_f32 != 0, splitk, ws,
+                                  ws_floats, ln_g, ln_b, (bf16_t*)ln_out_bf16, s));
+  GILL_CHECK_HIP(hipStreamSynchronize(s));
+  return 0;
+}

@@ -446,3 +446,27 @@ static inline int attn_padded_dim(int d) {
 }
 
 const bf16_t* gill_zero_page();   // >= 256 B of device zeros
+
+// ---- weight-only fp8 linear of the decode step (linear_w8.hip) ----
+#define W8_MAX_ROWS 16      // activation rows of one launch: the 16 columns of the MFMA's second operand
+struct W8Args {
+  const bf16_t* A = nullptr;               // [M][K]
+  int M = 0, N = 0, K = 0;                 // 1 <= M <= W8_MAX_ROWS; N, K multiples of 64
+  const unsigned char* W8 = nullptr;       // e4m3 bytes in the kernel's order [N / 16][K / 64][64][16] (w8_quant_launch)
+  const float* scale = nullptr;            // [N] powers of two
+  const float* bias = nullptr;             // [N] or null
+  const float* resid = nullptr;            // [M][N] fp32 or null, added after the activation; may be C
+  int act = ACT_NONE;                      // ACT_NONE or ACT_RELU
+  int out_f32 = 0;
+  void* C = nullptr;                       // [M][N] bf16 or fp32
+  int splitk = 0;                          // 0: w8_pick_splitk(N, K); 1: unsplit; k > 1: k slices
+  float* ws = nullptr;                     // [sk][M][N] fp32 partials of a split (or partials_only) launch
+  size_t ws_floats = 0;
+  int partials_only = 0;                   // stop at the partials (scale applied; bias, act, resid, C unused): the caller's reducer finishes
+};
+int w8_pick_splitk(int N, int K);          // a function of the matrix alone: no row's bits depend on M
+int linear_w8_splitk(const W8Args& a);     // the slices linear_w8_launch(a) writes
+int linear_w8_launch(const W8Args& a, hipStream_t s);
+// bf16 [N][K] (row-major, or blk: 64 x 64-blocked) -> e4m3 bytes in the kernel's order + scale[N]; and back (w8 * s, exact)
+int w8_quant_launch(const bf16_t* w, int blk, int N, int K, unsigned char* w8, float* scale, hipStream_t s);
+int w8_dequant_launch(const unsigned char* w8, const float* scale, int N, int K, int blk, bf16_t* out, hipStream_t s);

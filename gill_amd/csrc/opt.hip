@@ -12,6 +12,7 @@
 
 struct gill_opt {
   gill_opt_config cfg;
+  int weight_mode = 0;          // GILL_OPT_BF16 / GILL_OPT_W8 (gill_opt_create_ex)
   DevPool pool;
   bf16_t* embed = nullptr;      // [vocab][D]
   bf16_t* lm_head = nullptr;    // tied to embed unless lm_head.weight was supplied
@@ -61,7 +62,21 @@ __global__ __launch_bounds__(256) void opt_add_pos_kernel(const bf16_t* __restri
 }
 
 extern "C" int gill_opt_create(gill_opt** out, const gill_opt_config* cfg, const gill_tensor* weights, int n_weights) {
+  return gill_opt_create_ex(out, cfg, weights, n_weights, GILL_OPT_BF16);
+}
+
+extern "C" int gill_opt_weight_mode(const gill_opt* m) { return m ? m->weight_mode : -1; }
+
+// the decode step's branch, and the host-only query of it
+extern "C" int gill_opt_decode_uses_w8(const gill_opt* m, int B) {
+  return m && m->weight_mode == GILL_OPT_W8 && B >= 1 && B <= W8_MAX_ROWS ? 1 : 0;
+}
+
+extern "C" int gill_w8_max_rows(void) { return W8_MAX_ROWS; }
+
+extern "C" int gill_opt_create_ex(gill_opt** out, const gill_opt_config* cfg, const gill_tensor* weights, int n_weights, int weight_mode) {
   GILL_REQUIRE(out && cfg && weights, "null argument");
+  GILL_REQUIRE(weight_mode == GILL_OPT_BF16 || weight_mode == GILL_OPT_W8, "weight_mode is GILL_OPT_BF16 or GILL_OPT_W8");
   const int D = cfg->hidden_size, F = cfg->ffn_dim, H = cfg->num_heads;
   GILL_REQUIRE(D % 64 == 0 && F % 64 == 0 && H > 0 && D % H == 0, "OPT dims must be multiples of 64");
   const int hd = D / H;
@@ -69,6 +84,7 @@ extern "C" int gill_opt_create(gill_opt** out, const gill_opt_config* cfg, const
   GILL_REQUIRE(cfg->max_batch > 0 && cfg->max_seq > 0 && cfg->max_seq <= cfg->max_positions, "bad workspace sizing");
   gill_opt* m = new gill_opt();
   m->cfg = *cfg;
+  m->weight_mode = weight_mode;
   WeightTable wt(weights, n_weights);
   hipStream_t s = nullptr;
   int rc = 0;
@@ -90,6 +106,11 @@ extern "C" int gill_opt_create(gill_opt** out, const gill_opt_config* cfg, const
   // stream64: the skinny (M = B*T) GEMMs stream their weights; the blocked layout is what the STREAM64 kernel reads
   for (int i = 0; i < cfg->num_layers; ++i)
     if ((rc = tfm_load_layer(wt, m->pool, dec + "layers." + std::to_string(i) + ".", names, D, F, true, &m->layers[i], s))) return fail(rc);
+  // w8: the four matrices of every layer also as e4m3 bytes + power-of-two row scales (the decode step's operands), the bf16 copies
+  // replaced by the dequantised values (every other entry point: the same model on today's kernels)
+  if (weight_mode == GILL_OPT_W8)
+    for (int i = 0; i < cfg->num_layers; ++i)
+      if ((rc = tfm_quantize_layer_w8(m->pool, D, F, &m->layers[i], s))) return fail(rc);
   const size_t R = (size_t)cfg->max_batch * cfg->max_seq;
   if ((rc = m->pool.alloc(&m->h, R * D))) return fail(rc);
   if ((rc = m->tfm.alloc(m->pool, cfg->max_batch, cfg->max_seq, D, F, H, hd, round_up(hd, 32)))) return fail(rc);
@@ -490,15 +511,30 @@ extern "C" int gill_opt_decode_step(gill_opt* m, const void* new_embeds_bf16, co
   const TfmRun run{t, s};
   const TfmLayer* L = m->layers.data();
   if (n > 0) GILL_TRY(layernorm_launch(m->h, 1, L[0].ln1g, L[0].ln1b, t.nbuf, B, D, 1e-5f, s));
+  const bool w8 = gill_opt_decode_uses_w8(m, B) != 0;
+  const int F = t.F;
   for (int i = 0; i < n; ++i) {
     const TfmLayer* next = i + 1 < n ? &L[i + 1] : nullptr;
-    GILL_TRY(run.linear(t.nbuf, B, L[i].wqkv, L[i].blk_qkv, L[i].bqkv, 3 * D, D, nullptr, ACT_NONE, t.q, false));
+    // the four linears on the e4m3 bytes (linear_w8.hip): the wide ones finish in the kernel, the narrow ones through the reducer + LayerNorm
+    auto lin8 = [&](const bf16_t* A, const unsigned char* W8, const float* sc, const float* b, int N, int K, const float* resid, int act, void* out,
+                    bool out_f32, int splitk, const float* g, const float* be, bf16_t* ln_out) -> int {
+      return tfm_linear_w8_launch(A, B, W8, sc, b, N, K, resid, act, out, out_f32, splitk, t.splitk_ws, t.splitk_ws_floats, g, be, ln_out, s);
+    };
+    if (w8) GILL_TRY(lin8(t.nbuf, L[i].qkv8, L[i].sqkv, L[i].bqkv, 3 * D, D, nullptr, ACT_NONE, t.q, false, 1, nullptr, nullptr, nullptr));
+    else GILL_TRY(run.linear(t.nbuf, B, L[i].wqkv, L[i].blk_qkv, L[i].bqkv, 3 * D, D, nullptr, ACT_NONE, t.q, false));
     AttnDecodeArgs a;
     a.q = t.q; a.k = t.q + D; a.v = t.q + 2 * D; a.ld = 3 * D;
     a.K = m->cache[i].k; a.Vt = m->cache[i].vt; a.lens = lens_dev; a.O = t.o; a.ldo = D; a.flags = m->dec_flags;
     a.B = B; a.H = t.H; a.dp = t.dp; a.dpv = t.dpv; a.pitch = m->cache[i].pad;
     a.qscale = 1.4426950408889634f / sqrtf((float)t.dp);
     GILL_TRY(attention_decode_launch(a, s));
+    if (w8) {
+      GILL_TRY(lin8(t.o, L[i].o8, L[i].so, L[i].bo, D, D, m->h, ACT_NONE, m->h, true, 0, L[i].ln2g, L[i].ln2b, t.nbuf));
+      GILL_TRY(lin8(t.nbuf, L[i].w18, L[i].s1, L[i].b1, F, D, nullptr, ACT_RELU, t.ff, false, 1, nullptr, nullptr, nullptr));
+      GILL_TRY(lin8(t.ff, L[i].w28, L[i].s2, L[i].b2, D, F, m->h, ACT_NONE, m->h, true, 0, next ? next->ln1g : nullptr, next ? next->ln1b : nullptr,
+                    next ? t.nbuf : nullptr));
+      continue;
+    }
     GILL_TRY(run.linear(t.o, B, L[i].wo, L[i].blk_o, L[i].bo, D, D, m->h, ACT_NONE, m->h, true, L[i].ln2g, L[i].ln2b, t.nbuf));
     GILL_TRY(run.ffn(m->h, B, L[i], ACT_RELU, next ? next->ln1g : nullptr, next ? next->ln1b : nullptr));
   }

@@ -14,6 +14,10 @@ struct TfmLayer {
   bf16_t* w2 = nullptr; float* b2 = nullptr;
   float *ln1g = nullptr, *ln1b = nullptr, *ln2g = nullptr, *ln2b = nullptr;
   int blk_qkv = 0, blk_o = 0, blk_1 = 0, blk_2 = 0;   // matrix stored 64 x 64-blocked (gemm_stream64_weights: the STREAM64 layout)
+  // the four matrices as e4m3 bytes in linear_w8.hip's order with one power-of-two scale per row (tfm_quantize_layer_w8: the OPT engine's w8
+  // mode; the bf16 matrices above then hold bytes * scale); null for every other engine
+  unsigned char *qkv8 = nullptr, *o8 = nullptr, *w18 = nullptr, *w28 = nullptr;
+  float *sqkv = nullptr, *so = nullptr, *s1 = nullptr, *s2 = nullptr;
 };
 
 // Tensor names under a layer's prefix, each up to and including the separator in front of "weight" / "bias".
@@ -24,6 +28,17 @@ struct TfmNames {
 // stream64: store the matrices gemm_stream64_weights() names in the STREAM64 layout (convert_to_bf16_blk64_launch)
 int tfm_load_layer(const WeightTable& wt, DevPool& pool, const std::string& prefix, const TfmNames& names, int D, int F, bool stream64,
                    TfmLayer* L, hipStream_t s);
+
+// A loaded layer's four matrices -> e4m3 bytes + scales (new members of L), and the bf16 matrices replaced, in their own layouts, by the
+// dequantised values: the quantised model is an exact bf16 model and every bf16 kernel runs on it unchanged.  q | k | v are quantised as the stacked
+// [3D][D] matrix (a row's scale is its own either way).  About 1.5 x the layer's bf16 bytes afterwards.
+int tfm_quantize_layer_w8(DevPool& pool, int D, int F, TfmLayer* L, hipStream_t s);
+// tfm_linear_launch on the e4m3 bytes (M <= W8_MAX_ROWS).  ln_out: an in-place residual GEMM into the fp32 stream (out == resid, fp32, no act, a bias)
+// leaves partials [sk][M][N] and ends in opt_reduce_ln_launch, at any sk; without it the kernel's own epilogue (sk == 1) or its finishing pass.
+// splitk as W8Args::splitk.
+int tfm_linear_w8_launch(const bf16_t* A, int M, const unsigned char* W8, const float* scale, const float* b, int N, int K, const float* resid,
+                         int act, void* out, bool out_f32, int splitk, float* ws, size_t ws_floats, const float* ln_g, const float* ln_b,
+                         bf16_t* ln_out, hipStream_t s);
 
 // Geometry, per-engine switches and workspace of the block (the fp32 stream itself stays with the engine).
 struct Tfm {

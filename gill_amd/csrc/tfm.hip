@@ -126,6 +126,35 @@ int tfm_load_layer(const WeightTable& wt, DevPool& pool, const std::string& pref
   return norm_w(names.ln2, &L->ln2g, &L->ln2b);
 }
 
+int tfm_quantize_layer_w8(DevPool& pool, int D, int F, TfmLayer* L, hipStream_t s) {
+  auto quant = [&](bf16_t* w, int blk, int N, int K, unsigned char** w8, float** sc) -> int {
+    GILL_TRY(pool.alloc(w8, (size_t)N * K, false));
+    GILL_TRY(pool.alloc(sc, (size_t)N, false));
+    GILL_TRY(w8_quant_launch(w, blk, N, K, *w8, *sc, s));
+    return w8_dequant_launch(*w8, *sc, N, K, blk, w, s);
+  };
+  GILL_TRY(quant(L->wqkv, L->blk_qkv, 3 * D, D, &L->qkv8, &L->sqkv));
+  GILL_TRY(quant(L->wo, L->blk_o, D, D, &L->o8, &L->so));
+  GILL_TRY(quant(L->w1, L->blk_1, F, D, &L->w18, &L->s1));
+  return quant(L->w2, L->blk_2, D, F, &L->w28, &L->s2);
+}
+
+int tfm_linear_w8_launch(const bf16_t* A, int M, const unsigned char* W8, const float* scale, const float* b, int N, int K, const float* resid,
+                         int act, void* out, bool out_f32, int splitk, float* ws, size_t ws_floats, const float* ln_g, const float* ln_b,
+                         bf16_t* ln_out, hipStream_t s) {
+  W8Args a;
+  a.A = A; a.M = M; a.N = N; a.K = K; a.W8 = W8; a.scale = scale; a.bias = b; a.resid = resid; a.act = act; a.out_f32 = out_f32 ? 1 : 0; a.C = out;
+  a.splitk = splitk; a.ws = ws; a.ws_floats = ws_floats;
+  if (ln_out) {
+    GILL_REQUIRE(out_f32 && resid == (const float*)out && act == ACT_NONE && b && ln_g && ln_b && N % 4 == 0 && N <= 8192,
+                 "linear w8 + LayerNorm: an in-place fp32 residual launch with a bias, N a multiple of 4, at most 8192");
+    a.partials_only = 1;
+    GILL_TRY(linear_w8_launch(a, s));
+    return opt_reduce_ln_launch(ws, linear_w8_splitk(a), M, N, b, (float*)out, ln_g, ln_b, ln_out, 1e-5f, s);
+  }
+  return linear_w8_launch(a, s);
+}
+
 int Tfm::alloc(DevPool& pool, int max_batch, int max_tok, int D_, int F_, int H_, int dp_, int dpv_, size_t ws_cap_floats) {
   D = D_; F = F_; H = H_; dp = dp_; dpv = dpv_;
   const size_t R = (size_t)max_batch * max_tok;

@@ -61,6 +61,7 @@ _OPT_SHAPES = {  # hidden, layers, heads, ffn  (public OPT configs; 350m is post
   'opt-125m': (768, 12, 12, 3072), 'opt-1.3b': (2048, 24, 32, 8192), 'opt-2.7b': (2560, 32, 32, 10240),
   'opt-6.7b': (4096, 32, 32, 16384), 'opt-13b': (5120, 40, 40, 20480),
 }
+_OPT_WEIGHT_MODES = {'bf16': 0, 'fp8': 1}      # GILL_OPT_BF16, GILL_OPT_W8 (include/gill_amd.h)
 _CLIP_HIDDEN = {'clip-vit-large-patch14': 1024, 'clip-vit-base-patch16': 768, 'clip-vit-base-patch32': 768}
 
 
@@ -165,6 +166,7 @@ class GILLModel(nn.Module):
     self.logit_scale = nn.Parameter(torch.ones([]) * np.log(1 / 0.07))
     self._opt_handle = None
     self._opt_cap = (0, 0)
+    self.opt_weights = 'bf16'     # quantize_lm(): 'fp8' = the weight-only fp8 decoder (gill_opt_create_ex, GILL_OPT_W8)
     # native handles snapshot the weights: a state-dict load into this module (or, recursively, into a parent) drops them
     self.register_load_state_dict_post_hook(lambda module, incompatible_keys: module.refresh_native())
 
@@ -300,10 +302,26 @@ class GILLModel(nn.Module):
     arr, keep = N.make_tensor_table(self.lm.state_dict(), dev)
     h = C.c_void_p()
     with torch.cuda.device(dev):
-      N.check(N.lib().gill_opt_create(C.byref(h), C.byref(cfg), arr, len(keep)))
+      N.check(N.lib().gill_opt_create_ex(C.byref(h), C.byref(cfg), arr, len(keep), _OPT_WEIGHT_MODES[self.opt_weights]))
     del keep
     self._opt_handle, self._opt_cap = h, (cb, ct)
     return h
+
+  def quantize_lm(self, mode: Optional[str] = 'fp8'):
+    """Weight format of the OPT decoder's native handle.  'fp8': weight-only fp8 (OCP e4m3, one power-of-two scale per output row) for the
+    four matrices of every decoder layer; the ragged decode step of generate_batch / generate_for_images_and_texts_batch then reads half the
+    weight bytes.  Every other pass, generate() included, runs the dequantised weights on the bf16 kernels: the same model, no speed-up.
+    The handle holds both copies: about 1.5 x the decoder weights of a bf16 handle.  None or 'bf16': back to bf16.  The handle is rebuilt
+    at the next call."""
+    mode = 'bf16' if mode is None else mode
+    if mode not in _OPT_WEIGHT_MODES:
+      raise ValueError(f"quantize_lm: mode must be one of {sorted(_OPT_WEIGHT_MODES)} or None, got {mode!r}")
+    if mode != self.opt_weights:
+      self.opt_weights = mode
+      if self._opt_handle is not None:
+        N.lib().gill_opt_destroy(self._opt_handle)
+      self._opt_handle, self._opt_cap = None, (0, 0)
+    return self
 
   # ---- reference API -------------------------------------------------------------------------
   def get_visual_embs(self, pixel_values: torch.FloatTensor, mode: str = 'captioning'):
@@ -1479,8 +1497,10 @@ class GILL(nn.Module):
     return ids, lens, {'extra_rows': self._visual_rows(mine)}
 
 
-def load_gill(model_dir: str, load_ret_embs: bool = True, decision_model_fn: str = 'decision_model.pth.tar', ret_index: bool = False) -> GILL:
+def load_gill(model_dir: str, load_ret_embs: bool = True, decision_model_fn: str = 'decision_model.pth.tar', ret_index: bool = False,
+              opt_weights: str = 'bf16') -> GILL:
   """reference: gill/models.py:810-902.  Same files, same errors, same tokenizer surgery, same checkpoint format.
+  opt_weights (not a reference argument): 'fp8' = GILLModel.quantize_lm('fp8'), the weight-only fp8 decoder.
   ret_index (not a reference argument): also build model.ret_index from the raw cc3m rows with the device normalise (GILL.build_retrieval_index);
   emb_matrix is set as without it."""
   model_args_path = os.path.join(model_dir, 'model_args.json')
@@ -1536,6 +1556,7 @@ def load_gill(model_dir: str, load_ret_embs: bool = True, decision_model_fn: str
       assert model_kwargs['share_ret_gen'], 'Model loading only supports share_ret_gen=True for now.'
     model.model.input_embeddings.weight[-model_kwargs['num_tokens']:, :].copy_(img_token_embeddings)
   model.model.refresh_native()   # native handles snapshot the weights: rebuild after the in-place copy
+  model.model.quantize_lm(opt_weights)
   if emb_matrix is not None:     # models.py:895-900: unit rows scaled by exp(logit_scale), in the model's dtype, on its device
     scale = model.model.logit_scale.exp()
     m = torch.as_tensor(emb_matrix).to(device=scale.device, dtype=scale.dtype)

@@ -996,3 +996,62 @@ def lm_head_loss(x: torch.Tensor, w: torch.Tensor, target: torch.Tensor, check: 
   N.check(N.lib().gill_op_lm_head_loss(N.ptr(x), N.ptr(w), N.ptr(target), M, V, D, N.ptr(lse), N.ptr(tgt), N.ptr(rank), N.ptr(summary),
                                        N.current_stream()))
   return lse, tgt, rank, summary
+
+
+# ---- the quantised decoder's format and linear (csrc/linear_w8.hip; tests/test_w8_ops_gpu.py).  Bytes travel as uint8 in the kernel's order.
+def w8_max_rows() -> int:
+  """W8_MAX_ROWS: the most activation rows linear_w8 takes."""
+  return int(N.lib().gill_w8_max_rows())
+
+
+def w8_quant(w: torch.Tensor):
+  """bf16 (N,K) -> (w8 (N*K) uint8 in the kernel's order, scale (N) fp32 powers of two, guard_ok) (gill_op_w8_quant)."""
+  w = _bf(w)
+  Nn, K = w.shape
+  wbuf, w8 = _guarded((Nn * K,), torch.uint8, w.device)
+  sbuf, sc = _guarded((Nn,), torch.float32, w.device)
+  N.check(N.lib().gill_op_w8_quant(N.ptr(w), Nn, K, N.ptr(wbuf), N.ptr(sbuf), N.current_stream()))
+  return w8, sc, _guard_ok(wbuf) and _guard_ok(sbuf)
+
+
+def w8_dequant(w8: torch.Tensor, scale: torch.Tensor, Nn: int, K: int, blk64: bool = False):
+  """The bytes of w8_quant -> (bf16 (N,K) row-major, or with blk64 the 64 x 64-blocked order as a flat (N*K) tensor, guard_ok)."""
+  w8 = _u8(w8)
+  assert w8.numel() == Nn * K and scale.dtype == torch.float32 and scale.numel() == Nn
+  buf, out = _guarded((Nn * K,) if blk64 else (Nn, K), torch.bfloat16, w8.device)
+  N.check(N.lib().gill_op_w8_dequant(N.ptr(w8), N.ptr(scale.contiguous()), Nn, K, int(blk64), N.ptr(buf), N.current_stream()))
+  return out, _guard_ok(buf)
+
+
+def linear_w8(a: torch.Tensor, w8: torch.Tensor, scale: torch.Tensor, bias: Optional[torch.Tensor] = None, resid: Optional[torch.Tensor] = None,
+              act: str = "none", out_f32: bool = False, splitk: int = 0, ln: Optional[tuple] = None, out_rows: Optional[int] = None,
+              canary: float = 0.0):
+  """act(scale * (a @ bf16(w8).T) + bias) (+ resid) (gill_op_linear_w8): a (M,K) bf16, w8 / scale from w8_quant, bias (N) fp32, resid (M,N) fp32
+  (added in place in a copy: the result is the updated residual).  ln = (gamma, beta): the split-partials + reducer + LayerNorm finish
+  (needs bias and resid) -> (new resid fp32, LayerNorm bf16, guard_ok).  Otherwise -> (out (M,N), guard_ok).  out_rows > M: the output buffer
+  has out_rows rows, filled with `canary` beforehand, and all of them are returned."""
+  a, w8 = _bf(a), _u8(w8)
+  M, K = a.shape
+  Nn = scale.numel()
+  assert w8.numel() == Nn * K and scale.dtype == torch.float32
+  R = M if out_rows is None else int(out_rows)
+  f = lambda x: None if x is None else x.float().contiguous()   # noqa: E731
+  bias = f(bias)
+  odt = torch.float32 if (out_f32 or resid is not None) else torch.bfloat16
+  buf, out = _guarded((R, Nn), odt, a.device)
+  if out_rows is not None:
+    out.fill_(canary)
+  rp = None
+  if resid is not None:
+    assert resid.dtype == torch.float32 and tuple(resid.shape) == (M, Nn)
+    out[:M].copy_(resid)
+    rp = N.ptr(buf)
+  if ln is not None:
+    g, b = f(ln[0]), f(ln[1])
+    nbuf, nb = _guarded((M, Nn), torch.bfloat16, a.device)
+    N.check(N.lib().gill_op_linear_w8(N.ptr(a), N.ptr(w8), N.ptr(scale.contiguous()), N.ptr(bias), rp, N.ptr(buf), M, Nn, K, ACT[act], 1, int(splitk),
+                                      N.ptr(g), N.ptr(b), N.ptr(nbuf), N.current_stream()))
+    return out, nb, _guard_ok(buf) and _guard_ok(nbuf)
+  N.check(N.lib().gill_op_linear_w8(N.ptr(a), N.ptr(w8), N.ptr(scale.contiguous()), N.ptr(bias), rp, N.ptr(buf), M, Nn, K, ACT[act],
+                                    int(odt == torch.float32), int(splitk), None, None, None, N.current_stream()))
+  return out, _guard_ok(buf)

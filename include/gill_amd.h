@@ -59,6 +59,41 @@ typedef struct {
 int gill_opt_create(gill_opt** out, const gill_opt_config* cfg, const gill_tensor* weights, int n_weights);
 void gill_opt_destroy(gill_opt* h);
 
+/* Quantised decoder ("w8"): gill_opt_create with a weight mode.  GILL_OPT_BF16 is gill_opt_create itself.  GILL_OPT_W8 is weight-only
+ * fp8: per decoder layer the four matrices [q|k|v] stacked, out_proj, fc1 and fc2 (embeddings, positions, lm_head, biases and LayerNorms
+ * are untouched) are quantised from their bf16-rounded values, per output row n:
+ *   e[n] = ceil(log2(max_k |w[n][k]| / 448)), s[n] = 2^e[n] (an all-zero row: s = 1; e is kept >= -100),
+ *   w8[n][k] = e4m3fn(w[n][k] / s[n]), OCP e4m3, round to nearest even; max|w / s| lies in (224, 448]: nothing saturates.
+ * The quantised model is the model whose weights are w8[n][k] * s[n].  Every e4m3 code times a power of two is a bf16 number, so it is an
+ * exact bf16 model, and the handle keeps BOTH copies of those matrices: the dequantised bf16 values, in the layouts of a bf16 handle, and
+ * the fp8 bytes + fp32 scales: about 1.5 x the decoder weights of a bf16 handle in memory (OPT-6.7b: about 19 GB instead of 12.9).
+ *   gill_opt_decode_step at B <= gill_w8_max_rows() runs its four linears per layer on the fp8 bytes (csrc/linear_w8.hip: bf16
+ *     activations, weights converted to bf16 in registers, fp32 accumulation; half the weight bytes per step).  This is the one entry that
+ *     speeds up: the ragged loop of generate_batch.
+ *   gill_opt_decode_step at larger B and every other entry (forward, forward_cached, img_hidden*, prefill_ids, forward_loss, the logits)
+ *     run the kernels of a bf16 handle on the dequantised matrices: the same model, no speed-up.
+ * gill_opt_weight_mode: the handle's mode.  gill_opt_decode_uses_w8: host-only, 1 when gill_opt_decode_step at this B takes the fp8 path
+ * (the function the engine itself branches on), else 0. */
+enum { GILL_OPT_BF16 = 0, GILL_OPT_W8 = 1 };
+int gill_opt_create_ex(gill_opt** out, const gill_opt_config* cfg, const gill_tensor* weights, int n_weights, int weight_mode);
+int gill_opt_weight_mode(const gill_opt* h);
+int gill_opt_decode_uses_w8(const gill_opt* h, int B);
+int gill_w8_max_rows(void);     /* W8_MAX_ROWS: the most activation rows of one fp8 linear (16) */
+
+/* Operator entries of the w8 format (tests).  Bytes are in the kernel's order [N / 16][K / 64][64][16]: byte (n, k) at
+ * ((n / 16) * (K / 64) + k / 64) * 1024 + ((k % 64) / 16 * 16 + n % 16) * 16 + k % 16.  N and K multiples of 64.
+ *   gill_op_w8_quant:   w (N,K) bf16 row-major -> w8 (N*K bytes), scale (N) fp32.
+ *   gill_op_w8_dequant: -> out (N,K) bf16, row-major (blk64 = 0) or 64 x 64-blocked [N/64][K/64][64][64] (blk64 = 1); w8 * s, exact.
+ *   gill_op_linear_w8:  y = act(s[n] * sum_k A[m][k] * w8[n][k] + bias[n]) (+ resid_f32[m][n]); A (M,K) bf16, 1 <= M <= gill_w8_max_rows();
+ *     act 0 = none, 1 = ReLU; out (M,N) bf16 or fp32 (out_f32); resid fp32, may be out itself.  splitk: 0 = the launcher's own rule (a function
+ *     of N and K alone), 1 = unsplit, k > 1 = k slices of K.  With ln_out_bf16 (then out is fp32, resid == out, act 0, bias set): fp32 partials +
+ *     the engine's reducer: out = resid + sum + bias, ln_out = LayerNorm(out; ln_g, ln_b, eps 1e-5) in bf16.  Row m's result does not depend on M
+ *     or on the other rows.  Bad arguments are reported before anything is launched. */
+int gill_op_w8_quant(const void* w_bf16, int N, int K, void* w8, float* scale, void* stream);
+int gill_op_w8_dequant(const void* w8, const float* scale, int N, int K, int blk64, void* out_bf16, void* stream);
+int gill_op_linear_w8(const void* A_bf16, const void* w8, const float* scale, const float* bias, const float* resid_f32, void* out, int M, int N,
+                      int K, int act, int out_f32, int splitk, const float* ln_g, const float* ln_b, void* ln_out_bf16, void* stream);
+
 /* input_embeddings(ids): models.py:180 / :620.  ids (B*T) int64 -> out (B*T, D) bf16. */
 int gill_opt_embed(gill_opt* h, const int64_t* ids, int n, void* out_bf16, void* stream);
 
