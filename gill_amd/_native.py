@@ -161,7 +161,7 @@ SYMBOLS: Dict[str, Tuple[object, List[object]]] = {
   "gill_op_groupnorm": (_i, [_vp, _i, _vp, _i, _i, _i, _i, _vp, _vp, _f, _i, _vp, _vp]),
   "gill_op_conv3x3_gn_stats": (_i, [_vp, _i, _vp, _i, _vp, _vp, _vp, _vp, _vp, _i, _vp, _i, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i,
                                     C.POINTER(C.c_int), C.POINTER(C.c_int), _vp]),
-  "gill_op_gemm_gn_stats": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, C.POINTER(C.c_int), C.POINTER(C.c_int), _vp]),
+  "gill_op_gemm_gn_stats": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, C.POINTER(C.c_int), C.POINTER(C.c_int), _vp]),
   "gill_op_groupnorm_from_stats": (_i, [_vp, _i, _vp, _i, _i, _i, _i, _vp, _vp, _f, _i, _vp, _i, _i, _vp, _i, _i, _vp, _vp, _f, _vp]),
   "gill_op_conv3x3_gn": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _f, _i, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _vp]),
   "gill_op_conv3x3_shortcut": (_i, [_vp, _i, _vp, _i, _vp, _vp, _vp, _i, _vp, _i, _vp, _vp, _i, _i, _i, _i, _i, _vp]),
@@ -191,6 +191,7 @@ SYMBOLS: Dict[str, Tuple[object, List[object]]] = {
   "gill_op_lm_head_loss": (_i, [_vp, _vp, _vp, _i, _i, _i, _vp, _vp, _vp, _vp, _vp]),
   "gill_lm_loss_geometry": (_i, [_i, _i, _i, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int)]),
   "gill_gemm_plan": (_i, [_vp, _i, _i, _i, _i, _vp]),
+  "gill_gemm_plan_log": (_i, [_vp, _i, C.POINTER(C.c_int)]),
   "gill_unet_xf_plan": (_i, [_vp, _i, _i, _i, _i, _vp]),
   "gill_gemm_query": (_i, [_vp, _i, _i, _i, _i, _vp]),
   "gill_opt_forward_loss": (_i, [_vp, _vp, C.POINTER(C.c_int32), _i, _i, _i, _vp, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),

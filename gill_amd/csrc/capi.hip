@@ -35,6 +35,7 @@ static float* op_splitk_ws(size_t floats) {
 // splitk: 0 = the launcher's heuristic, n > 1 = forced.  splitk < 0: FORCE THE GENERAL ROW-MAJOR TILES — never the 64 x 64-blocked
 // blocked copy that weight-streaming shapes (N * K >= 4 Mi; the STREAM64 tile up to 256 rows, the general tiles on the blocked layout above) otherwise take — with the heuristic split (-1) or -splitk ways (< -1), so that
 // the operator tests can pin both paths on the same shape (the UNet and CLIP engines run such shapes on the general tiles).
+// out_f32: bit 0 = fp32 output, bit 1 = the residual is fp32 (GemmArgs::resid_f32, as the OPT / CLIP engines pass their residual stream).
 extern "C" int gill_op_gemm(const void* A, const void* W, const float* bias, const void* resid_bf16, void* C, int M, int N,
                             int K, float alpha, int act, int out_f32, int splitk, void* stream) {
   hipStream_t s = (hipStream_t)stream;
@@ -43,9 +44,9 @@ extern "C" int gill_op_gemm(const void* A, const void* W, const float* bias, con
   g.A = (const bf16_t*)A; g.lda = K;
   g.W = (const bf16_t*)W;
   g.alpha = alpha; g.bias = bias;
-  g.resid = resid_bf16; g.ldr = N; g.resid_f32 = 0;
+  g.resid = resid_bf16; g.ldr = N; g.resid_f32 = (out_f32 & 2) ? 1 : 0;
   g.act = act;
-  g.out_mode = out_f32 ? OUT_F32 : OUT_BF16;
+  g.out_mode = (out_f32 & 1) ? OUT_F32 : OUT_BF16;
   g.C = C; g.ldc = N;
   const bool row_major = splitk < 0;
   if (row_major) splitk = (splitk == -1) ? 0 : -splitk;
@@ -462,15 +463,15 @@ extern "C" int gill_op_conv3x3_gn_stats(const void* x1, int C1, const void* x2, 
 }
 
 extern "C" int gill_op_gemm_gn_stats(const void* A, const void* W, const float* bias, const void* resid, void* C, float* gn_stats, int bin, int M, int N,
-                                     int K, int rows_per_batch, int splitk, int* slab_rows, int* nslab, void* stream) {
+                                     int K, int rows_per_batch, int splitk, int act, int* slab_rows, int* nslab, void* stream) {
   hipStream_t s = (hipStream_t)stream;
-  GILL_REQUIRE(A && W && C && rows_per_batch > 0 && M % rows_per_batch == 0, "bad argument");
+  GILL_REQUIRE(A && W && C && rows_per_batch > 0 && M % rows_per_batch == 0 && act >= ACT_NONE && act <= ACT_SILU, "bad argument");
   DevBuf ws;
   GemmArgs g;
   g.M = M; g.N = N; g.K = K; g.K1 = K;
   g.A = (const bf16_t*)A; g.lda = K;
   g.W = (const bf16_t*)W; g.bias = bias;
-  g.resid = resid; g.ldr = N;
+  g.resid = resid; g.ldr = N; g.act = act;
   g.C = C; g.ldc = N;
   return op_gn_producer_launch(g, rows_per_batch, gn_stats, bin, splitk, slab_rows, nslab, ws, s);
 }
@@ -675,6 +676,18 @@ extern "C" int gill_gemm_plan(const int32_t* cases, int n, int pp, int coop, int
     int32_t* r = rows + (size_t)i * GILL_GEMM_PLAN_ROW_INTS;
     r[0] = gemm_plan(a, env, &p);      // (a refusal leaves the zero plan)
     const int* v = reinterpret_cast<const int*>(&p);      // (GemmPlan is GEMM_PLAN_INTS ints, in the row's order)
+    for (int k = 0; k < GEMM_PLAN_INTS; ++k) r[1 + k] = v[k];
+  }
+  return 0;
+}
+extern "C" int gill_gemm_plan_log(int32_t* rows, int cap, int* launched) {
+  GILL_REQUIRE(cap >= 0 && launched != nullptr && (cap == 0 || rows != nullptr), "gemm_plan_log: null output or negative capacity");
+  GemmPlan plans[GEMM_PLAN_LOG_CAP];
+  const int n = gemm_plan_log_take(plans, cap, launched);
+  for (int i = 0; i < n; ++i) {
+    int32_t* r = rows + (size_t)i * GILL_GEMM_PLAN_ROW_INTS;
+    r[0] = 0;
+    const int* v = reinterpret_cast<const int*>(&plans[i]);
     for (int k = 0; k < GEMM_PLAN_INTS; ++k) r[1 + k] = v[k];
   }
   return 0;

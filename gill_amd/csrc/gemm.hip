@@ -1228,6 +1228,10 @@ static int gemm_dispatch(const GemmPlan& p, const GemmDev& d, dim3 grid, hipStre
   return -2;
 }
 
+// the record behind gemm_plan_log_take() (gemm_plan.h): a ring of the most recent dispatched plans, per thread
+static thread_local GemmPlan g_plan_log[GEMM_PLAN_LOG_CAP];
+static thread_local unsigned g_plan_log_launched = 0;
+
 int gemm_launch(const GemmArgs& a, hipStream_t s) {
   GemmPlan p;
   GILL_TRY(gemm_plan(a, gemm_env_default(), &p));
@@ -1244,6 +1248,18 @@ int gemm_launch(const GemmArgs& a, hipStream_t s) {
   d.nwv = p.nwv; d.mi = p.mi; d.kt = p.kt;
   d.n_major = p.n_major; d.tiles_m = p.tiles_m; d.xb_m = p.xb_m; d.xb_n = p.xb_n;
   GILL_TRY(gemm_dispatch(p, d, dim3(p.grid_x, p.grid_y, p.grid_z), s));
+  g_plan_log[g_plan_log_launched++ % GEMM_PLAN_LOG_CAP] = p;
   if (p.reduce) return gemm_splitk_reduce_launch(red, s);
   return 0;
+}
+
+int gemm_plan_log_take(GemmPlan* out, int cap, int* launched) {
+  const unsigned total = g_plan_log_launched;
+  unsigned n = total < GEMM_PLAN_LOG_CAP ? total : GEMM_PLAN_LOG_CAP;
+  if (cap < 0) cap = 0;
+  if (n > (unsigned)cap) n = (unsigned)cap;
+  for (unsigned i = 0; i < n; ++i) out[i] = g_plan_log[(total - n + i) % GEMM_PLAN_LOG_CAP];
+  *launched = (int)total;
+  g_plan_log_launched = 0;
+  return (int)n;
 }

@@ -37,6 +37,13 @@ void gemm_plan_fill(const GemmArgs& a, const GemmEnv& env, GemmPlan* p);
 // gemm_launch()'s argument checks, then the plan.  A refused launch (non-zero return, gill_last_error) has no plan.
 int gemm_plan(const GemmArgs& a, const GemmEnv& env, GemmPlan* p);
 
+// What gemm_launch() ran: the plans of this thread's GEMM_PLAN_LOG_CAP most recent successful dispatches and the launches since the record was last
+// read (gemm.hip; host only, one struct copy per launch).  gemm_plan_log_take() writes the most recent min(cap, GEMM_PLAN_LOG_CAP, launched) plans,
+// oldest first, returns how many it wrote, sets *launched and clears the record.  For tests (gill_gemm_plan_log): an operator entry picks split
+// factors, blocked weights and per-sample operands itself, so only the launcher knows which instantiation an operator call executed.
+#define GEMM_PLAN_LOG_CAP 32
+int gemm_plan_log_take(GemmPlan* out, int cap, int* launched);
+
 // the engines' pre-launch choices under an explicit environment (ops.h declares the process-wide forms)
 int gemm_pick_splitk_env(const GemmEnv& env, int M, int N, int K, int act, bool plain, bool generic);
 int gemm_pick_splitk_blk64_env(const GemmEnv& env, int M, int N, int K);

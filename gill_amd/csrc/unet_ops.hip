@@ -308,11 +308,14 @@ extern "C" int gill_op_ln_gemm(int mode, const void* T, const float* planes, int
                                int splitk, void* stream) {
   hipStream_t s = (hipStream_t)stream;
   GILL_REQUIRE(mode == 0 || mode == 1, "ln_gemm: mode must be 0 (GEGLU) or 1 (QKV)");
-  GILL_REQUIRE(T && planes && ln_g && ln_b && W && M > 0 && C > 0 && P >= 1, "ln_gemm: null argument");
+  // no_ln (mode 1 only): the head-major scatter without a folded LayerNorm, as the OPT / CLIP engines' QKV GEMM runs — on a 64 x 64-blocked copy of
+  // the padded matrix where the engines block it (gemm_stream64_weights): the one way an operator call reaches the STREAM64 tile's scatter epilogue
+  const bool no_ln = mode == 1 && !planes && !ln_g && !ln_b;
+  GILL_REQUIRE(T && W && M > 0 && C > 0 && (no_ln || (planes && ln_g && ln_b && P >= 1)), "ln_gemm: null argument");
   GILL_REQUIRE(ln_rows >= 0 && ln_rows <= M && (ln_rows == 0 || 2 * ln_rows >= M), "ln_gemm: ln_rows must cover at least half the rows");
-  DevBuf idx, wf, cs, cb, ws;
+  DevBuf idx, wf, cs, cb, ws, wblk;
   GemmArgs g;
-  const XfLnRows ln = {planes, P, ln_rows};
+  const XfLnRows ln = {planes, no_ln ? 1 : P, ln_rows};
   if (mode == 0) {
     GILL_REQUIRE(out && b && inner > 0 && inner % 64 == 0, "ln_gemm (GEGLU): output / bias missing, or inner not a multiple of 64");
     const int N = 2 * inner;
@@ -332,7 +335,14 @@ extern "C" int gill_op_ln_gemm(int mode, const void* T, const float* planes, int
     HeadRows seg[3];
     for (int sg = 0; sg < nseg; ++sg) seg[sg] = HeadRows{(const bf16_t*)W + (size_t)sg * C * C, 0};
     GILL_TRY(xf_qkv_weights(seg, nseg, b, heads, d, dp, C, ln_g, ln_b, (bf16_t*)wf.p, (float*)cs.p, (float*)cb.p, nullptr, s));
-    g = xf_qkv_args((const bf16_t*)T, M, C, ln, (const bf16_t*)wf.p, (const float*)cs.p, (const float*)cb.p, nseg, hd, ntok, (bf16_t*)q, (bf16_t*)k, (bf16_t*)vt);
+    g = xf_qkv_args((const bf16_t*)T, M, C, ln, (const bf16_t*)wf.p, no_ln ? nullptr : (const float*)cs.p, (const float*)cb.p, nseg, hd, ntok, (bf16_t*)q,
+                    (bf16_t*)k, (bf16_t*)vt);
+    if (no_ln && gemm_stream64_weights(N, C)) {
+      GILL_TRY(wblk.alloc(sizeof(bf16_t) * (size_t)N * C));
+      GILL_TRY(convert_to_bf16_blk64_launch(wf.p, GILL_DTYPE_BF16, N, C, (bf16_t*)wblk.p, s));
+      g.W = (const bf16_t*)wblk.p; g.w_blk64 = 1;
+      if (splitk <= 0) splitk = gemm_pick_splitk_blk64(M, N, C);
+    }
   }
   GILL_TRY(op_ln_splitk(g, splitk, ws));
   for (int r = 0, rep = op_repeat(); r < rep; ++r) GILL_TRY(gemm_launch(g, s));

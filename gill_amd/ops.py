@@ -21,8 +21,9 @@ def _bf(t: torch.Tensor) -> torch.Tensor:
 
 
 def gemm(a: torch.Tensor, w: torch.Tensor, bias: Optional[torch.Tensor] = None, resid: Optional[torch.Tensor] = None,
-         alpha: float = 1.0, act: str = "none", out_f32: bool = False, splitk: int = 0, row_major: bool = False) -> torch.Tensor:
-  """act(alpha * a @ w.T + bias + resid); a (M,K) bf16, w (N,K) bf16, bias (N) fp32, resid (M,N) bf16.
+         alpha: float = 1.0, act: str = "none", out_f32: bool = False, splitk: int = 0, row_major: bool = False, guarded: bool = False):
+  """act(alpha * a @ w.T + bias + resid); a (M,K) bf16, w (N,K) bf16, bias (N) fp32, resid (M,N) bf16 or fp32 (the OPT / CLIP residual stream).
+  guarded: the output lives in a _guarded() buffer (NaN-prefilled, GUARD_WORDS sentinels behind it) and (out, guard_ok) is returned.
   row_major: keep weight-streaming shapes (N * K >= 4 Mi) on row-major weights instead of the 64 x 64-blocked copy (STREAM64 tile up to 256 rows, general
   tiles on the blocked layout above)."""
   if row_major:
@@ -30,14 +31,16 @@ def gemm(a: torch.Tensor, w: torch.Tensor, bias: Optional[torch.Tensor] = None, 
   a, w = _bf(a), _bf(w)
   M, K = a.shape
   Nn = w.shape[0]
-  out = torch.empty((M, Nn), device=a.device, dtype=torch.float32 if out_f32 else torch.bfloat16)
+  buf, out = _out_buffer((M, Nn), torch.float32 if out_f32 else torch.bfloat16, a.device, guarded)
   if bias is not None:
     bias = bias.float().contiguous()
+  resid_f32 = resid is not None and resid.dtype == torch.float32
   if resid is not None:
-    resid = _bf(resid)
+    resid = resid.contiguous() if resid_f32 else _bf(resid)
+    assert resid.is_cuda and tuple(resid.shape) == (M, Nn)
   N.check(N.lib().gill_op_gemm(N.ptr(a), N.ptr(w), N.ptr(bias), N.ptr(resid), N.ptr(out), M, Nn, K, alpha, ACT[act],
-                               int(out_f32), splitk, N.current_stream()))
-  return out
+                               int(out_f32) | (2 if resid_f32 else 0), splitk, N.current_stream()))
+  return (out, _guard_ok(buf)) if guarded else out
 
 
 def geglu_fp8(t: torch.Tensor, ln_g: torch.Tensor, ln_b: torch.Tensor, w: torch.Tensor, bias: torch.Tensor) -> torch.Tensor:
@@ -53,22 +56,22 @@ def geglu_fp8(t: torch.Tensor, ln_g: torch.Tensor, ln_b: torch.Tensor, w: torch.
   return out
 
 
-def geglu(a: torch.Tensor, w: torch.Tensor, bias: Optional[torch.Tensor]) -> torch.Tensor:
-  """diffusers GEGLU: h, g = (a @ w.T + bias).chunk(2, -1); h * gelu(g)."""
+def geglu(a: torch.Tensor, w: torch.Tensor, bias: Optional[torch.Tensor], guarded: bool = False):
+  """diffusers GEGLU: h, g = (a @ w.T + bias).chunk(2, -1); h * gelu(g).  guarded: as in gemm()."""
   a, w = _bf(a), _bf(w)
   M, K = a.shape
   inner = w.shape[0] // 2
-  out = torch.empty((M, inner), device=a.device, dtype=torch.bfloat16)
+  buf, out = _out_buffer((M, inner), torch.bfloat16, a.device, guarded)
   if bias is not None:
     bias = bias.float().contiguous()
   N.check(N.lib().gill_op_geglu(N.ptr(a), N.ptr(w), N.ptr(bias), N.ptr(out), M, inner, K, N.current_stream()))
-  return out
+  return (out, _guard_ok(buf)) if guarded else out
 
 
 def conv3x3(x1: torch.Tensor, w_oihw: torch.Tensor, bias: Optional[torch.Tensor] = None, x2: Optional[torch.Tensor] = None,
             rowvec: Optional[torch.Tensor] = None, resid: Optional[torch.Tensor] = None, stride: int = 1,
-            upsample: bool = False, splitk: int = 0, pad_shift: Optional[int] = None) -> torch.Tensor:
-  """3x3 / pad 1 conv over NHWC bf16 x1 (B,H,W,C1) [channel-concat x2], weights OIHW fp32 -> NHWC bf16.
+            upsample: bool = False, splitk: int = 0, pad_shift: Optional[int] = None, guarded: bool = False):
+  """3x3 / pad 1 conv over NHWC bf16 x1 (B,H,W,C1) [channel-concat x2], weights OIHW fp32 -> NHWC bf16.  guarded: as in gemm().
   pad_shift (None: gill_op_conv3x3; 0 | 1: gill_op_conv3x3_ex): 1 with stride 2 is F.pad(x, (0, 1, 0, 1)) + conv(stride 2, pad 0)."""
   x1 = _bf(x1)
   B, IH, IW, C1 = x1.shape
@@ -85,7 +88,7 @@ def conv3x3(x1: torch.Tensor, w_oihw: torch.Tensor, bias: Optional[torch.Tensor]
     OH, OW = (IH + 2 - 3) // stride + 1, (IW + 2 - 3) // stride + 1
   if pad_shift:
     OH, OW = IH // 2, IW // 2
-  y = torch.empty((B, OH, OW, Cout), device=x1.device, dtype=torch.bfloat16)
+  buf, y = _out_buffer((B, OH, OW, Cout), torch.bfloat16, x1.device, guarded)
   if bias is not None:
     bias = bias.float().contiguous()
   if rowvec is not None:
@@ -95,13 +98,13 @@ def conv3x3(x1: torch.Tensor, w_oihw: torch.Tensor, bias: Optional[torch.Tensor]
   if pad_shift is not None:
     N.check(N.lib().gill_op_conv3x3_ex(N.ptr(x1), C1, N.ptr(x2), C2, N.ptr(w), N.ptr(bias), N.ptr(rowvec), N.ptr(resid),
                                        N.ptr(y), B, IH, IW, Cout, stride, int(upsample), int(pad_shift), splitk, N.current_stream()))
-    return y
+    return (y, _guard_ok(buf)) if guarded else y
   N.check(N.lib().gill_op_conv3x3(N.ptr(x1), C1, N.ptr(x2), C2, N.ptr(w), N.ptr(bias), N.ptr(rowvec), N.ptr(resid),
                                   N.ptr(y), B, IH, IW, Cout, stride, int(upsample), splitk, N.current_stream()))
-  return y
+  return (y, _guard_ok(buf)) if guarded else y
 
 
-def conv3x3_ex(x1: torch.Tensor, w_oihw: torch.Tensor, pad_shift: int, **kw) -> torch.Tensor:
+def conv3x3_ex(x1: torch.Tensor, w_oihw: torch.Tensor, pad_shift: int, **kw):
   """gill_op_conv3x3_ex: conv3x3 with the gather's origin shift stated."""
   return conv3x3(x1, w_oihw, pad_shift=int(pad_shift), **kw)
 
@@ -129,8 +132,9 @@ def conv3x3_gn(x: torch.Tensor, w_oihw: torch.Tensor, bias: Optional[torch.Tenso
 
 
 def conv3x3_shortcut(x1: torch.Tensor, w_oihw: torch.Tensor, xs1: torch.Tensor, w_sc: torch.Tensor, bias: Optional[torch.Tensor] = None,
-                     x2: Optional[torch.Tensor] = None, xs2: Optional[torch.Tensor] = None, splitk: int = 0) -> torch.Tensor:
-  """conv3x3(x1 ++ x2, w_oihw) + bias + conv1x1(xs1 ++ xs2, w_sc) as one implicit GEMM (ResnetBlock2D conv2 + conv_shortcut)."""
+                     x2: Optional[torch.Tensor] = None, xs2: Optional[torch.Tensor] = None, splitk: int = 0, guarded: bool = False):
+  """conv3x3(x1 ++ x2, w_oihw) + bias + conv1x1(xs1 ++ xs2, w_sc) as one implicit GEMM (ResnetBlock2D conv2 + conv_shortcut).
+  guarded: as in gemm()."""
   x1, xs1 = _bf(x1), _bf(xs1)
   B, IH, IW, C1 = x1.shape
   C2 = CS2 = 0
@@ -142,12 +146,12 @@ def conv3x3_shortcut(x1: torch.Tensor, w_oihw: torch.Tensor, xs1: torch.Tensor, 
   w, wsc = w_oihw.float().contiguous(), w_sc.float().contiguous()
   Cout = w.shape[0]
   assert w.shape[1] == C1 + C2 and tuple(wsc.shape) == (Cout, CS1 + CS2)
-  y = torch.empty((B, IH, IW, Cout), device=x1.device, dtype=torch.bfloat16)
+  buf, y = _out_buffer((B, IH, IW, Cout), torch.bfloat16, x1.device, guarded)
   if bias is not None:
     bias = bias.float().contiguous()
   N.check(N.lib().gill_op_conv3x3_shortcut(N.ptr(x1), C1, N.ptr(x2), C2, N.ptr(w), N.ptr(bias), N.ptr(xs1), CS1, N.ptr(xs2), CS2,
                                            N.ptr(wsc), N.ptr(y), B, IH, IW, Cout, splitk, N.current_stream()))
-  return y
+  return (y, _guard_ok(buf)) if guarded else y
 
 
 def attention(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, heads: int, scale: Optional[float] = None,
@@ -247,8 +251,8 @@ def conv3x3_gn_stats(x1: torch.Tensor, w_oihw: torch.Tensor, bin: int, bias: Opt
 
 
 def gemm_gn_stats(a: torch.Tensor, w: torch.Tensor, bin: int, rows_per_batch: int, bias: Optional[torch.Tensor] = None,
-                  resid: Optional[torch.Tensor] = None, splitk: int = 1):
-  """a (M,K) @ w (N,K).T + bias + resid launched with fused GroupNorm statistics (gill_op_gemm_gn_stats): the VAE decoder's conv_in (im2col,
+                  resid: Optional[torch.Tensor] = None, splitk: int = 1, act: str = "none"):
+  """act(a (M,K) @ w (N,K).T + bias + resid) launched with fused GroupNorm statistics (gill_op_gemm_gn_stats): the VAE decoder's conv_in (im2col,
   K = 64) and attention to_out GEMMs.  Returns as conv3x3_gn_stats, y (M,N)."""
   a, w = _bf(a), _bf(w)
   M, K = a.shape
@@ -259,7 +263,7 @@ def gemm_gn_stats(a: torch.Tensor, w: torch.Tensor, bin: int, rows_per_batch: in
   stats = _gn_stats_buffer(M // rows_per_batch, rows_per_batch, Nn // bin, a.device)
   rows, nslab = ctypes.c_int(0), ctypes.c_int(0)
   N.check(N.lib().gill_op_gemm_gn_stats(N.ptr(a), N.ptr(w), N.ptr(bias), N.ptr(resid), N.ptr(y), N.ptr(stats), bin, M, Nn, K, rows_per_batch,
-                                        splitk, ctypes.byref(rows), ctypes.byref(nslab), N.current_stream()))
+                                        splitk, ACT[act], ctypes.byref(rows), ctypes.byref(nslab), N.current_stream()))
   return y, stats, rows.value, nslab.value
 
 
@@ -437,27 +441,34 @@ def ln_gemm_geglu(t: torch.Tensor, planes: torch.Tensor, ln_g: torch.Tensor, ln_
   return out
 
 
-def ln_gemm_qkv(t: torch.Tensor, planes: torch.Tensor, ln_g: torch.Tensor, ln_b: torch.Tensor, w: torch.Tensor, bias: Optional[torch.Tensor],
-                heads: int, ntok: int, ln_rows: int = 0, splitk: int = 1):
+def ln_gemm_qkv(t: torch.Tensor, planes: Optional[torch.Tensor], ln_g: Optional[torch.Tensor], ln_b: Optional[torch.Tensor], w: torch.Tensor,
+                bias: Optional[torch.Tensor], heads: int, ntok: int, ln_rows: int = 0, splitk: int = 1):
   """to_q [| to_k | to_v] of LayerNorm(t) scattered head-major, as UNet levels 1-3 run it (gill_op_ln_gemm, mode 1): t (B * ntok, C) bf16, planes as
   in ln_gemm_geglu, w (nseg C, C) bf16 with nseg = 1 | 3, bias (nseg C) or None.  Returns (q, k, vt): q, k (B, heads, ntok_pad, dp) with q pre-scaled
-  by log2(e) / sqrt(d), vt (B, heads, dpv, ntok_pad) with row dp = 1 where dpv > dp; k, vt None when nseg == 1.  All NaN-prefilled."""
+  by log2(e) / sqrt(d), vt (B, heads, dpv, ntok_pad) with row dp = 1 where dpv > dp; k, vt None when nseg == 1.  All NaN-prefilled.
+  planes, ln_g and ln_b all None: the same scatter of t itself, no LayerNorm (the OPT / CLIP engines' QKV GEMM; weight-streaming shapes run on
+  the 64 x 64-blocked copy of w as in gemm())."""
   t, w = _bf(t), _bf(w)
   M, Cc = t.shape
   nseg = w.shape[0] // Cc
   d = Cc // heads
   dp = padded_head_dim(d)
   dpv, ntok_pad, B = (dp + 31) // 32 * 32, (ntok + 31) // 32 * 32, M // ntok
-  planes = planes.float().contiguous()
-  assert planes.is_cuda and planes.shape[1:] == (ln_rows or M, 2)
   f = lambda x: x.float().contiguous()   # noqa: E731
-  ln_g, ln_b = f(ln_g), f(ln_b)
+  if planes is None:
+    assert ln_g is None and ln_b is None
+    nplanes = 0
+  else:
+    planes = planes.float().contiguous()
+    assert planes.is_cuda and planes.shape[1:] == (ln_rows or M, 2)
+    ln_g, ln_b = f(ln_g), f(ln_b)
+    nplanes = planes.shape[0]
   bias = None if bias is None else f(bias)
   nan = float("nan")
   q = torch.full((B, heads, ntok_pad, dp), nan, device=t.device, dtype=torch.bfloat16)
   k = torch.full_like(q, nan) if nseg == 3 else None
   vt = torch.full((B, heads, dpv, ntok_pad), nan, device=t.device, dtype=torch.bfloat16) if nseg == 3 else None
-  N.check(N.lib().gill_op_ln_gemm(1, N.ptr(t), N.ptr(planes), planes.shape[0], ln_rows, N.ptr(ln_g), N.ptr(ln_b), N.ptr(w), N.ptr(bias), None,
+  N.check(N.lib().gill_op_ln_gemm(1, N.ptr(t), N.ptr(planes), nplanes, ln_rows, N.ptr(ln_g), N.ptr(ln_b), N.ptr(w), N.ptr(bias), None,
                                   N.ptr(q), N.ptr(k), N.ptr(vt), M, Cc, 0, nseg, heads, d, ntok, splitk, N.current_stream()))
   return q, k, vt
 
@@ -662,6 +673,13 @@ def _guarded(shape, dtype, device):
 
 def _guard_ok(buf: torch.Tensor) -> bool:
   return bool((buf[-GUARD_WORDS:] == (_GUARD_BYTE if buf.dtype == torch.uint8 else _GUARD_VALUE)).all())
+
+
+def _out_buffer(shape, dtype, device, guarded: bool):
+  """(buffer, output view): a _guarded() pair, or (None, torch.empty) — the wrappers' default path."""
+  if guarded:
+    return _guarded(shape, dtype, device)
+  return None, torch.empty(shape, device=device, dtype=dtype)
 
 
 # ---- the fp8 mode's launchers on quantised operands (tests/test_fp8_ops_gpu.py).  e4m3 tensors travel as uint8; every output sits in a
@@ -953,6 +971,17 @@ def gemm_plan(cases, pp: int = 1, coop: int = 1, cus: int = 256):
   rows = np.zeros((cases.shape[0], 34), dtype=np.int32)
   N.check(N.lib().gill_gemm_plan(cases.ctypes.data, cases.shape[0], int(pp), int(coop), int(cus), rows.ctypes.data))
   return rows
+
+
+def gemm_plan_log():
+  """What the GEMM launcher ran on this thread since the previous call (host only: gill_gemm_plan_log): (rows, launched) — the plans of the
+  most recent min(32, launched) launches, oldest first, as (n, 34) int32 rows in gemm_plan()'s layout, and the number of launches.  Clears
+  the record."""
+  import numpy as np
+  rows = np.zeros((32, 34), dtype=np.int32)
+  launched = ctypes.c_int(0)
+  N.check(N.lib().gill_gemm_plan_log(rows.ctypes.data, 32, ctypes.byref(launched)))
+  return rows[:min(32, launched.value)].copy(), launched.value
 
 
 def unet_xf_plan(cases, lnproj: int = 1, xalg: int = 1, ffn_fused: int = 1):

@@ -580,11 +580,11 @@ int gill_coop_timeouts(void);
  * parity tests can pin each against the CPU oracle.  All bf16 unless noted.
  * ------------------------------------------------------------------------------------------ */
 /* C[M,N] = act(alpha * A[M,K] . W[N,K]^T + bias[N] + resid[M,N]); act: 0 none 1 relu 2 gelu(erf) 3 silu.
- * out_f32: C is fp32 instead of bf16.  splitk: 0 = auto, n > 1 = forced n-way split; < 0 = the general row-major tiles even for the
+ * out_f32: bit 0: C is fp32 instead of bf16; bit 1: resid is fp32 (as the OPT / CLIP engines keep their residual stream).  splitk: 0 = auto, n > 1 = forced n-way split; < 0 = the general row-major tiles even for the
  * weight-streaming shapes (N * K >= 4 Mi) that otherwise run on a 64 x 64-blocked copy of W — the STREAM64 tile up to 256 rows, the general tiles reading
  * the blocked layout above — (-1: auto split, -n: n ways).
  * Split-K launches share one grow-only workspace owned by the library: one caller at a time (as everywhere on this path). */
-int gill_op_gemm(const void* A, const void* W, const float* bias, const void* resid_bf16, void* C, int M, int N, int K,
+int gill_op_gemm(const void* A, const void* W, const float* bias, const void* resid, void* C, int M, int N, int K,
                  float alpha, int act, int out_f32, int splitk, void* stream);
 /* GEGLU projection: W (2*inner, K) in diffusers order [value rows | gate rows], bias (2*inner) ->
  * C (M, inner) = (A.Wv^T + bv) * gelu(A.Wg^T + bg) */
@@ -641,13 +641,14 @@ int gill_op_groupnorm(const void* x1, int C1, const void* x2, int C2, int B, int
  * gill_op_conv3x3_gn_stats: 3x3 / pad 1 / stride 1 convolution of x1 (B,IH,IW,C1) [++ x2 (…,C2)], w (Cout,C1+C2,3,3) fp32, optional bias (Cout),
  *   rowvec (B,Cout), resid (B,IH,IW,Cout) bf16; xs1 (…,CS1) [++ xs2 (…,CS2)] with w_sc (Cout,CS1+CS2) fp32: the fused 1x1 shortcut segment
  *   (then no rowvec / resid); ups = 1: the four-tap upsample form (y (B,2IH,2IW,Cout); no rowvec / resid / shortcut).
- * gill_op_gemm_gn_stats: C (M,N) bf16 = A (M,K) . W (N,K)^T + bias + resid (M,N), M = samples x rows_per_batch, ldc = N.
+ * gill_op_gemm_gn_stats: C (M,N) bf16 = act(A (M,K) . W (N,K)^T + bias + resid (M,N)), M = samples x rows_per_batch, ldc = N; act as gill_op_gemm
+ *   (the time-embedding style SiLU GEMM with statistics: the one launch that runs the two-wave 64 x 128 tile with an activation).
  * Synchronise.  For the operator tests. */
 int gill_op_conv3x3_gn_stats(const void* x1, int C1, const void* x2, int C2, const float* w_oihw, const float* bias, const float* rowvec,
                              const void* resid, const void* xs1, int CS1, const void* xs2, int CS2, const float* w_sc, void* y, float* gn_stats,
                              int bin, int B, int IH, int IW, int Cout, int ups, int splitk, int* slab_rows, int* nslab, void* stream);
 int gill_op_gemm_gn_stats(const void* A_bf16, const void* W_bf16, const float* bias, const void* resid_bf16, void* C_bf16, float* gn_stats, int bin,
-                          int M, int N, int K, int rows_per_batch, int splitk, int* slab_rows, int* nslab, void* stream);
+                          int M, int N, int K, int rows_per_batch, int splitk, int act, int* slab_rows, int* nslab, void* stream);
 /* ... consumer side: GroupNorm (+ SiLU) of x1 (B,HW,C1) [++ x2 (B,HW,C2)] from caller-supplied partials, never reading the tensors for
  * statistics.  stats1 [B][nslab1][C1 / bin1][2] covers the channels of x1, stats2 [B][nslab2][C2 / bin2][2] those of x2 (NULL when C2 == 0);
  * group boundaries must fall on bin boundaries of the block that holds them (an error otherwise); at most 128 bins per block; any partial
@@ -721,7 +722,9 @@ int gill_op_linear_rowstats(const void* A_bf16, const void* A2_bf16, int K1, con
  * out (M, inner) bf16.  mode 1: W (nseg C, C) = to_q [| to_k | to_v], nseg 1 | 3, heads * d == C, b (nseg C) or NULL, M = B * ntok -> q, k
  * [B][heads][ntok_pad][dp], vt [B][heads][dpv][ntok_pad] in the attention kernels' layout (dp = padded head dim, dpv = dp rounded up to 32,
  * ntok_pad = ntok rounded up to 32, q pre-scaled by log2(e) / sqrt(d), vt row dp = 1 where dpv > dp); k, vt unused when nseg == 1.
- * splitk as above (GEGLU cannot split).  Replaces norm1 + attn1.to_q/k/v, norm2 + attn2.to_q, norm3 + ff.net.0 of diffusers'
+ * splitk as above (GEGLU cannot split).  mode 1 with planes, ln_g and ln_b all NULL: the same scatter without a LayerNorm (the OPT / CLIP
+ * engines' QKV GEMM), on a 64 x 64-blocked copy of W where the engines block the matrix (N * C >= 4 Mi, C >= 1024; splitk 0 then picks the
+ * blocked split).  Replaces norm1 + attn1.to_q/k/v, norm2 + attn2.to_q, norm3 + ff.net.0 of diffusers'
  * BasicTransformerBlock inside gill_unet_forward (reference call site: gill/custom_sd.py:633-638).  Synchronises. */
 int gill_op_ln_gemm(int mode, const void* T_bf16, const float* planes, int P, int ln_rows, const float* ln_g, const float* ln_b, const void* W_bf16,
                     const float* b, void* out_bf16, void* q_bf16, void* k_bf16, void* vt_bf16, int M, int C, int inner, int nseg, int heads, int d,
@@ -852,6 +855,11 @@ int gill_lm_loss_geometry(int M, int V, int D, int* row_tile, int* col_tile, int
 #define GILL_GEMM_PLAN_CASE_INTS 54
 #define GILL_GEMM_PLAN_ROW_INTS 34
 int gill_gemm_plan(const int32_t* cases, int n, int pp, int coop, int cus, int32_t* rows);
+/* What the launcher actually ran (host only, for tests): every successful GEMM / convolution launch of the calling thread copies its plan into a
+ * ring of the 32 most recent ones.  Writes the most recent min(cap, 32, launches) plans into rows, oldest first, as rows of
+ * GILL_GEMM_PLAN_ROW_INTS int32 in the layout above (rc = 0), sets *launched to the number of launches since the previous call and clears the
+ * record.  cap == 0 (rows may be NULL) only counts and clears. */
+int gill_gemm_plan_log(int32_t* rows, int cap, int* launched);
 /* The engines' pre-launch choices under the same explicit environment (host only).  queries: n rows of 7 int32 = {what, six arguments}:
  *   0 split factor (M, N, K, act, plain, generic)    1 split factor on 64 x 64-blocked weights (M, N, K)    2 fused GroupNorm bins possible (N, cg)
  *   3 convolution on the ping-pong tile (rows, Cout)  4 chunk-major K order (HW, Cin, Cout)                  5 weights stored 64 x 64-blocked (N, K) */
