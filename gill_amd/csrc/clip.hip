@@ -11,7 +11,7 @@ struct gill_clip {
   gill_clip_config cfg;
   DevPool pool;
   int ntok = 0, npatch = 0, kpatch = 0, kpad = 0;
-  bf16_t* wpatch = nullptr;   // [D][kpad]: patch_embedding.weight flattened (c, ky, kx), zero-padded to a multiple of 64
+  TfmMat patch;               // [D][kpad], no bias: patch_embedding.weight flattened (c, ky, kx), zero-padded to a multiple of 64
   float* cls = nullptr;       // [D]
   float* pos = nullptr;       // [ntok][D]
   float *preg = nullptr, *preb = nullptr, *postg = nullptr, *postb = nullptr;
@@ -74,8 +74,9 @@ extern "C" int gill_clip_create(gill_clip** out, const gill_clip_config* cfg, co
     bf16_t* tmp;
     if ((rc = m->pool.alloc(&tmp, (size_t)D * m->kpatch, false))) return fail(rc);
     if ((rc = convert_to_bf16_launch(t->data, t->dtype, (int64_t)D * m->kpatch, tmp, s))) return fail(rc);
-    if ((rc = m->pool.alloc(&m->wpatch, (size_t)D * m->kpad, true))) return fail(rc);
-    if (hipMemcpy2D(m->wpatch, sizeof(bf16_t) * m->kpad, tmp, sizeof(bf16_t) * m->kpatch, sizeof(bf16_t) * m->kpatch, D,
+    m->patch.N = D; m->patch.K = m->kpad;
+    if ((rc = m->pool.alloc(&m->patch.w, (size_t)D * m->kpad, true))) return fail(rc);
+    if (hipMemcpy2D(m->patch.w, sizeof(bf16_t) * m->kpad, tmp, sizeof(bf16_t) * m->kpatch, sizeof(bf16_t) * m->kpatch, D,
                     hipMemcpyDeviceToDevice) != hipSuccess) { gill_set_error("clip create: weight re-layout failed"); return fail(-1); }
   }
   if ((rc = load_f32(wt, m->pool, vm + "embeddings.class_embedding", D, &m->cls, s))) return fail(rc);
@@ -126,8 +127,7 @@ extern "C" int gill_clip_forward(gill_clip* m, const float* pixel_values, int B,
                        c.image_size / c.patch_size, m->kpatch, m->kpad, m->col);
     GILL_CHECK_HIP(hipGetLastError());
     for (int b = 0; b < B; ++b)      // rows b*T+1 .. of the fp32 stream (row b*T is the class token)
-      GILL_TRY(r.linear(m->col + (size_t)b * m->npatch * m->kpad, m->npatch, m->wpatch, 0, nullptr, D, m->kpad, nullptr, ACT_NONE,
-                        m->h + ((size_t)b * T + 1) * D, true));
+      GILL_TRY(r.linear(m->col + (size_t)b * m->npatch * m->kpad, m->npatch, m->patch, nullptr, ACT_NONE, m->h + ((size_t)b * T + 1) * D, true));
     hipLaunchKernelGGL(clip_embed_finish_kernel, dim3(R), dim3(256), 0, s, m->h, m->cls, m->pos, T, D);
     GILL_CHECK_HIP(hipGetLastError());
   }

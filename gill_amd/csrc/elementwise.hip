@@ -12,16 +12,26 @@ static inline int grid_for(int64_t n, int per_block = 256, int cap = 8192) {
 }
 
 // ---------------------------------------------------------------- embeddings
-// out[b][t][:] = table[ids[b][t]][:] + pos_table[t + pos_offset][:]   (fp32 residual stream)
+// out[b][t][:] = row(ids[b][t])[:] + pos_table[t + pos_offset][:]   (fp32 residual stream; no pos_table: the row alone).  An id >= 0 names a
+// row of table; with n_extra > 0 an id < 0 names row -(id + 1) of extra (n_extra, D) bf16 — the visual embeddings of an image prompt
+// (models.py:606-613, 625).  Ids outside either range are clamped to the nearest valid row; with n_extra == 0 an id < 0 is row 0 of table.
 __global__ __launch_bounds__(256) void embed_tokens_kernel(const int64_t* __restrict__ ids, const bf16_t* __restrict__ table,
-                                                           int vocab, const bf16_t* __restrict__ pos, int pos_offset,
-                                                           int T, int D, float* __restrict__ out) {
+                                                           int vocab, const bf16_t* __restrict__ extra, int n_extra,
+                                                           const bf16_t* __restrict__ pos, int pos_offset, int T, int D,
+                                                           float* __restrict__ out) {
   const int row = blockIdx.x;  // b*T + t
   const int t = row % T;
   int64_t id = ids[row];
-  if (id < 0) id = 0;
-  if (id >= vocab) id = vocab - 1;
-  const bf16_t* e = table + (size_t)id * D;
+  const bf16_t* e;
+  if (id < 0 && n_extra > 0) {
+    int64_t x = -(id + 1);
+    if (x >= n_extra) x = n_extra - 1;
+    e = extra + (size_t)x * D;
+  } else {
+    if (id < 0) id = 0;
+    if (id >= vocab) id = vocab - 1;
+    e = table + (size_t)id * D;
+  }
   const bf16_t* pe = pos ? pos + (size_t)(t + pos_offset) * D : nullptr;
   float* o = out + (size_t)row * D;
   for (int c = threadIdx.x * 2; c < D; c += blockDim.x * 2) {
@@ -35,10 +45,10 @@ __global__ __launch_bounds__(256) void embed_tokens_kernel(const int64_t* __rest
   }
 }
 
-int embed_tokens_launch(const int64_t* ids, const bf16_t* table, int vocab, const bf16_t* pos_table, int pos_offset,
-                        int B, int T, int D, float* out_f32, hipStream_t s) {
-  GILL_REQUIRE(D % 2 == 0, "embedding dim must be even");
-  hipLaunchKernelGGL(embed_tokens_kernel, dim3(B * T), dim3(256), 0, s, ids, table, vocab, pos_table, pos_offset, T, D,
+int embed_tokens_launch(const int64_t* ids, const bf16_t* table, int vocab, const bf16_t* extra, int n_extra, const bf16_t* pos_table,
+                        int pos_offset, int B, int T, int D, float* out_f32, hipStream_t s) {
+  GILL_REQUIRE(D % 2 == 0 && n_extra >= 0 && (n_extra == 0 || extra), "embedding dim must be even; n_extra rows need a table");
+  hipLaunchKernelGGL(embed_tokens_kernel, dim3(B * T), dim3(256), 0, s, ids, table, vocab, extra, n_extra, pos_table, pos_offset, T, D,
                      out_f32);
   GILL_CHECK_HIP(hipGetLastError());
   return 0;

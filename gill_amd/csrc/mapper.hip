@@ -14,16 +14,15 @@
 
 namespace {
 
-struct LinearW { bf16_t* w = nullptr; float* b = nullptr; int out = 0, in = 0; };
 struct NormW { float* g = nullptr; float* b = nullptr; };
-struct DecLayer { TfmLayer blk; LinearW ca_in, ca_out; NormW ca_norm; };   // blk: self_attn (norm1) + feed-forward (norm3); ca: multihead_attn (norm2)
+struct DecLayer { TfmLayer blk; TfmMat ca_in, ca_out; NormW ca_norm; };   // blk: self_attn (norm1) + feed-forward (norm3); ca: multihead_attn (norm2)
 
 }  // namespace
 
 struct gill_mapper {
   gill_mapper_config cfg;
   DevPool pool;
-  LinearW fc, model;
+  TfmMat fc, model;
   float* query = nullptr;  // (n_out, hidden) fp32
   std::vector<TfmLayer> enc;
   std::vector<DecLayer> dec;
@@ -37,8 +36,8 @@ struct gill_mapper {
 };
 
 static int load_linear(const WeightTable& wt, DevPool& pool, const std::string& wname, const std::string& bname, int out,
-                       int in, LinearW* l, hipStream_t s) {
-  l->out = out; l->in = in;
+                       int in, TfmMat* l, hipStream_t s) {
+  l->N = out; l->K = in;
   GILL_TRY(load_bf16(wt, pool, wname, (int64_t)out * in, &l->w, s));
   GILL_TRY(load_f32(wt, pool, bname, out, &l->b, s));
   return 0;
@@ -124,7 +123,7 @@ extern "C" int gill_mapper_forward(gill_mapper* m, const void* x_bf16, const voi
     x0 = m->x0;
   }
   // fc (layers.py:42) -> fp32 encoder stream
-  GILL_TRY(r.linear(x0, B * Ti, m->fc.w, 0, m->fc.b, Hd, c.in_dim, nullptr, ACT_NONE, m->h_enc, true));
+  GILL_TRY(r.linear(x0, B * Ti, m->fc, nullptr, ACT_NONE, m->h_enc, true));
   GILL_TRY(r.layers(m->h_enc, m->enc.data(), (int)m->enc.size(), B, Ti, ACT_RELU, false));
   GILL_TRY(layernorm_launch(m->h_enc, 1, m->enc_norm.g, m->enc_norm.b, m->mem, B * Ti, Hd, 1e-5f, s));
   // tgt = query_embs.repeat(B,1,1) (layers.py:43)
@@ -136,13 +135,13 @@ extern "C" int gill_mapper_forward(gill_mapper* m, const void* x_bf16, const voi
     GILL_TRY(layernorm_launch(m->h_dec, 1, L.blk.ln1g, L.blk.ln1b, t.nbuf, B * To, Hd, 1e-5f, s));
     GILL_TRY(r.self_attn(m->h_dec, B, To, L.blk, false, L.ca_norm.g, L.ca_norm.b));
     // cross attention: q from the target stream, k/v from the encoder memory
-    GILL_TRY(r.qkv(t.nbuf, B, To, L.ca_in.w, L.ca_in.b, 1, 0, To_pad, Ti_pad, t.k, t.vt, 0, 0));
-    GILL_TRY(r.qkv(m->mem, B, Ti, L.ca_in.w + (size_t)Hd * Hd, L.ca_in.b + Hd, 2, 1, To_pad, Ti_pad, t.k, t.vt, 0, 0));
+    GILL_TRY(r.qkv(t.nbuf, B, To, L.ca_in, 1, 0, To_pad, Ti_pad, t.k, t.vt, 0));
+    GILL_TRY(r.qkv(m->mem, B, Ti, L.ca_in, 2, 1, To_pad, Ti_pad, t.k, t.vt, 0));
     GILL_TRY(r.attend(B, To, Ti, To_pad, Ti_pad, t.k, t.vt, false));
-    GILL_TRY(r.linear(t.o, B * To, L.ca_out.w, 0, L.ca_out.b, Hd, Hd, m->h_dec, ACT_NONE, m->h_dec, true, L.blk.ln2g, L.blk.ln2b, t.nbuf));
+    GILL_TRY(r.linear(t.o, B * To, L.ca_out, m->h_dec, ACT_NONE, m->h_dec, true, L.blk.ln2g, L.blk.ln2b, t.nbuf));
     GILL_TRY(r.ffn(m->h_dec, B * To, L.blk, ACT_RELU));
   }
   GILL_TRY(layernorm_launch(m->h_dec, 1, m->dec_norm.g, m->dec_norm.b, t.nbuf, B * To, Hd, 1e-5f, s));
   // model (layers.py:44)
-  return r.linear(t.nbuf, B * To, m->model.w, 0, m->model.b, c.out_dim, Hd, nullptr, ACT_NONE, out, true);
+  return r.linear(t.nbuf, B * To, m->model, nullptr, ACT_NONE, out, true);
 }

@@ -272,8 +272,8 @@ bool groupnorm_bins_align(int cg, int sc1, int bin1, int bin2);
 
 // ---- small elementwise / gather kernels ----
 int embed_rows_bf16_launch(const int64_t* ids, const bf16_t* table, int vocab, int n, int D, bf16_t* out, hipStream_t s);
-int embed_tokens_launch(const int64_t* ids, const bf16_t* table, int vocab, const bf16_t* pos_table, int pos_offset,
-                        int B, int T, int D, float* out_f32, hipStream_t s);
+int embed_tokens_launch(const int64_t* ids, const bf16_t* table, int vocab, const bf16_t* extra, int n_extra, const bf16_t* pos_table,
+                        int pos_offset, int B, int T, int D, float* out_f32, hipStream_t s);   // id < 0: row -(id + 1) of extra (n_extra > 0)
 int gather_rows_launch(const void* src, int src_f32, const int32_t* row_idx, int nrows, int D, void* dst, int dst_f32,
                        hipStream_t s);
 int add_cast_launch(const void* a, int a_f32, const void* b, int b_f32, int64_t n, int64_t b_period, bf16_t* out,

@@ -6,7 +6,8 @@
 // learned positions with the +2 offset, final LayerNorm; hidden_states[-1] is post-final-LN.
 // The residual stream is fp32; GEMMs are bf16 MFMA with fp32 accumulation, split-K so that the
 // skinny (M = B*T) weight-streaming GEMMs cover all 256 CUs; attention is the shared flash kernel.
-// The layer loop is the shared block of tfm.h; here: embeddings and positions, the KV cache, img_hidden, logits and the decode entry points.
+// Every layer loop — forward, cached forward, and the ragged decode step on bf16 weights or e4m3 bytes — is TfmRun::layers of tfm.h; here:
+// embeddings and positions, the KV cache, the hidden-rows pass of img_hidden / forward_loss, logits and the decode entry points.
 #include "tfm.h"
 #include "philox.h"
 
@@ -38,27 +39,48 @@ struct gill_opt {
   void* loss_ws = nullptr;
   float* ll_f32 = nullptr;      // [B][D]: the rows of last_logit_out after the final LayerNorm
   // layers over the fp32 stream h (B*T rows): ReLU, causal.  past < 0: plain forward over T tokens.  past >= 0: the T rows are
-  // the tokens past .. past+T-1 of each sequence; their K/V are appended to the cache and they attend to it.
-  int run_layers(int B, int T, hipStream_t s, int past = -1) const {
-    return TfmRun{tfm, s}.layers(h, layers.data(), (int)layers.size(), B, T, ACT_RELU, true, past >= 0 ? cache.data() : nullptr,
-                                 past >= 0 ? past : 0);
+  // the tokens past .. past+T-1 of each sequence; their K/V are appended to the cache and they attend to it.  dec (T == 1): the ragged
+  // decode step, every row at its own device length, on the e4m3 bytes where gill_opt_decode_uses_w8() says so.
+  int run_layers(int B, int T, hipStream_t s, int past = -1, const TfmDecode* dec = nullptr) const {
+    return TfmRun{tfm, s, dec && gill_opt_decode_uses_w8(this, B)}.layers(h, layers.data(), (int)layers.size(), B, T, ACT_RELU, true,
+                                                                          past >= 0 ? cache.data() : nullptr, past >= 0 ? past : 0, dec);
   }
 };
 
-// out[row][:] = bf16->f32(emb[row][:]) + pos[t + off][:]
+// h[row][:] = bf16->f32(emb[row][:]) + bf16->f32(pos[p][:]), p = pos_offset + row % T, or with lens (one token per row, the decode step)
+// 2 + lens[row], the length read on the device and clamped into the table (the attention kernel of the same step raises the flag).
+// 16-byte loads, 8 elements per thread (D % 64 == 0).
 __global__ __launch_bounds__(256) void opt_add_pos_kernel(const bf16_t* __restrict__ emb, const bf16_t* __restrict__ pos,
-                                                          int pos_offset, int T, int D, float* __restrict__ out) {
+                                                          const int32_t* __restrict__ lens, int max_positions, int pos_offset, int T, int D,
+                                                          float* __restrict__ out) {
   const int row = blockIdx.x;
-  const int t = row % T;
-  const bf16_t* e = emb + (size_t)row * D;
-  const bf16_t* pe = pos + (size_t)(t + pos_offset) * D;
-  float* o = out + (size_t)row * D;
-  for (int c = threadIdx.x * 2; c < D; c += blockDim.x * 2) {
-    const uint32_t u = *reinterpret_cast<const uint32_t*>(e + c);
-    const uint32_t v = *reinterpret_cast<const uint32_t*>(pe + c);
-    *reinterpret_cast<float2*>(o + c) = make_float2(bf2f((bf16_t)(u & 0xffff)) + bf2f((bf16_t)(v & 0xffff)),
-                                                    bf2f((bf16_t)(u >> 16)) + bf2f((bf16_t)(v >> 16)));
+  int p = pos_offset + row % T;
+  if (lens) {
+    const int n = lens[row];
+    p = 2 + (n < 0 ? 0 : (n > max_positions - 1 ? max_positions - 1 : n));
   }
+  const bf16_t* e = emb + (size_t)row * D;
+  const bf16_t* pe = pos + (size_t)p * D;
+  float* o = out + (size_t)row * D;
+  for (int c = threadIdx.x * 8; c < D; c += blockDim.x * 8) {
+    const uint4 u = *reinterpret_cast<const uint4*>(e + c);
+    const uint4 v = *reinterpret_cast<const uint4*>(pe + c);
+    const uint32_t uu[4] = {u.x, u.y, u.z, u.w}, vv[4] = {v.x, v.y, v.z, v.w};
+    float r[8];
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+      r[2 * i] = bf2f((bf16_t)(uu[i] & 0xffff)) + bf2f((bf16_t)(vv[i] & 0xffff));
+      r[2 * i + 1] = bf2f((bf16_t)(uu[i] >> 16)) + bf2f((bf16_t)(vv[i] >> 16));
+    }
+    *reinterpret_cast<float4*>(o + c) = make_float4(r[0], r[1], r[2], r[3]);
+    *reinterpret_cast<float4*>(o + c + 4) = make_float4(r[4], r[5], r[6], r[7]);
+  }
+}
+static int opt_add_pos(const gill_opt* m, const void* emb_bf16, const int32_t* lens, int rows, int T, int pos_offset, hipStream_t s) {
+  hipLaunchKernelGGL(opt_add_pos_kernel, dim3(rows), dim3(256), 0, s, (const bf16_t*)emb_bf16, m->pos, lens, m->cfg.max_positions, pos_offset, T,
+                     m->cfg.hidden_size, m->h);
+  GILL_CHECK_HIP(hipGetLastError());
+  return 0;
 }
 
 extern "C" int gill_opt_create(gill_opt** out, const gill_opt_config* cfg, const gill_tensor* weights, int n_weights) {
@@ -110,7 +132,7 @@ extern "C" int gill_opt_create_ex(gill_opt** out, const gill_opt_config* cfg, co
   // replaced by the dequantised values (every other entry point: the same model on today's kernels)
   if (weight_mode == GILL_OPT_W8)
     for (int i = 0; i < cfg->num_layers; ++i)
-      if ((rc = tfm_quantize_layer_w8(m->pool, D, F, &m->layers[i], s))) return fail(rc);
+      if ((rc = tfm_quantize_layer_w8(m->pool, &m->layers[i], s))) return fail(rc);
   const size_t R = (size_t)cfg->max_batch * cfg->max_seq;
   if ((rc = m->pool.alloc(&m->h, R * D))) return fail(rc);
   if ((rc = m->tfm.alloc(m->pool, cfg->max_batch, cfg->max_seq, D, F, H, hd, round_up(hd, 32)))) return fail(rc);
@@ -142,9 +164,7 @@ extern "C" int gill_opt_forward(gill_opt* m, const void* inputs_embeds_bf16, int
   GILL_REQUIRE(B >= 1 && B <= m->cfg.max_batch && T >= 1 && T <= m->cfg.max_seq, "B/T exceed the handle's workspace");
   hipStream_t s = (hipStream_t)stream;
   const int D = m->cfg.hidden_size;
-  hipLaunchKernelGGL(opt_add_pos_kernel, dim3(B * T), dim3(256), 0, s, (const bf16_t*)inputs_embeds_bf16, m->pos, 2, T, D,
-                     m->h);
-  GILL_CHECK_HIP(hipGetLastError());
+  GILL_TRY(opt_add_pos(m, inputs_embeds_bf16, nullptr, B * T, T, 2, s));
   GILL_TRY(m->run_layers(B, T, s));
   if (hidden_out) GILL_TRY(layernorm_f32out_launch(m->h, 1, m->lnfg, m->lnfb, hidden_out, B * T, D, 1e-5f, s));
   return 0;
@@ -174,51 +194,46 @@ extern "C" int gill_opt_forward_cached(gill_opt* m, const void* inputs_embeds_bf
   hipStream_t s = (hipStream_t)stream;
   const int D = m->cfg.hidden_size;
   GILL_TRY(opt_ensure_cache(m));
-  hipLaunchKernelGGL(opt_add_pos_kernel, dim3(B * T_new), dim3(256), 0, s, (const bf16_t*)inputs_embeds_bf16, m->pos,
-                     2 + past_len, T_new, D, m->h);
-  GILL_CHECK_HIP(hipGetLastError());
+  GILL_TRY(opt_add_pos(m, inputs_embeds_bf16, nullptr, B * T_new, T_new, 2 + past_len, s));
   GILL_TRY(m->run_layers(B, T_new, s, past_len));
   GILL_TRY(layernorm_f32out_launch(m->h, 1, m->lnfg, m->lnfb, hidden_out, B * T_new, D, 1e-5f, s));
   return 0;
 }
 
-// embed_tokens_kernel with a second table: out[b][t][:] = row(ids[b][t])[:] + pos[t + pos_offset][:], where an id < 0 names row -(id + 1) of
-// extra (n_extra, D) bf16 — the visual embeddings of an image prompt (models.py:606-613, 625) — and an id >= 0 a row of table.  Ids outside either
-// range are clamped to the nearest valid row.  The same arithmetic as embed_tokens_kernel on either kind of row.
-__global__ __launch_bounds__(256) void opt_embed_tokens_ex_kernel(const int64_t* __restrict__ ids, const bf16_t* __restrict__ table, int vocab,
-                                                                  const bf16_t* __restrict__ extra, int n_extra, const bf16_t* __restrict__ pos,
-                                                                  int pos_offset, int T, int D, float* __restrict__ out) {
-  const int row = blockIdx.x;  // b*T + t
-  const int t = row % T;
-  int64_t id = ids[row];
-  const bf16_t* e;
-  if (id < 0) {
-    int64_t x = -(id + 1);
-    if (x >= n_extra) x = n_extra - 1;
-    e = extra + (size_t)x * D;
-  } else {
-    if (id >= vocab) id = vocab - 1;
-    e = table + (size_t)id * D;
-  }
-  const bf16_t* pe = pos ? pos + (size_t)(t + pos_offset) * D : nullptr;
-  float* o = out + (size_t)row * D;
-  for (int c = threadIdx.x * 2; c < D; c += blockDim.x * 2) {
-    const uint32_t u = *reinterpret_cast<const uint32_t*>(e + c);
-    float a = bf2f((bf16_t)(u & 0xffff)), bq = bf2f((bf16_t)(u >> 16));
-    if (pe) {
-      const uint32_t v = *reinterpret_cast<const uint32_t*>(pe + c);
-      a += bf2f((bf16_t)(v & 0xffff)); bq += bf2f((bf16_t)(v >> 16));
+// The pass gill_opt_img_hidden_ex and gill_opt_forward_loss share: the gather indices (rows: the num_tokens rows ending at last_idx, slots
+// [0, B * num_tokens) of idx_dev; last_logit: the rows last_idx - 1, slots [max_batch * 64, + B)) checked and uploaded, the bf16 embedding rows
+// (-> emb_out), embeddings + learned positions -> the fp32 stream, the layers, and the final LayerNorm of the gathered rows -> raw_out.
+static int opt_hidden_rows(gill_opt* m, const int64_t* ids, const int32_t* last_idx_host, int B, int T, int num_tokens, const void* extra_rows_bf16,
+                           int n_extra, void* raw_out_bf16, void* emb_out_bf16, bool last_logit, hipStream_t s) {
+  const int D = m->cfg.hidden_size, V = m->cfg.vocab_size, ll_base = m->cfg.max_batch * 64;
+  const bf16_t* extra = (const bf16_t*)extra_rows_bf16;
+  const bool rows = raw_out_bf16 || emb_out_bf16;
+  if (rows || last_logit) {
+    std::vector<int32_t> idx(last_logit ? (size_t)ll_base + B : (size_t)B * num_tokens, 0);
+    for (int b = 0; b < B; ++b) {
+      if (rows) {
+        GILL_REQUIRE(last_idx_host[b] - num_tokens + 1 >= 0 && last_idx_host[b] < T, "last_idx out of range");
+        for (int j = 0; j < num_tokens; ++j) idx[(size_t)b * num_tokens + j] = b * T + last_idx_host[b] - num_tokens + 1 + j;
+      }
+      if (last_logit) {
+        GILL_REQUIRE(last_idx_host[b] - 1 >= 0 && last_idx_host[b] - 1 < T, "last_idx - 1 out of range");
+        idx[(size_t)ll_base + b] = b * T + last_idx_host[b] - 1;
+      }
     }
-    *reinterpret_cast<float2*>(o + c) = make_float2(a, bq);
+    GILL_CHECK_HIP(hipMemcpyAsync(m->idx_dev, idx.data(), sizeof(int32_t) * idx.size(), hipMemcpyHostToDevice, s));
+    GILL_CHECK_HIP(hipStreamSynchronize(s));  // idx is a stack-lifetime host buffer
   }
-}
-
-// the two embedding passes of img_hidden: token rows only through the shared kernel (as ever), with extra rows through the kernel above
-static int img_hidden_embed(const gill_opt* m, const int64_t* ids, const bf16_t* extra, int n_extra, const bf16_t* pos, int B, int T, hipStream_t s) {
-  const int D = m->cfg.hidden_size;
-  if (n_extra == 0) return embed_tokens_launch(ids, m->embed, m->cfg.vocab_size, pos, 2, B, T, D, m->h, s);
-  hipLaunchKernelGGL(opt_embed_tokens_ex_kernel, dim3(B * T), dim3(256), 0, s, ids, m->embed, m->cfg.vocab_size, extra, n_extra, pos, 2, T, D, m->h);
-  GILL_CHECK_HIP(hipGetLastError());
+  // input_embs = input_embeddings(labels)  (models.py:180), bf16 rows
+  GILL_TRY(embed_tokens_launch(ids, m->embed, V, extra, n_extra, nullptr, 2, B, T, D, m->h, s));
+  GILL_TRY(cast_f32_to_bf16_launch(m->h, m->emb_tmp, (int64_t)B * T * D, s));
+  if (emb_out_bf16) GILL_TRY(gather_rows_launch(m->emb_tmp, 0, m->idx_dev, B * num_tokens, D, emb_out_bf16, 0, s));
+  // + learned positions -> fp32 stream
+  GILL_TRY(embed_tokens_launch(ids, m->embed, V, extra, n_extra, m->pos, 2, B, T, D, m->h, s));
+  GILL_TRY(m->run_layers(B, T, s));
+  if (raw_out_bf16) {      // final LN only on the rows that are read (models.py:384)
+    GILL_TRY(gather_rows_launch(m->h, 1, m->idx_dev, B * num_tokens, D, m->gath, 1, s));
+    GILL_TRY(layernorm_launch(m->gath, 1, m->lnfg, m->lnfb, (bf16_t*)raw_out_bf16, B * num_tokens, D, 1e-5f, s));
+  }
   return 0;
 }
 
@@ -228,27 +243,7 @@ extern "C" int gill_opt_img_hidden_ex(gill_opt* m, const int64_t* ids, const int
   GILL_REQUIRE(B >= 1 && B <= m->cfg.max_batch && T >= 1 && T <= m->cfg.max_seq, "B/T exceed the handle's workspace");
   GILL_REQUIRE(num_tokens >= 1 && num_tokens <= 64, "num_tokens out of range");
   GILL_REQUIRE(n_extra >= 0 && (n_extra == 0 || extra_rows_bf16), "n_extra rows need a table");
-  hipStream_t s = (hipStream_t)stream;
-  const int D = m->cfg.hidden_size;
-  const bf16_t* extra = (const bf16_t*)extra_rows_bf16;
-  std::vector<int32_t> idx((size_t)B * num_tokens);
-  for (int b = 0; b < B; ++b) {
-    GILL_REQUIRE(last_idx_host[b] - num_tokens + 1 >= 0 && last_idx_host[b] < T, "last_idx out of range");
-    for (int j = 0; j < num_tokens; ++j) idx[(size_t)b * num_tokens + j] = b * T + last_idx_host[b] - num_tokens + 1 + j;
-  }
-  GILL_CHECK_HIP(hipMemcpyAsync(m->idx_dev, idx.data(), sizeof(int32_t) * idx.size(), hipMemcpyHostToDevice, s));
-  GILL_CHECK_HIP(hipStreamSynchronize(s));  // idx is a stack-lifetime host buffer
-  // input_embs = input_embeddings(labels)  (models.py:180), bf16 rows
-  GILL_TRY(img_hidden_embed(m, ids, extra, n_extra, nullptr, B, T, s));
-  GILL_TRY(cast_f32_to_bf16_launch(m->h, m->emb_tmp, (int64_t)B * T * D, s));
-  if (emb_out_bf16) GILL_TRY(gather_rows_launch(m->emb_tmp, 0, m->idx_dev, B * num_tokens, D, emb_out_bf16, 0, s));
-  // + learned positions -> fp32 stream
-  GILL_TRY(img_hidden_embed(m, ids, extra, n_extra, m->pos, B, T, s));
-  GILL_TRY(m->run_layers(B, T, s));
-  // final LN only on the rows that are read (models.py:384)
-  GILL_TRY(gather_rows_launch(m->h, 1, m->idx_dev, B * num_tokens, D, m->gath, 1, s));
-  GILL_TRY(layernorm_launch(m->gath, 1, m->lnfg, m->lnfb, (bf16_t*)raw_out_bf16, B * num_tokens, D, 1e-5f, s));
-  return 0;
+  return opt_hidden_rows(m, ids, last_idx_host, B, T, num_tokens, extra_rows_bf16, n_extra, raw_out_bf16, emb_out_bf16, false, (hipStream_t)stream);
 }
 
 extern "C" int gill_opt_img_hidden(gill_opt* m, const int64_t* ids, const int32_t* last_idx_host, int B, int T,
@@ -301,23 +296,7 @@ extern "C" int gill_opt_forward_loss(gill_opt* m, const int64_t* ids, const int3
   GILL_REQUIRE(!rows || (num_tokens >= 1 && num_tokens <= 64), "num_tokens out of range");
   hipStream_t s = (hipStream_t)stream;
   const int D = m->cfg.hidden_size, V = m->cfg.vocab_size;
-  const bf16_t* extra = (const bf16_t*)extra_rows_bf16;
-  const int ll_base = m->cfg.max_batch * 64;      // idx_dev: [0, B * num_tokens) the gathered rows, [ll_base, ll_base + B) the last-logit rows
-  if (last_idx_host && (rows || last_logit_out)) {
-    std::vector<int32_t> idx((size_t)ll_base + B, 0);
-    for (int b = 0; b < B; ++b) {
-      if (rows) {
-        GILL_REQUIRE(last_idx_host[b] - num_tokens + 1 >= 0 && last_idx_host[b] < T, "last_idx out of range");
-        for (int j = 0; j < num_tokens; ++j) idx[(size_t)b * num_tokens + j] = b * T + last_idx_host[b] - num_tokens + 1 + j;
-      }
-      if (last_logit_out) {
-        GILL_REQUIRE(last_idx_host[b] - 1 >= 0 && last_idx_host[b] - 1 < T, "last_idx - 1 out of range");
-        idx[(size_t)ll_base + b] = b * T + last_idx_host[b] - 1;
-      }
-    }
-    GILL_CHECK_HIP(hipMemcpyAsync(m->idx_dev, idx.data(), sizeof(int32_t) * idx.size(), hipMemcpyHostToDevice, s));
-    GILL_CHECK_HIP(hipStreamSynchronize(s));  // idx is a stack-lifetime host buffer
-  }
+  const int ll_base = m->cfg.max_batch * 64;      // idx_dev: the last-logit rows (opt_hidden_rows)
   if (!m->xn_bf) {
     const size_t R = (size_t)m->cfg.max_batch * m->cfg.max_seq;
     GILL_TRY(m->pool.alloc(&m->xn_bf, R * D));
@@ -330,16 +309,7 @@ extern "C" int gill_opt_forward_loss(gill_opt* m, const int64_t* ids, const int3
     GILL_TRY(m->pool.alloc(&ws, lm_loss_workspace_bytes((int)R, V), false));
     m->loss_ws = ws;
   }
-  // the pass of gill_opt_img_hidden_ex, launch for launch
-  GILL_TRY(img_hidden_embed(m, ids, extra, n_extra, nullptr, B, T, s));
-  GILL_TRY(cast_f32_to_bf16_launch(m->h, m->emb_tmp, (int64_t)B * T * D, s));
-  if (emb_out_bf16) GILL_TRY(gather_rows_launch(m->emb_tmp, 0, m->idx_dev, B * num_tokens, D, emb_out_bf16, 0, s));
-  GILL_TRY(img_hidden_embed(m, ids, extra, n_extra, m->pos, B, T, s));
-  GILL_TRY(m->run_layers(B, T, s));
-  if (raw_out_bf16) {
-    GILL_TRY(gather_rows_launch(m->h, 1, m->idx_dev, B * num_tokens, D, m->gath, 1, s));
-    GILL_TRY(layernorm_launch(m->gath, 1, m->lnfg, m->lnfb, (bf16_t*)raw_out_bf16, B * num_tokens, D, 1e-5f, s));
-  }
+  GILL_TRY(opt_hidden_rows(m, ids, last_idx_host, B, T, num_tokens, extra_rows_bf16, n_extra, raw_out_bf16, emb_out_bf16, last_logit_out != nullptr, s));
   // here the final LayerNorm runs on every row
   GILL_TRY(layernorm_launch(m->h, 1, m->lnfg, m->lnfb, m->xn_bf, B * T, D, 1e-5f, s));
   if (hidden_out) GILL_TRY(layernorm_f32out_launch(m->h, 1, m->lnfg, m->lnfb, hidden_out, B * T, D, 1e-5f, s));
@@ -469,31 +439,6 @@ extern "C" int gill_opt_filter_logits(gill_opt* m, const float* in, float* out, 
 
 // ---- ragged batched decoding: every row at its own length ----
 
-// opt_add_pos_kernel for one token per row at a per-row position: out[b][:] = bf16->f32(emb[b][:]) + pos[2 + lens[b]][:], the length read on
-// the device and clamped into the table (the attention kernel of the same step raises the flag).  16-byte loads, 8 elements per thread.
-__global__ __launch_bounds__(256) void opt_add_pos_rows_kernel(const bf16_t* __restrict__ emb, const bf16_t* __restrict__ pos,
-                                                               const int32_t* __restrict__ lens, int max_positions, int D, float* __restrict__ out) {
-  const int row = blockIdx.x;
-  int n = lens[row];
-  n = n < 0 ? 0 : (n > max_positions - 1 ? max_positions - 1 : n);
-  const bf16_t* e = emb + (size_t)row * D;
-  const bf16_t* pe = pos + (size_t)(2 + n) * D;
-  float* o = out + (size_t)row * D;
-  for (int c = threadIdx.x * 8; c < D; c += blockDim.x * 8) {
-    const uint4 u = *reinterpret_cast<const uint4*>(e + c);
-    const uint4 v = *reinterpret_cast<const uint4*>(pe + c);
-    const uint32_t uu[4] = {u.x, u.y, u.z, u.w}, vv[4] = {v.x, v.y, v.z, v.w};
-    float r[8];
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-      r[2 * i] = bf2f((bf16_t)(uu[i] & 0xffff)) + bf2f((bf16_t)(vv[i] & 0xffff));
-      r[2 * i + 1] = bf2f((bf16_t)(uu[i] >> 16)) + bf2f((bf16_t)(vv[i] >> 16));
-    }
-    *reinterpret_cast<float4*>(o + c) = make_float4(r[0], r[1], r[2], r[3]);
-    *reinterpret_cast<float4*>(o + c + 4) = make_float4(r[4], r[5], r[6], r[7]);
-  }
-}
-
 extern "C" int gill_opt_decode_step(gill_opt* m, const void* new_embeds_bf16, const int32_t* lens_dev, int B, int len_bound, float* hidden_out,
                                     void* stream) {
   GILL_REQUIRE(m && new_embeds_bf16 && lens_dev && hidden_out, "null argument");
@@ -501,44 +446,11 @@ extern "C" int gill_opt_decode_step(gill_opt* m, const void* new_embeds_bf16, co
   GILL_REQUIRE(len_bound >= 1 && len_bound <= m->cfg.max_seq, "len_bound exceeds the handle's max_seq");
   GILL_REQUIRE(len_bound <= m->cfg.max_positions, "sequence longer than the position table");
   hipStream_t s = (hipStream_t)stream;
-  const int D = m->cfg.hidden_size, n = (int)m->layers.size();
   GILL_TRY(opt_ensure_cache(m));
-  hipLaunchKernelGGL(opt_add_pos_rows_kernel, dim3(B), dim3(256), 0, s, (const bf16_t*)new_embeds_bf16, m->pos, lens_dev, m->cfg.max_positions, D,
-                     m->h);
-  GILL_CHECK_HIP(hipGetLastError());
-  // TfmRun::layers at T = 1, self-attention as projection -> decode attention with append -> out-projection
-  const Tfm& t = m->tfm;
-  const TfmRun run{t, s};
-  const TfmLayer* L = m->layers.data();
-  if (n > 0) GILL_TRY(layernorm_launch(m->h, 1, L[0].ln1g, L[0].ln1b, t.nbuf, B, D, 1e-5f, s));
-  const bool w8 = gill_opt_decode_uses_w8(m, B) != 0;
-  const int F = t.F;
-  for (int i = 0; i < n; ++i) {
-    const TfmLayer* next = i + 1 < n ? &L[i + 1] : nullptr;
-    // the four linears on the e4m3 bytes (linear_w8.hip): the wide ones finish in the kernel, the narrow ones through the reducer + LayerNorm
-    auto lin8 = [&](const bf16_t* A, const unsigned char* W8, const float* sc, const float* b, int N, int K, const float* resid, int act, void* out,
-                    bool out_f32, int splitk, const float* g, const float* be, bf16_t* ln_out) -> int {
-      return tfm_linear_w8_launch(A, B, W8, sc, b, N, K, resid, act, out, out_f32, splitk, t.splitk_ws, t.splitk_ws_floats, g, be, ln_out, s);
-    };
-    if (w8) GILL_TRY(lin8(t.nbuf, L[i].qkv8, L[i].sqkv, L[i].bqkv, 3 * D, D, nullptr, ACT_NONE, t.q, false, 1, nullptr, nullptr, nullptr));
-    else GILL_TRY(run.linear(t.nbuf, B, L[i].wqkv, L[i].blk_qkv, L[i].bqkv, 3 * D, D, nullptr, ACT_NONE, t.q, false));
-    AttnDecodeArgs a;
-    a.q = t.q; a.k = t.q + D; a.v = t.q + 2 * D; a.ld = 3 * D;
-    a.K = m->cache[i].k; a.Vt = m->cache[i].vt; a.lens = lens_dev; a.O = t.o; a.ldo = D; a.flags = m->dec_flags;
-    a.B = B; a.H = t.H; a.dp = t.dp; a.dpv = t.dpv; a.pitch = m->cache[i].pad;
-    a.qscale = 1.4426950408889634f / sqrtf((float)t.dp);
-    GILL_TRY(attention_decode_launch(a, s));
-    if (w8) {
-      GILL_TRY(lin8(t.o, L[i].o8, L[i].so, L[i].bo, D, D, m->h, ACT_NONE, m->h, true, 0, L[i].ln2g, L[i].ln2b, t.nbuf));
-      GILL_TRY(lin8(t.nbuf, L[i].w18, L[i].s1, L[i].b1, F, D, nullptr, ACT_RELU, t.ff, false, 1, nullptr, nullptr, nullptr));
-      GILL_TRY(lin8(t.ff, L[i].w28, L[i].s2, L[i].b2, D, F, m->h, ACT_NONE, m->h, true, 0, next ? next->ln1g : nullptr, next ? next->ln1b : nullptr,
-                    next ? t.nbuf : nullptr));
-      continue;
-    }
-    GILL_TRY(run.linear(t.o, B, L[i].wo, L[i].blk_o, L[i].bo, D, D, m->h, ACT_NONE, m->h, true, L[i].ln2g, L[i].ln2b, t.nbuf));
-    GILL_TRY(run.ffn(m->h, B, L[i], ACT_RELU, next ? next->ln1g : nullptr, next ? next->ln1b : nullptr));
-  }
-  GILL_TRY(layernorm_f32out_launch(m->h, 1, m->lnfg, m->lnfb, hidden_out, B, D, 1e-5f, s));
+  GILL_TRY(opt_add_pos(m, new_embeds_bf16, lens_dev, B, 1, 0, s));
+  const TfmDecode dec{lens_dev, m->dec_flags};
+  GILL_TRY(m->run_layers(B, 1, s, 0, &dec));
+  GILL_TRY(layernorm_f32out_launch(m->h, 1, m->lnfg, m->lnfb, hidden_out, B, m->cfg.hidden_size, 1e-5f, s));
   return 0;
 }
 
@@ -552,7 +464,7 @@ extern "C" int gill_opt_prefill_ids(gill_opt* m, const int64_t* ids, int B, int 
   const int D = m->cfg.hidden_size;
   GILL_TRY(opt_ensure_cache(m));
   // rows of embed_tokens (id >= 0) or of extra_rows (id < 0) + positions 2 + t -> the fp32 stream, then the cached forward at past_len = 0
-  GILL_TRY(img_hidden_embed(m, ids, (const bf16_t*)extra_rows_bf16, n_extra, m->pos, B, Tmax, s));
+  GILL_TRY(embed_tokens_launch(ids, m->embed, m->cfg.vocab_size, (const bf16_t*)extra_rows_bf16, n_extra, m->pos, 2, B, Tmax, D, m->h, s));
   GILL_TRY(m->run_layers(B, Tmax, s, 0));
   GILL_TRY(layernorm_f32out_launch(m->h, 1, m->lnfg, m->lnfb, hidden_out, B * Tmax, D, 1e-5f, s));
   return 0;

@@ -1,23 +1,26 @@
 // The pre-LayerNorm transformer block the OPT, CLIP vision, CLIP text and mapper engines share:
 //   h += out_proj(attn(q, k, v = qkv(LN1(h))))       q scaled by head_dim^-0.5
 //   h += fc2(act(fc1(LN2(h))))
-// fp32 residual stream, bf16 GEMM operands, fp32 accumulation; attention is the shared flash kernel.  One layer struct, one
-// weight loader, one workspace and one runner; an engine keeps what is particular to it (embeddings, caches, final norms) and
-// sets the switches of struct Tfm.  Nothing here allocates or builds strings per launch.
+// fp32 residual stream, bf16 GEMM operands, fp32 accumulation; attention is the shared flash kernel.  One matrix struct, one layer
+// struct, one weight loader, one workspace and one runner with the only layer loop (TfmRun::layers); an engine keeps what is particular
+// to it (embeddings, caches, final norms) and sets the switches of struct Tfm.  OPT's ragged decode step is that loop with a TfmDecode
+// argument (decode attention with append in place of the flash kernel), its fp8-weight mode the same loop with TfmRun::use_w8.
+// Nothing here allocates or builds strings per launch.
 #pragma once
 #include "engine_util.h"
 
+// One matrix of the block, y = x . W^T + b: the bf16 weights [N][K], row-major or 64 x 64-blocked (blk: gemm_stream64_weights, the STREAM64
+// layout), the bias (may be null) and, in the OPT engine's w8 mode only, the same matrix as e4m3 bytes in linear_w8.hip's order with one
+// power-of-two scale per row (tfm_quantize_layer_w8; w then holds bytes * scale).  TfmRun::linear picks the kernel.
+struct TfmMat {
+  bf16_t* w = nullptr; int blk = 0; float* b = nullptr;
+  int N = 0, K = 0;
+  unsigned char* w8 = nullptr; float* scale = nullptr;
+};
+
 struct TfmLayer {
-  bf16_t* wqkv = nullptr; float* bqkv = nullptr;   // [3D][D] rows: q | k | v
-  bf16_t* wo = nullptr; float* bo = nullptr;
-  bf16_t* w1 = nullptr; float* b1 = nullptr;
-  bf16_t* w2 = nullptr; float* b2 = nullptr;
+  TfmMat qkv, o, fc1, fc2;   // qkv: [3D][D] rows q | k | v
   float *ln1g = nullptr, *ln1b = nullptr, *ln2g = nullptr, *ln2b = nullptr;
-  int blk_qkv = 0, blk_o = 0, blk_1 = 0, blk_2 = 0;   // matrix stored 64 x 64-blocked (gemm_stream64_weights: the STREAM64 layout)
-  // the four matrices as e4m3 bytes in linear_w8.hip's order with one power-of-two scale per row (tfm_quantize_layer_w8: the OPT engine's w8
-  // mode; the bf16 matrices above then hold bytes * scale); null for every other engine
-  unsigned char *qkv8 = nullptr, *o8 = nullptr, *w18 = nullptr, *w28 = nullptr;
-  float *sqkv = nullptr, *so = nullptr, *s1 = nullptr, *s2 = nullptr;
 };
 
 // Tensor names under a layer's prefix, each up to and including the separator in front of "weight" / "bias".
@@ -29,10 +32,10 @@ struct TfmNames {
 int tfm_load_layer(const WeightTable& wt, DevPool& pool, const std::string& prefix, const TfmNames& names, int D, int F, bool stream64,
                    TfmLayer* L, hipStream_t s);
 
-// A loaded layer's four matrices -> e4m3 bytes + scales (new members of L), and the bf16 matrices replaced, in their own layouts, by the
+// A loaded layer's four matrices -> e4m3 bytes + scales (TfmMat::w8 / scale), and the bf16 matrices replaced, in their own layouts, by the
 // dequantised values: the quantised model is an exact bf16 model and every bf16 kernel runs on it unchanged.  q | k | v are quantised as the stacked
 // [3D][D] matrix (a row's scale is its own either way).  About 1.5 x the layer's bf16 bytes afterwards.
-int tfm_quantize_layer_w8(DevPool& pool, int D, int F, TfmLayer* L, hipStream_t s);
+int tfm_quantize_layer_w8(DevPool& pool, TfmLayer* L, hipStream_t s);
 // tfm_linear_launch on the e4m3 bytes (M <= W8_MAX_ROWS).  ln_out: an in-place residual GEMM into the fp32 stream (out == resid, fp32, no act, a bias)
 // leaves partials [sk][M][N] and ends in opt_reduce_ln_launch, at any sk; without it the kernel's own epilogue (sk == 1) or its finishing pass.
 // splitk as W8Args::splitk.
@@ -59,30 +62,40 @@ struct TfmKv { bf16_t* k = nullptr; bf16_t* vt = nullptr; int pad = 0; };
 // split-K reducer + bias + fp32 residual (h, updated in place) + LayerNorm -> nb (opt_reduce_ln_kernel): ws [sk][M][D] fp32, D % 4 == 0, D <= 8192
 int opt_reduce_ln_launch(const float* ws, int sk, int M, int D, const float* bias, float* h, const float* g, const float* b, bf16_t* nb,
                          float eps, hipStream_t s);
-// TfmRun::linear with the split factor, its workspace and the fuse_ln switch stated (the operator tests force them): fuse_ln and a split-K
-// in-place residual GEMM into the fp32 stream -> partials + opt_reduce_ln_launch, every other launch -> the GEMM (its own reducer) + layernorm_launch
+// TfmRun::linear's bf16 launch with the split factor, its workspace and the fuse_ln switch stated (the operator tests force them): fuse_ln and a
+// split-K in-place residual GEMM into the fp32 stream -> partials + opt_reduce_ln_launch, every other launch -> the GEMM (its own reducer) +
+// layernorm_launch.  This and tfm_linear_w8_launch have two callers each: TfmRun::linear and the operator entries of capi.hip.
 int tfm_linear_launch(const bf16_t* A, int M, const bf16_t* W, int blk, const float* b, int N, int K, const float* resid, int act, void* out,
                       bool out_f32, int splitk, float* ws, bool fuse_ln, const float* ln_g, const float* ln_b, bf16_t* ln_out, hipStream_t s);
+
+// The ragged decode step as a mode of self_attn / layers (T = 1, a cache): row b is the token at position lens[b] of sequence b.  Self-attention is
+// then a plain QKV linear into Tfm::q as [B][3D] -> attention_decode_launch (appends the row's K / V at lens[b], clamps a length beyond the cache
+// and raises flags[b]) -> the out-projection.
+struct TfmDecode { const int32_t* lens = nullptr; int32_t* flags = nullptr; };
 
 struct TfmRun {
   const Tfm& t;
   hipStream_t s;
+  bool use_w8 = false;      // linear() runs a matrix that has e4m3 bytes on them (the caller has checked M <= W8_MAX_ROWS)
   int splitk(int M, int N, int K, int act, int blk) const;
   // y = act(A . W^T + b [+ resid_f32]); out fp32 or bf16.  ln_g / ln_b / ln_out: the LayerNorm that consumes the result (in-place
-  // residual GEMMs into the fp32 stream: out == resid).  With Tfm::fuse_ln a split-K launch hands it to the reducer
-  // (opt_reduce_ln_kernel); every other launch is followed by the stand-alone pass.
-  int linear(const bf16_t* A, int M, const bf16_t* W, int blk, const float* b, int N, int K, const float* resid, int act, void* out,
-             bool out_f32, const float* ln_g = nullptr, const float* ln_b = nullptr, bf16_t* ln_out = nullptr) const;
-  // scatter nseg segments of a projection into the head-major attention operands; seg_base: 0 = q(, k, v); 1 = k, v only
-  int qkv(const bf16_t* A, int B, int ntok, const bf16_t* W, const float* b, int nseg, int seg_base, int npad_q, int npad_kv,
-          bf16_t* K, bf16_t* Vt, int kv_tok_offset, int blk) const;
+  // residual GEMMs into the fp32 stream: out == resid).  bf16 weights: with Tfm::fuse_ln a split-K launch hands it to the reducer
+  // (opt_reduce_ln_kernel); every other launch is followed by the stand-alone pass.  e4m3 bytes (use_w8): unsplit without a residual, the
+  // launcher's own split factor with one, and the LayerNorm always through the reducer.
+  int linear(const bf16_t* A, int M, const TfmMat& m, const float* resid, int act, void* out, bool out_f32, const float* ln_g = nullptr,
+             const float* ln_b = nullptr, bf16_t* ln_out = nullptr) const;
+  // scatter the segments seg_base .. seg_base + nseg - 1 of the packed projection m (q | k | v row blocks of D) into the head-major attention operands
+  int qkv(const bf16_t* A, int B, int ntok, const TfmMat& m, int nseg, int seg_base, int npad_q, int npad_kv, bf16_t* K, bf16_t* Vt,
+          int kv_tok_offset) const;
   int attend(int B, int nq, int nkv, int npad_q, int npad_kv, const bf16_t* K, const bf16_t* Vt, bool causal) const;
   // the two sub-blocks over the stream h (B * T rows); nbuf holds their LayerNorm of h on entry and, with next_g, that of next_g / next_b on exit.
-  // kv: the T rows are the tokens past .. past + T - 1 of each sequence; their K / Vt are appended to the cache and they attend to it
+  // kv: the T rows are the tokens past .. past + T - 1 of each sequence; their K / Vt are appended to the cache and they attend to it.
+  // dec (needs kv, T == 1): every row at its own length instead of `past`
   int self_attn(float* h, int B, int T, const TfmLayer& L, bool causal, const float* next_g, const float* next_b, const TfmKv* kv = nullptr,
-                int past = 0) const;
+                int past = 0, const TfmDecode* dec = nullptr) const;
   int ffn(float* h, int rows, const TfmLayer& L, int act, const float* next_g = nullptr, const float* next_b = nullptr) const;
   // n layers: LN1 stand-alone for the first, every later LayerNorm rides on the GEMM in front of it (see linear).
   // kv: one cache per layer holding `past` tokens (OPT's cached decode); nullptr: plain forward over T tokens
-  int layers(float* h, const TfmLayer* L, int n, int B, int T, int act, bool causal, const TfmKv* kv = nullptr, int past = 0) const;
+  int layers(float* h, const TfmLayer* L, int n, int B, int T, int act, bool causal, const TfmKv* kv = nullptr, int past = 0,
+             const TfmDecode* dec = nullptr) const;
 };

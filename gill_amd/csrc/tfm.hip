@@ -1,5 +1,5 @@
-// Shared pre-LayerNorm transformer block (tfm.h): layer weight loader, workspace, and the runner whose launches are the OPT,
-// CLIP vision, CLIP text and mapper layer loops.
+// Shared pre-LayerNorm transformer block (tfm.h): layer weight loader and w8 quantiser, workspace, and the runner whose launches are the OPT
+// (forward, cached forward and the ragged decode step, on bf16 weights or e4m3 bytes), CLIP vision, CLIP text and mapper layer loops.
 #include "tfm.h"
 
 // REDUCE + RESIDUAL + LAYERNORM.  The narrow GEMMs of a layer (out_proj, fc2: N = D) run split-K; their reducer is also the natural place
@@ -90,53 +90,48 @@ int opt_reduce_ln_launch(const float* ws, int sk, int M, int D, const float* bia
 
 int tfm_load_layer(const WeightTable& wt, DevPool& pool, const std::string& prefix, const TfmNames& names, int D, int F, bool stream64,
                    TfmLayer* L, hipStream_t s) {
-  if (stream64) {
-    L->blk_qkv = gemm_stream64_weights(3 * D, D); L->blk_o = gemm_stream64_weights(D, D);
-    L->blk_1 = gemm_stream64_weights(F, D); L->blk_2 = gemm_stream64_weights(D, F);
-  }
   auto load_w = [&](const std::string& name, int N, int K, int blk, bf16_t* dst) -> int {
     const gill_tensor* t;
     GILL_TRY(wt.get(name + "weight", (int64_t)N * K, &t));
     return blk ? convert_to_bf16_blk64_launch(t->data, t->dtype, N, K, dst, s) : convert_to_bf16_launch(t->data, t->dtype, (int64_t)N * K, dst, s);
   };
-  auto linear_w = [&](const char* name, int N, int K, int blk, bf16_t** w, float** b) -> int {
-    GILL_TRY(pool.alloc(w, (size_t)N * K, false));
-    GILL_TRY(load_w(prefix + name, N, K, blk, *w));
-    return load_f32(wt, pool, prefix + name + "bias", N, b, s);
+  // geometry, layout and the owned bf16 matrix of m; the bias with it unless the caller fills its own
+  auto mat = [&](TfmMat* m, const char* name, int N, int K) -> int {
+    m->N = N; m->K = K; m->blk = stream64 ? gemm_stream64_weights(N, K) : 0;
+    GILL_TRY(pool.alloc(&m->w, (size_t)N * K, false));
+    if (!name) return pool.alloc(&m->b, (size_t)N, false);
+    GILL_TRY(load_w(prefix + name, N, K, m->blk, m->w));
+    return load_f32(wt, pool, prefix + name + "bias", N, &m->b, s);
   };
   auto norm_w = [&](const char* name, float** g, float** b) -> int {
     GILL_TRY(load_f32(wt, pool, prefix + name + "weight", D, g, s));
     return load_f32(wt, pool, prefix + name + "bias", D, b, s);
   };
-  GILL_TRY(pool.alloc(&L->wqkv, (size_t)3 * D * D, false));
-  GILL_TRY(pool.alloc(&L->bqkv, (size_t)3 * D, false));
+  GILL_TRY(mat(&L->qkv, nullptr, 3 * D, D));
   // q | k | v stacked into [3D][D], or one packed in_proj copied whole (blocked or row-major, a [D][D] third of the stacked matrix is a
   // contiguous range of whole 64-row blocks)
   const int parts = names.qkv[1] ? 3 : 1, rows = 3 * D / parts;
   for (int j = 0; j < parts; ++j) {
     const gill_tensor* t;
-    GILL_TRY(load_w(prefix + names.qkv[j], rows, D, L->blk_qkv, L->wqkv + (size_t)j * rows * D));
+    GILL_TRY(load_w(prefix + names.qkv[j], rows, D, L->qkv.blk, L->qkv.w + (size_t)j * rows * D));
     GILL_TRY(wt.get(prefix + names.qkv[j] + "bias", rows, &t));
-    GILL_TRY(convert_to_f32_launch(t->data, t->dtype, rows, L->bqkv + (size_t)j * rows, s));
+    GILL_TRY(convert_to_f32_launch(t->data, t->dtype, rows, L->qkv.b + (size_t)j * rows, s));
   }
-  GILL_TRY(linear_w(names.o, D, D, L->blk_o, &L->wo, &L->bo));
-  GILL_TRY(linear_w(names.fc1, F, D, L->blk_1, &L->w1, &L->b1));
-  GILL_TRY(linear_w(names.fc2, D, F, L->blk_2, &L->w2, &L->b2));
+  GILL_TRY(mat(&L->o, names.o, D, D));
+  GILL_TRY(mat(&L->fc1, names.fc1, F, D));
+  GILL_TRY(mat(&L->fc2, names.fc2, D, F));
   GILL_TRY(norm_w(names.ln1, &L->ln1g, &L->ln1b));
   return norm_w(names.ln2, &L->ln2g, &L->ln2b);
 }
 
-int tfm_quantize_layer_w8(DevPool& pool, int D, int F, TfmLayer* L, hipStream_t s) {
-  auto quant = [&](bf16_t* w, int blk, int N, int K, unsigned char** w8, float** sc) -> int {
-    GILL_TRY(pool.alloc(w8, (size_t)N * K, false));
-    GILL_TRY(pool.alloc(sc, (size_t)N, false));
-    GILL_TRY(w8_quant_launch(w, blk, N, K, *w8, *sc, s));
-    return w8_dequant_launch(*w8, *sc, N, K, blk, w, s);
-  };
-  GILL_TRY(quant(L->wqkv, L->blk_qkv, 3 * D, D, &L->qkv8, &L->sqkv));
-  GILL_TRY(quant(L->wo, L->blk_o, D, D, &L->o8, &L->so));
-  GILL_TRY(quant(L->w1, L->blk_1, F, D, &L->w18, &L->s1));
-  return quant(L->w2, L->blk_2, D, F, &L->w28, &L->s2);
+int tfm_quantize_layer_w8(DevPool& pool, TfmLayer* L, hipStream_t s) {
+  for (TfmMat* m : {&L->qkv, &L->o, &L->fc1, &L->fc2}) {
+    GILL_TRY(pool.alloc(&m->w8, (size_t)m->N * m->K, false));
+    GILL_TRY(pool.alloc(&m->scale, (size_t)m->N, false));
+    GILL_TRY(w8_quant_launch(m->w, m->blk, m->N, m->K, m->w8, m->scale, s));
+    GILL_TRY(w8_dequant_launch(m->w8, m->scale, m->N, m->K, m->blk, m->w, s));
+  }
+  return 0;
 }
 
 int tfm_linear_w8_launch(const bf16_t* A, int M, const unsigned char* W8, const float* scale, const float* b, int N, int K, const float* resid,
@@ -195,21 +190,27 @@ int tfm_linear_launch(const bf16_t* A, int M, const bf16_t* W, int blk, const fl
   return 0;
 }
 
-int TfmRun::linear(const bf16_t* A, int M, const bf16_t* W, int blk, const float* b, int N, int K, const float* resid, int act, void* out,
-                   bool out_f32, const float* ln_g, const float* ln_b, bf16_t* ln_out) const {
-  return tfm_linear_launch(A, M, W, blk, b, N, K, resid, act, out, out_f32, splitk(M, N, K, act, blk), t.splitk_ws, t.fuse_ln, ln_g, ln_b, ln_out, s);
+int TfmRun::linear(const bf16_t* A, int M, const TfmMat& m, const float* resid, int act, void* out, bool out_f32, const float* ln_g,
+                   const float* ln_b, bf16_t* ln_out) const {
+  // the e4m3 bytes (linear_w8.hip): the wide matrices (no residual) finish in the kernel, the narrow in-place ones split by the launcher's rule
+  if (use_w8 && m.w8)
+    return tfm_linear_w8_launch(A, M, m.w8, m.scale, m.b, m.N, m.K, resid, act, out, out_f32, resid ? 0 : 1, t.splitk_ws, t.splitk_ws_floats, ln_g,
+                                ln_b, ln_out, s);
+  return tfm_linear_launch(A, M, m.w, m.blk, m.b, m.N, m.K, resid, act, out, out_f32, splitk(M, m.N, m.K, act, m.blk), t.splitk_ws, t.fuse_ln, ln_g,
+                           ln_b, ln_out, s);
 }
 
-int TfmRun::qkv(const bf16_t* A, int B, int ntok, const bf16_t* W, const float* b, int nseg, int seg_base, int npad_q, int npad_kv,
-                bf16_t* K, bf16_t* Vt, int kv_tok_offset, int blk) const {
+int TfmRun::qkv(const bf16_t* A, int B, int ntok, const TfmMat& m, int nseg, int seg_base, int npad_q, int npad_kv, bf16_t* K, bf16_t* Vt,
+                int kv_tok_offset) const {
   GemmArgs g;
-  g.M = B * ntok; g.N = nseg * t.D; g.K = t.D; g.K1 = t.D; g.A = A; g.lda = t.D; g.W = W; g.bias = b;
+  g.M = B * ntok; g.N = nseg * t.D; g.K = t.D; g.K1 = t.D; g.A = A; g.lda = t.D;
+  g.W = m.w + (size_t)seg_base * t.D * t.D; g.bias = m.b + (size_t)seg_base * t.D;
   g.out_mode = OUT_QKV; g.Cq = t.q; g.Ck = K; g.Cvt = Vt;
   g.heads = t.H; g.dp = t.dp; g.dpv = t.dpv; g.ntok = ntok; g.ntok_pad_q = npad_q; g.ntok_pad_kv = npad_kv;
   g.seg_base = seg_base; g.kv_tok_offset = kv_tok_offset;
   g.qscale = 1.4426950408889634f / sqrtf((float)t.dp);   // log2(e) / sqrt(head dim): HF scales q by head_dim^-0.5, attention.hip works in log2
-  g.w_blk64 = blk;
-  g.splitk = t.split_qkv ? splitk(g.M, g.N, g.K, 0, blk) : 1;
+  g.w_blk64 = m.blk;
+  g.splitk = t.split_qkv ? splitk(g.M, g.N, g.K, 0, m.blk) : 1;
   g.ws = t.splitk_ws;
   return gemm_launch(g, s);
 }
@@ -223,25 +224,36 @@ int TfmRun::attend(int B, int nq, int nkv, int npad_q, int npad_kv, const bf16_t
 }
 
 int TfmRun::self_attn(float* h, int B, int T, const TfmLayer& L, bool causal, const float* next_g, const float* next_b, const TfmKv* kv,
-                      int past) const {
-  const int Tpad = round_up(T, 32), kvpad = kv ? kv->pad : Tpad;
-  bf16_t* kbuf = kv ? kv->k : t.k;
-  bf16_t* vbuf = kv ? kv->vt : t.vt;
-  GILL_TRY(qkv(t.nbuf, B, T, L.wqkv, L.bqkv, 3, 0, Tpad, kvpad, kbuf, vbuf, past, L.blk_qkv));
-  GILL_TRY(attend(B, T, past + T, Tpad, kvpad, kbuf, vbuf, causal));
-  return linear(t.o, B * T, L.wo, L.blk_o, L.bo, t.D, t.D, h, ACT_NONE, h, true, next_g, next_b, next_g ? t.nbuf : nullptr);
+                      int past, const TfmDecode* dec) const {
+  if (dec) {
+    GILL_REQUIRE(kv && T == 1, "decode attention: one token per row and a cache");
+    GILL_TRY(linear(t.nbuf, B, L.qkv, nullptr, ACT_NONE, t.q, false));
+    AttnDecodeArgs a;
+    a.q = t.q; a.k = t.q + t.D; a.v = t.q + 2 * t.D; a.ld = 3 * t.D;
+    a.K = kv->k; a.Vt = kv->vt; a.lens = dec->lens; a.O = t.o; a.ldo = t.D; a.flags = dec->flags;
+    a.B = B; a.H = t.H; a.dp = t.dp; a.dpv = t.dpv; a.pitch = kv->pad;
+    a.qscale = 1.4426950408889634f / sqrtf((float)t.dp);
+    GILL_TRY(attention_decode_launch(a, s));
+  } else {
+    const int Tpad = round_up(T, 32), kvpad = kv ? kv->pad : Tpad;
+    bf16_t* kbuf = kv ? kv->k : t.k;
+    bf16_t* vbuf = kv ? kv->vt : t.vt;
+    GILL_TRY(qkv(t.nbuf, B, T, L.qkv, 3, 0, Tpad, kvpad, kbuf, vbuf, past));
+    GILL_TRY(attend(B, T, past + T, Tpad, kvpad, kbuf, vbuf, causal));
+  }
+  return linear(t.o, B * T, L.o, h, ACT_NONE, h, true, next_g, next_b, next_g ? t.nbuf : nullptr);
 }
 
 int TfmRun::ffn(float* h, int rows, const TfmLayer& L, int act, const float* next_g, const float* next_b) const {
-  GILL_TRY(linear(t.nbuf, rows, L.w1, L.blk_1, L.b1, t.F, t.D, nullptr, act, t.ff, false));
-  return linear(t.ff, rows, L.w2, L.blk_2, L.b2, t.D, t.F, h, ACT_NONE, h, true, next_g, next_b, next_g ? t.nbuf : nullptr);
+  GILL_TRY(linear(t.nbuf, rows, L.fc1, nullptr, act, t.ff, false));
+  return linear(t.ff, rows, L.fc2, h, ACT_NONE, h, true, next_g, next_b, next_g ? t.nbuf : nullptr);
 }
 
-int TfmRun::layers(float* h, const TfmLayer* L, int n, int B, int T, int act, bool causal, const TfmKv* kv, int past) const {
+int TfmRun::layers(float* h, const TfmLayer* L, int n, int B, int T, int act, bool causal, const TfmKv* kv, int past, const TfmDecode* dec) const {
   if (n > 0) GILL_TRY(layernorm_launch(h, 1, L[0].ln1g, L[0].ln1b, t.nbuf, B * T, t.D, 1e-5f, s));
   for (int i = 0; i < n; ++i) {
     const TfmLayer* next = i + 1 < n ? &L[i + 1] : nullptr;
-    GILL_TRY(self_attn(h, B, T, L[i], causal, L[i].ln2g, L[i].ln2b, kv ? &kv[i] : nullptr, past));
+    GILL_TRY(self_attn(h, B, T, L[i], causal, L[i].ln2g, L[i].ln2b, kv ? &kv[i] : nullptr, past, dec));
     GILL_TRY(ffn(h, B * T, L[i], act, next ? next->ln1g : nullptr, next ? next->ln1b : nullptr));
   }
   return 0;
