@@ -86,6 +86,7 @@ SYMBOLS: Dict[str, Tuple[object, List[object]]] = {
   "gill_opt_create_ex": (_i, [C.POINTER(_vp), C.POINTER(gill_opt_config), C.POINTER(gill_tensor), _i, _i]),
   "gill_opt_weight_mode": (_i, [_vp]),
   "gill_opt_decode_uses_w8": (_i, [_vp, _i]),
+  "gill_opt_cached_uses_w8": (_i, [_vp, _i, _i, _i]),
   "gill_w8_max_rows": (_i, []),
   "gill_op_w8_quant": (_i, [_vp, _i, _i, _vp, _vp, _vp]),
   "gill_op_w8_dequant": (_i, [_vp, _vp, _i, _i, _i, _vp, _vp]),
@@ -105,6 +106,7 @@ SYMBOLS: Dict[str, Tuple[object, List[object]]] = {
   "gill_opt_draw_token": (_i, [_vp, _vp, _i, C.POINTER(gill_decode_rule), C.POINTER(gill_decode_sampler), _vp, _i, _i, _vp, _vp, _vp]),
   "gill_decode_uniforms": (_i, [C.c_uint64, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.POINTER(C.c_float)]),
   "gill_attention_decode": (_i, [_vp, _vp, _vp, _i, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp, _vp]),
+  "gill_attention_append": (_i, [_vp, _vp, _vp, _i, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp, _vp]),
   "gill_opt_decode_step": (_i, [_vp, _vp, _vp, _i, _i, _vp, _vp]),
   "gill_opt_prefill_ids": (_i, [_vp, _vp, _i, _i, _vp, _i, _vp, _vp]),
   "gill_opt_next_token_ragged": (_i, [_vp, _vp, _i, C.POINTER(gill_decode_rule), _i, C.POINTER(gill_decode_sampler), _vp, _vp, _vp, _i, _vp,

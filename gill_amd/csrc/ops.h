@@ -190,6 +190,15 @@ struct AttnDecodeArgs {
 };
 int attention_decode_launch(const AttnDecodeArgs& a, hipStream_t s);
 
+// Decode attention with a multi-token append (attention_append.hip): row b brings nq consecutive new tokens, 1 <= nq <= 16, at its own cache length
+// n = lens[b] (clamped into [0, pitch - nq]; a clamp sets flags[b]).  q / k / v / O hold B * nq rows, row b * nq + i the token n + i of sequence b.
+// Token i is stored at slot n + i and attends to K[0 .. n - 1] and the tokens 0 .. i of its block; slots beyond are never read as data.  A row's O and
+// cache are, bit for bit, those of nq successive attention_decode_launch calls with lens = n + i; nq == 1 is that launch.
+struct AttnAppendArgs : AttnDecodeArgs {
+  int nq = 1;
+};
+int attention_append_launch(const AttnAppendArgs& a, hipStream_t s);
+
 
 // The feed-forward sub-block + proj_out + outer residual of a level-0 transformer block (C = 320) as one kernel (ffn.hip):
 //   out = [Wp.W2 | Wp] . [ value * gelu(gate) | t ] + bo + resid,  [value | gate] = W1' . LN(t) + b1'  (LN from the row-sum planes).

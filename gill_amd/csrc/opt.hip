@@ -30,6 +30,7 @@ struct gill_opt {
   // KV cache of gill_opt_forward_cached (allocated at its first call): per layer K [B][H][Tcap][dp], Vt [B][H][dpv][Tcap]
   std::vector<TfmKv> cache;
   int32_t* dec_flags = nullptr;   // [max_batch]: length clamps of gill_opt_decode_step's attention, folded into the rows' flags by the ragged decision
+  int32_t* cached_lens = nullptr; // [max_batch]: past_len per row, filled on the stream by gill_opt_forward_cached where it runs on the e4m3 bytes
   // scoring workspace of gill_opt_forward_loss (allocated at its first call): the final LayerNorm of every row, the shifted targets, the
   // per-row results and the partials of lmloss.hip
   bf16_t* xn_bf = nullptr;      // [B*T][D]
@@ -39,11 +40,11 @@ struct gill_opt {
   void* loss_ws = nullptr;
   float* ll_f32 = nullptr;      // [B][D]: the rows of last_logit_out after the final LayerNorm
   // layers over the fp32 stream h (B*T rows): ReLU, causal.  past < 0: plain forward over T tokens.  past >= 0: the T rows are
-  // the tokens past .. past+T-1 of each sequence; their K/V are appended to the cache and they attend to it.  dec (T == 1): the ragged
-  // decode step, every row at its own device length, on the e4m3 bytes where gill_opt_decode_uses_w8() says so.
-  int run_layers(int B, int T, hipStream_t s, int past = -1, const TfmDecode* dec = nullptr) const {
-    return TfmRun{tfm, s, dec && gill_opt_decode_uses_w8(this, B)}.layers(h, layers.data(), (int)layers.size(), B, T, ACT_RELU, true,
-                                                                          past >= 0 ? cache.data() : nullptr, past >= 0 ? past : 0, dec);
+  // the tokens past .. past+T-1 of each sequence; their K/V are appended to the cache and they attend to it.  dec: the decode step, every
+  // row's T tokens at its own device length (T == 1: the ragged step); w8: on the e4m3 bytes (the caller's gill_opt_*_uses_w8() says so).
+  int run_layers(int B, int T, hipStream_t s, int past = -1, const TfmDecode* dec = nullptr, bool w8 = false) const {
+    return TfmRun{tfm, s, w8}.layers(h, layers.data(), (int)layers.size(), B, T, ACT_RELU, true, past >= 0 ? cache.data() : nullptr,
+                                     past >= 0 ? past : 0, dec);
   }
 };
 
@@ -92,6 +93,11 @@ extern "C" int gill_opt_weight_mode(const gill_opt* m) { return m ? m->weight_mo
 // the decode step's branch, and the host-only query of it
 extern "C" int gill_opt_decode_uses_w8(const gill_opt* m, int B) {
   return m && m->weight_mode == GILL_OPT_W8 && B >= 1 && B <= W8_MAX_ROWS ? 1 : 0;
+}
+
+// the cached forward's branch, and the host-only query of it
+extern "C" int gill_opt_cached_uses_w8(const gill_opt* m, int B, int T_new, int past_len) {
+  return m && m->weight_mode == GILL_OPT_W8 && past_len > 0 && B >= 1 && T_new >= 1 && (int64_t)B * T_new <= W8_MAX_ROWS ? 1 : 0;
 }
 
 extern "C" int gill_w8_max_rows(void) { return W8_MAX_ROWS; }
@@ -182,7 +188,13 @@ static int opt_ensure_cache(gill_opt* m) {
     GILL_TRY(m->pool.alloc(&c.k, kn, true));
     GILL_TRY(m->pool.alloc(&c.vt, vn, true));
   }
+  GILL_TRY(m->pool.alloc(&m->cached_lens, (size_t)m->cfg.max_batch, true));
   return m->pool.alloc(&m->dec_flags, (size_t)m->cfg.max_batch, true);
+}
+
+__global__ void opt_fill_lens_kernel(int32_t* __restrict__ lens, int B, int v) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i < B) lens[i] = v;
 }
 
 extern "C" int gill_opt_forward_cached(gill_opt* m, const void* inputs_embeds_bf16, int B, int T_new, int past_len,
@@ -195,7 +207,16 @@ extern "C" int gill_opt_forward_cached(gill_opt* m, const void* inputs_embeds_bf
   const int D = m->cfg.hidden_size;
   GILL_TRY(opt_ensure_cache(m));
   GILL_TRY(opt_add_pos(m, inputs_embeds_bf16, nullptr, B * T_new, T_new, 2 + past_len, s));
-  GILL_TRY(m->run_layers(B, T_new, s, past_len));
+  if (gill_opt_cached_uses_w8(m, B, T_new, past_len)) {
+    // at most 16 rows on a w8 handle: the decode mode of the layer loop on the e4m3 bytes, every row at length past_len (checked above against
+    // max_seq <= the cache pitch: no clamp can occur, so no flags)
+    hipLaunchKernelGGL(opt_fill_lens_kernel, dim3(cdiv(B, 64)), dim3(64), 0, s, m->cached_lens, B, past_len);
+    GILL_CHECK_HIP(hipGetLastError());
+    const TfmDecode dec{m->cached_lens, nullptr};
+    GILL_TRY(m->run_layers(B, T_new, s, 0, &dec, true));
+  } else {
+    GILL_TRY(m->run_layers(B, T_new, s, past_len));
+  }
   GILL_TRY(layernorm_f32out_launch(m->h, 1, m->lnfg, m->lnfb, hidden_out, B * T_new, D, 1e-5f, s));
   return 0;
 }
@@ -449,7 +470,7 @@ extern "C" int gill_opt_decode_step(gill_opt* m, const void* new_embeds_bf16, co
   GILL_TRY(opt_ensure_cache(m));
   GILL_TRY(opt_add_pos(m, new_embeds_bf16, lens_dev, B, 1, 0, s));
   const TfmDecode dec{lens_dev, m->dec_flags};
-  GILL_TRY(m->run_layers(B, 1, s, 0, &dec));
+  GILL_TRY(m->run_layers(B, 1, s, 0, &dec, gill_opt_decode_uses_w8(m, B) != 0));
   GILL_TRY(layernorm_f32out_launch(m->h, 1, m->lnfg, m->lnfb, hidden_out, B, m->cfg.hidden_size, 1e-5f, s));
   return 0;
 }

@@ -3,8 +3,9 @@
 //   h += fc2(act(fc1(LN2(h))))
 // fp32 residual stream, bf16 GEMM operands, fp32 accumulation; attention is the shared flash kernel.  One matrix struct, one layer
 // struct, one weight loader, one workspace and one runner with the only layer loop (TfmRun::layers); an engine keeps what is particular
-// to it (embeddings, caches, final norms) and sets the switches of struct Tfm.  OPT's ragged decode step is that loop with a TfmDecode
-// argument (decode attention with append in place of the flash kernel), its fp8-weight mode the same loop with TfmRun::use_w8.
+// to it (embeddings, caches, final norms) and sets the switches of struct Tfm.  OPT's ragged decode step, and its cached forward on the e4m3
+// bytes, are that loop with a TfmDecode argument (decode attention with append in place of the flash kernel), the fp8-weight mode the same loop
+// with TfmRun::use_w8.
 // Nothing here allocates or builds strings per launch.
 #pragma once
 #include "engine_util.h"
@@ -68,9 +69,10 @@ int opt_reduce_ln_launch(const float* ws, int sk, int M, int D, const float* bia
 int tfm_linear_launch(const bf16_t* A, int M, const bf16_t* W, int blk, const float* b, int N, int K, const float* resid, int act, void* out,
                       bool out_f32, int splitk, float* ws, bool fuse_ln, const float* ln_g, const float* ln_b, bf16_t* ln_out, hipStream_t s);
 
-// The ragged decode step as a mode of self_attn / layers (T = 1, a cache): row b is the token at position lens[b] of sequence b.  Self-attention is
-// then a plain QKV linear into Tfm::q as [B][3D] -> attention_decode_launch (appends the row's K / V at lens[b], clamps a length beyond the cache
-// and raises flags[b]) -> the out-projection.
+// The decode step as a mode of self_attn / layers (a cache): the T rows of sequence b are its tokens at positions lens[b] .. lens[b] + T - 1.
+// Self-attention is then a plain QKV linear into Tfm::q as [B * T][3D] -> attention_decode_launch (T == 1: the ragged step) or
+// attention_append_launch (T > 1, at most 16: the cached forward on the e4m3 bytes), which append the rows' K / V at lens[b] .., clamp a length
+// beyond the cache and raise flags[b] (nullable) -> the out-projection.
 struct TfmDecode { const int32_t* lens = nullptr; int32_t* flags = nullptr; };
 
 struct TfmRun {
@@ -90,7 +92,7 @@ struct TfmRun {
   int attend(int B, int nq, int nkv, int npad_q, int npad_kv, const bf16_t* K, const bf16_t* Vt, bool causal) const;
   // the two sub-blocks over the stream h (B * T rows); nbuf holds their LayerNorm of h on entry and, with next_g, that of next_g / next_b on exit.
   // kv: the T rows are the tokens past .. past + T - 1 of each sequence; their K / Vt are appended to the cache and they attend to it.
-  // dec (needs kv, T == 1): every row at its own length instead of `past`
+  // dec (needs kv, T <= 16): every row at its own length instead of `past`
   int self_attn(float* h, int B, int T, const TfmLayer& L, bool causal, const float* next_g, const float* next_b, const TfmKv* kv = nullptr,
                 int past = 0, const TfmDecode* dec = nullptr) const;
   int ffn(float* h, int rows, const TfmLayer& L, int act, const float* next_g = nullptr, const float* next_b = nullptr) const;

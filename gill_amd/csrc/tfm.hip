@@ -156,7 +156,9 @@ int Tfm::alloc(DevPool& pool, int max_batch, int max_tok, int D_, int F_, int H_
   const size_t Tpad = round_up(max_tok, 32);
   GILL_TRY(pool.alloc(&nbuf, R * D));
   GILL_TRY(pool.alloc(&ff, R * F));
-  GILL_TRY(pool.alloc(&q, (size_t)max_batch * H * Tpad * dp));
+  // q doubles as the decode mode's [rows][3D] projection (rows <= 16): 48 D elements at the least
+  const size_t qn = (size_t)max_batch * H * Tpad * dp, qdec = (size_t)3 * 16 * D;
+  GILL_TRY(pool.alloc(&q, qn > qdec ? qn : qdec));
   GILL_TRY(pool.alloc(&k, (size_t)max_batch * H * Tpad * dp));
   GILL_TRY(pool.alloc(&vt, (size_t)max_batch * H * dpv * Tpad));
   GILL_TRY(pool.alloc(&o, R * D));
@@ -226,14 +228,15 @@ int TfmRun::attend(int B, int nq, int nkv, int npad_q, int npad_kv, const bf16_t
 int TfmRun::self_attn(float* h, int B, int T, const TfmLayer& L, bool causal, const float* next_g, const float* next_b, const TfmKv* kv,
                       int past, const TfmDecode* dec) const {
   if (dec) {
-    GILL_REQUIRE(kv && T == 1, "decode attention: one token per row and a cache");
-    GILL_TRY(linear(t.nbuf, B, L.qkv, nullptr, ACT_NONE, t.q, false));
-    AttnDecodeArgs a;
+    GILL_REQUIRE(kv && T >= 1, "decode attention: a cache");
+    GILL_TRY(linear(t.nbuf, B * T, L.qkv, nullptr, ACT_NONE, t.q, false));
+    AttnAppendArgs a;
+    a.nq = T;
     a.q = t.q; a.k = t.q + t.D; a.v = t.q + 2 * t.D; a.ld = 3 * t.D;
     a.K = kv->k; a.Vt = kv->vt; a.lens = dec->lens; a.O = t.o; a.ldo = t.D; a.flags = dec->flags;
     a.B = B; a.H = t.H; a.dp = t.dp; a.dpv = t.dpv; a.pitch = kv->pad;
     a.qscale = 1.4426950408889634f / sqrtf((float)t.dp);
-    GILL_TRY(attention_decode_launch(a, s));
+    GILL_TRY(T == 1 ? attention_decode_launch(a, s) : attention_append_launch(a, s));
   } else {
     const int Tpad = round_up(T, 32), kvpad = kv ? kv->pad : Tpad;
     bf16_t* kbuf = kv ? kv->k : t.k;

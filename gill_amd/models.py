@@ -309,10 +309,13 @@ class GILLModel(nn.Module):
 
   def quantize_lm(self, mode: Optional[str] = 'fp8'):
     """Weight format of the OPT decoder's native handle.  'fp8': weight-only fp8 (OCP e4m3, one power-of-two scale per output row) for the
-    four matrices of every decoder layer; the ragged decode step of generate_batch / generate_for_images_and_texts_batch then reads half the
-    weight bytes.  Every other pass, generate() included, runs the dequantised weights on the bf16 kernels: the same model, no speed-up.
-    The handle holds both copies: about 1.5 x the decoder weights of a bf16 handle.  None or 'bf16': back to bf16.  The handle is rebuilt
-    at the next call."""
+    four matrices of every decoder layer.  The decode steps then read half the weight bytes: the ragged step of generate_batch /
+    generate_for_images_and_texts_batch at up to 16 rows, and every KV-cached step of generate() (greedy, seeded draw and host-decision
+    paths, and with it generate_for_images_and_texts) that carries at most 16 rows in all, batch x new tokens: single tokens at batch <= 16
+    and the 8-token [IMG] block at batch 1.  Every other pass (the prefill, a step of more than 16 rows, generate(use_kv_cache=False), the
+    training-style forwards, the retrieval and likelihood scores) runs the dequantised weights on the bf16 kernels: the same model, no
+    speed-up.  The handle holds both copies: about 1.5 x the decoder weights of a bf16 handle.  None or 'bf16': back to bf16.  The handle is
+    rebuilt at the next call."""
     mode = 'bf16' if mode is None else mode
     if mode not in _OPT_WEIGHT_MODES:
       raise ValueError(f"quantize_lm: mode must be one of {sorted(_OPT_WEIGHT_MODES)} or None, got {mode!r}")
@@ -582,6 +585,8 @@ class GILLModel(nn.Module):
     whole sequence through the LM at every step; with use_kv_cache (default) only the tokens appended since the last
     step go through the layers, against keys/values cached in the native handle — causal attention makes the hidden
     states of earlier positions independent of later tokens, so the outputs are the same up to rounding.
+    After quantize_lm('fp8') the cached steps behind the prefill run on the e4m3 weight bytes wherever batch x new tokens <= 16
+    (gill_opt_cached_uses_w8); the prefill and use_kv_cache=False stay on the bf16 kernels.
     With decode_on_device (default) the logit rule and the pick run in libgill_amd: greedy decoding at batch > 1 never
     waits for the device inside the loop, at batch 1 it reads one 4-byte count per step (the [IMG] forcing decides how
     many tokens the next forward takes).  Outputs: out (N,T) token ids, output_embeddings list of hidden_states[-1],

@@ -185,6 +185,24 @@ def attention_decode(q: torch.Tensor, k_new: torch.Tensor, v_new: torch.Tensor, 
   return o
 
 
+def attention_append(q: torch.Tensor, k_new: torch.Tensor, v_new: torch.Tensor, K: torch.Tensor, Vt: torch.Tensor, lens: torch.Tensor,
+                     flags: Optional[torch.Tensor] = None) -> torch.Tensor:
+  """Decode attention with a multi-token append: q / k_new / v_new (B, nq, H*d) bf16, row b's nq consecutive new tokens (1 <= nq <= 16) at its
+  cache length lens[b]; K (B,H,pitch,d) and Vt (B,H,round_up(d,32),pitch) bf16 caches, updated IN PLACE at slots lens[b] .. lens[b] + nq - 1; lens
+  (B) int32 on the device; flags (B) int32 (optional) receives 1 where a length was clamped into [0, pitch - nq].  Returns (B, nq, H*d) bf16: bit for
+  bit what nq successive attention_decode calls at lens, lens + 1, .. give."""
+  B, H, pitch, d = K.shape
+  nq = q.shape[1]
+  for t in (q, k_new, v_new):
+    assert t.dtype == torch.bfloat16 and t.is_contiguous() and tuple(t.shape) == (B, nq, H * d)
+  assert K.dtype == torch.bfloat16 and Vt.dtype == torch.bfloat16 and tuple(Vt.shape) == (B, H, (d + 31) // 32 * 32, pitch)
+  assert lens.dtype == torch.int32 and lens.numel() == B and (flags is None or (flags.dtype == torch.int32 and flags.numel() == B))
+  o = torch.empty_like(q)
+  N.check(N.lib().gill_attention_append(N.ptr(q), N.ptr(k_new), N.ptr(v_new), H * d, N.ptr(K), N.ptr(Vt), N.ptr(lens), N.ptr(o), B, nq, H, d, pitch,
+                                        N.ptr(flags), N.current_stream()))
+  return o
+
+
 def layernorm(x: torch.Tensor, gamma: torch.Tensor, beta: torch.Tensor, eps: float = 1e-5) -> torch.Tensor:
   assert x.is_cuda and x.dtype in (torch.bfloat16, torch.float32)
   x = x.contiguous()

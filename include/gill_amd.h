@@ -68,16 +68,22 @@ void gill_opt_destroy(gill_opt* h);
  * exact bf16 model, and the handle keeps BOTH copies of those matrices: the dequantised bf16 values, in the layouts of a bf16 handle, and
  * the fp8 bytes + fp32 scales: about 1.5 x the decoder weights of a bf16 handle in memory (OPT-6.7b: about 19 GB instead of 12.9).
  *   gill_opt_decode_step at B <= gill_w8_max_rows() runs its four linears per layer on the fp8 bytes (csrc/linear_w8.hip: bf16
- *     activations, weights converted to bf16 in registers, fp32 accumulation; half the weight bytes per step).  This is the one entry that
- *     speeds up: the ragged loop of generate_batch.
- *   gill_opt_decode_step at larger B and every other entry (forward, forward_cached, img_hidden*, prefill_ids, forward_loss, the logits)
- *     run the kernels of a bf16 handle on the dequantised matrices: the same model, no speed-up.
- * gill_opt_weight_mode: the handle's mode.  gill_opt_decode_uses_w8: host-only, 1 when gill_opt_decode_step at this B takes the fp8 path
- * (the function the engine itself branches on), else 0. */
+ *     activations, weights converted to bf16 in registers, fp32 accumulation; half the weight bytes per step): the ragged loop of
+ *     generate_batch.
+ *   gill_opt_forward_cached with past_len > 0 and B * T_new <= gill_w8_max_rows() runs the same four linears on the bytes, with
+ *     self-attention as projection -> gill_attention_append (every row at length past_len) -> out-projection: the decode steps of
+ *     generate(), its 8-token [IMG] block at B = 1 included.  The cache is the one layout either way: routed and un-routed calls of a
+ *     sequence may alternate.
+ *   gill_opt_decode_step and gill_opt_forward_cached at more rows, gill_opt_forward_cached at past_len = 0 (the prefill) and every other
+ *     entry (forward, img_hidden*, prefill_ids, forward_loss, the logits) run the kernels of a bf16 handle on the dequantised matrices:
+ *     the same model, no speed-up.
+ * gill_opt_weight_mode: the handle's mode.  gill_opt_decode_uses_w8 / gill_opt_cached_uses_w8: host-only, 1 when gill_opt_decode_step at
+ * this B / gill_opt_forward_cached at this (B, T_new, past_len) takes the fp8 path (the functions the engine itself branches on), else 0. */
 enum { GILL_OPT_BF16 = 0, GILL_OPT_W8 = 1 };
 int gill_opt_create_ex(gill_opt** out, const gill_opt_config* cfg, const gill_tensor* weights, int n_weights, int weight_mode);
 int gill_opt_weight_mode(const gill_opt* h);
 int gill_opt_decode_uses_w8(const gill_opt* h, int B);
+int gill_opt_cached_uses_w8(const gill_opt* h, int B, int T_new, int past_len);
 int gill_w8_max_rows(void);     /* W8_MAX_ROWS: the most activation rows of one fp8 linear (16) */
 
 /* Operator entries of the w8 format (tests).  Bytes are in the kernel's order [N / 16][K / 64][64][16]: byte (n, k) at
@@ -217,6 +223,19 @@ int gill_decode_uniforms(uint64_t seed, int32_t row, int32_t draw, int32_t first
  * buffers is touched.  A row's output is a fixed function of its own operands and length: the same bits at any B, on any run. */
 int gill_attention_decode(const void* q, const void* k_new, const void* v_new, int ld, void* K, void* Vt, const int32_t* lens,
                           void* o, int B, int H, int d, int pitch, int32_t* flags, void* stream);
+
+/* Decode attention with a multi-token append, the operator under gill_opt_forward_cached on a w8 handle (below).  Row b brings nq
+ * consecutive new tokens, 1 <= nq <= gill_w8_max_rows(), at its own cache length n = lens[b]: q, k_new, v_new and o hold B * nq rows (ld
+ * elements; o: H*d), row b * nq + i the token n + i of sequence b; K, Vt, lens, d and flags as in gill_attention_decode.  Token i's key /
+ * value are stored at slot n + i (and the ones-row entry Vt[b][h][d][n + i] = 1 where round_up(d,32) > d), and
+ *   o[b * nq + i] = softmax(q_i . [K[0..n-1]; k_0..k_i] / sqrt(d)) . [V[0..n-1]; v_0..v_i].
+ * Slots at or beyond n + nq, and for token i the slots n + i + 1 .., are excluded by selection whatever they hold.  n outside
+ * [0, pitch - nq] is clamped into it and flags[b] is set to 1; nothing outside the buffers is touched.  A row's output and cache are, bit
+ * for bit, those of nq successive gill_attention_decode calls, the i-th with lens = n + i: the same bits at any B, under any grouping of
+ * the tokens into calls, on any run; nq == 1 is gill_attention_decode itself.  nq outside its range, a misaligned pointer or an
+ * unsupported d are errors, reported before anything is launched. */
+int gill_attention_append(const void* q, const void* k_new, const void* v_new, int ld, void* K, void* Vt, const int32_t* lens,
+                          void* o, int B, int nq, int H, int d, int pitch, int32_t* flags, void* stream);
 
 /* One decode step of B rows at B different lengths.  new_embeds (B,1,D) bf16: row b's token sits at position lens_dev[b] (device
  * int32): it takes position embedding 2 + lens_dev[b], its key / value go to slot lens_dev[b] of row b's cache and it attends to

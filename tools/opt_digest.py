@@ -10,6 +10,9 @@ Cases `<entry>-<geometry>[-<variant>]`, geometries "opt125" / "opt67" of tests/k
   dec-*-b3, b9   gill_opt_prefill_ids + four gill_opt_decode_step at ragged lengths on a bf16 handle; row 0 of the last step holds a device
                  length beyond the cache (clamped; its flag is read back through the ragged decision)
   w8-*-b3, b16, b17   the same on a w8 handle (b17: past W8_MAX_ROWS, the bf16 kernels on the dequantised weights)
+  w8cached       gill_opt_forward_cached on a w8 handle: a 30-token prefill (the bf16 kernels), then on the e4m3 bytes three single-token steps,
+                 one 8-token block and two more single steps at B = 2, and on the same handle one single step at B = 1 and at B = 8 and an
+                 8-token block at B = 3 (24 rows: the bf16 kernels again, on the cache the routed steps wrote)
   mapper, clipvision, cliptext   one forward each on the smallest configurations their GPU tests use
 Every output a case produces goes into its digest; hidden states of the ragged cases only at the valid rows."""
 import ctypes as C
@@ -22,7 +25,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 GEOS = ("opt125", "opt67")
 CASES = [f"{e}-{g}" for g in GEOS for e in ("forward", "cached", "img", "imgx", "loss", "loss0")] + \
         [f"dec-{g}-{b}" for g in GEOS for b in ("b3", "b9")] + [f"w8-{g}-{b}" for g in GEOS for b in ("b3", "b16", "b17")] + \
-        ["mapper", "clipvision", "cliptext"]
+        ["mapper", "clipvision", "cliptext"] + [f"w8cached-{g}" for g in GEOS]
 
 todo = CASES if sys.argv[1:] == ["all"] else sys.argv[1:]
 if not todo or any(c not in CASES for c in todo):
@@ -90,6 +93,20 @@ def run_forward(geo, cached):
   past = 0
   for tn in (17, 13, 1, 1, 1):
     xs, out = x[:, past:past + tn].contiguous(), new(B, tn, D)
+    N.check(lib.gill_opt_forward_cached(h, N.ptr(xs), B, tn, past, N.ptr(out), stream))
+    feed(out)
+    past += tn
+
+
+def run_w8_cached(geo):
+  import kv_cache_util as U
+  h, cfg, sd = opt_handle(geo, 1, 8, 64)
+  D = cfg.hidden_size
+  x = U.token_embeds(sd, cfg, 8, 56, 6).to(dev, torch.bfloat16)
+  past = 0
+  for B, tn in ((2, 30), (2, 1), (2, 1), (2, 1), (2, 8), (2, 1), (2, 1), (1, 1), (8, 1), (3, 8)):
+    assert lib.gill_opt_cached_uses_w8(h, B, tn, past) == int(past > 0 and B * tn <= 16)
+    xs, out = x[:B, past:past + tn].contiguous(), new(B, tn, D)
     N.check(lib.gill_opt_forward_cached(h, N.ptr(xs), B, tn, past, N.ptr(out), stream))
     feed(out)
     past += tn
@@ -202,6 +219,8 @@ elif parts[0] in ("img", "imgx"):
   run_img(parts[1], parts[0] == "imgx")
 elif parts[0] in ("loss", "loss0"):
   run_loss(parts[1], parts[0] == "loss")
+elif parts[0] == "w8cached":
+  run_w8_cached(parts[1])
 elif parts[0] in ("dec", "w8"):
   run_decode(parts[1], 1 if parts[0] == "w8" else 0, int(parts[2][1:]))
 else:
