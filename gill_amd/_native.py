@@ -192,6 +192,8 @@ SYMBOLS: Dict[str, Tuple[object, List[object]]] = {
   "gill_op_skinny_gemm": (_i, [_vp, _vp, _vp, _i, _i, _i, _vp]),
   "gill_op_lm_head_loss": (_i, [_vp, _vp, _vp, _i, _i, _i, _vp, _vp, _vp, _vp, _vp]),
   "gill_lm_loss_geometry": (_i, [_i, _i, _i, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int)]),
+  "gill_op_img_block_heads": (_i, [_vp, C.c_int64, _i, _vp, _i, _vp, _vp, _i, _vp, _vp, _i, _vp, _vp, _vp, _vp]),
+  "gill_op_img_rerank_scores": (_i, [_vp, _vp, _i, _i, _i, _vp, _vp]),
   "gill_gemm_plan": (_i, [_vp, _i, _i, _i, _i, _vp]),
   "gill_gemm_plan_log": (_i, [_vp, _i, C.POINTER(C.c_int)]),
   "gill_unet_xf_plan": (_i, [_vp, _i, _i, _i, _i, _vp]),

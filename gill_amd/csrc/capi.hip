@@ -649,6 +649,23 @@ extern "C" int gill_op_lm_head_loss(const void* X_bf16, const void* W_bf16, cons
   return 0;
 }
 
+// The image-block heads and the rerank score (img_heads.hip): no host wait.
+extern "C" int gill_op_img_block_heads(const float* hidden_f32, int64_t rows, int D, const int32_t* row_idx, int n, const void* Wr_bf16,
+                                       const float* br, int E, const void* Wd_bf16, const float* bd, int C, float* ret_emb, float* probs,
+                                       int32_t* choice, void* stream) {
+  hipStream_t s = (hipStream_t)stream;
+  for (int r = 0; r < op_repeat(); ++r)
+    GILL_TRY(img_heads_launch(hidden_f32, rows, D, (const int*)row_idx, n, (const bf16_t*)Wr_bf16, br, E, (const bf16_t*)Wd_bf16, bd, C, ret_emb, probs,
+                              (int*)choice, s));
+  return 0;
+}
+
+extern "C" int gill_op_img_rerank_scores(const float* visual_f32, const float* ret_emb_f32, int n, int g, int E, float* scores, void* stream) {
+  hipStream_t s = (hipStream_t)stream;
+  for (int r = 0; r < op_repeat(); ++r) GILL_TRY(img_rerank_launch(visual_f32, ret_emb_f32, n, g, E, scores, s));
+  return 0;
+}
+
 extern "C" int gill_lm_loss_geometry(int M, int V, int D, int* row_tile, int* col_tile, int* n_slabs, int* cols_per_slab) {
   GILL_REQUIRE(M >= 1 && V >= 1 && D >= 32 && D % 32 == 0, "lm_loss_geometry: M, V >= 1 and D a positive multiple of 32");
   lm_loss_geometry(M, V, D, row_tile, col_tile, n_slabs, cols_per_slab);

@@ -307,6 +307,12 @@ void lm_loss_geometry(int M, int V, int D, int* row_tile, int* col_tile, int* n_
 size_t lm_loss_workspace_bytes(int M, int V);
 int lm_loss_launch(const bf16_t* X, const bf16_t* W, const int64_t* target, int M, int V, int D, float* lse, float* tgt, int* rank, float* summary,
                    void* workspace, hipStream_t s);
+// ---- the image-block heads and the rerank score (img_heads.hip; models.py:671-676, :698-704, :733-751) ----
+// n blocks in one launch, one workgroup each; Wr / br and Wd / bd nullable as pairs (not both).  Arguments are checked before anything is enqueued.
+int img_heads_launch(const float* hidden, int64_t rows, int D, const int* row_idx, int n, const bf16_t* Wr, const float* br, int E, const bf16_t* Wd,
+                     const float* bd, int C, float* ret_emb, float* probs, int* choice, hipStream_t s);
+// scores (n, g) = cos(visual[b g + j], ret_emb[b]); zero rows give 0
+int img_rerank_launch(const float* visual, const float* ret_emb, int n, int g, int E, float* scores, hipStream_t s);
 // ---- decode decision of the generate loop (decode.hip; models.py:471-520) ----
 constexpr int kDecodeMaxIds = 16;
 struct DecodeRuleDev {          // gill_decode_rule resolved on the host: ids in [0, vocab), conditions evaluated

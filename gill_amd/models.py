@@ -1118,18 +1118,26 @@ class GILL(nn.Module):
                                           ret_scale_factor: float = 1.0, gen_scale_factor: float = 1.0, top_p: float = 1.0,
                                           temperature: float = 0.0, max_num_rets: int = 1, generator=None,
                                           always_add_bos: bool = False, guidance_scale: float = 7.5, num_inference_steps: int = 50,
-                                          seed: Optional[int] = None):
+                                          seed: Optional[int] = None, all_branches: bool = False, skip_gen_on_ret: bool = False):
     """generate_for_images_and_texts for several dialogues at once: prompt_lists[b] is one prompt list (PIL images and strings); returns,
     per prompt list, the list the one-sequence method returns for it.  The prompts are segmented as the batched entries segment them
     (_interleaved_ids, _visual_rows), decoded as ONE ragged batch (GILLModel.generate_batch: every row at its own length, an [IMG]
     block forced per row), then per row the reference's newline truncation, the [IMG] blocks up to max_num_rets and the captions; the
     raw_emb blocks of ALL rows go through gen_text_hidden_fcs[0] in one call and, with load_sd, through the SD pipeline in chunks of 8.
-    Scope: the 'gen' branch only.  With a retrieval embedding matrix or a decision model attached this raises NotImplementedError:
-    retrieval, the decision MLP and the CLIP rerank stay with generate_for_images_and_texts, one sequence at a time.  Nothing is
-    sharded over ranks.  temperature > 0 needs seed (row b draws with row id b)."""
-    if self.emb_matrix is not None or self.decision_model is not None:
-      raise NotImplementedError('generate_for_images_and_texts_batch covers the generation branch only: with retrieval embeddings or a '
-                                'decision model attached, call generate_for_images_and_texts per prompt list.')
+    Scope by default (all_branches=False): the 'gen' branch only.  With a retrieval embedding matrix or a decision model attached this
+    raises NotImplementedError: retrieval, the decision MLP and the CLIP rerank then stay with generate_for_images_and_texts, one
+    sequence at a time.  all_branches=True runs every branch of that method for the batch (_batch_branches): one img_block_heads launch
+    turns the first [IMG] hidden row of every block of every row into retrieval embeddings and decisions, retrieval runs in rounds
+    (round j: the j-th block of every row, one search per round), and with a VAE and a retrieval matrix the generated images of all
+    blocks are reranked together on the device.  skip_gen_on_ret=True (a stated divergence: the reference always computes both lists;
+    ignored without a decision model) leaves blocks decided 'ret' out of the mapper, SD and rerank calls: their 'gen' is [].
+    all_branches=True needs ret_text_fc_mode 'linear' (the mode of every shipped checkpoint; the heads kernel is that Linear): any other
+    mode raises NotImplementedError, where the one-sequence method takes any mode.
+    Nothing is sharded over ranks.  temperature > 0 needs seed (row b draws with row id b)."""
+    if not all_branches and (self.emb_matrix is not None or self.decision_model is not None):
+      raise NotImplementedError('generate_for_images_and_texts_batch covers the generation branch only by default: with retrieval '
+                                'embeddings or a decision model attached, pass all_branches=True or call generate_for_images_and_texts '
+                                'per prompt list.')
     prompts = [[p] if isinstance(p, str) else list(p) for p in prompt_lists]
     for pl in prompts:
       for p in pl:
@@ -1151,6 +1159,7 @@ class GILL(nn.Module):
     newline_token_id = m.tokenizer('\n', add_special_tokens=False).input_ids[0]
     gen_prefix = ''.join([f'[IMG{i}]' for i in range(m.args.num_tokens)])
     outputs, blocks = [], []          # blocks: (the image_outputs dict to fill, raw_emb (1, 8, D))
+    where = []                        # per block: (prompt list b, the flat row of its first [IMG] hidden state in `hidden`)
     for b in range(len(prompts)):
       generated_ids = tokens[b:b + 1, :n_tok[b]]
       embeddings = hidden[b:b + 1, :n_hid[b]].to(m.logit_scale.dtype)
@@ -1173,11 +1182,19 @@ class GILL(nn.Module):
         assert len(m.args.text_emb_layers) == 1
         image_outputs = {'gen': [], 'ret': [], 'decision': ['gen', [0, 1]]}
         blocks.append((image_outputs, embeddings[:, ret_idx:ret_idx + m.num_tokens, :]))
+        where.append((b, b * hidden.shape[1] + ret_idx))
         caption = m.tokenizer.batch_decode(generated_ids[:, last_ret_idx:ret_idx], skip_special_tokens=True)[0]
         last_ret_idx = ret_idx + 1
         row_out.append(utils.truncate_caption(caption) + f' {gen_prefix}')
         row_out.append(image_outputs)
       outputs.append(row_out)
+    ret_emb = None
+    if all_branches and blocks:
+      ret_emb = self._batch_branches(blocks, where, hidden, max_num_rets)
+      if skip_gen_on_ret and self.emb_matrix is not None and self.decision_model is not None:
+        keep = [k for k, (image_outputs, _) in enumerate(blocks) if image_outputs['decision'][0] != 'ret']
+        blocks = [blocks[k] for k in keep]
+        ret_emb = ret_emb[torch.tensor(keep, dtype=torch.int64, device=dev)] if keep else None
     if blocks:
       gen_prefx_ids = m.tokenizer(gen_prefix, add_special_tokens=False, return_tensors="pt").input_ids.to(dev)
       gen_prefix_embs = m.input_embeddings(gen_prefx_ids)                                  # (1, T, D)
@@ -1188,17 +1205,118 @@ class GILL(nn.Module):
         gen_emb = torch.cat([gen_emb, torch.zeros((gen_emb.shape[0], 77 - gen_emb.shape[1], 768), device=dev, dtype=gen_emb.dtype)], dim=1)
       gen_emb = gen_emb.repeat_interleave(self.num_gen_images, dim=0)                      # block k: rows k * num_gen_images ..
       if self.load_sd:
-        gen_images = []
+        gen_images, gen_u8 = [], []
         for i in range(0, gen_emb.shape[0], 8):
-          gen_images.extend(self.sd_pipe(prompt_embeds=gen_emb[i:i + 8], generator=generator, guidance_scale=guidance_scale,
-                                         num_inference_steps=num_inference_steps,
-                                         output_type="pil" if getattr(self.sd_pipe, "_vae", None) else "latent").images)
-        for k, (image_outputs, _) in enumerate(blocks):
-          image_outputs['gen'] = [(gen_images[k * self.num_gen_images], 0)]
+          res = self.sd_pipe(prompt_embeds=gen_emb[i:i + 8], generator=generator, guidance_scale=guidance_scale,
+                             num_inference_steps=num_inference_steps,
+                             output_type="pil" if getattr(self.sd_pipe, "_vae", None) else "latent")
+          gen_images.extend(res.images)
+          gen_u8.append(getattr(res, 'images_u8', None))
+        if ret_emb is not None and getattr(self.sd_pipe, "_vae", None):
+          self._batch_rerank(blocks, gen_images, gen_u8, ret_emb)
+        else:
+          for k, (image_outputs, _) in enumerate(blocks):
+            image_outputs['gen'] = [(gen_images[k * self.num_gen_images], 0)]
       else:
         for k, (image_outputs, _) in enumerate(blocks):
           image_outputs['gen'] = [gen_emb[k * self.num_gen_images:(k + 1) * self.num_gen_images]]
     return outputs
+
+  def _batch_branches(self, blocks, where, hidden: Tensor, max_num_rets: int) -> Optional[Tensor]:
+    """The retrieval and decision branches of generate_for_images_and_texts (models.py:671-704) for every [IMG] block of a batch.
+    blocks: (image_outputs, raw_emb) per block, filled in place; where: (prompt list, flat row of `hidden`) per block; hidden: what
+    generate_batch returned.  One ops.img_block_heads launch for all blocks, one search (or one _scores GEMM + topk) and one copy to
+    the host per round of retrieval, one copy for all decisions.  Returns ret_emb (n, E) fp32 in block order, None without emb_matrix."""
+    if self.emb_matrix is None:       # no embedding matrix: generate instead; every block keeps ['gen', [0, 1]] (models.py:706)
+      return None
+    from . import ops
+    from PIL import UnidentifiedImageError
+    m = self.model
+    dev = m.logit_scale.device
+    fc = m.ret_text_hidden_fcs[0]
+    if getattr(fc, 'mode', None) != 'linear':
+      raise NotImplementedError(f'generate_for_images_and_texts_batch(all_branches=True) needs ret_text_fc_mode "linear", got {fc.mode!r}')
+    decision = None
+    if self.decision_model is not None:
+      lin = self.decision_model[1]
+      assert hidden.shape[-1] == lin.in_features, hidden.shape
+      decision = (lin.weight.to(dev, torch.bfloat16), lin.bias.to(dev).float())
+    row_idx = torch.tensor([r for _, r in where], dtype=torch.int32).to(dev)          # the one upload of the block rows
+    ret_emb, probs, choice = ops.img_block_heads(hidden, row_idx, ret=(fc.model.weight.to(torch.bfloat16), fc.model.bias.float()),
+                                                 decision=decision)
+    # retrieval in rounds: round j holds the j-th block of every prompt list, in block order
+    rounds, nth = [], {}
+    for k, (b, _) in enumerate(where):
+      j = nth.get(b, 0)
+      nth[b] = j + 1
+      if j == len(rounds):
+        rounds.append([])
+      rounds[j].append(k)
+    seen = {b: [] for b, _ in where}      # per prompt list: avoid showing the same image multiple times
+    for ks in rounds:
+      q = ret_emb if len(ks) == len(blocks) else ret_emb[torch.tensor(ks, dtype=torch.int64).to(dev)]
+      q = q.type(self.emb_matrix.dtype)
+      seen_lists = [[int(i) for i in seen[where[k][0]]] for k in ks]
+      if self.ret_index is not None:
+        top_scores, top_idx = self.ret_index.search(q.float(), 3, normalize=False, penalty=1000.0,
+                                                    exclude=seen_lists if any(seen_lists) else None)
+      else:
+        scores = self._scores(self.emb_matrix, q)                                       # emb_matrix @ q.T, (N, Q)
+        for c, lst in enumerate(seen_lists):
+          for seen_idx in lst:      # Downweight seen images.
+            scores[seen_idx, c] -= 1000
+        top_scores, top_idx = scores.t().float().topk(3, dim=1)
+      top_scores, top_idx = top_scores.cpu(), top_idx.cpu()                             # the round's one wait for the device
+      for c, k in enumerate(ks):
+        image_outputs, seen_image_idx = blocks[k][0], seen[where[k][0]]
+        for img_idx, score in zip(top_idx[c].tolist(), top_scores[c].tolist()):     # Find the first image that does not error out.
+          if img_idx < 0:           # the index holds fewer than 3 rows
+            continue
+          try:
+            seen_image_idx.append(img_idx)
+            img = utils.get_image_from_url(self.path_array[img_idx])
+            image_outputs['ret'].append((img, 'ret', score))
+            if len(image_outputs) == max_num_rets:
+              break
+          except (UnidentifiedImageError, ConnectionError, OSError):
+            pass
+    if decision is not None:          # Make decision with MLP (models.py:698-704): one copy for all blocks
+      probs, choice = probs.cpu().tolist(), choice.cpu().tolist()
+      for k, (image_outputs, _) in enumerate(blocks):
+        image_outputs['decision'] = [self.idx2dec[choice[k]]] + [probs[k]]
+    else:
+      for image_outputs, _ in blocks:
+        image_outputs['decision'] = None
+    return ret_emb
+
+  def _batch_rerank(self, blocks, gen_images, gen_u8, ret_emb: Tensor) -> None:
+    """The CLIP rerank of the generated images (models.py:733-751) for all blocks at once: block k owns gen_images[k g : (k + 1) g].
+    The pixels stay on the device where the pipeline handed them back (PipelineOutput.images_u8; otherwise the PIL bytes go up in one
+    copy): ops.clip_preprocess, the CLIP tower in chunks, ops.img_rerank_scores, one copy of the (n, g) scores to the host."""
+    from . import ops
+    m = self.model
+    dev = m.logit_scale.device
+    g = self.num_gen_images
+    if all(u is not None for u in gen_u8):
+      images = torch.cat(gen_u8, dim=0)
+    else:
+      images = torch.from_numpy(np.stack([np.asarray(img.convert('RGB')) for img in gen_images])).to(dev)
+    # img.resize((224, 224)), then the feature extractor (models.py:737): one pass when the extractor's own size is 224, as in every
+    # shipped checkpoint; otherwise the 224 x 224 uint8 pixels of the first pass go through a second one at the extractor's size
+    size = int(m.feature_extractor.size)
+    if size == 224:
+      px = ops.clip_preprocess(images, 224, dev)
+    else:
+      px = ops.clip_preprocess(ops.clip_preprocess(images, 224, dev, return_u8=True)[1], size, dev)
+    chunk = self._clip_chunk_size(px.shape[0])
+    visual = torch.cat([m.get_visual_embs(px[i:i + chunk], mode='retrieval') for i in range(0, px.shape[0], chunk)], dim=0)
+    scores = ops.img_rerank_scores(visual.reshape(px.shape[0], -1).float(), ret_emb).cpu()
+    for k, (image_outputs, _) in enumerate(blocks):
+      if g > 1:   # Rank images by retrieval score.
+        order = torch.argsort(-scores[k])
+        image_outputs['gen'] = [(gen_images[k * g + int(i)], scores[k, int(i)].item()) for i in order]
+      else:
+        image_outputs['gen'] = [(gen_images[k * g], scores[k, 0].item())]
 
   @torch.no_grad()
   def get_log_likelihood_scores(self, prompts: List) -> float:
@@ -1246,17 +1364,18 @@ class GILL(nn.Module):
 
   @staticmethod
   def _scores(matrix: Tensor, query: Tensor) -> Tensor:
-    """matrix (N, D) @ query (1, D).T -> (N, 1) in matrix's dtype, through the native GEMM (the query is padded to the 4
-    output columns the kernel's epilogue writes at a time)."""
+    """matrix (N, D) @ query (Q, D).T -> (N, Q) in matrix's dtype, through the native GEMM (the queries are padded to a multiple of
+    the 4 output columns the kernel's epilogue writes at a time; Q = 1 in the one-sequence method)."""
     from . import ops
     dev = query.device
     Nq, D = matrix.shape
     Dp = (D + 63) // 64 * 64
+    Q = query.numel() // D
     a = torch.zeros((Nq, Dp), device=dev, dtype=torch.bfloat16)
     a[:, :D] = matrix.to(dev)
-    q4 = torch.zeros((4, Dp), device=dev, dtype=torch.bfloat16)
-    q4[0, :D] = query.reshape(-1).to(torch.bfloat16)
-    return ops.gemm(a, q4, out_f32=True)[:, :1].to(matrix.dtype)
+    q4 = torch.zeros(((Q + 3) // 4 * 4, Dp), device=dev, dtype=torch.bfloat16)
+    q4[:Q, :D] = query.reshape(Q, D).to(torch.bfloat16)
+    return ops.gemm(a, q4, out_f32=True)[:, :Q].to(matrix.dtype)
 
   # ---- NEW, build-defined retrieval entries (not reference functions) -------------------------------------
   def build_retrieval_index(self, raw=None, scale: Optional[float] = None):
@@ -1477,6 +1596,11 @@ class GILL(nn.Module):
 
   clip_chunk = 16     # images per CLIP forward of _visual_rows when the tower's handle has to grow
 
+  def _clip_chunk_size(self, n: int) -> int:
+    """Images per CLIP forward for n images: the tower handle's capacity when it has one, else at most clip_chunk."""
+    m = self.model
+    return max(m._clip_cap if m._clip_handle is not None else 0, min(n, self.clip_chunk))
+
   def _visual_rows(self, images) -> Tensor:
     """The images of a shard -> (len(images) * n_visual_tokens, D) bf16: ops.clip_preprocess, then get_visual_embs(mode='captioning') in chunks
     of the CLIP handle's capacity, cast as generate_for_images_and_texts casts them on their way into the LM."""
@@ -1484,7 +1608,7 @@ class GILL(nn.Module):
     m = self.model
     dev = m.logit_scale.device
     px = ops.clip_preprocess(images, m.feature_extractor.size, dev)
-    chunk = max(m._clip_cap if m._clip_handle is not None else 0, min(len(images), self.clip_chunk))
+    chunk = self._clip_chunk_size(len(images))
     rows = [m.get_visual_embs(px[i:i + chunk], mode='captioning').to(torch.bfloat16) for i in range(0, len(images), chunk)]
     return torch.cat(rows, dim=0).reshape(-1, m.opt_cfg.hidden_size)
 

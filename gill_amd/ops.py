@@ -1102,3 +1102,58 @@ def linear_w8(a: torch.Tensor, w8: torch.Tensor, scale: torch.Tensor, bias: Opti
   N.check(N.lib().gill_op_linear_w8(N.ptr(a), N.ptr(w8), N.ptr(scale.contiguous()), N.ptr(bias), rp, N.ptr(buf), M, Nn, K, ACT[act],
                                     int(odt == torch.float32), int(splitk), None, None, None, N.current_stream()))
   return out, _guard_ok(buf)
+
+
+# ---- the image-block heads and the rerank score (csrc/img_heads.hip; tests/test_img_heads_gpu.py)
+def img_block_heads(hidden: torch.Tensor, row_idx: torch.Tensor, ret: Optional[tuple] = None, decision: Optional[tuple] = None, _out=None):
+  """What generate_for_images_and_texts computes from a block's first [IMG] hidden state, for n blocks in one launch (gill_op_img_block_heads).
+  hidden (..., D) fp32 on the device (generate_batch's `hidden`; read as (rows, D)), row_idx (n,) int32 on the device: the flat rows, any order,
+  repeats allowed, clamped into [0, rows) on the device.  ret = (W (E, D) bf16, b (E) fp32): ret_emb (n, E) fp32 = y / ||y||, y = W bf16(x) + b.
+  decision = (W (C, D) bf16, b (C) fp32), C <= 4: probs (n, C) fp32 = softmax(z) and choice (n,) int32 = argmax z (tie: lower index).  Returns
+  (ret_emb | None, probs | None, choice | None).  No host wait.  _out: caller-allocated (ret_emb, probs, choice) (the tests pass guarded ones)."""
+  assert hidden.is_cuda and hidden.dtype == torch.float32 and hidden.dim() >= 2
+  hidden = hidden.contiguous()
+  D = int(hidden.shape[-1])
+  rows = hidden.numel() // max(1, D)
+  assert row_idx.is_cuda and row_idx.dtype == torch.int32 and row_idx.dim() == 1
+  row_idx = row_idx.contiguous()
+  n = int(row_idx.shape[0])
+  dev = hidden.device
+
+  def pair(p, name):
+    if p is None:
+      return None, None, 0
+    w, b = _bf(p[0]), p[1].to(dev, torch.float32).contiguous()
+    if w.dim() != 2 or w.shape[1] != D or b.shape != (w.shape[0],):
+      raise ValueError(f'img_block_heads: {name} is (W (cols, {D}) bf16, b (cols,)), got {tuple(w.shape)} and {tuple(b.shape)}')
+    return w, b, int(w.shape[0])
+  wr, br, E = pair(ret, 'ret')
+  wd, bd, Cc = pair(decision, 'decision')
+  if _out is not None:
+    ret_emb, probs, choice = _out
+  else:
+    ret_emb = torch.empty((n, E), device=dev, dtype=torch.float32) if ret is not None else None
+    probs = torch.empty((n, Cc), device=dev, dtype=torch.float32) if decision is not None else None
+    choice = torch.empty((n,), device=dev, dtype=torch.int32) if decision is not None else None
+  with torch.cuda.device(dev):
+    N.check(N.lib().gill_op_img_block_heads(N.ptr(hidden), rows, D, N.ptr(row_idx), n, N.ptr(wr), N.ptr(br), E, N.ptr(wd), N.ptr(bd), Cc,
+                                            N.ptr(ret_emb), N.ptr(probs), N.ptr(choice), N.current_stream()))
+  return ret_emb, probs, choice
+
+
+def img_rerank_scores(visual: torch.Tensor, ret_emb: torch.Tensor, _out: Optional[torch.Tensor] = None) -> torch.Tensor:
+  """The CLIP rerank score of generated images (gill_op_img_rerank_scores): visual (n * g, E) fp32 un-normalised rows, block b's images at rows
+  b g .. b g + g - 1, ret_emb (n, E) fp32 -> scores (n, g) fp32 = the cosine of each image's row with its block's ret_emb; zero rows give 0.
+  One launch, no host wait."""
+  assert visual.is_cuda and visual.dtype == torch.float32 and visual.dim() == 2
+  assert ret_emb.is_cuda and ret_emb.dtype == torch.float32 and ret_emb.dim() == 2 and ret_emb.shape[1] == visual.shape[1]
+  visual, ret_emb = visual.contiguous(), ret_emb.contiguous()
+  n, E = int(ret_emb.shape[0]), int(ret_emb.shape[1])
+  if n == 0 or visual.shape[0] % n != 0 or visual.shape[0] == 0:
+    raise ValueError(f'img_rerank_scores: visual holds {visual.shape[0]} rows for {n} blocks')
+  g = int(visual.shape[0]) // n
+  scores = torch.empty((n, g), device=visual.device, dtype=torch.float32) if _out is None else _out
+  assert scores.shape == (n, g) and scores.dtype == torch.float32 and scores.is_contiguous()
+  with torch.cuda.device(visual.device):
+    N.check(N.lib().gill_op_img_rerank_scores(N.ptr(visual), N.ptr(ret_emb), n, g, E, N.ptr(scores), N.current_stream()))
+  return scores

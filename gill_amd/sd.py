@@ -39,6 +39,8 @@ from .synth import ClipTextConfig, UNetConfig, VAEConfig
 class PipelineOutput:
   images: object                      # latents tensor (B,4,L,L) when output_type == "latent"
   nsfw_content_detected: Optional[List[bool]] = None
+  images_u8: Optional[torch.Tensor] = None      # output_type "pil" / "np": the (B,8L,8L,3) uint8 device tensor the images were built from
+                                                # (None when a safety checker rewrote them on the host); not a reference field
 
 
 SAMPLER_KINDS = ("pndm", "ddim", "dpmsolver++", "euler", "euler_ancestral")      # gill_sd_sampler.kind, in order
@@ -618,10 +620,11 @@ class GillSDPipeline:
         N.check(N.lib().gill_sd_denoise_ex(self._h, C.byref(sp), N.ptr(cond), N.ptr(uncond), int(uncond.shape[0]), N.ptr(lat0), B,
                                            int(num_inference_steps), float(guidance_scale), N.ptr(out),
                                            None if noise is None else N.ptr(noise), N.current_stream()))
-    has_nsfw = None
+    has_nsfw, dev_u8 = None, None
     if output_type in ("pil", "np"):      # custom_sd.py:654-661: decode_latents -> run_safety_checker -> numpy_to_pil
       from PIL import Image
-      u8 = self.decode_latents(out, as_uint8=True).cpu().numpy()
+      dev_u8 = self.decode_latents(out, as_uint8=True)
+      u8 = dev_u8.cpu().numpy()
       n = N.lib().gill_coop_timeouts()      # (the copy above synchronised: the loop's give-up count is final — include/gill_amd.h "Exclusive-device contract")
       if n != 0:
         raise N.GillNativeError(f"{n} in-kernel GroupNorm finish(es) of the denoise loop timed out and NaN-poisoned the latents: the GPU is shared with "
@@ -629,9 +632,10 @@ class GillSDPipeline:
       if self.safety_checker is not None:
         img01, has_nsfw = self.safety_checker(u8.astype("float32") / 255.0, [Image.fromarray(im) for im in u8])
         u8 = (img01 * 255).round().astype("uint8")
+        dev_u8 = None
       out = [Image.fromarray(im) for im in u8] if output_type == "pil" else u8.astype("float32") / 255.0
     elif output_type == "pt":
       out = self.decode_latents(out, as_uint8=False)
     if not return_dict:
       return (out, has_nsfw)
-    return PipelineOutput(images=out, nsfw_content_detected=has_nsfw)
+    return PipelineOutput(images=out, nsfw_content_detected=has_nsfw, images_u8=dev_u8)

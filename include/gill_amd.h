@@ -857,6 +857,26 @@ int gill_op_lm_head_loss(const void* X_bf16, const void* W_bf16, const int64_t* 
  * launch merges in ascending order.  The slabs cover [0, V) exactly once.  Any output may be NULL. */
 int gill_lm_loss_geometry(int M, int V, int D, int* row_tile, int* col_tile, int* n_slabs, int* cols_per_slab);
 
+/* ------------------------------------------------------------------------------------------
+ * Image-block heads (csrc/img_heads.hip).  What generate_for_images_and_texts computes from the first [IMG] hidden state of a block
+ * (gill/models.py:671-676 retrieval embedding, :698-704 decision MLP), for n blocks in one launch.
+ *
+ * hidden (rows, D) fp32, row_idx (n) int32 on the device: the flat row of each block's first [IMG] hidden state, in any order, repeats
+ * allowed; a value outside [0, rows) is clamped on the device and nothing outside the buffers is touched.  Wr (E, D) bf16 with br (E)
+ * fp32 and Wd (C, D) bf16 with bd (C) fp32 are nullable as pairs, not both.  D a multiple of 8, at most 8192; 1 <= E <= 1024;
+ * 1 <= C <= 4; hidden and the weights 16-byte aligned.  Per block, with x = bf16(hidden[row]):
+ *   ret_emb (n, E) fp32 = y / ||y||_2,  y = Wr x + br in fp32 (an all-zero y stays zero)
+ *   probs (n, C) fp32 = softmax(z),  z = Wd x + bd;  choice (n) int32 = argmax z, a tie to the lower index
+ * Outputs of an absent pair may be NULL.  One launch on `stream`, no host wait; an argument error is reported before anything is
+ * enqueued.  No atomics and one fixed summation order: a block's outputs have the same bits at any n, at any position of row_idx and
+ * on any run (the rule gill_attention_decode states for rows).  Honours GILL_OP_REPEAT. */
+int gill_op_img_block_heads(const float* hidden_f32, int64_t rows, int D, const int32_t* row_idx, int n, const void* Wr_bf16, const float* br,
+                            int E, const void* Wd_bf16, const float* bd, int C, float* ret_emb, float* probs, int32_t* choice, void* stream);
+/* The CLIP rerank score (gill/models.py:733-751) of n blocks with g generated images each: visual (n g, E) fp32 un-normalised rows,
+ * ret_emb (n, E) fp32 -> scores (n, g) fp32 = cos(visual[b g + j], ret_emb[b]), 0 where either row is all zero.  One launch, no host
+ * wait; a score is a function of its own two rows alone (same bits at any n). */
+int gill_op_img_rerank_scores(const float* visual_f32, const float* ret_emb_f32, int n, int g, int E, float* scores, void* stream);
+
 /* What the GEMM / convolution launcher decides for a launch (host only, for tests; no GPU is touched).  Every decision of a launch — kernel
  * instantiation, grid, tile -> workgroup map, in-kernel finish, reducer — is made once, by a pure function of the arguments and of an environment
  * (pp = GILL_GEMM_PP, coop = GILL_GEMM_COOP, cus = compute units of the device), given explicitly here.
