@@ -107,6 +107,8 @@ SYMBOLS: Dict[str, Tuple[object, List[object]]] = {
   "gill_decode_uniforms": (_i, [C.c_uint64, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.POINTER(C.c_float)]),
   "gill_attention_decode": (_i, [_vp, _vp, _vp, _i, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp, _vp]),
   "gill_attention_append": (_i, [_vp, _vp, _vp, _i, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp, _vp]),
+  "gill_attention_extend": (_i, [_vp, _vp, _vp, _i, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp, _vp]),
+  "gill_opt_extend": (_i, [_vp, _vp, _vp, _vp, _i, _vp, _vp, _i, _i, _i, _i, _vp, _vp, _vp]),
   "gill_opt_decode_step": (_i, [_vp, _vp, _vp, _i, _i, _vp, _vp]),
   "gill_opt_prefill_ids": (_i, [_vp, _vp, _i, _i, _vp, _i, _vp, _vp]),
   "gill_opt_next_token_ragged": (_i, [_vp, _vp, _i, C.POINTER(gill_decode_rule), _i, C.POINTER(gill_decode_sampler), _vp, _vp, _vp, _i, _vp,

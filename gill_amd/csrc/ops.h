@@ -199,6 +199,18 @@ struct AttnAppendArgs : AttnDecodeArgs {
 };
 int attention_append_launch(const AttnAppendArgs& a, hipStream_t s);
 
+// Ragged multi-token attention with append (attention_extend.hip): row b brings cu_new[b + 1] - cu_new[b] consecutive new tokens (zero is legal:
+// the row is left untouched) at its own cache length n = lens[b], clamped into [0, pitch - count] (a clamp sets flags[b]).  q / k / v / O hold
+// total_new packed rows, row cu_new[b] + i the token n + i of sequence b; B in AttnDecodeArgs counts sequences.  Token i is stored at slot n + i
+// and attends to the slots 0 .. n + i; slots beyond are excluded by selection.  max_new / total_new: host bounds of the per-row count and of
+// cu_new[B] (they size the grid; a row whose device values exceed them is treated as empty and flagged).  Flash pattern on bf16 MFMA; the
+// accuracy bar of the decode kernels, not their bits.
+struct AttnExtendArgs : AttnDecodeArgs {
+  const int32_t* cu_new = nullptr;               // [B + 1] device
+  int total_new = 0, max_new = 0;
+};
+int attention_extend_launch(const AttnExtendArgs& a, hipStream_t s);
+
 
 // The feed-forward sub-block + proj_out + outer residual of a level-0 transformer block (C = 320) as one kernel (ffn.hip):
 //   out = [Wp.W2 | Wp] . [ value * gelu(gate) | t ] + bo + resid,  [value | gate] = W1' . LN(t) + b1'  (LN from the row-sum planes).

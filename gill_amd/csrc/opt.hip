@@ -6,8 +6,9 @@
 // learned positions with the +2 offset, final LayerNorm; hidden_states[-1] is post-final-LN.
 // The residual stream is fp32; GEMMs are bf16 MFMA with fp32 accumulation, split-K so that the
 // skinny (M = B*T) weight-streaming GEMMs cover all 256 CUs; attention is the shared flash kernel.
-// Every layer loop — forward, cached forward, and the ragged decode step on bf16 weights or e4m3 bytes — is TfmRun::layers of tfm.h; here:
-// embeddings and positions, the KV cache, the hidden-rows pass of img_hidden / forward_loss, logits and the decode entry points.
+// Every layer loop — forward, cached forward, the ragged decode step on bf16 weights or e4m3 bytes, and the packed extend pass of a dialogue
+// session — is TfmRun::layers of tfm.h; here: embeddings and positions, the KV cache, the hidden-rows pass of img_hidden / forward_loss, logits
+// and the decode and extend entry points.
 #include "tfm.h"
 #include "philox.h"
 
@@ -31,6 +32,9 @@ struct gill_opt {
   std::vector<TfmKv> cache;
   int32_t* dec_flags = nullptr;   // [max_batch]: length clamps of gill_opt_decode_step's attention, folded into the rows' flags by the ragged decision
   int32_t* cached_lens = nullptr; // [max_batch]: past_len per row, filled on the stream by gill_opt_forward_cached where it runs on the e4m3 bytes
+  // workspace of gill_opt_extend (allocated at its first call): the packed [B*T][3D] projection and the last new row of every sequence
+  bf16_t* ext_qkv = nullptr;
+  float* ext_last = nullptr;      // [max_batch][D]
   // scoring workspace of gill_opt_forward_loss (allocated at its first call): the final LayerNorm of every row, the shifted targets, the
   // per-row results and the partials of lmloss.hip
   bf16_t* xn_bf = nullptr;      // [B*T][D]
@@ -488,6 +492,101 @@ extern "C" int gill_opt_prefill_ids(gill_opt* m, const int64_t* ids, int B, int 
   GILL_TRY(embed_tokens_launch(ids, m->embed, m->cfg.vocab_size, (const bf16_t*)extra_rows_bf16, n_extra, m->pos, 2, B, Tmax, D, m->h, s));
   GILL_TRY(m->run_layers(B, Tmax, s, 0));
   GILL_TRY(layernorm_f32out_launch(m->h, 1, m->lnfg, m->lnfb, hidden_out, B * Tmax, D, 1e-5f, s));
+  return 0;
+}
+
+// ---- dialogue sessions: packed new tokens at per-row cache lengths ----
+
+// opt_add_pos_kernel / embed_tokens_kernel per token position: packed row r = cu_new[b] + i takes the embedding row of ids[r] (id < 0: row
+// -(id + 1) of extra) or emb[r], plus position 2 + lens[b] + i, the length read on the device and kept inside the table (the attention kernel of
+// the same pass raises the flag).  A row that no sequence owns (r >= cu_new[B]) is zero-filled: finite, and nothing reads it.
+__global__ __launch_bounds__(256) void opt_extend_embed_kernel(const int64_t* __restrict__ ids, const bf16_t* __restrict__ emb,
+                                                               const bf16_t* __restrict__ table, int vocab, const bf16_t* __restrict__ extra,
+                                                               int n_extra, const bf16_t* __restrict__ pos, int max_positions,
+                                                               const int32_t* __restrict__ cu_new, const int32_t* __restrict__ lens, int B, int D,
+                                                               float* __restrict__ out) {
+  const int row = blockIdx.x;
+  int b = -1;
+  for (int j = 0; j < B; ++j)       // (uniform: every thread walks the same few words)
+    if (row >= cu_new[j] && row < cu_new[j + 1]) { b = j; break; }
+  float* o = out + (size_t)row * D;
+  if (b < 0) {
+    for (int c = threadIdx.x * 2; c < D; c += blockDim.x * 2) *reinterpret_cast<float2*>(o + c) = make_float2(0.f, 0.f);
+    return;
+  }
+  const int n = lens[b];
+  int p = (n < 0 ? 0 : n) + (row - cu_new[b]);
+  p = 2 + (p > max_positions - 1 ? max_positions - 1 : p);
+  const bf16_t* e;
+  if (ids) {
+    int64_t id = ids[row];
+    if (id < 0 && n_extra > 0) {
+      int64_t x = -(id + 1);
+      if (x >= n_extra) x = n_extra - 1;
+      e = extra + (size_t)x * D;
+    } else {
+      if (id < 0) id = 0;
+      if (id >= vocab) id = vocab - 1;
+      e = table + (size_t)id * D;
+    }
+  } else {
+    e = emb + (size_t)row * D;
+  }
+  const bf16_t* pe = pos + (size_t)p * D;
+  for (int c = threadIdx.x * 2; c < D; c += blockDim.x * 2) {
+    const uint32_t u = *reinterpret_cast<const uint32_t*>(e + c);
+    const uint32_t v = *reinterpret_cast<const uint32_t*>(pe + c);
+    *reinterpret_cast<float2*>(o + c) = make_float2(bf2f((bf16_t)(u & 0xffff)) + bf2f((bf16_t)(v & 0xffff)), bf2f((bf16_t)(u >> 16)) + bf2f((bf16_t)(v >> 16)));
+  }
+}
+
+// idx[b] = the packed row of sequence b's last new token (0 for a sequence without new tokens: gathered, never copied out)
+__global__ void opt_extend_last_idx_kernel(const int32_t* __restrict__ cu_new, int B, int total_new, int32_t* __restrict__ idx) {
+  const int b = blockIdx.x * blockDim.x + threadIdx.x;
+  if (b >= B) return;
+  const int last = cu_new[b + 1] - 1;
+  idx[b] = (last >= cu_new[b] && last >= 0 && last < total_new) ? last : 0;
+}
+// dst[b][:] = src[b][:] for the sequences that brought new tokens
+__global__ __launch_bounds__(256) void opt_extend_copy_last_kernel(const float* __restrict__ src, const int32_t* __restrict__ cu_new, int total_new,
+                                                                   int D, float* __restrict__ dst) {
+  const int b = blockIdx.x;
+  const int last = cu_new[b + 1] - 1;
+  if (!(last >= cu_new[b] && last >= 0 && last < total_new)) return;
+  for (int c = threadIdx.x; c < D; c += blockDim.x) dst[(size_t)b * D + c] = src[(size_t)b * D + c];
+}
+
+extern "C" int gill_opt_extend(gill_opt* m, const int64_t* ids, const void* embeds_bf16, const void* extra_rows_bf16, int n_extra,
+                               const int32_t* cu_new, const int32_t* lens_dev, int B, int total_new, int max_new, int len_bound, float* hidden_last,
+                               float* hidden_all, void* stream) {
+  GILL_REQUIRE(m && (ids || embeds_bf16) && cu_new && lens_dev && hidden_last, "null argument");
+  GILL_REQUIRE(B >= 1 && B <= m->cfg.max_batch, "B exceeds the handle's workspace");
+  GILL_REQUIRE(max_new >= 1 && total_new >= max_new && (int64_t)total_new <= (int64_t)B * max_new &&
+               (int64_t)total_new <= (int64_t)m->cfg.max_batch * m->cfg.max_seq, "extend: max_new <= total_new <= B * max_new, within the workspace");
+  GILL_REQUIRE(len_bound >= max_new && len_bound <= m->cfg.max_seq, "len_bound exceeds the handle's max_seq");
+  GILL_REQUIRE(len_bound <= m->cfg.max_positions, "sequence longer than the position table");
+  GILL_REQUIRE(n_extra >= 0 && (n_extra == 0 || extra_rows_bf16), "n_extra rows need a table");
+  hipStream_t s = (hipStream_t)stream;
+  const int D = m->cfg.hidden_size;
+  GILL_TRY(opt_ensure_cache(m));
+  if (!m->ext_qkv) {
+    GILL_TRY(m->pool.alloc(&m->ext_qkv, (size_t)m->cfg.max_batch * m->cfg.max_seq * 3 * D, false));
+    GILL_TRY(m->pool.alloc(&m->ext_last, (size_t)m->cfg.max_batch * D, false));
+  }
+  hipLaunchKernelGGL(opt_extend_embed_kernel, dim3(total_new), dim3(256), 0, s, ids, (const bf16_t*)embeds_bf16, m->embed, m->cfg.vocab_size,
+                     (const bf16_t*)extra_rows_bf16, n_extra, m->pos, m->cfg.max_positions, cu_new, lens_dev, B, D, m->h);
+  GILL_CHECK_HIP(hipGetLastError());
+  // the one layer loop over the packed rows, on the bf16 matrices (a w8 handle: the dequantised ones, as the prefill)
+  TfmDecode dec{lens_dev, m->dec_flags};
+  dec.cu_new = cu_new; dec.nseq = B; dec.max_new = max_new; dec.qkv = m->ext_qkv;
+  GILL_TRY(m->run_layers(1, total_new, s, 0, &dec, false));
+  if (hidden_all) GILL_TRY(layernorm_f32out_launch(m->h, 1, m->lnfg, m->lnfb, hidden_all, total_new, D, 1e-5f, s));
+  hipLaunchKernelGGL(opt_extend_last_idx_kernel, dim3(cdiv(B, 64)), dim3(64), 0, s, cu_new, B, total_new, m->idx_dev);
+  GILL_CHECK_HIP(hipGetLastError());
+  GILL_TRY(gather_rows_launch(m->h, 1, m->idx_dev, B, D, m->gath, 1, s));
+  GILL_TRY(layernorm_f32out_launch(m->gath, 1, m->lnfg, m->lnfb, m->ext_last, B, D, 1e-5f, s));
+  hipLaunchKernelGGL(opt_extend_copy_last_kernel, dim3(B), dim3(256), 0, s, m->ext_last, cu_new, total_new, D, hidden_last);
+  GILL_CHECK_HIP(hipGetLastError());
   return 0;
 }
 

@@ -5,7 +5,7 @@
 // struct, one weight loader, one workspace and one runner with the only layer loop (TfmRun::layers); an engine keeps what is particular
 // to it (embeddings, caches, final norms) and sets the switches of struct Tfm.  OPT's ragged decode step, and its cached forward on the e4m3
 // bytes, are that loop with a TfmDecode argument (decode attention with append in place of the flash kernel), the fp8-weight mode the same loop
-// with TfmRun::use_w8.
+// with TfmRun::use_w8; the extend pass of a dialogue session (packed new tokens at per-row lengths) is the same argument with cu_new set.
 // Nothing here allocates or builds strings per launch.
 #pragma once
 #include "engine_util.h"
@@ -73,7 +73,13 @@ int tfm_linear_launch(const bf16_t* A, int M, const bf16_t* W, int blk, const fl
 // Self-attention is then a plain QKV linear into Tfm::q as [B * T][3D] -> attention_decode_launch (T == 1: the ragged step) or
 // attention_append_launch (T > 1, at most 16: the cached forward on the e4m3 bytes), which append the rows' K / V at lens[b] .., clamp a length
 // beyond the cache and raise flags[b] (nullable) -> the out-projection.
-struct TfmDecode { const int32_t* lens = nullptr; int32_t* flags = nullptr; };
+// With cu_new (the extend pass, gill_opt_extend): the stream holds T = total_new PACKED rows (layers is called with B = 1), rows
+// cu_new[b] .. cu_new[b + 1] - 1 the new tokens of sequence b < nseq at positions lens[b] ..; the projection goes to qkv ([total_new][3D], the
+// caller's: Tfm::q is sized for 16 rows of it) and attention is attention_extend_launch with the host bound max_new of a row's count.
+struct TfmDecode {
+  const int32_t* lens = nullptr; int32_t* flags = nullptr;
+  const int32_t* cu_new = nullptr; int nseq = 0, max_new = 0; bf16_t* qkv = nullptr;
+};
 
 struct TfmRun {
   const Tfm& t;

@@ -227,7 +227,16 @@ int TfmRun::attend(int B, int nq, int nkv, int npad_q, int npad_kv, const bf16_t
 
 int TfmRun::self_attn(float* h, int B, int T, const TfmLayer& L, bool causal, const float* next_g, const float* next_b, const TfmKv* kv,
                       int past, const TfmDecode* dec) const {
-  if (dec) {
+  if (dec && dec->cu_new) {
+    GILL_REQUIRE(kv && B == 1 && T >= 1 && dec->qkv, "extend attention: a cache and packed rows");
+    GILL_TRY(linear(t.nbuf, T, L.qkv, nullptr, ACT_NONE, dec->qkv, false));
+    AttnExtendArgs a;
+    a.q = dec->qkv; a.k = dec->qkv + t.D; a.v = dec->qkv + 2 * t.D; a.ld = 3 * t.D;
+    a.K = kv->k; a.Vt = kv->vt; a.lens = dec->lens; a.cu_new = dec->cu_new; a.O = t.o; a.ldo = t.D; a.flags = dec->flags;
+    a.B = dec->nseq; a.total_new = T; a.max_new = dec->max_new; a.H = t.H; a.dp = t.dp; a.dpv = t.dpv; a.pitch = kv->pad;
+    a.qscale = 1.4426950408889634f / sqrtf((float)t.dp);
+    GILL_TRY(attention_extend_launch(a, s));
+  } else if (dec) {
     GILL_REQUIRE(kv && T >= 1, "decode attention: a cache");
     GILL_TRY(linear(t.nbuf, B * T, L.qkv, nullptr, ACT_NONE, t.q, false));
     AttnAppendArgs a;

@@ -166,6 +166,7 @@ class GILLModel(nn.Module):
     self.logit_scale = nn.Parameter(torch.ones([]) * np.log(1 / 0.07))
     self._opt_handle = None
     self._opt_cap = (0, 0)
+    self._cache_epoch = 0         # bumped by every entry that writes or rebuilds the handle's KV cache: open sessions go stale (dialogue.py)
     self.opt_weights = 'bf16'     # quantize_lm(): 'fp8' = the weight-only fp8 decoder (gill_opt_create_ex, GILL_OPT_W8)
     # native handles snapshot the weights: a state-dict load into this module (or, recursively, into a parent) drops them
     self.register_load_state_dict_post_hook(lambda module, incompatible_keys: module.refresh_native())
@@ -274,6 +275,7 @@ class GILLModel(nn.Module):
 
   def refresh_native(self):
     """Call after mutating weights in place once a forward has already run (handles snapshot the weights)."""
+    self._cache_epoch += 1
     self.release_native()
     for fcs in (self.gen_text_hidden_fcs, getattr(self, 'ret_text_hidden_fcs', [])):
       for fc in fcs:
@@ -294,6 +296,7 @@ class GILLModel(nn.Module):
     cb, ct = self._opt_cap
     if self._opt_handle is not None and B <= cb and T <= ct:
       return self._opt_handle
+    self._cache_epoch += 1
     self.release_native()
     cb, ct = max(cb, B, 8), max(ct, T, 64)
     c = self.opt_cfg
@@ -320,6 +323,7 @@ class GILLModel(nn.Module):
     if mode not in _OPT_WEIGHT_MODES:
       raise ValueError(f"quantize_lm: mode must be one of {sorted(_OPT_WEIGHT_MODES)} or None, got {mode!r}")
     if mode != self.opt_weights:
+      self._cache_epoch += 1
       self.opt_weights = mode
       if self._opt_handle is not None:
         N.lib().gill_opt_destroy(self._opt_handle)
@@ -362,6 +366,7 @@ class GILLModel(nn.Module):
     """hidden_states[-1] rows of the tokens past_len .. past_len+T_new-1, computed against the handle's KV cache
     (gill_opt_forward_cached).  past_len == 0 starts a new sequence."""
     B, Tn, D = new_embeds.shape
+    self._cache_epoch += 1
     cb, ct = self._opt_cap
     if past_len > 0 and (self._opt_handle is None or B > cb or past_len + Tn > ct):
       # growing would rebuild the handle and lose the keys / values cached so far
@@ -597,6 +602,7 @@ class GILLModel(nn.Module):
     not depend on the other rows of the batch, no temperature overflows, torch's generators are not touched, and the loop waits
     for the device as the greedy one does: never at batch > 1, one 4-byte count per step at batch 1."""
     self._decode_host_waits = 0
+    self._cache_epoch += 1
     if seed is not None:
       if not self.decode_on_device:
         raise ValueError('seed needs decode_on_device: the seeded draw runs in libgill_amd only.')
@@ -786,6 +792,73 @@ class GILLModel(nn.Module):
     out = tokens[:, :col].clone() if max_len > 0 else None
     return out, output_embeddings, output_logits
 
+  def _ragged_decode_loop(self, h, B: int, st: Tensor, hid: Tensor, steps: Tensor, nxt: Tensor, logits: Tensor, tokens: Tensor, rule,
+                          sampler, max_len: int, L: int, len0: int, len_floor: int = 0) -> None:
+    """The ragged loop generate_batch and a dialogue session share: per iteration one decode step over all B rows (from the second
+    iteration on) and one decision; the count of active rows of iteration i is read after iteration i + 1 has been enqueued.  hid (B, D):
+    the hidden rows the first decision reads; len0: the host's bound on the deciding rows' lengths at the first decode step (it grows by one
+    per iteration); len_floor: the bound of rows that take no decision (a session's idle rows: their lengths stand)."""
+    dev = st.device
+    lib = N.lib()
+    count = torch.zeros(2, dtype=torch.int32, pin_memory=True)
+    evs = [torch.cuda.Event(), torch.cuda.Event()]
+    with torch.cuda.device(dev):
+      for it in range(L):
+        if it > 0:
+          N.check(lib.gill_opt_decode_step(h, N.ptr(nxt), N.ptr(st), B, max(len0 + it, len_floor), N.ptr(steps[it - 1]), N.current_stream()))
+          hid = steps[it - 1]
+        N.check(lib.gill_opt_next_token_ragged(h, N.ptr(hid), B, C.byref(rule), max_len, C.byref(sampler) if sampler is not None else None,
+                                               N.ptr(logits), N.ptr(st), N.ptr(tokens), tokens.shape[1], N.ptr(nxt), N.current_stream()))
+        count[it & 1:(it & 1) + 1].copy_(st[6 * B:], non_blocking=True)
+        evs[it & 1].record()
+        if it > 0:                    # one iteration late: the device already has iteration `it` to run
+          evs[(it - 1) & 1].synchronize()
+          self._decode_host_waits += 1
+          if int(count[(it - 1) & 1]) == 0:
+            break
+
+  def _ragged_results(self, B: int, st: Tensor, tokens: Tensor, steps: Tensor, L: int, n_ret: int):
+    """The state a ragged loop left -> (n_tokens (B,), n_hidden (B,) on the host, hidden (B, L, D)); raises on the rows' error flags."""
+    D = steps.shape[2]
+    state = st.cpu()
+    flags = state[5 * B:6 * B]
+    if bool((flags & 1).any()):
+      raise AssertionError((self.retrieval_token_idx, self.gen_token_idx))   # :519
+    if bool((flags & 6).any()):
+      raise N.GillNativeError(f'ragged decode: a row outgrew the cache or the token buffer (flags {flags.tolist()})')
+    n_tokens = state[3 * B:4 * B].to(torch.int64)
+    toks = tokens.cpu()
+    n_hidden = torch.zeros(B, dtype=torch.int64)
+    for b in range(B):
+      nt = int(n_tokens[b])
+      last = 1
+      if n_ret > 1 and nt >= n_ret and int(toks[b, nt - n_ret]) == int(self.retrieval_token_idx[0]):
+        last = n_ret            # the row's last decision opened an [IMG] block, which ends the row
+      n_hidden[b] = max(nt - last, 0)
+    hidden = steps.transpose(0, 1)[:, :L].contiguous() if L > 0 else steps.new_zeros((B, 0, D))
+    return n_tokens, n_hidden, hidden
+
+  def _lm_extend(self, cu_new: Tensor, lens_dev: Tensor, B: int, total_new: int, max_new: int, len_bound: int, hidden_last: Tensor,
+                 ids: Optional[Tensor] = None, embeds: Optional[Tensor] = None, extra_rows: Optional[Tensor] = None,
+                 hidden_all: Optional[Tensor] = None) -> None:
+    """gill_opt_extend on the handle as it stands (never grown here: that would drop the cache): packed new tokens, ids (total_new) int64 or
+    embeds (total_new, D) bf16, row cu_new[b] + i at position lens_dev[b] + i of sequence b; -> hidden_last (B, 1, D) fp32 in place, and
+    hidden_all (total_new, D) fp32 when given."""
+    cb, ct = self._opt_cap
+    if self._opt_handle is None or B > cb or len_bound > ct:
+      raise N.GillNativeError(f'KV cache of the OPT handle holds {ct} tokens x {cb} sequences; extend needs {len_bound} x {B}.')
+    n_extra = 0 if extra_rows is None else int(extra_rows.shape[0])
+    with torch.cuda.device(cu_new.device):
+      N.check(N.lib().gill_opt_extend(self._opt_handle, N.ptr(ids), N.ptr(embeds), N.ptr(extra_rows) if n_extra else None, n_extra,
+                                      N.ptr(cu_new), N.ptr(lens_dev), B, total_new, max_new, len_bound, N.ptr(hidden_last),
+                                      N.ptr(hidden_all), N.current_stream()))
+
+  def open_session(self, B: int, capacity: int):
+    """A dialogue session over the handle's KV cache: B rows of up to `capacity` tokens whose caches are kept across turns
+    (dialogue.DialogueSession).  Any other entry that writes or rebuilds the cache makes the session stale."""
+    from .dialogue import DialogueSession
+    return DialogueSession(self, B, capacity)
+
   def generate_batch(self, embeddings: Optional[Tensor] = None, lengths=None, ids: Optional[Tensor] = None,
                      extra_rows: Optional[Tensor] = None, max_len: int = 32, temperature: float = 0.0, top_p: float = 1.0,
                      min_word_tokens: int = 0, ret_scale_factor: float = 1.0, gen_scale_factor: float = 1.0,
@@ -804,6 +877,7 @@ class GILLModel(nn.Module):
     hidden_states[-1] at generated token j's position for j < n_hidden[b] = n_tokens[b] minus what the row's last decision emitted
     — the rows generated_embeddings[-1][:, T0:] holds in the one-sequence call."""
     self._decode_host_waits = 0
+    self._cache_epoch += 1
     if (embeddings is None) == (ids is None):
       raise ValueError('generate_batch takes embeddings (B, Tmax, D) or ids (B, Tmax), one of the two.')
     src = embeddings if embeddings is not None else ids
@@ -871,38 +945,8 @@ class GILLModel(nn.Module):
       if temperature != 0.0:
         sampler = N.gill_decode_sampler()
         sampler.temperature, sampler.top_p, sampler.seed = float(temperature), min(float(top_p), 1.0), seed
-      count = torch.zeros(2, dtype=torch.int32, pin_memory=True)
-      evs = [torch.cuda.Event(), torch.cuda.Event()]
-      with torch.cuda.device(dev):
-        for it in range(L):
-          if it > 0:
-            N.check(lib.gill_opt_decode_step(h, N.ptr(nxt), N.ptr(st), B, max(lens) + it, N.ptr(steps[it - 1]), N.current_stream()))
-            hid = steps[it - 1]
-          N.check(lib.gill_opt_next_token_ragged(h, N.ptr(hid), B, C.byref(rule), max_len, C.byref(sampler) if sampler is not None else None,
-                                                 N.ptr(logits), N.ptr(st), N.ptr(tokens), tokens.shape[1], N.ptr(nxt), N.current_stream()))
-          count[it & 1:(it & 1) + 1].copy_(st[6 * B:], non_blocking=True)
-          evs[it & 1].record()
-          if it > 0:                    # one iteration late: the device already has iteration `it` to run
-            evs[(it - 1) & 1].synchronize()
-            self._decode_host_waits += 1
-            if int(count[(it - 1) & 1]) == 0:
-              break
-      state = st.cpu()
-      flags = state[5 * B:6 * B]
-      if bool((flags & 1).any()):
-        raise AssertionError((self.retrieval_token_idx, self.gen_token_idx))   # :519
-      if bool((flags & 6).any()):
-        raise N.GillNativeError(f'ragged decode: a row outgrew the cache or the token buffer (flags {flags.tolist()})')
-      n_tokens = state[3 * B:4 * B].to(torch.int64)
-      toks = tokens.cpu()
-      n_hidden = torch.zeros(B, dtype=torch.int64)
-      for b in range(B):
-        nt = int(n_tokens[b])
-        last = 1
-        if n_ret > 1 and nt >= n_ret and int(toks[b, nt - n_ret]) == int(self.retrieval_token_idx[0]):
-          last = n_ret            # the row's last decision opened an [IMG] block, which ends the row
-        n_hidden[b] = max(nt - last, 0)
-      hidden = steps.transpose(0, 1)[:, :L].contiguous() if L > 0 else steps.new_zeros((B, 0, D))
+      self._ragged_decode_loop(h, B, st, hid, steps, nxt, logits, tokens, rule, sampler, max_len, L, max(lens))
+      n_tokens, n_hidden, hidden = self._ragged_results(B, st, tokens, steps, L, n_ret)
     return tokens[:, :L], n_tokens.to(dev), hidden, n_hidden.to(dev)
 
 class _TopScores:
@@ -1155,12 +1199,31 @@ class GILL(nn.Module):
     tokens, n_tok, hidden, n_hid = m.generate_batch(ids=ids, lengths=lens, extra_rows=extra, max_len=num_words, temperature=temperature,
                                                     top_p=top_p, min_word_tokens=min_word_tokens, ret_scale_factor=ret_scale_factor,
                                                     gen_scale_factor=gen_scale_factor, seed=seed)
+    return self._batch_outputs(list(range(len(prompts))), tokens, n_tok, hidden, n_hid, max_num_rets, generator, guidance_scale,
+                               num_inference_steps, all_branches, skip_gen_on_ret)[0]
+
+  def open_dialogues(self, n: int, capacity: Optional[int] = None):
+    """n multi-turn dialogues whose KV caches are kept across turns (dialogue.GillDialogues): .say(turns, ...) sends each dialogue's new
+    turn only and returns what generate_for_images_and_texts_batch returns per prompt list.  capacity: tokens per dialogue (default: the LM's
+    position table)."""
+    from .dialogue import GillDialogues
+    return GillDialogues(self, n, capacity)
+
+  def _batch_outputs(self, rows, tokens: Tensor, n_tok: Tensor, hidden: Tensor, n_hid: Tensor, max_num_rets: int, generator,
+                     guidance_scale: float, num_inference_steps: int, all_branches: bool, skip_gen_on_ret: bool):
+    """What generate_for_images_and_texts_batch and GillDialogues.say do with a ragged decode's results (tokens (B, L), n_tokens, hidden
+    (B, L, D), n_hidden as generate_batch returns them) for the rows `rows` of the batch: per row the reference's newline truncation, the
+    [IMG] blocks up to max_num_rets and the captions; the raw_emb blocks of all rows through gen_text_hidden_fcs[0] in one call and, with
+    load_sd, through the SD pipeline in chunks of 8; with all_branches the retrieval, decision and rerank branches (_batch_branches).
+    -> (per row of `rows` the list the one-sequence method returns, per row the index its ids were truncated at, 0: not truncated)."""
+    m = self.model
+    dev = m.logit_scale.device
     n_tok, n_hid = n_tok.tolist(), n_hid.tolist()
     newline_token_id = m.tokenizer('\n', add_special_tokens=False).input_ids[0]
     gen_prefix = ''.join([f'[IMG{i}]' for i in range(m.args.num_tokens)])
-    outputs, blocks = [], []          # blocks: (the image_outputs dict to fill, raw_emb (1, 8, D))
+    outputs, blocks, truncs = [], [], []          # blocks: (the image_outputs dict to fill, raw_emb (1, 8, D))
     where = []                        # per block: (prompt list b, the flat row of its first [IMG] hidden state in `hidden`)
-    for b in range(len(prompts)):
+    for b in rows:
       generated_ids = tokens[b:b + 1, :n_tok[b]]
       embeddings = hidden[b:b + 1, :n_hid[b]].to(m.logit_scale.dtype)
       trunc_idx = 0
@@ -1168,6 +1231,7 @@ class GILL(nn.Module):
         if t == newline_token_id:
           trunc_idx = j
           break
+      truncs.append(trunc_idx)
       if trunc_idx > 0:
         generated_ids = generated_ids[:, :trunc_idx]
         embeddings = embeddings[:, :trunc_idx]
@@ -1220,7 +1284,7 @@ class GILL(nn.Module):
       else:
         for k, (image_outputs, _) in enumerate(blocks):
           image_outputs['gen'] = [gen_emb[k * self.num_gen_images:(k + 1) * self.num_gen_images]]
-    return outputs
+    return outputs, truncs
 
   def _batch_branches(self, blocks, where, hidden: Tensor, max_num_rets: int) -> Optional[Tensor]:
     """The retrieval and decision branches of generate_for_images_and_texts (models.py:671-704) for every [IMG] block of a batch.

@@ -203,6 +203,29 @@ def attention_append(q: torch.Tensor, k_new: torch.Tensor, v_new: torch.Tensor, 
   return o
 
 
+def attention_extend(q: torch.Tensor, k_new: torch.Tensor, v_new: torch.Tensor, K: torch.Tensor, Vt: torch.Tensor, lens: torch.Tensor,
+                     cu_new: torch.Tensor, max_new: int, flags: Optional[torch.Tensor] = None) -> torch.Tensor:
+  """Ragged multi-token attention with append: q / k_new / v_new (total_new, H*d) bf16, packed rows (each contiguous, or the three column thirds
+  of one (total_new, 3*H*d) projection); cu_new (B + 1) int32 on the device, the prefix sums of the per-row new-token counts (zero is legal);
+  row cu_new[b] + i is token lens[b] + i of sequence b.  K (B,H,pitch,d) and Vt (B,H,round_up(d,32),pitch) bf16 caches, updated IN PLACE at
+  slots lens[b] .. lens[b] + count - 1; lens (B) int32 on the device; max_new: the host's bound on a row's count; flags (B) int32 (optional)
+  receives 1 where a length was clamped into [0, pitch - count].  Returns (total_new, H*d) bf16."""
+  B, H, pitch, d = K.shape
+  total = q.shape[0]
+  ld = q.stride(0)
+  for t in (q, k_new, v_new):
+    assert t.dtype == torch.bfloat16 and t.is_cuda and tuple(t.shape) == (total, H * d) and t.stride(1) == 1 and t.stride(0) == ld
+  assert K.dtype == torch.bfloat16 and Vt.dtype == torch.bfloat16 and tuple(Vt.shape) == (B, H, (d + 31) // 32 * 32, pitch)
+  assert lens.dtype == torch.int32 and lens.numel() == B and cu_new.dtype == torch.int32 and cu_new.numel() == B + 1
+  assert flags is None or (flags.dtype == torch.int32 and flags.numel() == B)
+  o = torch.empty((total, H * d), dtype=torch.bfloat16, device=q.device)
+  if total == 0:      # no row brought a token: nothing to store, nothing to attend
+    return o
+  N.check(N.lib().gill_attention_extend(q.data_ptr(), k_new.data_ptr(), v_new.data_ptr(), ld, N.ptr(K), N.ptr(Vt), N.ptr(lens), N.ptr(cu_new),
+                                        N.ptr(o), B, total, int(max_new), H, d, pitch, N.ptr(flags), N.current_stream()))
+  return o
+
+
 def layernorm(x: torch.Tensor, gamma: torch.Tensor, beta: torch.Tensor, eps: float = 1e-5) -> torch.Tensor:
   assert x.is_cuda and x.dtype in (torch.bfloat16, torch.float32)
   x = x.contiguous()

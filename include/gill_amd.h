@@ -286,6 +286,44 @@ int gill_opt_pick_token_ragged(gill_opt* h, float* logits, int B, const gill_dec
                                const gill_decode_sampler* sampler, int32_t* state, int64_t* tokens, int ld, void* next_embeds_bf16,
                                void* stream);
 
+/* ---- Dialogue sessions: a row's cache is kept across turns and extended by a turn's worth of new tokens. ----
+ *
+ * Ragged multi-token attention with append, the operator under gill_opt_extend.  Row b brings cu_new[b + 1] - cu_new[b] consecutive new
+ * tokens at its own cache length n = lens[b]: cu_new (B + 1) int32 on the DEVICE holds the prefix sums of the per-row counts, and q, k_new,
+ * v_new (rows of ld bf16 elements, head h at column h * d, d = 64, 80 or 128: the three thirds of one [total_new][3D] projection) and
+ * o (H*d per row) hold total_new packed rows, row cu_new[b] + i the token n + i of sequence b.  K, Vt, lens and flags as in
+ * gill_attention_decode.  Token i's key goes to slot n + i of K, its value to column n + i of Vt (and the ones-row entry
+ * Vt[b][h][d][n + i] = 1 where round_up(d,32) > d, as gill_attention_append writes it: the decode kernels read the cache afterwards), and
+ *   o[cu_new[b] + i] = softmax(q_i . [K[0..n-1]; k_0..k_i] / sqrt(d)) . [V[0..n-1]; v_0..v_i]      (the scale applied in fp32).
+ * Slots at or beyond n + i + 1 are excluded by selection whatever they hold.  A row with no new tokens is legal and is left untouched.
+ * max_new and total_new are HOST bounds on the per-row count and on cu_new[B]; they size the grid, 1 <= max_new <= pitch.  n outside
+ * [0, pitch - count] is clamped into it and flags[b] is set to 1; a row whose device count exceeds max_new, or whose packed range leaves
+ * [0, total_new), is treated as empty and flagged; nothing outside the buffers is touched.  Q.K^T and P.V run on bf16 MFMA with fp32
+ * accumulation and an online softmax in fp32 over tiles of 32 keys (csrc/attention_extend.hip): a row's output and cache bits are a fixed
+ * function of its own operands, n and count (the same at any B, at any place in the pack, on any run); they meet the accuracy bar of
+ * gill_attention_append, not its bits (another reduction order).  An unsupported d, a misaligned pointer or max_new < 1 are errors,
+ * reported before anything is launched. */
+int gill_attention_extend(const void* q, const void* k_new, const void* v_new, int ld, void* K, void* Vt, const int32_t* lens,
+                          const int32_t* cu_new, void* o, int B, int total_new, int max_new, int H, int d, int pitch, int32_t* flags,
+                          void* stream);
+
+/* The layers over packed new tokens at per-row cache lengths: a dialogue turn appended to each row's cache (the first feed of a row,
+ * lens_dev[b] = 0, is its prefill, without pad rows).  Input: ids (total_new) int64 on the device (an id < 0 selects row -(id + 1) of
+ * extra_rows (n_extra, D) bf16, as in gill_opt_prefill_ids), or, with ids NULL, embeds (total_new, D) bf16.  cu_new (B + 1) and lens_dev (B)
+ * int32 on the device as in gill_attention_extend: packed row cu_new[b] + i is the token at position lens_dev[b] + i of row b, takes
+ * position embedding 2 + lens_dev[b] + i, stores its key / value at that slot and attends to the slots up to it.  The layers are the one
+ * loop of every other entry with self-attention as projection -> gill_attention_extend -> out-projection.
+ *   hidden_last (B,1,D) fp32 = hidden_states[-1] of each row's last new token; rows without new tokens keep what they held.
+ *   hidden_all (total_new, D) fp32, nullable: hidden_states[-1] of every new token.
+ * max_new / total_new: host bounds as in gill_attention_extend (total_new <= max_batch * max_seq); len_bound: the host's upper bound on
+ * max_b(lens_dev[b] + count[b]), checked against max_seq and the position table before anything is enqueued.  A length the device holds
+ * beyond that is clamped and reported through the rows' flags by the next ragged decision.  The entry does not advance lens_dev.  No host
+ * wait.  On a GILL_OPT_W8 handle the pass runs the dequantised bf16 matrices (the same model, the rule of the prefill: a turn has more rows
+ * than the fp8 linear takes); the decode steps that follow keep their fp8 path, on the same cache. */
+int gill_opt_extend(gill_opt* h, const int64_t* ids, const void* embeds_bf16, const void* extra_rows_bf16, int n_extra, const int32_t* cu_new,
+                    const int32_t* lens_dev, int B, int total_new, int max_new, int len_bound, float* hidden_last, float* hidden_all,
+                    void* stream);
+
 /* ------------------------------------------------------------------------------------------
  * Image prompts — the frozen CLIP vision tower (transformers CLIPVisionModel built at gill/models.py:78-96 and called by
  * GILLModel.get_visual_embs, gill/models.py:129-145: `self.visual_model(pixel_values).pooler_output`).
