@@ -109,6 +109,11 @@ SYMBOLS: Dict[str, Tuple[object, List[object]]] = {
   "gill_attention_append": (_i, [_vp, _vp, _vp, _i, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp, _vp]),
   "gill_attention_extend": (_i, [_vp, _vp, _vp, _i, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp, _vp]),
   "gill_opt_extend": (_i, [_vp, _vp, _vp, _vp, _i, _vp, _vp, _i, _i, _i, _i, _vp, _vp, _vp]),
+  "gill_opt_set_kv_format": (_i, [_vp, _i]),
+  "gill_opt_kv_format": (_i, [_vp]),
+  "gill_opt_kv_bytes": (C.c_int64, [_vp]),
+  "gill_attention_decode_kv8": (_i, [_vp, _vp, _vp, _i, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp, _vp]),
+  "gill_attention_extend_kv8": (_i, [_vp, _vp, _vp, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp, _vp]),
   "gill_opt_decode_step": (_i, [_vp, _vp, _vp, _i, _i, _vp, _vp]),
   "gill_opt_prefill_ids": (_i, [_vp, _vp, _i, _i, _vp, _i, _vp, _vp]),
   "gill_opt_next_token_ragged": (_i, [_vp, _vp, _i, C.POINTER(gill_decode_rule), _i, C.POINTER(gill_decode_sampler), _vp, _vp, _vp, _i, _vp,

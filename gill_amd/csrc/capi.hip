@@ -309,6 +309,31 @@ extern "C" int gill_attention_extend(const void* q, const void* k_new, const voi
   return 0;
 }
 
+extern "C" int gill_attention_decode_kv8(const void* q, const void* k_new, const void* v_new, int ld, void* K8, void* Vt8, void* Kexp, void* Vexp,
+                                         const int32_t* lens, void* o, int B, int H, int d, int pitch, int32_t* flags, void* stream) {
+  AttnDecodeKv8Args a;
+  a.q = (const bf16_t*)q; a.k = (const bf16_t*)k_new; a.v = (const bf16_t*)v_new; a.ld = ld;
+  a.K8 = (uint8_t*)K8; a.Vt8 = (uint8_t*)Vt8; a.Kexp = (int8_t*)Kexp; a.Vexp = (int8_t*)Vexp;
+  a.lens = lens; a.O = (bf16_t*)o; a.ldo = H * d; a.flags = flags;
+  a.B = B; a.H = H; a.dp = d; a.dpv = round_up(d, 32); a.pitch = pitch;
+  a.qscale = 1.4426950408889634f / sqrtf((float)d);
+  for (int r = 0; r < op_repeat(); ++r) GILL_TRY(attention_decode_kv8_launch(a, (hipStream_t)stream));
+  return 0;
+}
+
+extern "C" int gill_attention_extend_kv8(const void* q, const void* k_new, const void* v_new, int ld, void* K8, void* Vt8, void* Kexp, void* Vexp,
+                                         const int32_t* lens, const int32_t* cu_new, void* o, int B, int total_new, int max_new, int H, int d,
+                                         int pitch, int32_t* flags, void* stream) {
+  AttnExtendKv8Args a;
+  a.q = (const bf16_t*)q; a.k = (const bf16_t*)k_new; a.v = (const bf16_t*)v_new; a.ld = ld;
+  a.K8 = (uint8_t*)K8; a.Vt8 = (uint8_t*)Vt8; a.Kexp = (int8_t*)Kexp; a.Vexp = (int8_t*)Vexp;
+  a.lens = lens; a.cu_new = cu_new; a.O = (bf16_t*)o; a.ldo = H * d; a.flags = flags;
+  a.B = B; a.total_new = total_new; a.max_new = max_new; a.H = H; a.dp = d; a.dpv = round_up(d, 32); a.pitch = pitch;
+  a.qscale = 1.4426950408889634f / sqrtf((float)d);
+  for (int r = 0; r < op_repeat(); ++r) GILL_TRY(attention_extend_kv8_launch(a, (hipStream_t)stream));
+  return 0;
+}
+
 extern "C" int gill_op_layernorm(const void* x, int x_f32, const float* gamma, const float* beta, void* y_bf16, int rows,
                                  int C, float eps, void* stream) {
   return layernorm_launch(x, x_f32, gamma, beta, (bf16_t*)y_bf16, rows, C, eps, (hipStream_t)stream);

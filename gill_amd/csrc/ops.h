@@ -211,6 +211,27 @@ struct AttnExtendArgs : AttnDecodeArgs {
 };
 int attention_extend_launch(const AttnExtendArgs& a, hipStream_t s);
 
+// The same two operators on an e4m3 cache (attention_decode_kv8.hip, attention_extend_kv8.hip; the format: attention_kv8_dev.h).  Every key row
+// and value row of a (token, head) is dp e4m3 bytes and one int8 exponent e (scale 2^e): K8 [B][H][pitch][dp], Vt8 [B][H][dpv][pitch] bytes (rows
+// dp .. dpv - 1 are never read as data and never written: no ones-row), Kexp / Vexp [B][H][pitch].  Every key and value, the new tokens' own
+// included, is rounded to its e4m3 row before any query uses it, so the result is a function of the token sequence, not of how it was fed.
+// Lengths, clamps, flags, q / k / v and O as in AttnDecodeArgs / AttnExtendArgs.
+struct AttnDecodeKv8Args {
+  const bf16_t* q = nullptr; const bf16_t* k = nullptr; const bf16_t* v = nullptr; int ld = 0;
+  uint8_t* K8 = nullptr; uint8_t* Vt8 = nullptr; int8_t* Kexp = nullptr; int8_t* Vexp = nullptr;
+  const int32_t* lens = nullptr;
+  bf16_t* O = nullptr; int ldo = 0;
+  int32_t* flags = nullptr;
+  int B = 0, H = 0, dp = 0, dpv = 0, pitch = 0;
+  float qscale = 1.f;
+};
+int attention_decode_kv8_launch(const AttnDecodeKv8Args& a, hipStream_t s);
+struct AttnExtendKv8Args : AttnDecodeKv8Args {
+  const int32_t* cu_new = nullptr;
+  int total_new = 0, max_new = 0;
+};
+int attention_extend_kv8_launch(const AttnExtendKv8Args& a, hipStream_t s);
+
 
 // The feed-forward sub-block + proj_out + outer residual of a level-0 transformer block (C = 320) as one kernel (ffn.hip):
 //   out = [Wp.W2 | Wp] . [ value * gelu(gate) | t ] + bo + resid,  [value | gate] = W1' . LN(t) + b1'  (LN from the row-sum planes).

@@ -30,6 +30,7 @@ struct gill_opt {
   int32_t* idx_dev = nullptr; // [B*8 + B*8]
   // KV cache of gill_opt_forward_cached (allocated at its first call): per layer K [B][H][Tcap][dp], Vt [B][H][dpv][Tcap]
   std::vector<TfmKv> cache;
+  int kv_format = GILL_KV_BF16;   // gill_opt_set_kv_format: GILL_KV_E4M3 = per layer K8 / Vt8 bytes and Kexp / Vexp [B][H][Tcap] (attention_kv8_dev.h)
   int32_t* dec_flags = nullptr;   // [max_batch]: length clamps of gill_opt_decode_step's attention, folded into the rows' flags by the ragged decision
   int32_t* cached_lens = nullptr; // [max_batch]: past_len per row, filled on the stream by gill_opt_forward_cached where it runs on the e4m3 bytes
   // workspace of gill_opt_extend (allocated at its first call): the packed [B*T][3D] projection and the last new row of every sequence
@@ -189,12 +190,44 @@ static int opt_ensure_cache(gill_opt* m) {
   const size_t vn = (size_t)m->cfg.max_batch * m->cfg.num_heads * m->tfm.dpv * tcap;
   m->cache.assign(m->layers.size(), TfmKv{nullptr, nullptr, tcap});
   for (TfmKv& c : m->cache) {
-    GILL_TRY(m->pool.alloc(&c.k, kn, true));
-    GILL_TRY(m->pool.alloc(&c.vt, vn, true));
+    c.fmt = m->kv_format;
+    if (m->kv_format == GILL_KV_E4M3) {     // zero bytes are zero codes, zero exponents a scale of 1
+      GILL_TRY(m->pool.alloc(&c.k8, kn, true));
+      GILL_TRY(m->pool.alloc(&c.vt8, vn, true));
+      GILL_TRY(m->pool.alloc(&c.kexp, kn / m->tfm.dp, true));
+      GILL_TRY(m->pool.alloc(&c.vexp, kn / m->tfm.dp, true));
+    } else {
+      GILL_TRY(m->pool.alloc(&c.k, kn, true));
+      GILL_TRY(m->pool.alloc(&c.vt, vn, true));
+    }
   }
   GILL_TRY(m->pool.alloc(&m->cached_lens, (size_t)m->cfg.max_batch, true));
   return m->pool.alloc(&m->dec_flags, (size_t)m->cfg.max_batch, true);
 }
+
+extern "C" int gill_opt_set_kv_format(gill_opt* m, int fmt) {
+  GILL_REQUIRE(m, "null handle");
+  GILL_REQUIRE(fmt == GILL_KV_BF16 || fmt == GILL_KV_E4M3, "kv format is GILL_KV_BF16 or GILL_KV_E4M3");
+  GILL_REQUIRE(m->cache.empty() || fmt == m->kv_format, "the KV cache is allocated: its format can no longer change");
+  if (fmt == GILL_KV_E4M3) {
+    const int dp = m->tfm.dp;
+    GILL_REQUIRE(dp == 64 || dp == 80 || dp == 128, "an e4m3 KV cache needs a head dim of 64, 80 or 128");
+  }
+  m->kv_format = fmt;
+  return 0;
+}
+
+extern "C" int gill_opt_kv_format(const gill_opt* m) { return m ? m->kv_format : -1; }
+
+extern "C" int64_t gill_opt_kv_bytes(const gill_opt* m) {
+  if (!m || m->cache.empty()) return 0;
+  const int64_t slots = (int64_t)m->layers.size() * m->cfg.max_batch * m->cfg.num_heads * m->cache[0].pad;
+  return slots * (m->kv_format == GILL_KV_E4M3 ? m->tfm.dp + m->tfm.dpv + 2 : 2 * (m->tfm.dp + m->tfm.dpv));
+}
+
+// the entries whose flash kernel writes and reads a bf16 cache
+#define OPT_REQUIRE_BF16_CACHE(m, what) \
+  GILL_REQUIRE((m)->kv_format == GILL_KV_BF16, what ": the handle's KV cache format is e4m3 (GILL_KV_E4M3); prefill through gill_opt_extend at lengths 0")
 
 __global__ void opt_fill_lens_kernel(int32_t* __restrict__ lens, int B, int v) {
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
@@ -204,6 +237,7 @@ __global__ void opt_fill_lens_kernel(int32_t* __restrict__ lens, int B, int v) {
 extern "C" int gill_opt_forward_cached(gill_opt* m, const void* inputs_embeds_bf16, int B, int T_new, int past_len,
                                        float* hidden_out, void* stream) {
   GILL_REQUIRE(m && inputs_embeds_bf16 && hidden_out, "null argument");
+  OPT_REQUIRE_BF16_CACHE(m, "gill_opt_forward_cached");
   GILL_REQUIRE(B >= 1 && B <= m->cfg.max_batch && T_new >= 1 && past_len >= 0 && past_len + T_new <= m->cfg.max_seq,
                "B / past_len + T_new exceed the handle's workspace");
   GILL_REQUIRE(past_len + T_new + 2 <= m->cfg.max_positions + 2, "sequence longer than the position table");
@@ -482,6 +516,7 @@ extern "C" int gill_opt_decode_step(gill_opt* m, const void* new_embeds_bf16, co
 extern "C" int gill_opt_prefill_ids(gill_opt* m, const int64_t* ids, int B, int Tmax, const void* extra_rows_bf16, int n_extra, float* hidden_out,
                                     void* stream) {
   GILL_REQUIRE(m && ids && hidden_out, "null argument");
+  OPT_REQUIRE_BF16_CACHE(m, "gill_opt_prefill_ids");
   GILL_REQUIRE(B >= 1 && B <= m->cfg.max_batch && Tmax >= 1 && Tmax <= m->cfg.max_seq, "B / Tmax exceed the handle's workspace");
   GILL_REQUIRE(Tmax <= m->cfg.max_positions, "sequence longer than the position table");
   GILL_REQUIRE(n_extra >= 0 && (n_extra == 0 || extra_rows_bf16), "n_extra rows need a table");

@@ -57,8 +57,13 @@ struct Tfm {
   int alloc(DevPool& pool, int max_batch, int max_tok, int D, int F, int H, int dp, int dpv, size_t ws_cap_floats = 0);
 };
 
-// a K / Vt cache of one layer: K [B][H][pad][dp], Vt [B][H][dpv][pad]
-struct TfmKv { bf16_t* k = nullptr; bf16_t* vt = nullptr; int pad = 0; };
+// a K / Vt cache of one layer: K [B][H][pad][dp], Vt [B][H][dpv][pad].  fmt GILL_KV_E4M3: the four e4m3 buffers of AttnDecodeKv8Args (ops.h) in
+// their place (k / vt stay null): only the two `dec` branches of self_attn can run on it, the flash kernel writes and reads a bf16 cache
+struct TfmKv {
+  bf16_t* k = nullptr; bf16_t* vt = nullptr; int pad = 0;
+  int fmt = 0;
+  uint8_t* k8 = nullptr; uint8_t* vt8 = nullptr; int8_t* kexp = nullptr; int8_t* vexp = nullptr;
+};
 
 // split-K reducer + bias + fp32 residual (h, updated in place) + LayerNorm -> nb (opt_reduce_ln_kernel): ws [sk][M][D] fp32, D % 4 == 0, D <= 8192
 int opt_reduce_ln_launch(const float* ws, int sk, int M, int D, const float* bias, float* h, const float* g, const float* b, bf16_t* nb,

@@ -230,23 +230,45 @@ int TfmRun::self_attn(float* h, int B, int T, const TfmLayer& L, bool causal, co
   if (dec && dec->cu_new) {
     GILL_REQUIRE(kv && B == 1 && T >= 1 && dec->qkv, "extend attention: a cache and packed rows");
     GILL_TRY(linear(t.nbuf, T, L.qkv, nullptr, ACT_NONE, dec->qkv, false));
-    AttnExtendArgs a;
-    a.q = dec->qkv; a.k = dec->qkv + t.D; a.v = dec->qkv + 2 * t.D; a.ld = 3 * t.D;
-    a.K = kv->k; a.Vt = kv->vt; a.lens = dec->lens; a.cu_new = dec->cu_new; a.O = t.o; a.ldo = t.D; a.flags = dec->flags;
-    a.B = dec->nseq; a.total_new = T; a.max_new = dec->max_new; a.H = t.H; a.dp = t.dp; a.dpv = t.dpv; a.pitch = kv->pad;
-    a.qscale = 1.4426950408889634f / sqrtf((float)t.dp);
-    GILL_TRY(attention_extend_launch(a, s));
+    if (kv->fmt == GILL_KV_E4M3) {
+      AttnExtendKv8Args a;
+      a.q = dec->qkv; a.k = dec->qkv + t.D; a.v = dec->qkv + 2 * t.D; a.ld = 3 * t.D;
+      a.K8 = kv->k8; a.Vt8 = kv->vt8; a.Kexp = kv->kexp; a.Vexp = kv->vexp;
+      a.lens = dec->lens; a.cu_new = dec->cu_new; a.O = t.o; a.ldo = t.D; a.flags = dec->flags;
+      a.B = dec->nseq; a.total_new = T; a.max_new = dec->max_new; a.H = t.H; a.dp = t.dp; a.dpv = t.dpv; a.pitch = kv->pad;
+      a.qscale = 1.4426950408889634f / sqrtf((float)t.dp);
+      GILL_TRY(attention_extend_kv8_launch(a, s));
+    } else {
+      AttnExtendArgs a;
+      a.q = dec->qkv; a.k = dec->qkv + t.D; a.v = dec->qkv + 2 * t.D; a.ld = 3 * t.D;
+      a.K = kv->k; a.Vt = kv->vt; a.lens = dec->lens; a.cu_new = dec->cu_new; a.O = t.o; a.ldo = t.D; a.flags = dec->flags;
+      a.B = dec->nseq; a.total_new = T; a.max_new = dec->max_new; a.H = t.H; a.dp = t.dp; a.dpv = t.dpv; a.pitch = kv->pad;
+      a.qscale = 1.4426950408889634f / sqrtf((float)t.dp);
+      GILL_TRY(attention_extend_launch(a, s));
+    }
   } else if (dec) {
     GILL_REQUIRE(kv && T >= 1, "decode attention: a cache");
     GILL_TRY(linear(t.nbuf, B * T, L.qkv, nullptr, ACT_NONE, t.q, false));
-    AttnAppendArgs a;
-    a.nq = T;
-    a.q = t.q; a.k = t.q + t.D; a.v = t.q + 2 * t.D; a.ld = 3 * t.D;
-    a.K = kv->k; a.Vt = kv->vt; a.lens = dec->lens; a.O = t.o; a.ldo = t.D; a.flags = dec->flags;
-    a.B = B; a.H = t.H; a.dp = t.dp; a.dpv = t.dpv; a.pitch = kv->pad;
-    a.qscale = 1.4426950408889634f / sqrtf((float)t.dp);
-    GILL_TRY(T == 1 ? attention_decode_launch(a, s) : attention_append_launch(a, s));
+    if (kv->fmt == GILL_KV_E4M3) {
+      GILL_REQUIRE(T == 1, "decode attention: an e4m3 KV cache takes one token per row (the multi-token append is not built for it)");
+      AttnDecodeKv8Args a;
+      a.q = t.q; a.k = t.q + t.D; a.v = t.q + 2 * t.D; a.ld = 3 * t.D;
+      a.K8 = kv->k8; a.Vt8 = kv->vt8; a.Kexp = kv->kexp; a.Vexp = kv->vexp;
+      a.lens = dec->lens; a.O = t.o; a.ldo = t.D; a.flags = dec->flags;
+      a.B = B; a.H = t.H; a.dp = t.dp; a.dpv = t.dpv; a.pitch = kv->pad;
+      a.qscale = 1.4426950408889634f / sqrtf((float)t.dp);
+      GILL_TRY(attention_decode_kv8_launch(a, s));
+    } else {
+      AttnAppendArgs a;
+      a.nq = T;
+      a.q = t.q; a.k = t.q + t.D; a.v = t.q + 2 * t.D; a.ld = 3 * t.D;
+      a.K = kv->k; a.Vt = kv->vt; a.lens = dec->lens; a.O = t.o; a.ldo = t.D; a.flags = dec->flags;
+      a.B = B; a.H = t.H; a.dp = t.dp; a.dpv = t.dpv; a.pitch = kv->pad;
+      a.qscale = 1.4426950408889634f / sqrtf((float)t.dp);
+      GILL_TRY(T == 1 ? attention_decode_launch(a, s) : attention_append_launch(a, s));
+    }
   } else {
+    GILL_REQUIRE(!kv || kv->fmt != GILL_KV_E4M3, "flash attention: the cache is e4m3; this pass writes and reads a bf16 cache");
     const int Tpad = round_up(T, 32), kvpad = kv ? kv->pad : Tpad;
     bf16_t* kbuf = kv ? kv->k : t.k;
     bf16_t* vbuf = kv ? kv->vt : t.vt;

@@ -28,7 +28,7 @@ class StaleSessionError(RuntimeError):
 def check_epoch(session_epoch: int, model_epoch: int) -> None:
   if session_epoch != model_epoch:
     raise StaleSessionError(f'dialogue session is stale: the OPT handle\'s KV cache was written or rebuilt by another entry (generate, '
-                            f'generate_batch, a cached forward, a handle rebuild or quantize_lm) since the session used it '
+                            f'generate_batch, a cached forward, a handle rebuild, quantize_lm or quantize_kv) since the session used it '
                             f'(epoch {model_epoch}, the session holds {session_epoch}); open a new session.')
 
 

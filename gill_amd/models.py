@@ -62,6 +62,7 @@ _OPT_SHAPES = {  # hidden, layers, heads, ffn  (public OPT configs; 350m is post
   'opt-6.7b': (4096, 32, 32, 16384), 'opt-13b': (5120, 40, 40, 20480),
 }
 _OPT_WEIGHT_MODES = {'bf16': 0, 'fp8': 1}      # GILL_OPT_BF16, GILL_OPT_W8 (include/gill_amd.h)
+_KV_CACHE_FORMATS = {'bf16': 0, 'fp8': 1}      # GILL_KV_BF16, GILL_KV_E4M3
 _CLIP_HIDDEN = {'clip-vit-large-patch14': 1024, 'clip-vit-base-patch16': 768, 'clip-vit-base-patch32': 768}
 
 
@@ -168,6 +169,7 @@ class GILLModel(nn.Module):
     self._opt_cap = (0, 0)
     self._cache_epoch = 0         # bumped by every entry that writes or rebuilds the handle's KV cache: open sessions go stale (dialogue.py)
     self.opt_weights = 'bf16'     # quantize_lm(): 'fp8' = the weight-only fp8 decoder (gill_opt_create_ex, GILL_OPT_W8)
+    self.kv_cache = 'bf16'        # quantize_kv(): 'fp8' = the e4m3 KV cache (gill_opt_set_kv_format, GILL_KV_E4M3)
     # native handles snapshot the weights: a state-dict load into this module (or, recursively, into a parent) drops them
     self.register_load_state_dict_post_hook(lambda module, incompatible_keys: module.refresh_native())
 
@@ -307,6 +309,10 @@ class GILLModel(nn.Module):
     with torch.cuda.device(dev):
       N.check(N.lib().gill_opt_create_ex(C.byref(h), C.byref(cfg), arr, len(keep), _OPT_WEIGHT_MODES[self.opt_weights]))
     del keep
+    if self.kv_cache != 'bf16' and N.lib().gill_opt_set_kv_format(h, _KV_CACHE_FORMATS[self.kv_cache]) != 0:
+      msg = N.lib().gill_last_error()
+      N.lib().gill_opt_destroy(h)
+      raise N.GillNativeError(msg.decode() if msg else 'gill_opt_set_kv_format failed')
     self._opt_handle, self._opt_cap = h, (cb, ct)
     return h
 
@@ -329,6 +335,31 @@ class GILLModel(nn.Module):
         N.lib().gill_opt_destroy(self._opt_handle)
       self._opt_handle, self._opt_cap = None, (0, 0)
     return self
+
+  def quantize_kv(self, mode: Optional[str] = 'fp8'):
+    """Format of the KV cache in the OPT decoder's native handle.  'fp8': every key row and value row of a (token, head) is stored as OCP
+    e4m3 bytes with one power-of-two scale (csrc/attention_kv8_dev.h), about half the cache bytes; every key and value, a token's own
+    included, is e4m3-rounded before any query uses it, so the tokens can differ from those of the bf16 cache, and they are the same however
+    the sequence was fed.  The entries that honour it are the ragged ones: generate_batch (its prefill then runs through the packed extend
+    pass at lengths 0), generate_for_images_and_texts_batch, open_session / open_dialogues; with either weight format.  generate() with
+    use_kv_cache, the cached forward and generate_for_images_and_texts raise a ValueError (their flash kernel writes and reads a bf16 cache):
+    a batch of one row through the batch entries is the equivalent.  Entries that use no cache are untouched.  None or 'bf16': back to bf16.
+    A change drops the handle (rebuilt at the next call) and makes open sessions stale."""
+    mode = 'bf16' if mode is None else mode
+    if mode not in _KV_CACHE_FORMATS:
+      raise ValueError(f"quantize_kv: mode must be one of {sorted(_KV_CACHE_FORMATS)} or None, got {mode!r}")
+    if mode != self.kv_cache:
+      self._cache_epoch += 1
+      self.kv_cache = mode
+      if self._opt_handle is not None:
+        N.lib().gill_opt_destroy(self._opt_handle)
+      self._opt_handle, self._opt_cap = None, (0, 0)
+    return self
+
+  def _require_bf16_kv(self, what: str):
+    if self.kv_cache != 'bf16':
+      raise ValueError(f"{what} runs on a bf16 KV cache only and this model's is {self.kv_cache!r} (quantize_kv): use generate_batch / "
+                       f"generate_for_images_and_texts_batch / open_session (a batch of one row is the equivalent), or quantize_kv('bf16').")
 
   # ---- reference API -------------------------------------------------------------------------
   def get_visual_embs(self, pixel_values: torch.FloatTensor, mode: str = 'captioning'):
@@ -366,6 +397,7 @@ class GILLModel(nn.Module):
     """hidden_states[-1] rows of the tokens past_len .. past_len+T_new-1, computed against the handle's KV cache
     (gill_opt_forward_cached).  past_len == 0 starts a new sequence."""
     B, Tn, D = new_embeds.shape
+    self._require_bf16_kv('the cached forward')
     self._cache_epoch += 1
     cb, ct = self._opt_cap
     if past_len > 0 and (self._opt_handle is None or B > cb or past_len + Tn > ct):
@@ -601,6 +633,8 @@ class GILLModel(nn.Module):
     step), over exp(logit / temperature - max) and the top-p filter's kept set).  It is repeatable bit for bit, a row's tokens do
     not depend on the other rows of the batch, no temperature overflows, torch's generators are not touched, and the loop waits
     for the device as the greedy one does: never at batch > 1, one 4-byte count per step at batch 1."""
+    if use_kv_cache:
+      self._require_bf16_kv('generate() with use_kv_cache')
     self._decode_host_waits = 0
     self._cache_epoch += 1
     if seed is not None:
@@ -917,7 +951,13 @@ class GILLModel(nn.Module):
       st[6 * B] = B if max_len > 0 else 0
       st = st.to(dev)
       tokens = torch.full((B, max(L, 1)), -1, device=dev, dtype=torch.int64)
-      full = torch.empty((B, Tmax, D), device=dev, dtype=torch.float32)
+      kv8 = self.kv_cache != 'bf16'
+      full = None if kv8 else torch.empty((B, Tmax, D), device=dev, dtype=torch.float32)
+      # an e4m3 cache: the prompts packed, without their pad positions, through the extend pass at lengths 0 (a session's first turn)
+      keep = (torch.arange(Tmax)[None, :] < torch.tensor(lens)[:, None]).reshape(-1).to(dev) if kv8 else None
+      last = torch.zeros((B, 1, D), device=dev, dtype=torch.float32) if kv8 else None
+      cu = torch.tensor([0] + list(np.cumsum(lens)), dtype=torch.int32, device=dev) if kv8 else None
+      zero_lens = torch.zeros(B, dtype=torch.int32, device=dev) if kv8 else None
       with torch.cuda.device(dev):
         if ids is not None:
           idt = ids.to(dev, torch.int64).contiguous()
@@ -930,13 +970,23 @@ class GILLModel(nn.Module):
           lowest = int(idt.min())
           if lowest < -n_extra:
             raise ValueError(f'id {lowest} selects extra row {-(lowest + 1)} of {n_extra}')
-          N.check(lib.gill_opt_prefill_ids(h, N.ptr(idt), B, Tmax, N.ptr(extra_rows) if n_extra else None, n_extra, N.ptr(full),
-                                           N.current_stream()))
+          if kv8:
+            self._lm_extend(cu, zero_lens, B, sum(lens), max(lens), max(lens), last, ids=idt.reshape(-1)[keep].contiguous(),
+                            extra_rows=extra_rows if n_extra else None)
+          else:
+            N.check(lib.gill_opt_prefill_ids(h, N.ptr(idt), B, Tmax, N.ptr(extra_rows) if n_extra else None, n_extra, N.ptr(full),
+                                             N.current_stream()))
         else:
           x = embeddings.to(dev, torch.bfloat16).contiguous()
-          N.check(lib.gill_opt_forward_cached(h, N.ptr(x), B, Tmax, 0, N.ptr(full), N.current_stream()))
-      lens_dev = torch.tensor(lens, device=dev, dtype=torch.int64)
-      hid = full[torch.arange(B, device=dev), lens_dev - 1].contiguous()       # the rows len[b] - 1
+          if kv8:
+            self._lm_extend(cu, zero_lens, B, sum(lens), max(lens), max(lens), last, embeds=x.reshape(B * Tmax, D)[keep].contiguous())
+          else:
+            N.check(lib.gill_opt_forward_cached(h, N.ptr(x), B, Tmax, 0, N.ptr(full), N.current_stream()))
+      if kv8:
+        hid = last[:, 0].contiguous()
+      else:
+        lens_dev = torch.tensor(lens, device=dev, dtype=torch.int64)
+        hid = full[torch.arange(B, device=dev), lens_dev - 1].contiguous()       # the rows len[b] - 1
       steps = torch.zeros((max(L, 1), B, D), device=dev, dtype=torch.float32)
       nxt = torch.zeros((B, D), device=dev, dtype=torch.bfloat16)
       logits = torch.empty((B, vocab), device=dev, dtype=torch.float32)
@@ -1014,6 +1064,7 @@ class GILL(nn.Module):
         raise ValueError(f'Input prompts should be either PIL.Image.Image or str types, got {type(p)} instead.')
     if num_words == 0:
       raise NotImplementedError('Generation not implemented for num_words=0.')
+    self.model._require_bf16_kv('generate_for_images_and_texts')
     with torch.no_grad():
       for p in prompts:
         if type(p) == str:
@@ -1691,9 +1742,10 @@ class GILL(nn.Module):
 
 
 def load_gill(model_dir: str, load_ret_embs: bool = True, decision_model_fn: str = 'decision_model.pth.tar', ret_index: bool = False,
-              opt_weights: str = 'bf16') -> GILL:
+              opt_weights: str = 'bf16', kv_cache: str = 'bf16') -> GILL:
   """reference: gill/models.py:810-902.  Same files, same errors, same tokenizer surgery, same checkpoint format.
   opt_weights (not a reference argument): 'fp8' = GILLModel.quantize_lm('fp8'), the weight-only fp8 decoder.
+  kv_cache (not a reference argument): 'fp8' = GILLModel.quantize_kv('fp8'), the e4m3 KV cache of the batch and session entries.
   ret_index (not a reference argument): also build model.ret_index from the raw cc3m rows with the device normalise (GILL.build_retrieval_index);
   emb_matrix is set as without it."""
   model_args_path = os.path.join(model_dir, 'model_args.json')
@@ -1750,6 +1802,7 @@ def load_gill(model_dir: str, load_ret_embs: bool = True, decision_model_fn: str
     model.model.input_embeddings.weight[-model_kwargs['num_tokens']:, :].copy_(img_token_embeddings)
   model.model.refresh_native()   # native handles snapshot the weights: rebuild after the in-place copy
   model.model.quantize_lm(opt_weights)
+  model.model.quantize_kv(kv_cache)
   if emb_matrix is not None:     # models.py:895-900: unit rows scaled by exp(logit_scale), in the model's dtype, on its device
     scale = model.model.logit_scale.exp()
     m = torch.as_tensor(emb_matrix).to(device=scale.device, dtype=scale.dtype)

@@ -226,6 +226,51 @@ def attention_extend(q: torch.Tensor, k_new: torch.Tensor, v_new: torch.Tensor, 
   return o
 
 
+def _kv8_cache_checks(K8: torch.Tensor, Vt8: torch.Tensor, Kexp: torch.Tensor, Vexp: torch.Tensor):
+  B, H, pitch, d = K8.shape
+  assert K8.dtype == torch.uint8 and Vt8.dtype == torch.uint8 and tuple(Vt8.shape) == (B, H, (d + 31) // 32 * 32, pitch)
+  assert Kexp.dtype == torch.int8 and Vexp.dtype == torch.int8 and tuple(Kexp.shape) == (B, H, pitch) and tuple(Vexp.shape) == (B, H, pitch)
+  for t in (K8, Vt8, Kexp, Vexp):
+    assert t.is_cuda and t.is_contiguous()
+  return B, H, pitch, d
+
+
+def attention_decode_kv8(q: torch.Tensor, k_new: torch.Tensor, v_new: torch.Tensor, K8: torch.Tensor, Vt8: torch.Tensor, Kexp: torch.Tensor,
+                         Vexp: torch.Tensor, lens: torch.Tensor, flags: Optional[torch.Tensor] = None) -> torch.Tensor:
+  """attention_decode on an e4m3 cache: K8 (B,H,pitch,d) and Vt8 (B,H,round_up(d,32),pitch) uint8 (OCP e4m3 codes), Kexp / Vexp (B,H,pitch)
+  int8 (a row's scale is 2^e), all updated IN PLACE at slot lens[b]: the new key and value rows are quantised by the kernel, and the
+  quantised rows are what the token itself attends to.  q / k_new / v_new (B, H*d) bf16.  Returns (B, H*d) bf16."""
+  B, H, pitch, d = _kv8_cache_checks(K8, Vt8, Kexp, Vexp)
+  for t in (q, k_new, v_new):
+    assert t.dtype == torch.bfloat16 and t.is_contiguous() and tuple(t.shape) == (B, H * d)
+  assert lens.dtype == torch.int32 and lens.numel() == B and (flags is None or (flags.dtype == torch.int32 and flags.numel() == B))
+  o = torch.empty_like(q)
+  N.check(N.lib().gill_attention_decode_kv8(N.ptr(q), N.ptr(k_new), N.ptr(v_new), H * d, N.ptr(K8), N.ptr(Vt8), N.ptr(Kexp), N.ptr(Vexp),
+                                            N.ptr(lens), N.ptr(o), B, H, d, pitch, N.ptr(flags), N.current_stream()))
+  return o
+
+
+def attention_extend_kv8(q: torch.Tensor, k_new: torch.Tensor, v_new: torch.Tensor, K8: torch.Tensor, Vt8: torch.Tensor, Kexp: torch.Tensor,
+                         Vexp: torch.Tensor, lens: torch.Tensor, cu_new: torch.Tensor, max_new: int,
+                         flags: Optional[torch.Tensor] = None) -> torch.Tensor:
+  """attention_extend on an e4m3 cache (the buffers of attention_decode_kv8, updated IN PLACE at slots lens[b] .. lens[b] + count - 1); q /
+  k_new / v_new (total_new, H*d) bf16 packed rows, cu_new, max_new and flags as in attention_extend.  Returns (total_new, H*d) bf16."""
+  B, H, pitch, d = _kv8_cache_checks(K8, Vt8, Kexp, Vexp)
+  total = q.shape[0]
+  ld = q.stride(0)
+  for t in (q, k_new, v_new):
+    assert t.dtype == torch.bfloat16 and t.is_cuda and tuple(t.shape) == (total, H * d) and t.stride(1) == 1 and t.stride(0) == ld
+  assert lens.dtype == torch.int32 and lens.numel() == B and cu_new.dtype == torch.int32 and cu_new.numel() == B + 1
+  assert flags is None or (flags.dtype == torch.int32 and flags.numel() == B)
+  o = torch.empty((total, H * d), dtype=torch.bfloat16, device=q.device)
+  if total == 0:      # no row brought a token: nothing to store, nothing to attend
+    return o
+  N.check(N.lib().gill_attention_extend_kv8(q.data_ptr(), k_new.data_ptr(), v_new.data_ptr(), ld, N.ptr(K8), N.ptr(Vt8), N.ptr(Kexp),
+                                            N.ptr(Vexp), N.ptr(lens), N.ptr(cu_new), N.ptr(o), B, total, int(max_new), H, d, pitch,
+                                            N.ptr(flags), N.current_stream()))
+  return o
+
+
 def layernorm(x: torch.Tensor, gamma: torch.Tensor, beta: torch.Tensor, eps: float = 1e-5) -> torch.Tensor:
   assert x.is_cuda and x.dtype in (torch.bfloat16, torch.float32)
   x = x.contiguous()

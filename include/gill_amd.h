@@ -324,6 +324,41 @@ int gill_opt_extend(gill_opt* h, const int64_t* ids, const void* embeds_bf16, co
                     const int32_t* lens_dev, int B, int total_new, int max_new, int len_bound, float* hidden_last, float* hidden_all,
                     void* stream);
 
+/* ---- e4m3 KV cache ("kv8"): the cache of the ragged decode step and of the extend pass at half its bytes. ----
+ *
+ * The format.  Every key row and every value row of one token and one head (d elements, d = 64, 80 or 128) is d OCP e4m3 bytes and one
+ * power-of-two scale 2^e, e an int8 per (row, head, slot), by the rule of the w8 weights above applied to the row's bf16 values:
+ *   e = ceil(log2(max |x| / 448)) from the maximum's mantissa and exponent, kept >= -100 (an all-zero row: e = 0), code = e4m3fn(x / 2^e),
+ *   round to nearest even; max |x / 2^e| lies in (224, 448]: nothing saturates, and every code times 2^e is a bf16 number.
+ * Layouts mirror the bf16 cache: K8 (B,H,pitch,d) bytes, Vt8 (B,H,round_up(d,32),pitch) bytes (rows d .. are never read as data and never
+ * written: there is no ones-row), Kexp and Vexp (B,H,pitch) int8: d + round_up(d,32) + 2 bytes per (row, head, slot) instead of
+ * 2 (d + round_up(d,32)).  Semantics: every key and value is rounded to its e4m3 row, THE TOKEN'S OWN INCLUDED, before any query uses it.  The
+ * quantised-cache model is therefore an exact function of the token sequence, whichever way the tokens were fed (extend, single steps, alone
+ * or in a batch); its tokens can differ from those of the bf16 cache.
+ *
+ * gill_attention_decode_kv8 / gill_attention_extend_kv8: gill_attention_decode / gill_attention_extend on that cache; q, k_new, v_new, o,
+ * lens, cu_new, the bounds, the clamps and flags as there (k_new / v_new arrive as bf16 and are quantised by the kernel; the stored slots hold
+ * the rule's codes and exponents).  Slots beyond a token's own are excluded by selection whatever bytes (the two NaN codes included) and
+ * exponents they hold; no read leaves a (b, h) slab; nothing outside the buffers is touched.  Each is a fixed function of a row's own operands,
+ * length and count: the same output and cache bits at any B, anywhere in a pack, on any run.  K8 / Vt8 16-byte aligned, Kexp / Vexp 4-byte
+ * aligned.  Bad arguments are reported before anything is launched.  Both honour GILL_OP_REPEAT.
+ *
+ * gill_opt_set_kv_format: GILL_KV_BF16 (the default) or GILL_KV_E4M3 for the handle's cache; an error once the cache is allocated (the
+ * first cached entry allocates it) and for any other value.  gill_opt_kv_format: the format.  gill_opt_kv_bytes: the bytes the cache holds
+ * (all layers; K and V^T, and on an e4m3 handle the exponents), 0 before it exists.  On a GILL_KV_E4M3 handle gill_opt_decode_step and
+ * gill_opt_extend run on the e4m3 cache with either weight mode; gill_opt_forward_cached and gill_opt_prefill_ids are errors that name the
+ * format (their flash kernel writes and reads a bf16 cache: prefill through gill_opt_extend at lengths 0); entries without a cache are
+ * untouched. */
+enum { GILL_KV_BF16 = 0, GILL_KV_E4M3 = 1 };
+int gill_opt_set_kv_format(gill_opt* h, int fmt);
+int gill_opt_kv_format(const gill_opt* h);
+int64_t gill_opt_kv_bytes(const gill_opt* h);
+int gill_attention_decode_kv8(const void* q, const void* k_new, const void* v_new, int ld, void* K8, void* Vt8, void* Kexp, void* Vexp,
+                              const int32_t* lens, void* o, int B, int H, int d, int pitch, int32_t* flags, void* stream);
+int gill_attention_extend_kv8(const void* q, const void* k_new, const void* v_new, int ld, void* K8, void* Vt8, void* Kexp, void* Vexp,
+                              const int32_t* lens, const int32_t* cu_new, void* o, int B, int total_new, int max_new, int H, int d, int pitch,
+                              int32_t* flags, void* stream);
+
 /* ------------------------------------------------------------------------------------------
  * Image prompts — the frozen CLIP vision tower (transformers CLIPVisionModel built at gill/models.py:78-96 and called by
  * GILLModel.get_visual_embs, gill/models.py:129-145: `self.visual_model(pixel_values).pooler_output`).
