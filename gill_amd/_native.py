@@ -205,6 +205,7 @@ SYMBOLS: Dict[str, Tuple[object, List[object]]] = {
   "gill_gemm_plan_log": (_i, [_vp, _i, C.POINTER(C.c_int)]),
   "gill_unet_xf_plan": (_i, [_vp, _i, _i, _i, _i, _vp]),
   "gill_gemm_query": (_i, [_vp, _i, _i, _i, _i, _vp]),
+  "gill_attention_plan": (_i, [_i, _i, _i, _i, _i, _i, _i, _vp]),
   "gill_opt_forward_loss": (_i, [_vp, _vp, C.POINTER(C.c_int32), _i, _i, _i, _vp, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
 }
 

@@ -28,6 +28,7 @@
 // DP (padded head dim, multiple of 16): 48 (d=40), 64, 80, 128, 160.  Padding columns of Q/K are exact zeros
 // (zero weight rows); padding rows of Vt (up to dpv = roundup(DP,32)) only feed output rows that are never stored.
 #include "ops.h"
+#include "attention_plan.h"
 #include <stdlib.h>
 #include <type_traits>
 
@@ -602,57 +603,43 @@ __global__ __launch_bounds__(ATT_THREADS, 4) void attention_dma_kernel(const Att
 }
 
 template <int DP, int NTHR>
-static int attention_dma_launch(const AttnArgs& a, hipStream_t s) {
+static int attention_dma_launch(const AttnArgs& a, int grid_x, hipStream_t s) {
   static bool attr_set = false;
   constexpr int smem = 2 * 2 * 64 * 128 + 64;     // two stages of (K | V^T) images + the constant K fragment
   if (!attr_set) {
     GILL_CHECK_HIP(hipFuncSetAttribute((const void*)attention_dma_kernel<DP, NTHR>, hipFuncAttributeMaxDynamicSharedMemorySize, smem));
     attr_set = true;
   }
-  constexpr int xcd_on = 1;
   AttnArgs b = a;
-  b.xcd_map = xcd_on;
-  dim3 grid((xcd_on ? 8 * cdiv(a.H * a.B, 8) : a.H * a.B) * (a.nq / (NTHR / 2)), 1, 1);
-  hipLaunchKernelGGL((attention_dma_kernel<DP, NTHR>), grid, dim3(NTHR), smem, s, b);
+  b.xcd_map = 1;
+  hipLaunchKernelGGL((attention_dma_kernel<DP, NTHR>), dim3(grid_x, 1, 1), dim3(NTHR), smem, s, b);
   GILL_CHECK_HIP(hipGetLastError());
   return 0;
 }
-// GILL_ATT_DMA=0: the register-staged kernel everywhere (A/B switch)
-static bool attention_dma_ok(const AttnArgs& a, int nthr) {
-  static const bool on = [] { const char* e = getenv("GILL_ATT_DMA"); return !(e && e[0] == '0'); }();
-  return on && a.dp == 48 && a.d == 40 && !a.causal && a.nq % (nthr / 2) == 0 && a.nkv_pad % 64 == 0 && a.dpv >= 64 && a.nkv >= 1;
-}
 
 template <int DP, int NTHR>
-static int attention_launch_inst(const AttnArgs& a, hipStream_t s) {
+static int attention_launch_inst(const AttnArgs& a, int grid_x, hipStream_t s) {
   static bool attr_set = false;
   constexpr int smem = AttCfg<DP, NTHR>::SMEM_BYTES;
   if (!attr_set) {
     GILL_CHECK_HIP(hipFuncSetAttribute((const void*)attention_kernel<DP, NTHR>, hipFuncAttributeMaxDynamicSharedMemorySize, smem));
     attr_set = true;
   }
-  constexpr int xcd_on = 1;
   AttnArgs b = a;
-  b.xcd_map = xcd_on;
-  dim3 grid((xcd_on ? 8 * cdiv(a.H * a.B, 8) : a.H * a.B) * cdiv(a.nq, NTHR / 2), 1, 1);   // (XCD, pair slot, query tile): see the kernel's map
-  hipLaunchKernelGGL((attention_kernel<DP, NTHR>), grid, dim3(NTHR), smem, s, b);
+  b.xcd_map = 1;
+  hipLaunchKernelGGL((attention_kernel<DP, NTHR>), dim3(grid_x, 1, 1), dim3(NTHR), smem, s, b);
   GILL_CHECK_HIP(hipGetLastError());
   return 0;
 }
 
-// 256 queries per workgroup when that still gives every CU a workgroup (measured: level 1, 256 workgroups, is 2 % faster
-// this way; level 2, 64 workgroups, 15-22 % faster with 128-query workgroups); shorter query ranges (UNet levels 1-2, OPT, the
-// mapper) get 128-query workgroups instead of leaving most CUs idle (each workgroup stages the whole K/V itself,
-// which is L2-resident at those sizes)
+// The plan (attention_plan.h) names the kernel — family, DP, NTHR — and its grid; this only maps the names to the instantiations.
 template <int DP>
-static int attention_launch_dp(const AttnArgs& a, hipStream_t s) {
-  const int64_t bh = (int64_t)a.H * a.B;
-  const bool big = cdiv(a.nq, 256) * bh >= 256;
+static int attention_launch_dp(const AttnArgs& a, const AttnPlan& p, hipStream_t s) {
   if constexpr (DP == 48) {
-    if (attention_dma_ok(a, big ? 512 : 256)) return big ? attention_dma_launch<DP, 512>(a, s) : attention_dma_launch<DP, 256>(a, s);
+    if (p.family == ATT_FAMILY_DMA) return p.nthr == 512 ? attention_dma_launch<DP, 512>(a, p.grid, s) : attention_dma_launch<DP, 256>(a, p.grid, s);
   }
-  if (big) return attention_launch_inst<DP, 512>(a, s);
-  return attention_launch_inst<DP, 256>(a, s);   // (128-thread workgroups would stage 10+ chunks per thread: spills)
+  GILL_REQUIRE(p.family == ATT_FAMILY_REG, "internal: LDS-DMA attention planned for a padded head dim other than 48");
+  return p.nthr == 512 ? attention_launch_inst<DP, 512>(a, p.grid, s) : attention_launch_inst<DP, 256>(a, p.grid, s);
 }
 
 int attention_launch(const AttnArgs& a, hipStream_t s) {
@@ -661,12 +648,13 @@ int attention_launch(const AttnArgs& a, hipStream_t s) {
   GILL_REQUIRE(a.nq_pad >= a.nq, "nq_pad must cover nq");
   GILL_REQUIRE(a.dpv >= round_up(a.dp, 32), "dpv must cover roundup(dp, 32)");
   GILL_REQUIRE(a.ldo >= a.H * a.dp, "ldo too small");
-  switch (a.dp) {
-    case 48:  return attention_launch_dp<48>(a, s);
-    case 64:  return attention_launch_dp<64>(a, s);
-    case 80:  return attention_launch_dp<80>(a, s);
-    case 128: return attention_launch_dp<128>(a, s);
-    case 160: return attention_launch_dp<160>(a, s);
+  const AttnPlan p = attention_plan(a, attention_env_dma());
+  switch (p.dp) {
+    case 48:  return attention_launch_dp<48>(a, p, s);
+    case 64:  return attention_launch_dp<64>(a, p, s);
+    case 80:  return attention_launch_dp<80>(a, p, s);
+    case 128: return attention_launch_dp<128>(a, p, s);
+    case 160: return attention_launch_dp<160>(a, p, s);
     default:
       gill_set_error("attention: unsupported padded head dim (supported: 48, 64, 80, 128, 160)");
       return -2;

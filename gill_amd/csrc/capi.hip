@@ -7,6 +7,7 @@
 #include "tfm.h"
 #include "xf_weights.h"
 #include "gemm_plan.h"
+#include "attention_plan.h"
 #include "xf_plan.h"
 #include <vector>
 
@@ -793,6 +794,21 @@ extern "C" int gill_unet_xf_plan(const int32_t* cases, int n, int lnproj, int xa
     for (int k = 0; k < nf; ++k) r[k] = reinterpret_cast<const int*>(&f)[k];
     for (int k = 0; k < np; ++k) r[nf + k] = reinterpret_cast<const int*>(&p)[k];
   }
+  return 0;
+}
+
+// ---- which attention kernel gill_op_attention runs, host only (attention_plan.h; tests/test_attention_inst_host.py)
+static_assert(sizeof(AttnPlan) == GILL_ATTENTION_PLAN_INTS * sizeof(int), "a row = the plan, all int");
+extern "C" int gill_attention_plan(int B, int H, int nq, int nkv, int d, int causal, int att_dma, int32_t* out) {
+  GILL_REQUIRE(out != nullptr, "attention_plan: null output");
+  GILL_REQUIRE(B > 0 && H > 0 && nq > 0 && nkv > 0 && d > 0, "attention_plan: empty attention");
+  const int dp = attn_padded_dim(d);
+  GILL_REQUIRE(dp > 0, "attention_plan: head dim > 160 unsupported");
+  AttnArgs a;      // the geometry gill_op_attention gives the launcher; a plan reads no pointer
+  a.B = B; a.H = H; a.nq = nq; a.nkv = nkv; a.nq_pad = round_up(nq, 32); a.nkv_pad = round_up(nkv, 32); a.dp = dp; a.dpv = round_up(dp, 32);
+  a.ldo = H * dp; a.causal = causal; a.d = d;
+  const AttnPlan p = attention_plan(a, att_dma != 0);
+  for (int k = 0; k < GILL_ATTENTION_PLAN_INTS; ++k) out[k] = reinterpret_cast<const int*>(&p)[k];
   return 0;
 }
 

@@ -1081,6 +1081,15 @@ def unet_xf_plan(cases, lnproj: int = 1, xalg: int = 1, ffn_fused: int = 1):
   return rows
 
 
+def attention_plan(B: int, H: int, nq: int, nkv: int, d: int, causal: bool = False, att_dma: int = 1):
+  """Which kernel attention() runs for a shape (host only: gill_attention_plan): (family, dp, nthr, grid) — family 0 the register-staged
+  attention_kernel<dp, nthr>, 1 the LDS-DMA attention_dma_kernel<dp, nthr>; grid in workgroups.  att_dma: GILL_ATT_DMA."""
+  import numpy as np
+  out = np.zeros(4, dtype=np.int32)
+  N.check(N.lib().gill_attention_plan(int(B), int(H), int(nq), int(nkv), int(d), int(causal), int(att_dma), out.ctypes.data))
+  return tuple(int(x) for x in out)
+
+
 def gemm_query(queries, pp: int = 1, coop: int = 1, cus: int = 256):
   """The engines' pre-launch GEMM choices (host only: gill_gemm_query).  queries (n, 7) int32 = [what, six arguments] -> (n,) int32."""
   import numpy as np

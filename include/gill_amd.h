@@ -993,6 +993,15 @@ int gill_gemm_query(const int32_t* queries, int n, int pp, int coop, int cus, in
 #define GILL_UNET_XF_PLAN_ROW_INTS 11
 int gill_unet_xf_plan(const int32_t* cases, int n, int lnproj, int xalg, int ffn_fused, int32_t* rows);
 
+/* Which attention kernel gill_op_attention runs for a shape (host only, for tests; no GPU is touched).  The launcher decides it in one pure
+ * function of the launch geometry — gill_op_attention's: head dim padded to 48 / 64 / 80 / 128 / 160, nq and nkv padded to multiples of 32 —
+ * and of att_dma, the switch GILL_ATT_DMA (0 = off), given explicitly here.
+ * out: GILL_ATTENTION_PLAN_INTS int32:
+ *   family dp nthr grid        0 register-staged attention_kernel<dp, nthr> / 1 LDS-DMA attention_dma_kernel<dp, nthr>; padded head dim;
+ *                              threads per workgroup (256 | 512 = 128 | 256 queries); workgroups launched */
+#define GILL_ATTENTION_PLAN_INTS 4
+int gill_attention_plan(int B, int H, int nq, int nkv, int d, int causal, int att_dma, int32_t* out);
+
 /* Scoring pass of the OPT engine: gill_opt_img_hidden_ex (same embedding, same negative ids, same gathered rows; raw_out / emb_out
  * bit-equal to its outputs, either may be NULL) with the final LayerNorm on EVERY row, and row (b, t) scored against
  * labels[b][t + 1] by the fused loss above (HF's shifted CrossEntropyLoss).  labels (B,T) int64 on the device, -100 ignored; NULL
