@@ -109,6 +109,9 @@ SYMBOLS: Dict[str, Tuple[object, List[object]]] = {
   "gill_attention_append": (_i, [_vp, _vp, _vp, _i, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp, _vp]),
   "gill_attention_extend": (_i, [_vp, _vp, _vp, _i, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp, _vp]),
   "gill_opt_extend": (_i, [_vp, _vp, _vp, _vp, _i, _vp, _vp, _i, _i, _i, _i, _vp, _vp, _vp]),
+  "gill_attention_fork_ws_bytes": (C.c_int64, [_i, _i, _i, _i]),
+  "gill_attention_fork": (_i, [_vp, _vp, _vp, _i, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _vp, _vp, C.c_int64, _vp]),
+  "gill_opt_score_candidates": (_i, [_vp, _vp, _vp, _vp, _i, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
   "gill_opt_set_kv_format": (_i, [_vp, _i]),
   "gill_opt_kv_format": (_i, [_vp]),
   "gill_opt_kv_bytes": (C.c_int64, [_vp]),

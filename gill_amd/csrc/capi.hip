@@ -310,6 +310,24 @@ extern "C" int gill_attention_extend(const void* q, const void* k_new, const voi
   return 0;
 }
 
+extern "C" int64_t gill_attention_fork_ws_bytes(int C, int H, int d, int max_new) {
+  return (int64_t)attention_fork_ws_bytes(C, H, d, max_new);
+}
+
+extern "C" int gill_attention_fork(const void* q, const void* k_new, const void* v_new, int ld, const void* K, const void* Vt, const int32_t* parent,
+                                   const int32_t* plen, const int32_t* cu_new, void* o, int C, int Bc, int total_new, int max_new, int H, int d,
+                                   int pitch, int32_t* flags, void* ws, int64_t ws_bytes, void* stream) {
+  GILL_REQUIRE(ws_bytes >= 0, "fork attention: negative workspace size");
+  AttnForkArgs a;
+  a.q = (const bf16_t*)q; a.k = (const bf16_t*)k_new; a.v = (const bf16_t*)v_new; a.ld = ld;
+  a.K = (const bf16_t*)K; a.Vt = (const bf16_t*)Vt; a.parent = parent; a.plen = plen; a.cu_new = cu_new; a.O = (bf16_t*)o; a.ldo = H * d;
+  a.flags = flags; a.C = C; a.Bc = Bc; a.total_new = total_new; a.max_new = max_new; a.H = H; a.dp = d; a.dpv = round_up(d, 32); a.pitch = pitch;
+  a.qscale = 1.4426950408889634f / sqrtf((float)d);
+  a.ws = ws; a.ws_bytes = (size_t)ws_bytes;
+  for (int r = 0; r < op_repeat(); ++r) GILL_TRY(attention_fork_launch(a, (hipStream_t)stream));
+  return 0;
+}
+
 extern "C" int gill_attention_decode_kv8(const void* q, const void* k_new, const void* v_new, int ld, void* K8, void* Vt8, void* Kexp, void* Vexp,
                                          const int32_t* lens, void* o, int B, int H, int d, int pitch, int32_t* flags, void* stream) {
   AttnDecodeKv8Args a;

@@ -232,6 +232,25 @@ struct AttnExtendKv8Args : AttnDecodeKv8Args {
 };
 int attention_extend_kv8_launch(const AttnExtendKv8Args& a, hipStream_t s);
 
+// Fork attention (attention_fork.hip): C packed candidate continuations against the read-only prefixes of a bf16 cache.  Candidate c brings
+// cu_new[c + 1] - cu_new[c] packed rows (zero is legal: nothing is stored for it), names its cache row parent[c] in [0, Bc) and sees that row's
+// slots 0 .. plen[c] - 1 (zero is legal: it attends to itself only); token i attends to [K[p][0 .. n - 1] ; k_0 .. k_i].  K / Vt are never
+// written.  n outside [0, pitch] is clamped (flags[c] = 1); a parent outside [0, Bc), a count outside [0, max_new] or a packed range outside
+// [0, total_new) make the candidate empty and flagged.  A candidate's output bits depend on its own packed operands, its prefix and n only.
+// ws / ws_bytes: the caller's workspace of at least attention_fork_ws_bytes(C, H, dp, max_new) bytes (0 today: ws may then be null).
+struct AttnForkArgs {
+  const bf16_t* q = nullptr; const bf16_t* k = nullptr; const bf16_t* v = nullptr; int ld = 0;
+  const bf16_t* K = nullptr; const bf16_t* Vt = nullptr;      // [Bc][H][pitch][dp], [Bc][H][dpv][pitch]
+  const int32_t* parent = nullptr; const int32_t* plen = nullptr; const int32_t* cu_new = nullptr;   // [C], [C], [C + 1] device
+  bf16_t* O = nullptr; int ldo = 0;
+  int32_t* flags = nullptr;                                   // [C] device, nullable
+  int C = 0, Bc = 0, H = 0, dp = 0, dpv = 0, pitch = 0, total_new = 0, max_new = 0;
+  float qscale = 1.f;                                         // log2(e) / sqrt(head dim)
+  void* ws = nullptr; size_t ws_bytes = 0;
+};
+size_t attention_fork_ws_bytes(int C, int H, int d, int max_new);   // host only
+int attention_fork_launch(const AttnForkArgs& a, hipStream_t s);
+
 
 // The feed-forward sub-block + proj_out + outer residual of a level-0 transformer block (C = 320) as one kernel (ffn.hip):
 //   out = [Wp.W2 | Wp] . [ value * gelu(gate) | t ] + bo + resid,  [value | gate] = W1' . LN(t) + b1'  (LN from the row-sum planes).

@@ -6,9 +6,9 @@
 // learned positions with the +2 offset, final LayerNorm; hidden_states[-1] is post-final-LN.
 // The residual stream is fp32; GEMMs are bf16 MFMA with fp32 accumulation, split-K so that the
 // skinny (M = B*T) weight-streaming GEMMs cover all 256 CUs; attention is the shared flash kernel.
-// Every layer loop — forward, cached forward, the ragged decode step on bf16 weights or e4m3 bytes, and the packed extend pass of a dialogue
-// session — is TfmRun::layers of tfm.h; here: embeddings and positions, the KV cache, the hidden-rows pass of img_hidden / forward_loss, logits
-// and the decode and extend entry points.
+// Every layer loop — forward, cached forward, the ragged decode step on bf16 weights or e4m3 bytes, the packed extend pass of a dialogue
+// session and the candidate-scoring pass over the same cache — is TfmRun::layers of tfm.h; here: embeddings and positions, the KV cache, the
+// hidden-rows pass of img_hidden / forward_loss, logits and the decode, extend and score-candidates entry points.
 #include "tfm.h"
 #include "philox.h"
 
@@ -36,6 +36,8 @@ struct gill_opt {
   // workspace of gill_opt_extend (allocated at its first call): the packed [B*T][3D] projection and the last new row of every sequence
   bf16_t* ext_qkv = nullptr;
   float* ext_last = nullptr;      // [max_batch][D]
+  // workspace of the fork attention under gill_opt_score_candidates (attention_fork_ws_bytes; grown at a call that needs more)
+  void* fork_ws = nullptr; size_t fork_ws_bytes = 0;
   // scoring workspace of gill_opt_forward_loss (allocated at its first call): the final LayerNorm of every row, the shifted targets, the
   // per-row results and the partials of lmloss.hip
   bf16_t* xn_bf = nullptr;      // [B*T][D]
@@ -343,6 +345,23 @@ __global__ __launch_bounds__(256) void opt_token_loss_kernel(const float* __rest
   token_rank[i] = rank[r];
 }
 
+// the scoring workspace of gill_opt_forward_loss and gill_opt_score_candidates, allocated at the first call of either
+static int opt_ensure_loss_ws(gill_opt* m) {
+  if (m->xn_bf) return 0;
+  const int D = m->cfg.hidden_size, V = m->cfg.vocab_size;
+  const size_t R = (size_t)m->cfg.max_batch * m->cfg.max_seq;
+  GILL_TRY(m->pool.alloc(&m->xn_bf, R * D));
+  GILL_TRY(m->pool.alloc(&m->loss_tgt, R));
+  GILL_TRY(m->pool.alloc(&m->loss_lse, R));
+  GILL_TRY(m->pool.alloc(&m->loss_tl, R));
+  GILL_TRY(m->pool.alloc(&m->loss_rank, R));
+  GILL_TRY(m->pool.alloc(&m->ll_f32, (size_t)m->cfg.max_batch * D));
+  unsigned char* ws = nullptr;
+  GILL_TRY(m->pool.alloc(&ws, lm_loss_workspace_bytes((int)R, V), false));
+  m->loss_ws = ws;
+  return 0;
+}
+
 extern "C" int gill_opt_forward_loss(gill_opt* m, const int64_t* ids, const int32_t* last_idx_host, int B, int T, int num_tokens,
                                      const void* extra_rows_bf16, int n_extra, const int64_t* labels, void* raw_out_bf16, void* emb_out_bf16,
                                      float* token_loss, int32_t* token_rank, float* summary, float* last_logit_out, float* hidden_out,
@@ -356,18 +375,7 @@ extern "C" int gill_opt_forward_loss(gill_opt* m, const int64_t* ids, const int3
   hipStream_t s = (hipStream_t)stream;
   const int D = m->cfg.hidden_size, V = m->cfg.vocab_size;
   const int ll_base = m->cfg.max_batch * 64;      // idx_dev: the last-logit rows (opt_hidden_rows)
-  if (!m->xn_bf) {
-    const size_t R = (size_t)m->cfg.max_batch * m->cfg.max_seq;
-    GILL_TRY(m->pool.alloc(&m->xn_bf, R * D));
-    GILL_TRY(m->pool.alloc(&m->loss_tgt, R));
-    GILL_TRY(m->pool.alloc(&m->loss_lse, R));
-    GILL_TRY(m->pool.alloc(&m->loss_tl, R));
-    GILL_TRY(m->pool.alloc(&m->loss_rank, R));
-    GILL_TRY(m->pool.alloc(&m->ll_f32, (size_t)m->cfg.max_batch * D));
-    unsigned char* ws = nullptr;
-    GILL_TRY(m->pool.alloc(&ws, lm_loss_workspace_bytes((int)R, V), false));
-    m->loss_ws = ws;
-  }
+  GILL_TRY(opt_ensure_loss_ws(m));
   GILL_TRY(opt_hidden_rows(m, ids, last_idx_host, B, T, num_tokens, extra_rows_bf16, n_extra, raw_out_bf16, emb_out_bf16, last_logit_out != nullptr, s));
   // here the final LayerNorm runs on every row
   GILL_TRY(layernorm_launch(m->h, 1, m->lnfg, m->lnfb, m->xn_bf, B * T, D, 1e-5f, s));
@@ -621,6 +629,86 @@ extern "C" int gill_opt_extend(gill_opt* m, const int64_t* ids, const void* embe
   GILL_TRY(gather_rows_launch(m->h, 1, m->idx_dev, B, D, m->gath, 1, s));
   GILL_TRY(layernorm_f32out_launch(m->gath, 1, m->lnfg, m->lnfb, m->ext_last, B, D, 1e-5f, s));
   hipLaunchKernelGGL(opt_extend_copy_last_kernel, dim3(B), dim3(256), 0, s, m->ext_last, cu_new, total_new, D, hidden_last);
+  GILL_CHECK_HIP(hipGetLastError());
+  return 0;
+}
+
+// ---- candidate ranking: packed continuations scored against the rows' cached prefixes, nothing appended ----
+
+// One thread per candidate, its tokens in packed order: token_logprob = tgt - lse of a scored row (0 where the target is -100), token_rank, and
+// the candidate's sum, count and mean (NaN over zero targets, HF's mean).  The candidate's range and parent are checked as the attention
+// kernel checks them: one it treats as empty scores nothing.  A fixed summation order: the same inputs give the same bits.
+__global__ __launch_bounds__(64) void opt_score_reduce_kernel(const float* __restrict__ lse, const float* __restrict__ tl, const int* __restrict__ rank,
+                                                              const int64_t* __restrict__ target, const int32_t* __restrict__ cu_new,
+                                                              const int32_t* __restrict__ parent, int C, int rows, int total_new, int max_new,
+                                                              float* __restrict__ token_logprob, int32_t* __restrict__ token_rank,
+                                                              float* __restrict__ score_sum, int32_t* __restrict__ n_scored,
+                                                              float* __restrict__ score_mean) {
+  const int c = blockIdx.x * blockDim.x + threadIdx.x;
+  if (c >= C) return;
+  const int64_t lo = cu_new[c], hi = cu_new[c + 1];
+  int64_t cnt = hi - lo;
+  const int par = parent[c];
+  if (cnt < 0 || cnt > max_new || lo < 0 || hi > total_new || par < 0 || par >= rows) cnt = 0;
+  float sum = 0.f;
+  int n = 0;
+  for (int64_t i = 0; i < cnt; ++i) {
+    const int64_t r = lo + i;
+    const bool scored = target[r] != -100;
+    const float lp = scored ? tl[r] - lse[r] : 0.f;
+    token_logprob[r] = lp;
+    if (token_rank) token_rank[r] = rank[r];
+    if (scored) { sum += lp; ++n; }
+  }
+  score_sum[c] = sum;
+  n_scored[c] = n;
+  score_mean[c] = n > 0 ? sum / (float)n : __builtin_nanf("");
+}
+
+extern "C" int gill_opt_score_candidates(gill_opt* m, const int64_t* ids, const void* embeds_bf16, const void* extra_rows_bf16, int n_extra,
+                                         const int32_t* cu_new, const int32_t* parent, const int32_t* plen, const int64_t* target, int C,
+                                         int total_new, int max_new, int len_bound, float* token_logprob, int32_t* token_rank, float* score_sum,
+                                         int32_t* n_scored, float* score_mean, float* hidden_all, int32_t* flags, void* stream) {
+  GILL_REQUIRE(m && (ids || embeds_bf16) && cu_new && parent && plen && target && token_logprob && score_sum && n_scored && score_mean,
+               "null argument");
+  GILL_REQUIRE(m->kv_format == GILL_KV_BF16,
+               "gill_opt_score_candidates: the handle's KV cache format is e4m3 (GILL_KV_E4M3); candidate scoring reads a bf16 cache");
+  GILL_REQUIRE(!m->cache.empty(), "gill_opt_score_candidates: the handle has no KV cache yet (a cached entry such as gill_opt_extend fills it)");
+  const int64_t R = (int64_t)m->cfg.max_batch * m->cfg.max_seq;
+  GILL_REQUIRE(C >= 1 && C <= 65535, "score candidates: 1 <= C <= 65535");
+  GILL_REQUIRE(max_new >= 1 && total_new >= 1 && (int64_t)total_new <= R, "score candidates: total_new within the workspace (max_batch * max_seq), max_new >= 1");
+  GILL_REQUIRE(len_bound >= 1 && len_bound <= m->cfg.max_positions, "score candidates: sequence longer than the position table");
+  GILL_REQUIRE(n_extra >= 0 && (n_extra == 0 || extra_rows_bf16), "n_extra rows need a table");
+  hipStream_t s = (hipStream_t)stream;
+  const int D = m->cfg.hidden_size, V = m->cfg.vocab_size;
+  if (!m->ext_qkv) {
+    GILL_TRY(m->pool.alloc(&m->ext_qkv, (size_t)m->cfg.max_batch * m->cfg.max_seq * 3 * D, false));
+    GILL_TRY(m->pool.alloc(&m->ext_last, (size_t)m->cfg.max_batch * D, false));
+  }
+  GILL_TRY(opt_ensure_loss_ws(m));
+  const size_t fork_need = attention_fork_ws_bytes(C, m->cfg.num_heads, m->tfm.dp, max_new);
+  if (fork_need > m->fork_ws_bytes) {
+    unsigned char* ws = nullptr;
+    GILL_TRY(m->pool.alloc(&ws, fork_need, false));
+    m->fork_ws = ws; m->fork_ws_bytes = fork_need;
+  }
+  // rows no candidate owns: log-probability 0, rank -1
+  GILL_CHECK_HIP(hipMemsetAsync(token_logprob, 0, sizeof(float) * (size_t)total_new, s));
+  if (token_rank) GILL_CHECK_HIP(hipMemsetAsync(token_rank, 0xFF, sizeof(int32_t) * (size_t)total_new, s));
+  // packed row cu_new[c] + i: its embedding (or visual) row + position 2 + plen[c] + i
+  hipLaunchKernelGGL(opt_extend_embed_kernel, dim3(total_new), dim3(256), 0, s, ids, (const bf16_t*)embeds_bf16, m->embed, V,
+                     (const bf16_t*)extra_rows_bf16, n_extra, m->pos, m->cfg.max_positions, cu_new, plen, C, D, m->h);
+  GILL_CHECK_HIP(hipGetLastError());
+  // the one layer loop over the packed rows in fork mode, on the bf16 matrices (a w8 handle: the dequantised ones, the extend pass's rule)
+  TfmDecode dec{nullptr, flags};
+  dec.cu_new = cu_new; dec.nseq = C; dec.max_new = max_new; dec.qkv = m->ext_qkv;
+  dec.fork_parent = parent; dec.fork_plen = plen; dec.fork_rows = m->cfg.max_batch; dec.fork_ws = m->fork_ws; dec.fork_ws_bytes = m->fork_ws_bytes;
+  GILL_TRY(m->run_layers(1, total_new, s, 0, &dec, false));
+  GILL_TRY(layernorm_launch(m->h, 1, m->lnfg, m->lnfb, m->xn_bf, total_new, D, 1e-5f, s));
+  if (hidden_all) GILL_TRY(layernorm_f32out_launch(m->h, 1, m->lnfg, m->lnfb, hidden_all, total_new, D, 1e-5f, s));
+  GILL_TRY(lm_loss_launch(m->xn_bf, m->lm_head, target, total_new, V, D, m->loss_lse, m->loss_tl, m->loss_rank, nullptr, m->loss_ws, s));
+  hipLaunchKernelGGL(opt_score_reduce_kernel, dim3(cdiv(C, 64)), dim3(64), 0, s, m->loss_lse, m->loss_tl, m->loss_rank, target, cu_new, parent, C,
+                     m->cfg.max_batch, total_new, max_new, token_logprob, token_rank, score_sum, n_scored, score_mean);
   GILL_CHECK_HIP(hipGetLastError());
   return 0;
 }

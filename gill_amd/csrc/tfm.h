@@ -81,9 +81,14 @@ int tfm_linear_launch(const bf16_t* A, int M, const bf16_t* W, int blk, const fl
 // With cu_new (the extend pass, gill_opt_extend): the stream holds T = total_new PACKED rows (layers is called with B = 1), rows
 // cu_new[b] .. cu_new[b + 1] - 1 the new tokens of sequence b < nseq at positions lens[b] ..; the projection goes to qkv ([total_new][3D], the
 // caller's: Tfm::q is sized for 16 rows of it) and attention is attention_extend_launch with the host bound max_new of a row's count.
+// Fork mode (the scoring pass, gill_opt_score_candidates): cu_new set and fork_parent set.  The packed rows are nseq CANDIDATES; candidate c reads
+// the slots 0 .. fork_plen[c] - 1 of cache row fork_parent[c] < fork_rows and its own tokens (attention_fork_launch); the cache is not written
+// and lens is not read.  fork_ws / fork_ws_bytes: the operator's workspace, reused by every layer.
 struct TfmDecode {
   const int32_t* lens = nullptr; int32_t* flags = nullptr;
   const int32_t* cu_new = nullptr; int nseq = 0, max_new = 0; bf16_t* qkv = nullptr;
+  const int32_t* fork_parent = nullptr; const int32_t* fork_plen = nullptr; int fork_rows = 0;
+  void* fork_ws = nullptr; size_t fork_ws_bytes = 0;
 };
 
 struct TfmRun {

@@ -230,7 +230,16 @@ int TfmRun::self_attn(float* h, int B, int T, const TfmLayer& L, bool causal, co
   if (dec && dec->cu_new) {
     GILL_REQUIRE(kv && B == 1 && T >= 1 && dec->qkv, "extend attention: a cache and packed rows");
     GILL_TRY(linear(t.nbuf, T, L.qkv, nullptr, ACT_NONE, dec->qkv, false));
-    if (kv->fmt == GILL_KV_E4M3) {
+    if (dec->fork_parent) {
+      GILL_REQUIRE(kv->fmt == GILL_KV_BF16 && dec->fork_plen, "fork attention: a bf16 cache, parents and prefix lengths");
+      AttnForkArgs a;
+      a.q = dec->qkv; a.k = dec->qkv + t.D; a.v = dec->qkv + 2 * t.D; a.ld = 3 * t.D;
+      a.K = kv->k; a.Vt = kv->vt; a.parent = dec->fork_parent; a.plen = dec->fork_plen; a.cu_new = dec->cu_new; a.O = t.o; a.ldo = t.D;
+      a.flags = dec->flags; a.C = dec->nseq; a.Bc = dec->fork_rows; a.total_new = T; a.max_new = dec->max_new; a.H = t.H; a.dp = t.dp;
+      a.dpv = t.dpv; a.pitch = kv->pad; a.qscale = 1.4426950408889634f / sqrtf((float)t.dp);
+      a.ws = dec->fork_ws; a.ws_bytes = dec->fork_ws_bytes;
+      GILL_TRY(attention_fork_launch(a, s));
+    } else if (kv->fmt == GILL_KV_E4M3) {
       AttnExtendKv8Args a;
       a.q = dec->qkv; a.k = dec->qkv + t.D; a.v = dec->qkv + 2 * t.D; a.ld = 3 * t.D;
       a.K8 = kv->k8; a.Vt8 = kv->vt8; a.Kexp = kv->kexp; a.Vexp = kv->vexp;

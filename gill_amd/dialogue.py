@@ -98,6 +98,81 @@ def pack_feed(feeds: Sequence[Sequence[int]], extra_offsets: Sequence[int]) -> T
   return packed, cu, max((b - a for a, b in zip(cu, cu[1:])), default=0)
 
 
+class CandidatePack:
+  """One gill_opt_score_candidates call's worth of packed candidates (pack_candidates): ids / targets (total_new), cu_new (C + 1), parent and
+  plen (C), the host bounds max_new and len_bound, and per candidate `own` = (index into the caller's rows, index of the candidate in that row,
+  packed row of its first own token's predictor, number of own tokens scored)."""
+
+  def __init__(self):
+    self.ids: List[int] = []
+    self.targets: List[int] = []
+    self.cu: List[int] = [0]
+    self.parent: List[int] = []
+    self.plen: List[int] = []
+    self.own: List[Tuple[int, int, int, int]] = []
+    self.max_new = 0
+    self.len_bound = 0
+
+  @property
+  def n_candidates(self) -> int:
+    return len(self.parent)
+
+  @property
+  def total_new(self) -> int:
+    return len(self.ids)
+
+
+def pack_candidates(rows: Sequence[Tuple[int, Sequence[int], int, int]], candidates: Sequence[Sequence[Sequence[int]]],
+                    limit: Optional[int] = None) -> List[CandidatePack]:
+  """The packing of DialogueSession.score, pure host code.  rows: per scored row (cache row index, history ids, cached, extra offset);
+  candidates: per scored row its candidate token-id sequences (ids >= 0: text only).  For a row with history `ids` whose cache holds `cached`
+  tokens, plen = max(min(cached, len(ids) - 1), 0): the last history token is always re-run, as the predictor of cand[0], whether the row is
+  fresh from extend (cached == len(ids)) or carries a pending token.  A candidate's feed is ids[plen:] + cand[:-1]; its targets are -100 for
+  all but the last history position of the feed, then cand.  With an empty history cand[0] has no predictor: the feed is cand[:-1] and the
+  targets are cand[1:] (a one-token candidate then scores nothing).  An empty candidate brings no rows and scores nothing.  A negative history
+  id is moved by the row's extra offset, as in pack_feed.  Candidates stay grouped by row, in the order given.  limit: the most packed rows one
+  call may carry (the handle's workspace); the candidates are split into as many packs as that takes, none of them split itself."""
+  if len(rows) != len(candidates):
+    raise ValueError(f'score needs one candidate list per named row ({len(rows)}), got {len(candidates)}')
+  packs = [CandidatePack()]
+  for k, ((parent, ids, cached, off), cands) in enumerate(zip(rows, candidates)):
+    ids = [int(v) for v in ids]
+    plen = max(min(int(cached), len(ids) - 1), 0)
+    tail = [v - off if v < 0 else v for v in ids[plen:]]
+    for j, cand in enumerate(cands):
+      cand = [int(v) for v in cand]
+      if any(v < 0 for v in cand):
+        raise NotImplementedError(f'row {parent} candidate {j}: candidates are text only (ids >= 0); images inside a candidate are not scored')
+      if not cand:
+        feed, tgt, first, n_own = [], [], 0, 0
+      elif tail:
+        feed, tgt, first, n_own = tail + cand[:-1], [-100] * (len(tail) - 1) + cand, len(tail) - 1, len(cand)
+      else:
+        feed, tgt, first, n_own = cand[:-1], cand[1:], 0, len(cand) - 1
+      if limit is not None and len(feed) > limit:
+        raise ValueError(f'row {parent} candidate {j}: {len(feed)} packed tokens exceed the handle\'s workspace ({limit})')
+      p = packs[-1]
+      if limit is not None and p.total_new + len(feed) > limit:
+        p = CandidatePack()
+        packs.append(p)
+      p.own.append((k, j, p.total_new + first, n_own))
+      p.ids += feed
+      p.targets += tgt
+      p.cu.append(len(p.ids))
+      p.parent.append(int(parent))
+      p.plen.append(plen)
+      p.max_new = max(p.max_new, len(feed))
+      p.len_bound = max(p.len_bound, plen + len(feed))
+  return [p for p in packs if p.n_candidates]
+
+
+def rank_order(scores: torch.Tensor) -> dict:
+  """(n,) scores -> dict(scores, order: indices from the highest score down, ties in index order, NaN last; best: order[0] or None)."""
+  sc = [float(v) for v in scores.tolist()]
+  order = sorted(range(len(sc)), key=lambda j: (sc[j] != sc[j], -sc[j] if sc[j] == sc[j] else 0.0, j))
+  return dict(scores=scores, order=order, best=order[0] if order and sc[order[0]] == sc[order[0]] else None)
+
+
 class DialogueSession:
   """GILLModel.open_session(B, capacity): B dialogues over the handle's KV cache, each of at most capacity - 1 tokens (one slot of a row is
   kept free for the decode step's store).  The handle is sized once; any other entry that writes or rebuilds its cache makes the session stale
@@ -245,6 +320,51 @@ class DialogueSession:
         self.books[r].generated(toks[r, :int(n_tokens[r])].tolist())
     return tokens[:, :L], n_tokens.to(dev), hidden, n_hidden.to(dev)
 
+  def score(self, rows, candidates, reduce: str = 'mean', return_tokens: bool = False, max_packed: Optional[int] = None):
+    """Log-likelihood of candidate continuations of the named rows' dialogues: candidates[k] is a list of token-id sequences (text only) for
+    rows[k].  The rows' cached prefixes are read where they lie and shared by all their candidates (gill_opt_score_candidates over
+    csrc/attention_fork.hip): only each row's last history token (plus what is still pending) and the candidates' own tokens run through
+    the layers, and nothing is appended.  Returns per named row a host fp32 tensor (n_candidates,): the sum or the mean (reduce) of the
+    candidate's own tokens' log-probabilities (the mean of a candidate with nothing scored is NaN, its sum 0); with return_tokens also, per
+    named row, the list of the candidates' per-token log-probabilities.  Unlike GILL.get_log_likelihood_scores the history's own tokens are
+    not part of the score.  One device-to-host copy per call of the engine (one call unless the packed rows exceed the handle's workspace, or
+    max_packed).  The session is untouched: books, hidden_last, cache and epoch stay as they are."""
+    self._check()
+    if reduce not in ('mean', 'sum'):
+      raise ValueError(f"reduce should be 'mean' or 'sum', got {reduce!r}")
+    rows = self._rows(rows)
+    if candidates is None or len(candidates) != len(rows):
+      raise ValueError(f'score needs one candidate list per named row ({len(rows)})')
+    m = self.model
+    dev = m.logit_scale.device
+    offsets, tables, n_tab = [0] * len(rows), [], 0
+    for k, r in enumerate(rows):
+      bk = self.books[r]
+      if any(v < 0 for v in bk.ids[max(min(bk.cached, len(bk.ids) - 1), 0):]):
+        offsets[k] = n_tab
+        tables.append(self.extras[r])
+        n_tab += int(self.extras[r].shape[0])
+    cb, ct = m._opt_cap
+    limit = cb * ct if max_packed is None else min(int(max_packed), cb * ct)
+    packs = pack_candidates([(r, self.books[r].ids, self.books[r].cached, offsets[k]) for k, r in enumerate(rows)], candidates, limit)
+    for p in packs:
+      if p.len_bound > m.opt_cfg.max_positions:
+        raise ValueError(f'a history plus its candidate holds {p.len_bound} tokens: beyond the position table ({m.opt_cfg.max_positions})')
+    scores = [torch.full((len(c),), float('nan') if reduce == 'mean' else 0.0, dtype=torch.float32) for c in candidates]
+    tokens = [[torch.zeros(0)] * len(c) for c in candidates]
+    extra = torch.cat(tables, dim=0) if tables else None
+    with torch.no_grad():
+      for p in packs:
+        if p.total_new == 0:
+          continue
+        out = m._lm_score_candidates(p, extra_rows=extra).cpu()      # the one copy of this call
+        T, C = p.total_new, p.n_candidates
+        pick = out[T:T + C] if reduce == 'sum' else out[T + C:T + 2 * C]
+        for c, (k, j, first, n_own) in enumerate(p.own):
+          scores[k][j] = pick[c]
+          tokens[k][j] = out[first:first + n_own].clone()
+    return (scores, tokens) if return_tokens else scores
+
   def rollback(self, row: int, keep: int) -> None:
     """Keeps only the first `keep` generated tokens of the row's last turn.  Costs nothing on the device."""
     self._check()
@@ -350,6 +470,30 @@ class GillDialogues:
     out = [None] * s.B
     for b, o in zip(rows, outputs):
       out[b] = o
+    return out
+
+  def rank(self, candidates, reduce: str = 'mean'):
+    """candidates[b]: None, or a list of candidate reply strings for dialogue b.  Each is tokenised without <bos> (with it when the dialogue
+    is still empty, as the first string of a prompt) and scored as a continuation of the dialogue as it stands (DialogueSession.score: the
+    candidate's own tokens only, the dialogue untouched).  Returns per dialogue None or dict(scores=(n,) host fp32 tensor, order=the candidate
+    indices from the most to the least likely (NaN scores last), best=order[0] or None)."""
+    s = self.session
+    if len(candidates) != s.B:
+      raise ValueError(f'rank() takes one entry per dialogue ({s.B}), got {len(candidates)}')
+    s._check()
+    rows = [b for b, c in enumerate(candidates) if c is not None]
+    tok = self.gill.model.tokenizer
+    ids = []
+    for b in rows:
+      if any(type(c) != str for c in candidates[b]):
+        raise NotImplementedError('rank() takes candidate strings: images inside a candidate are not scored')
+      ids.append([[int(v) for v in tok(c, add_special_tokens=not self._bos_done[b], return_tensors="pt").input_ids[0].tolist()]
+                  for c in candidates[b]])
+    out = [None] * s.B
+    if not rows:
+      return out
+    for b, sc in zip(rows, s.score(rows, ids, reduce=reduce)):
+      out[b] = rank_order(sc)
     return out
 
   def reset(self, rows) -> None:

@@ -887,6 +887,27 @@ class GILLModel(nn.Module):
                                       N.ptr(cu_new), N.ptr(lens_dev), B, total_new, max_new, len_bound, N.ptr(hidden_last),
                                       N.ptr(hidden_all), N.current_stream()))
 
+  def _lm_score_candidates(self, pack, extra_rows: Optional[Tensor] = None, token_rank: Optional[Tensor] = None,
+                           hidden_all: Optional[Tensor] = None, flags: Optional[Tensor] = None) -> Tensor:
+    """gill_opt_score_candidates on the handle as it stands (never grown here: that would drop the cache) for one dialogue.CandidatePack.
+    -> one fp32 device tensor [token_logprob (total_new) | score_sum (C) | score_mean (C) | n_scored (C, int32 bits)]: the caller's single
+    device-to-host copy.  Reads the cache, writes nothing of the handle's state: the cache epoch stands."""
+    dev = self.logit_scale.device
+    if self._opt_handle is None:
+      raise N.GillNativeError('the OPT handle has no KV cache to score against: open a session and extend it first.')
+    T, Cn = pack.total_new, pack.n_candidates
+    i32 = torch.tensor(pack.cu + pack.parent + pack.plen, dtype=torch.int32).to(dev)
+    i64 = torch.tensor(pack.ids + pack.targets, dtype=torch.int64).to(dev)
+    out = torch.zeros(T + 3 * Cn, dtype=torch.float32, device=dev)
+    n_extra = 0 if extra_rows is None else int(extra_rows.shape[0])
+    with torch.cuda.device(dev):
+      N.check(N.lib().gill_opt_score_candidates(self._opt_handle, i64.data_ptr(), None, N.ptr(extra_rows) if n_extra else None, n_extra,
+                                                i32.data_ptr(), i32[Cn + 1:].data_ptr(), i32[2 * Cn + 1:].data_ptr(), i64[T:].data_ptr(), Cn, T,
+                                                max(pack.max_new, 1), max(pack.len_bound, 1), out.data_ptr(), N.ptr(token_rank),
+                                                out[T:].data_ptr(), out[T + 2 * Cn:].data_ptr(), out[T + Cn:].data_ptr(), N.ptr(hidden_all),
+                                                N.ptr(flags), N.current_stream()))
+    return out
+
   def open_session(self, B: int, capacity: int):
     """A dialogue session over the handle's KV cache: B rows of up to `capacity` tokens whose caches are kept across turns
     (dialogue.DialogueSession).  Any other entry that writes or rebuilds the cache makes the session stale."""
@@ -1259,6 +1280,29 @@ class GILL(nn.Module):
     position table)."""
     from .dialogue import GillDialogues
     return GillDialogues(self, n, capacity)
+
+  def rank_candidates(self, prompts: List, candidates: List[str], reduce: str = 'mean'):
+    """Ranks candidate reply strings as continuations of one interleaved image / text prompt list (NEW, not a reference function).  The
+    one-shot form of GillDialogues.rank: opens a one-row session sized for the context, runs the prompt through it once (images through
+    _visual_rows, segmented as generate_for_images_and_texts segments a prompt) and scores every candidate against that cached context
+    (gill_opt_score_candidates); the context is not re-run per candidate.  Returns dict(scores, order, best) as GillDialogues.rank.
+    Stated divergence from get_log_likelihood_scores: that method averages over every text position of the whole prompt, history included;
+    this one scores the candidate's own tokens only (reduce='sum' ranks equal-length candidates as the old method does; otherwise the
+    normalisation differs).  Like any session opening it takes over the handle's KV cache: an open session goes stale."""
+    from .dialogue import rank_order, segment_turn
+    m = self.model
+    if any(type(c) != str for c in candidates):
+      raise NotImplementedError('rank_candidates takes candidate strings: images inside a candidate are not scored')
+    nv = m.args.n_visual_tokens
+    ids, images, done = segment_turn(m.tokenizer, [prompts] if isinstance(prompts, str) else list(prompts), nv, False, False, self._is_image)
+    extra = None
+    if images:
+      m._require_vision()
+      extra = self._visual_rows(images)
+    cand_ids = [[int(v) for v in m.tokenizer(c, add_special_tokens=not done, return_tensors="pt").input_ids[0].tolist()] for c in candidates]
+    s = m.open_session(1, len(ids) + 1)
+    s.extend([0], ids=[ids], extra_rows=[extra])
+    return rank_order(s.score([0], [cand_ids], reduce=reduce)[0])
 
   def _batch_outputs(self, rows, tokens: Tensor, n_tok: Tensor, hidden: Tensor, n_hid: Tensor, max_num_rets: int, generator,
                      guidance_scale: float, num_inference_steps: int, all_branches: bool, skip_gen_on_ret: bool):

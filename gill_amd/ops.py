@@ -226,6 +226,34 @@ def attention_extend(q: torch.Tensor, k_new: torch.Tensor, v_new: torch.Tensor, 
   return o
 
 
+def attention_fork(q: torch.Tensor, k_new: torch.Tensor, v_new: torch.Tensor, K: torch.Tensor, Vt: torch.Tensor, parent: torch.Tensor,
+                   plen: torch.Tensor, cu_new: torch.Tensor, max_new: int, flags: Optional[torch.Tensor] = None) -> torch.Tensor:
+  """Fork attention: C packed candidate continuations, q / k_new / v_new (total_new, H*d) bf16 packed rows as in attention_extend; candidate c
+  attends to the slots 0 .. plen[c] - 1 of cache row parent[c] and causally to its own tokens.  K (Bc,H,pitch,d) and Vt
+  (Bc,H,round_up(d,32),pitch) bf16 caches are READ ONLY; parent, plen (C) and cu_new (C + 1) int32 on the device; max_new: the host's bound on
+  a candidate's count; flags (C) int32 (optional) receives 1 where a candidate was clamped or emptied.  The workspace
+  (gill_attention_fork_ws_bytes) is allocated here.  Returns (total_new, H*d) bf16."""
+  Bc, H, pitch, d = K.shape
+  total = q.shape[0]
+  ld = q.stride(0)
+  C = parent.numel()
+  for t in (q, k_new, v_new):
+    assert t.dtype == torch.bfloat16 and t.is_cuda and tuple(t.shape) == (total, H * d) and t.stride(1) == 1 and t.stride(0) == ld
+  assert K.dtype == torch.bfloat16 and Vt.dtype == torch.bfloat16 and tuple(Vt.shape) == (Bc, H, (d + 31) // 32 * 32, pitch)
+  assert K.is_contiguous() and Vt.is_contiguous()
+  assert parent.dtype == torch.int32 and plen.dtype == torch.int32 and plen.numel() == C and cu_new.dtype == torch.int32 and cu_new.numel() == C + 1
+  assert flags is None or (flags.dtype == torch.int32 and flags.numel() == C)
+  o = torch.empty((total, H * d), dtype=torch.bfloat16, device=q.device)
+  if total == 0:      # no candidate brought a token
+    return o
+  nws = int(N.lib().gill_attention_fork_ws_bytes(C, H, d, int(max_new)))
+  ws = torch.empty(nws, dtype=torch.uint8, device=q.device) if nws > 0 else None
+  N.check(N.lib().gill_attention_fork(q.data_ptr(), k_new.data_ptr(), v_new.data_ptr(), ld, N.ptr(K), N.ptr(Vt), N.ptr(parent), N.ptr(plen),
+                                      N.ptr(cu_new), N.ptr(o), C, Bc, total, int(max_new), H, d, pitch, N.ptr(flags), N.ptr(ws), nws,
+                                      N.current_stream()))
+  return o
+
+
 def _kv8_cache_checks(K8: torch.Tensor, Vt8: torch.Tensor, Kexp: torch.Tensor, Vexp: torch.Tensor):
   B, H, pitch, d = K8.shape
   assert K8.dtype == torch.uint8 and Vt8.dtype == torch.uint8 and tuple(Vt8.shape) == (B, H, (d + 31) // 32 * 32, pitch)

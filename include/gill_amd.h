@@ -324,6 +324,50 @@ int gill_opt_extend(gill_opt* h, const int64_t* ids, const void* embeds_bf16, co
                     const int32_t* lens_dev, int B, int total_new, int max_new, int len_bound, float* hidden_last, float* hidden_all,
                     void* stream);
 
+/* ---- Candidate ranking: packed continuations scored against the rows' cached prefixes; the cache is read, never written. ----
+ *
+ * Fork attention, the operator under gill_opt_score_candidates.  C candidates are packed as in gill_attention_extend: cu_new (C + 1) int32 on
+ * the DEVICE holds the prefix sums of their token counts, q / k_new / v_new / o hold total_new packed rows.  Candidate c names a cache row
+ * p = parent[c] in [0, Bc) and sees that row's slots 0 .. n - 1, n = plen[c] (parent, plen: (C) int32 on the device).  K (Bc,H,pitch,d) and
+ * Vt (Bc,H,round_up(d,32),pitch) are a bf16 cache as gill_attention_extend / gill_attention_decode leave it; they are const here.
+ *   o[cu_new[c] + i] = softmax(q_i . [K[p][0..n-1]; k_0..k_i] / sqrt(d)) . [V[p][0..n-1]; v_0..v_i]      (the scale applied in fp32).
+ * Slots of row p at or beyond n are excluded by selection whatever they hold (their scores are selected to -inf, and in the tile that
+ * straddles n their V^T elements are replaced by zero).  n = 0 is legal (the candidate attends to itself only), a count of 0 is legal
+ * (nothing is stored), candidates may come in any order, any number may share a parent and a cache row may have none.  n outside
+ * [0, pitch] is clamped and flags[c] (nullable) set to 1; a parent outside [0, Bc), a count outside [0, max_new] or a packed range outside
+ * [0, total_new) make the candidate empty and flagged, with no read through it; nothing outside the buffers is touched.  A candidate's
+ * output bits are a fixed function of its own packed operands, K[p][0..n-1] / V[p][0..n-1] and n: the same at any C, anywhere in the
+ * pack, beside any siblings, at any row index p.  The accuracy class of gill_attention_extend, not its bits: the candidate's own tokens
+ * are tiled from its token 0, not from slot 0.  One candidate per 32-query wave tile (csrc/attention_fork.hip); the candidate's keys and
+ * values are read from the packed rows, so gill_attention_fork_ws_bytes (host only) returns 0 today and ws may then be null.  An
+ * unsupported d, a misaligned pointer, max_new < 1 or ws_bytes below the query's answer are errors, reported before anything is launched.
+ * Honours GILL_OP_REPEAT. */
+int64_t gill_attention_fork_ws_bytes(int C, int H, int d, int max_new);
+int gill_attention_fork(const void* q, const void* k_new, const void* v_new, int ld, const void* K, const void* Vt, const int32_t* parent,
+                        const int32_t* plen, const int32_t* cu_new, void* o, int C, int Bc, int total_new, int max_new, int H, int d, int pitch,
+                        int32_t* flags, void* ws, int64_t ws_bytes, void* stream);
+
+/* The layers over C packed candidates in fork mode, then the fused LM-head loss of every packed row.  Input as in gill_opt_extend: ids
+ * (total_new) int64 on the device (an id < 0 selects row -(id + 1) of extra_rows), or, with ids NULL, embeds (total_new, D) bf16.  Packed
+ * row cu_new[c] + i takes position embedding 2 + plen[c] + i and attends to the slots 0 .. plen[c] - 1 of cache row parent[c] and to the
+ * rows cu_new[c] .. cu_new[c] + i (gill_attention_fork).  target (total_new) int64 on the device: the vocabulary id row r is scored
+ * against, -100 to ignore it.  Outputs, all on the device, no host wait:
+ *   token_logprob (total_new) fp32   logit[target] - logsumexp of the row, 0 where ignored and for rows no candidate owns
+ *   token_rank (total_new) int32     nullable; the target's rank as in gill_opt_forward_loss, -1 where ignored
+ *   score_sum (C) fp32, n_scored (C) int32, score_mean (C) fp32: per candidate, over its scored rows in packed order by one small kernel
+ *                                    with a fixed summation order; the mean is NaN when nothing is scored (HF's mean over zero targets)
+ *   hidden_all (total_new, D) fp32   nullable; hidden_states[-1] of every packed row
+ *   flags (C) int32                  nullable, zeroed by the caller; 1 where gill_attention_fork clamped or emptied a candidate
+ * The entry writes neither the cache nor any length and does not allocate the cache: a handle whose cache does not exist yet is an error,
+ * and so is a GILL_KV_E4M3 handle (the message names the format).  On a GILL_OPT_W8 handle the pass runs the dequantised bf16 matrices,
+ * the rule of gill_opt_extend.  Checked before anything is enqueued: C >= 1, total_new <= max_batch * max_seq, max_new >= 1, and len_bound,
+ * the host's bound on max_c(plen[c] + count[c]), against the position table.  The same call twice gives equal bits; bit equality across
+ * pack sizes is the operator's property, not this entry's (the GEMMs' split depends on the number of rows). */
+int gill_opt_score_candidates(gill_opt* h, const int64_t* ids, const void* embeds_bf16, const void* extra_rows_bf16, int n_extra,
+                              const int32_t* cu_new, const int32_t* parent, const int32_t* plen, const int64_t* target, int C, int total_new,
+                              int max_new, int len_bound, float* token_logprob, int32_t* token_rank, float* score_sum, int32_t* n_scored,
+                              float* score_mean, float* hidden_all, int32_t* flags, void* stream);
+
 /* ---- e4m3 KV cache ("kv8"): the cache of the ragged decode step and of the extend pass at half its bytes. ----
  *
  * The format.  Every key row and every value row of one token and one head (d elements, d = 64, 80 or 128) is d OCP e4m3 bytes and one
