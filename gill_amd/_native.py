@@ -111,6 +111,14 @@ SYMBOLS: Dict[str, Tuple[object, List[object]]] = {
   "gill_opt_extend": (_i, [_vp, _vp, _vp, _vp, _i, _vp, _vp, _i, _i, _i, _i, _vp, _vp, _vp]),
   "gill_attention_fork_ws_bytes": (C.c_int64, [_i, _i, _i, _i]),
   "gill_attention_fork": (_i, [_vp, _vp, _vp, _i, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _vp, _vp, C.c_int64, _vp]),
+  "gill_attention_branch": (_i, [_vp, _vp, _vp, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _vp, _vp]),
+  "gill_kv_branch_adopt": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _vp]),
+  "gill_opt_branch_reserve": (_i, [_vp, _i, _i]),
+  "gill_opt_branch_bytes": (C.c_int64, [_vp]),
+  "gill_opt_decode_step_branch": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _vp, _vp]),
+  "gill_opt_next_token_branch": (_i, [_vp, _vp, _i, C.POINTER(gill_decode_rule), _i, C.POINTER(gill_decode_sampler), _vp, _vp, _vp, _i, _vp,
+                                      _vp]),
+  "gill_opt_branch_adopt": (_i, [_vp, _i, _i, _i, _i, _vp]),
   "gill_opt_score_candidates": (_i, [_vp, _vp, _vp, _vp, _i, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
   "gill_opt_set_kv_format": (_i, [_vp, _i]),
   "gill_opt_kv_format": (_i, [_vp]),

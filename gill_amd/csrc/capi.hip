@@ -328,6 +328,29 @@ extern "C" int gill_attention_fork(const void* q, const void* k_new, const void*
   return 0;
 }
 
+extern "C" int gill_attention_branch(const void* q, const void* k_new, const void* v_new, int ld, const void* K, const void* Vt, void* Kb, void* Vtb,
+                                     const int32_t* gstart, const int32_t* gparent, const int32_t* gplen, const int32_t* lens, void* o, int S,
+                                     int G, int Sb, int Bc, int H, int d, int pitch, int bpitch, int32_t* flags, void* stream) {
+  AttnBranchArgs a;
+  a.q = (const bf16_t*)q; a.k = (const bf16_t*)k_new; a.v = (const bf16_t*)v_new; a.ld = ld;
+  a.K = (const bf16_t*)K; a.Vt = (const bf16_t*)Vt; a.Kb = (bf16_t*)Kb; a.Vtb = (bf16_t*)Vtb;
+  a.gstart = gstart; a.gparent = gparent; a.gplen = gplen; a.lens = lens; a.O = (bf16_t*)o; a.ldo = H * d; a.flags = flags;
+  a.S = S; a.G = G; a.Sb = Sb; a.Bc = Bc; a.H = H; a.dp = d; a.dpv = round_up(d, 32); a.pitch = pitch; a.bpitch = bpitch;
+  a.qscale = 1.4426950408889634f / sqrtf((float)d);
+  // a repeat stores the same new key and value at the same slot and reads only the slots below it: the same bits every time
+  for (int r = 0; r < op_repeat(); ++r) GILL_TRY(attention_branch_launch(a, (hipStream_t)stream));
+  return 0;
+}
+
+extern "C" int gill_kv_branch_adopt(const void* Kb, const void* Vtb, void* K, void* Vt, int Sb, int Bc, int H, int d, int pitch, int bpitch, int s,
+                                    int r, int plen, int count, void* stream) {
+  KvBranchAdoptArgs a;
+  a.Kb = (const bf16_t*)Kb; a.Vtb = (const bf16_t*)Vtb; a.K = (bf16_t*)K; a.Vt = (bf16_t*)Vt;
+  a.Sb = Sb; a.Bc = Bc; a.H = H; a.dp = d; a.dpv = round_up(d > 0 ? d : 1, 32); a.pitch = pitch; a.bpitch = bpitch;
+  a.s = s; a.r = r; a.plen = plen; a.count = count;
+  return kv_branch_adopt_launch(a, (hipStream_t)stream);
+}
+
 extern "C" int gill_attention_decode_kv8(const void* q, const void* k_new, const void* v_new, int ld, void* K8, void* Vt8, void* Kexp, void* Vexp,
                                          const int32_t* lens, void* o, int B, int H, int d, int pitch, int32_t* flags, void* stream) {
   AttnDecodeKv8Args a;

@@ -251,6 +251,35 @@ struct AttnForkArgs {
 size_t attention_fork_ws_bytes(int C, int H, int d, int max_new);   // host only
 int attention_fork_launch(const AttnForkArgs& a, hipStream_t s);
 
+// Branch decode attention (attention_branch.hip): S branches, ONE new token each, packed in G groups of at most 32 siblings.  Group g holds the
+// branches gstart[g] .. gstart[g + 1] - 1; all of them attend to the slots 0 .. gplen[g] - 1 of main-cache row gparent[g] (K / Vt: const, read
+// once per (group, head)) and each to its own branch-cache row: branch s has m = lens[s] - gplen[g] own cached tokens in Kb[s] / Vtb[s] and
+// stores its new key / value at slot m there.  O[s] = softmax(qscale * q_s . [K[p][0 .. n - 1] ; Kb[s][0 .. m - 1] ; k_s]) . [V.. ; Vb.. ; v_s].
+// n outside [0, pitch] or m outside [0, bpitch - 1] is clamped (flags[s] = 1); a parent outside [0, Bc) or a group of more than 32 / a range
+// outside [0, S] empties the group (flagged, no read through it).  A branch's bits depend on its own operands, its prefix, n, its row and m only.
+struct AttnBranchArgs {
+  const bf16_t* q = nullptr; const bf16_t* k = nullptr; const bf16_t* v = nullptr; int ld = 0;       // S rows
+  const bf16_t* K = nullptr; const bf16_t* Vt = nullptr;      // [Bc][H][pitch][dp], [Bc][H][dpv][pitch]
+  bf16_t* Kb = nullptr; bf16_t* Vtb = nullptr;                // [Sb][H][bpitch][dp], [Sb][H][dpv][bpitch]
+  const int32_t* gstart = nullptr; const int32_t* gparent = nullptr; const int32_t* gplen = nullptr;   // [G + 1], [G], [G] device
+  const int32_t* lens = nullptr;                              // [S] device: the branch's total position
+  bf16_t* O = nullptr; int ldo = 0;
+  int32_t* flags = nullptr;                                   // [S] device, nullable
+  int S = 0, G = 0, Sb = 0, Bc = 0, H = 0, dp = 0, dpv = 0, pitch = 0, bpitch = 0;
+  float qscale = 1.f;                                         // log2(e) / sqrt(head dim)
+};
+int attention_branch_launch(const AttnBranchArgs& a, hipStream_t s);
+
+// Adopt a branch into its dialogue (attention_branch.hip): Kb[s][h][0 .. count - 1] -> K[r][h][plen .. plen + count - 1], the matching columns of
+// Vtb[s] -> Vt[r], and the ones-row entry Vt[r][h][dp][slot] = 1 where dpv > dp (as attention_append writes it).  Host values; errors that
+// launch nothing: plen + count > pitch - 1, count > bpitch, s outside [0, Sb), r outside [0, Bc).  count == 0 is legal (nothing is launched).
+struct KvBranchAdoptArgs {
+  const bf16_t* Kb = nullptr; const bf16_t* Vtb = nullptr; bf16_t* K = nullptr; bf16_t* Vt = nullptr;
+  int Sb = 0, Bc = 0, H = 0, dp = 0, dpv = 0, pitch = 0, bpitch = 0;
+  int s = 0, r = 0, plen = 0, count = 0;
+};
+int kv_branch_adopt_launch(const KvBranchAdoptArgs& a, hipStream_t s);
+
 
 // The feed-forward sub-block + proj_out + outer residual of a level-0 transformer block (C = 320) as one kernel (ffn.hip):
 //   out = [Wp.W2 | Wp] . [ value * gelu(gate) | t ] + bo + resid,  [value | gate] = W1' . LN(t) + b1'  (LN from the row-sum planes).

@@ -38,6 +38,13 @@ struct gill_opt {
   float* ext_last = nullptr;      // [max_batch][D]
   // workspace of the fork attention under gill_opt_score_candidates (attention_fork_ws_bytes; grown at a call that needs more)
   void* fork_ws = nullptr; size_t fork_ws_bytes = 0;
+  // branch cache of gill_opt_decode_step_branch (gill_opt_branch_reserve): one slab, per layer Kb [br_rows][H][bpitch][dp] and
+  // Vtb [br_rows][H][dpv][bpitch] (TfmKv::pad = bpitch), then br_flags [br_rows]: the clamps of the branch attention, folded into the
+  // branches' flags by gill_opt_next_token_branch.  Not in the pool: a larger request frees and reallocates it
+  std::vector<TfmKv> br_cache;
+  void* br_slab = nullptr; size_t br_bytes = 0; int br_rows = 0;
+  int32_t* br_flags = nullptr;
+  ~gill_opt() { if (br_slab) (void)hipFree(br_slab); }
   // scoring workspace of gill_opt_forward_loss (allocated at its first call): the final LayerNorm of every row, the shifted targets, the
   // per-row results and the partials of lmloss.hip
   bf16_t* xn_bf = nullptr;      // [B*T][D]
@@ -736,9 +743,10 @@ extern "C" int gill_opt_pick_token_ragged(gill_opt* m, float* logits, int B, con
                               m->embed, m->cfg.hidden_size, tokens, ld, (bf16_t*)next_embeds_bf16, (hipStream_t)stream);
 }
 
-extern "C" int gill_opt_next_token_ragged(gill_opt* m, const float* hidden, int B, const gill_decode_rule* rule, int max_steps,
-                                          const gill_decode_sampler* sampler, float* logits_out, int32_t* state, int64_t* tokens, int ld,
-                                          void* next_embeds_bf16, void* stream) {
+// the ragged decision over B rows; clamp_flags: the [>= B] words the rows' attention step raised (the handle's dec_flags, or br_flags for branches)
+static int opt_next_token_ragged(gill_opt* m, const float* hidden, int B, const gill_decode_rule* rule, int max_steps,
+                                 const gill_decode_sampler* sampler, float* logits_out, int32_t* state, int64_t* tokens, int ld,
+                                 void* next_embeds_bf16, int32_t* clamp_flags, void* stream) {
   GILL_REQUIRE(m && hidden && logits_out && state && tokens && next_embeds_bf16, "null argument");
   DecodeRuleDev r;
   DecodeSampler sm;
@@ -746,6 +754,103 @@ extern "C" int gill_opt_next_token_ragged(gill_opt* m, const float* hidden, int 
   if (sampler) GILL_TRY(decode_sample_check(B, m->cfg.vocab_size, r, sm, m->cfg.hidden_size, kDecodeMaxIds + 1, 0));
   GILL_REQUIRE(ld >= 1 && m->cfg.hidden_size % 2 == 0, "ragged decode: bad shape");
   GILL_TRY(gill_opt_last_logits(m, hidden, B, 1, logits_out, stream));
-  return decode_ragged_launch(logits_out, B, m->cfg.vocab_size, r, rule->min_word_tokens, max_steps, sampler ? &sm : nullptr, state, m->dec_flags,
+  return decode_ragged_launch(logits_out, B, m->cfg.vocab_size, r, rule->min_word_tokens, max_steps, sampler ? &sm : nullptr, state, clamp_flags,
                               m->embed, m->cfg.hidden_size, tokens, ld, (bf16_t*)next_embeds_bf16, (hipStream_t)stream);
+}
+
+extern "C" int gill_opt_next_token_ragged(gill_opt* m, const float* hidden, int B, const gill_decode_rule* rule, int max_steps,
+                                          const gill_decode_sampler* sampler, float* logits_out, int32_t* state, int64_t* tokens, int ld,
+                                          void* next_embeds_bf16, void* stream) {
+  GILL_REQUIRE(m, "null argument");
+  return opt_next_token_ragged(m, hidden, B, rule, max_steps, sampler, logits_out, state, tokens, ld, next_embeds_bf16, m->dec_flags, stream);
+}
+
+// ---- branch decode: S sampled continuations of cached dialogues, one token each per step (csrc/attention_branch.hip) ----
+
+#define OPT_REQUIRE_BRANCH_BF16(m, what) \
+  GILL_REQUIRE((m)->kv_format == GILL_KV_BF16, what ": the handle's KV cache format is e4m3 (GILL_KV_E4M3); a branch cache is bf16 beside a bf16 cache")
+
+extern "C" int gill_opt_branch_reserve(gill_opt* m, int max_branches, int branch_capacity) {
+  GILL_REQUIRE(m, "null handle");
+  OPT_REQUIRE_BRANCH_BF16(m, "gill_opt_branch_reserve");
+  const int D = m->cfg.hidden_size, H = m->cfg.num_heads, dp = m->tfm.dp, dpv = m->tfm.dpv;
+  GILL_REQUIRE(dp == 64 || dp == 80 || dp == 128, "gill_opt_branch_reserve: branch attention needs a head dim of 64, 80 or 128");
+  GILL_REQUIRE(max_branches >= 1 && branch_capacity >= 1 && branch_capacity <= 1024, "gill_opt_branch_reserve: max_branches >= 1, 1 <= branch_capacity <= 1024");
+  // every buffer a step over max_branches rows writes: the stream, nbuf, ff and o hold max_batch * max_seq rows; the projection lands in
+  // Tfm::q, which takes 3 * S * D elements (Tfm::alloc: the larger of the flash operand and 48 D)
+  const int64_t R = (int64_t)m->cfg.max_batch * m->cfg.max_seq;
+  const int64_t qn = (int64_t)m->cfg.max_batch * H * round_up(m->cfg.max_seq, 32) * dp, qdec = (int64_t)48 * D;
+  GILL_REQUIRE(max_branches <= R, "gill_opt_branch_reserve: max_branches exceeds the workspace rows (max_batch * max_seq)");
+  GILL_REQUIRE((int64_t)3 * max_branches * D <= (qn > qdec ? qn : qdec), "gill_opt_branch_reserve: the projection of max_branches rows (3 * S * D) exceeds the workspace");
+  const int bpitch = round_up(branch_capacity, 32);
+  if (m->br_slab && m->br_rows >= max_branches && m->br_cache[0].pad >= bpitch) return 0;
+  if (m->br_slab) {
+    GILL_CHECK_HIP(hipDeviceSynchronize());
+    GILL_CHECK_HIP(hipFree(m->br_slab));
+    m->br_slab = nullptr; m->br_bytes = 0; m->br_rows = 0; m->br_flags = nullptr; m->br_cache.clear();
+  }
+  const size_t kn = (size_t)max_branches * H * bpitch * dp, vn = (size_t)max_branches * H * dpv * bpitch;     // elements; both byte sizes % 256 == 0
+  const size_t nl = m->layers.size();
+  const size_t bytes = nl * (kn + vn) * sizeof(bf16_t) + (((size_t)max_branches * sizeof(int32_t) + 255) & ~(size_t)255);
+  void* p = nullptr;
+  GILL_CHECK_HIP(hipMalloc(&p, bytes));
+  if (hipMemset(p, 0, bytes) != hipSuccess) {
+    (void)hipFree(p);
+    GILL_REQUIRE(false, "gill_opt_branch_reserve: hipMemset failed");
+  }
+  m->br_slab = p; m->br_bytes = bytes; m->br_rows = max_branches;
+  bf16_t* base = (bf16_t*)p;
+  m->br_cache.assign(nl, TfmKv{nullptr, nullptr, bpitch});
+  for (size_t i = 0; i < nl; ++i) {
+    m->br_cache[i].k = base + i * (kn + vn);
+    m->br_cache[i].vt = base + i * (kn + vn) + kn;
+    m->br_cache[i].fmt = GILL_KV_BF16;
+  }
+  m->br_flags = (int32_t*)(base + nl * (kn + vn));
+  return 0;
+}
+
+extern "C" int64_t gill_opt_branch_bytes(const gill_opt* m) { return m ? (int64_t)m->br_bytes : 0; }
+
+extern "C" int gill_opt_decode_step_branch(gill_opt* m, const void* new_embeds_bf16, const int32_t* lens_dev, const int32_t* gstart,
+                                           const int32_t* gparent, const int32_t* gplen, int S, int G, int len_bound, float* hidden_out,
+                                           void* stream) {
+  GILL_REQUIRE(m && new_embeds_bf16 && lens_dev && gstart && gparent && gplen && hidden_out, "null argument");
+  OPT_REQUIRE_BRANCH_BF16(m, "gill_opt_decode_step_branch");
+  GILL_REQUIRE(!m->cache.empty(), "gill_opt_decode_step_branch: the handle has no KV cache yet (a cached entry such as gill_opt_extend fills it)");
+  GILL_REQUIRE(m->br_slab, "gill_opt_decode_step_branch: no branch cache (gill_opt_branch_reserve)");
+  GILL_REQUIRE(S >= 1 && S <= m->br_rows, "gill_opt_decode_step_branch: S exceeds the reserved branches");
+  GILL_REQUIRE(G >= 1 && G <= S, "gill_opt_decode_step_branch: 1 <= G <= S");
+  GILL_REQUIRE(len_bound >= 1 && len_bound <= m->cfg.max_positions, "sequence longer than the position table");
+  hipStream_t s = (hipStream_t)stream;
+  GILL_TRY(opt_add_pos(m, new_embeds_bf16, lens_dev, S, 1, 0, s));
+  TfmDecode dec{lens_dev, m->br_flags};
+  dec.br = m->br_cache.data(); dec.br_main = m->cache.data();
+  dec.br_gstart = gstart; dec.br_gparent = gparent; dec.br_gplen = gplen;
+  dec.br_groups = G; dec.br_rows = m->br_rows; dec.br_main_rows = m->cfg.max_batch;
+  GILL_TRY(m->run_layers(S, 1, s, 0, &dec, gill_opt_decode_uses_w8(m, S) != 0));
+  return layernorm_f32out_launch(m->h, 1, m->lnfg, m->lnfb, hidden_out, S, m->cfg.hidden_size, 1e-5f, s);
+}
+
+extern "C" int gill_opt_next_token_branch(gill_opt* m, const float* hidden, int S, const gill_decode_rule* rule, int max_steps,
+                                          const gill_decode_sampler* sampler, float* logits_out, int32_t* state, int64_t* tokens, int ld,
+                                          void* next_embeds_bf16, void* stream) {
+  GILL_REQUIRE(m, "null argument");
+  GILL_REQUIRE(m->br_slab && S >= 1 && S <= m->br_rows, "gill_opt_next_token_branch: S exceeds the reserved branches (gill_opt_branch_reserve)");
+  return opt_next_token_ragged(m, hidden, S, rule, max_steps, sampler, logits_out, state, tokens, ld, next_embeds_bf16, m->br_flags, stream);
+}
+
+extern "C" int gill_opt_branch_adopt(gill_opt* m, int sidx, int r, int plen, int count, void* stream) {
+  GILL_REQUIRE(m, "null handle");
+  OPT_REQUIRE_BRANCH_BF16(m, "gill_opt_branch_adopt");
+  GILL_REQUIRE(!m->cache.empty() && m->br_slab, "gill_opt_branch_adopt: the handle needs its KV cache and a branch cache (gill_opt_branch_reserve)");
+  KvBranchAdoptArgs a;
+  a.Sb = m->br_rows; a.Bc = m->cfg.max_batch; a.H = m->cfg.num_heads; a.dp = m->tfm.dp; a.dpv = m->tfm.dpv;
+  a.s = sidx; a.r = r; a.plen = plen; a.count = count;
+  for (size_t i = 0; i < m->layers.size(); ++i) {      // the first layer's argument check speaks for all: nothing is launched before it
+    a.Kb = m->br_cache[i].k; a.Vtb = m->br_cache[i].vt; a.K = m->cache[i].k; a.Vt = m->cache[i].vt;
+    a.pitch = m->cache[i].pad; a.bpitch = m->br_cache[i].pad;
+    GILL_TRY(kv_branch_adopt_launch(a, (hipStream_t)stream));
+  }
+  return 0;
 }

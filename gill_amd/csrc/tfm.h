@@ -84,11 +84,18 @@ int tfm_linear_launch(const bf16_t* A, int M, const bf16_t* W, int blk, const fl
 // Fork mode (the scoring pass, gill_opt_score_candidates): cu_new set and fork_parent set.  The packed rows are nseq CANDIDATES; candidate c reads
 // the slots 0 .. fork_plen[c] - 1 of cache row fork_parent[c] < fork_rows and its own tokens (attention_fork_launch); the cache is not written
 // and lens is not read.  fork_ws / fork_ws_bytes: the operator's workspace, reused by every layer.
+// Branch mode (gill_opt_decode_step_branch): br set, cu_new null, T == 1.  The B rows are BRANCHES packed in br_groups groups (br_gstart /
+// br_gparent / br_gplen on the device, AttnBranchArgs); row s at position lens[s] reads the slots 0 .. br_gplen[g] - 1 of main-cache row
+// br_gparent[g] < br_main_rows and appends to row s < br_rows of the layer's branch cache br[layer] (pad = the branch pitch), layer = kv - br_main:
+// attention_branch_launch.  The main cache is not written.
 struct TfmDecode {
   const int32_t* lens = nullptr; int32_t* flags = nullptr;
   const int32_t* cu_new = nullptr; int nseq = 0, max_new = 0; bf16_t* qkv = nullptr;
   const int32_t* fork_parent = nullptr; const int32_t* fork_plen = nullptr; int fork_rows = 0;
   void* fork_ws = nullptr; size_t fork_ws_bytes = 0;
+  const TfmKv* br = nullptr; const TfmKv* br_main = nullptr;
+  const int32_t* br_gstart = nullptr; const int32_t* br_gparent = nullptr; const int32_t* br_gplen = nullptr;
+  int br_groups = 0, br_rows = 0, br_main_rows = 0;
 };
 
 struct TfmRun {

@@ -255,6 +255,18 @@ int TfmRun::self_attn(float* h, int B, int T, const TfmLayer& L, bool causal, co
       a.qscale = 1.4426950408889634f / sqrtf((float)t.dp);
       GILL_TRY(attention_extend_launch(a, s));
     }
+  } else if (dec && dec->br) {
+    GILL_REQUIRE(kv && T == 1 && kv->fmt == GILL_KV_BF16 && dec->br_main && dec->br_gstart && dec->br_gparent && dec->br_gplen,
+                 "branch attention: a bf16 cache, one token per branch and the groups");
+    const TfmKv& bk = dec->br[kv - dec->br_main];
+    GILL_TRY(linear(t.nbuf, B, L.qkv, nullptr, ACT_NONE, t.q, false));
+    AttnBranchArgs a;
+    a.q = t.q; a.k = t.q + t.D; a.v = t.q + 2 * t.D; a.ld = 3 * t.D;
+    a.K = kv->k; a.Vt = kv->vt; a.Kb = bk.k; a.Vtb = bk.vt;
+    a.gstart = dec->br_gstart; a.gparent = dec->br_gparent; a.gplen = dec->br_gplen; a.lens = dec->lens; a.O = t.o; a.ldo = t.D;
+    a.flags = dec->flags; a.S = B; a.G = dec->br_groups; a.Sb = dec->br_rows; a.Bc = dec->br_main_rows; a.H = t.H; a.dp = t.dp; a.dpv = t.dpv;
+    a.pitch = kv->pad; a.bpitch = bk.pad; a.qscale = 1.4426950408889634f / sqrtf((float)t.dp);
+    GILL_TRY(attention_branch_launch(a, s));
   } else if (dec) {
     GILL_REQUIRE(kv && T >= 1, "decode attention: a cache");
     GILL_TRY(linear(t.nbuf, B * T, L.qkv, nullptr, ACT_NONE, t.q, false));

@@ -166,6 +166,51 @@ def pack_candidates(rows: Sequence[Tuple[int, Sequence[int], int, int]], candida
   return [p for p in packs if p.n_candidates]
 
 
+BRANCH_GROUP = 32      # siblings per group of gill_attention_branch: the query lanes of one MFMA tile
+
+
+def pack_branches(rows: Sequence[int], n: int, lengths: Sequence[int]):
+  """The packing of DialogueSession.sample, pure host code.  rows: the cache rows of the sampled dialogues; n: branches per dialogue; lengths:
+  per dialogue the visible length of its cache row (len(history)).  Branches are ordered by dialogue (branch k * n + j is number j of rows[k])
+  and a dialogue's branches are cut into groups of at most BRANCH_GROUP.  -> (gstart (G + 1), gparent (G), gplen (G), [(row, index)] per
+  branch)."""
+  n = int(n)
+  if n < 1:
+    raise ValueError(f'n should be at least 1, got {n}')
+  if len(rows) != len(lengths):
+    raise ValueError(f'pack_branches needs one length per row ({len(rows)}), got {len(lengths)}')
+  gstart, gparent, gplen, own = [0], [], [], []
+  for r, ln in zip(rows, lengths):
+    for j0 in range(0, n, BRANCH_GROUP):
+      cnt = min(BRANCH_GROUP, n - j0)
+      own += [(int(r), j0 + j) for j in range(cnt)]
+      gstart.append(len(own))
+      gparent.append(int(r))
+      gplen.append(int(ln))
+  return gstart, gparent, gplen, own
+
+
+class BranchSet:
+  """What DialogueSession.sample returns: tokens (S, L) int64 on the device, padded with -1; n_tokens (S,) on the host; row (S,) the dialogue
+  each branch belongs to and index (S,) its number within that dialogue.  The branches' keys / values live in the handle's branch cache until
+  the next sample: adopt() is valid only while the set is current."""
+
+  def __init__(self, tokens, n_tokens, row, index, plen, serial):
+    self.tokens, self.n_tokens, self.row, self.index = tokens, n_tokens, row, index
+    self._plen, self._serial = plen, serial         # per branch its dialogue's length at sample time; the session's write serial
+    self._adopted = set()
+
+  def find(self, row: int, index: int) -> int:
+    for s, (r, j) in enumerate(zip(self.row, self.index)):
+      if r == int(row) and j == int(index):
+        return s
+    raise ValueError(f'the branch set holds no branch {index} of row {row}')
+
+  def reply(self, row: int, index: int) -> List[int]:
+    s = self.find(row, index)
+    return [int(v) for v in self.tokens[s, :int(self.n_tokens[s])].tolist()]
+
+
 def rank_order(scores: torch.Tensor) -> dict:
   """(n,) scores -> dict(scores, order: indices from the highest score down, ties in index order, NaN last; best: order[0] or None)."""
   sc = [float(v) for v in scores.tolist()]
@@ -192,6 +237,7 @@ class DialogueSession:
     self.extras: List[Optional[torch.Tensor]] = [None] * B      # per row (n_extra, D) bf16
     dev = model.logit_scale.device
     self.hidden_last = torch.zeros((B, 1, model.opt_cfg.hidden_size), device=dev, dtype=torch.float32)
+    self._serial = 0      # counts the calls that write the cache or change a book: a BranchSet is current while it stands (sample, adopt)
 
   def _check(self) -> None:
     check_epoch(self.epoch, self.model._cache_epoch)
@@ -211,6 +257,7 @@ class DialogueSession:
     if embeddings is not None:
       raise NotImplementedError('a session keeps token ids and visual rows: pass ids (negative ids for the rows of extra_rows), not embeddings')
     rows = self._rows(rows)
+    self._serial += 1
     if ids is None or len(ids) != len(rows):
       raise ValueError(f'extend needs one id sequence per named row ({len(rows)})')
     extra_rows = [None] * len(rows) if extra_rows is None else list(extra_rows)
@@ -265,6 +312,7 @@ class DialogueSession:
     decision, state untouched, cache intact, n_tokens 0.  row_ids: the Philox row ids of ALL B rows (default 0 .. B - 1)."""
     self._check()
     rows = self._rows(rows)
+    self._serial += 1
     m, B = self.model, self.B
     for r in rows:
       if not self.books[r].ready:
@@ -365,14 +413,111 @@ class DialogueSession:
           tokens[k][j] = out[first:first + n_own].clone()
     return (scores, tokens) if return_tokens else scores
 
+  def sample(self, rows, n: int, max_len: int = 32, temperature: float = 0.0, top_p: float = 1.0, seed: Optional[int] = None,
+             min_word_tokens: int = 0, ret_scale_factor: float = 1.0, gen_scale_factor: float = 1.0, filter_value: float = -float('Inf'),
+             keys=None) -> BranchSet:
+    """Draws n replies per named row from the row's cached history: S = len(rows) * n branches decode together, the siblings of a row sharing
+    its prefix where it lies (gill_opt_decode_step_branch over csrc/attention_branch.hip: the prefix is read once per group of up to 32
+    siblings, head and step; every branch keeps its own tokens in the handle's branch cache, reserved here for S branches of
+    max_len * len(retrieval_token_idx) + 1 tokens).  Every named row must be ready (extend ran); the first decision of all n branches of a row
+    reads that row's hidden_last.  temperature > 0 needs seed; branch j of row r draws with the Philox key (seed, keys[k * n + j], its decision
+    count), keys defaulting to r * n + j, so it draws what generate_batch(row_ids=[key]) draws from the same history.  n > 1 with
+    temperature == 0 is refused: all branches would be equal.  Returns a BranchSet.  The session is untouched: books, hidden_last, main cache
+    and epoch stay as they are; an e4m3 handle raises, naming the format."""
+    self._check()
+    rows = self._rows(rows)
+    m = self.model
+    n = int(n)
+    if n < 1 or not rows:
+      raise ValueError(f'sample needs at least one row and n >= 1, got {len(rows)} rows, n = {n}')
+    for r in rows:
+      if not self.books[r].ready:
+        raise RuntimeError(f'row {r} has nothing to decode from: extend it first (after a turn, a rollback or a reset)')
+    if temperature == 0.0 and top_p != 1.0:
+      raise ValueError('top_p cannot be set if temperature is 0 (greedy decoding).')
+    if temperature == 0.0 and n > 1:
+      raise ValueError(f'n = {n} branches with temperature 0 would all be equal: sample with temperature > 0 and a seed.')
+    if temperature != 0.0:
+      if seed is None:
+        raise ValueError('a session draws on the device only: temperature > 0 needs seed.')
+      seed = int(seed)
+      if not 0 <= seed < 2 ** 64:
+        raise ValueError(f'seed should be in [0, 2**64), got {seed} instead.')
+      assert top_p > 0, f'top_p should be above 0, got {top_p} instead.'
+    max_len = int(max_len)
+    n_ret = max(1, len(m.retrieval_token_idx))
+    L = max_len * n_ret
+    lengths = [len(self.books[r].ids) for r in rows]
+    if max(lengths) + L > m.opt_cfg.max_positions:
+      raise ValueError(f'{max(lengths)} tokens + max_len * {n_ret} = {max(lengths) + L} exceed the position table ({m.opt_cfg.max_positions}).')
+    S = len(rows) * n
+    keys = [r * n + j for r in rows for j in range(n)] if keys is None else [int(v) for v in torch.as_tensor(keys).reshape(-1).tolist()]
+    if len(keys) != S or min(keys) < 0:
+      raise ValueError(f'keys should be {S} integers >= 0 (one per branch, ordered by row).')
+    gstart, gparent, gplen, own = pack_branches(rows, n, lengths)
+    G = len(gparent)
+    dev = m.logit_scale.device
+    D, vocab = m.opt_cfg.hidden_size, m.opt_cfg.vocab_size
+    with torch.no_grad(), torch.cuda.device(dev):
+      N.check(N.lib().gill_opt_branch_reserve(self.handle, S, L + 1))      # an e4m3 handle: the engine's error names the format
+      self._serial += 1           # the branch cache is about to be rewritten: an earlier BranchSet is no longer current
+      st = torch.zeros(6 * S + 1, dtype=torch.int32)
+      st[:S] = torch.tensor([lengths[k] - 1 for k in range(len(rows)) for _ in range(n)], dtype=torch.int32)     # the newest token's position
+      st[4 * S:5 * S] = torch.tensor(keys, dtype=torch.int32)
+      st[6 * S] = S if max_len > 0 else 0
+      st = st.to(dev)
+      groups = torch.tensor(gstart + gparent + gplen, dtype=torch.int32).to(dev)
+      tokens = torch.full((S, max(L, 1)), -1, device=dev, dtype=torch.int64)
+      hid = self.hidden_last[rows, 0].repeat_interleave(n, dim=0).contiguous()        # a copy: hidden_last itself is never written
+      steps = torch.zeros((max(L, 1), S, D), device=dev, dtype=torch.float32)
+      nxt = torch.zeros((S, D), device=dev, dtype=torch.bfloat16)
+      logits = torch.empty((S, vocab), device=dev, dtype=torch.float32)
+      rule = m._decode_rule(0, min_word_tokens, ret_scale_factor, gen_scale_factor, filter_value)
+      sampler = None
+      if temperature != 0.0:
+        sampler = N.gill_decode_sampler()
+        sampler.temperature, sampler.top_p, sampler.seed = float(temperature), min(float(top_p), 1.0), seed
+      m._decode_host_waits = 0
+      m._branch_decode_loop(self.handle, S, G, groups, st, hid, steps, nxt, logits, tokens, rule, sampler, max_len, L, max(lengths))
+      n_tokens, _, _ = m._ragged_results(S, st, tokens, steps, L, n_ret)
+    return BranchSet(tokens[:, :L], n_tokens, [r for r, _ in own], [j for _, j in own], [lengths[rows.index(r)] for r, _ in own], self._serial)
+
+  def adopt(self, branch_set: BranchSet, row: int, index: int, keep: Optional[int] = None) -> None:
+    """Makes branch `index` of `row` the row's last turn: the first `keep` tokens of that reply (default: all) join the history, the keys /
+    values of all but the newest of them are copied from the branch cache into the row (gill_opt_branch_adopt; the newest token stays pending,
+    as after a generate).  rollback, extend, generate and score then behave as after a generate that had emitted those tokens.  Valid only
+    while the set is current: no later sample and no extend, generate, rollback or reset since, and one adopt per row."""
+    self._check()
+    r = self._rows([row])[0]
+    s = branch_set.find(r, index)
+    bk = self.books[r]
+    if branch_set._serial != self._serial or r in branch_set._adopted or len(bk.ids) != branch_set._plen[s]:
+      raise RuntimeError(f'the branch set is no longer current for row {r}: a later sample, extend, generate, rollback, reset or adopt changed the '
+                         f'branch cache or the row since it was drawn; sample again.')
+    nt = int(branch_set.n_tokens[s])
+    keep = nt if keep is None else int(keep)
+    if not 0 <= keep <= nt:
+      raise ValueError(f'adopt keeps 0 .. {nt} tokens of the reply, got {keep}')
+    plen = len(bk.ids)
+    if plen + keep > self.capacity - 1:
+      raise ValueError(f'row {r}: {plen} + {keep} tokens exceed the session\'s capacity - 1 = {self.capacity - 1}')
+    toks = branch_set.tokens[s, :keep].tolist()
+    if keep > 1:
+      with torch.cuda.device(self.model.logit_scale.device):
+        N.check(N.lib().gill_opt_branch_adopt(self.handle, s, r, plen, keep - 1, N.current_stream()))
+    branch_set._adopted.add(r)
+    bk.generated(toks)
+
   def rollback(self, row: int, keep: int) -> None:
     """Keeps only the first `keep` generated tokens of the row's last turn.  Costs nothing on the device."""
     self._check()
+    self._serial += 1
     self.books[self._rows([row])[0]].rollback(int(keep))
 
   def reset(self, rows) -> None:
     """Empties the rows: new dialogues can start in them while the others go on."""
     self._check()
+    self._serial += 1
     for r in self._rows(rows):
       self.books[r].reset()
       self.extras[r] = None
@@ -417,6 +562,32 @@ class GillDialogues:
     self.session = m.open_session(n, m.opt_cfg.max_positions if capacity is None else capacity)
     self._bos_done = [False] * int(n)
 
+  def _extend_turn(self, rows, turns, always_add_bos: bool) -> None:
+    """Segments the named dialogues' new turns (segment_turn), runs only the turn's images through the CLIP tower and extends the session."""
+    g, s = self.gill, self.session
+    m = g.model
+    nv = m.args.n_visual_tokens
+    ids, images, done = [], [], []
+    for b in rows:
+      p = turns[b]
+      i, im, d = segment_turn(m.tokenizer, [p] if isinstance(p, str) else list(p), nv, self._bos_done[b], always_add_bos, g._is_image)
+      ids.append(i)
+      images.append(im)
+      done.append(d)
+    flat = [im for row in images for im in row]
+    extra = [None] * len(rows)
+    if flat:
+      m._require_vision()
+      vis = g._visual_rows(flat)                       # only the new turn's images
+      at = 0
+      for k, row in enumerate(images):
+        if row:
+          extra[k] = vis[at:at + len(row) * nv]
+          at += len(row) * nv
+    s.extend(rows, ids=ids, extra_rows=extra)
+    for b, d in zip(rows, done):
+      self._bos_done[b] = d
+
   def say(self, turns, num_words: int = 32, min_word_tokens: int = 0, ret_scale_factor: float = 1.0, gen_scale_factor: float = 1.0,
           top_p: float = 1.0, temperature: float = 0.0, max_num_rets: int = 1, generator=None, always_add_bos: bool = False,
           guidance_scale: float = 7.5, num_inference_steps: int = 50, seed: Optional[int] = None, all_branches: bool = False,
@@ -439,27 +610,7 @@ class GillDialogues:
     rows = [b for b, t in enumerate(turns) if t is not None]
     if not rows:
       return [None] * s.B
-    nv = m.args.n_visual_tokens
-    ids, images, done = [], [], []
-    for b in rows:
-      p = turns[b]
-      i, im, d = segment_turn(m.tokenizer, [p] if isinstance(p, str) else list(p), nv, self._bos_done[b], always_add_bos, g._is_image)
-      ids.append(i)
-      images.append(im)
-      done.append(d)
-    flat = [im for row in images for im in row]
-    extra = [None] * len(rows)
-    if flat:
-      m._require_vision()
-      vis = g._visual_rows(flat)                       # only the new turn's images
-      at = 0
-      for k, row in enumerate(images):
-        if row:
-          extra[k] = vis[at:at + len(row) * nv]
-          at += len(row) * nv
-    s.extend(rows, ids=ids, extra_rows=extra)
-    for b, d in zip(rows, done):
-      self._bos_done[b] = d
+    self._extend_turn(rows, turns, always_add_bos)
     tokens, n_tok, hidden, n_hid = s.generate(rows, max_len=num_words, temperature=temperature, top_p=top_p, min_word_tokens=min_word_tokens,
                                               ret_scale_factor=ret_scale_factor, gen_scale_factor=gen_scale_factor, seed=seed)
     outputs, truncs = g._batch_outputs(rows, tokens, n_tok, hidden, n_hid, max_num_rets, generator, guidance_scale, num_inference_steps,
@@ -471,6 +622,54 @@ class GillDialogues:
     for b, o in zip(rows, outputs):
       out[b] = o
     return out
+
+  def propose(self, turns, n: int = 4, num_words: int = 32, temperature: float = 0.7, top_p: float = 0.95, seed: Optional[int] = None,
+              min_word_tokens: int = 0, always_add_bos: bool = False):
+    """Best-of-n for a turn: segments and extends turns[b] (None: dialogue b is idle) as say() does, samples n replies per active dialogue
+    from its cached history (DialogueSession.sample: the history is read once per group of siblings, not once per reply), truncates each
+    reply at the newline as say() does, and scores the truncated replies as continuations of the dialogue (DialogueSession.score,
+    reduce='mean').  Returns per dialogue None or dict(texts, tokens: the n truncated replies as strings and id lists, scores (n,) host fp32,
+    order: the reply indices from the most to the least likely, best).  Nothing is adopted: the dialogues hold the turn and wait for
+    choose(b, j), or for another propose / say.  temperature > 0 needs seed.
+    Scope: replies are returned as text and ids; no images are produced for an [IMG] block inside a proposed reply; all_branches is not
+    offered; nothing is sharded."""
+    g, s = self.gill, self.session
+    m = g.model
+    if len(turns) != s.B:
+      raise ValueError(f'propose() takes one entry per dialogue ({s.B}), got {len(turns)}')
+    if num_words <= 0:
+      raise ValueError(f'propose() needs num_words >= 1, got {num_words}')
+    s._check()
+    rows = [b for b, t in enumerate(turns) if t is not None]
+    out = [None] * s.B
+    self._proposal = None
+    if not rows:
+      return out
+    self._extend_turn(rows, turns, always_add_bos)
+    bs = s.sample(rows, n, max_len=num_words, temperature=temperature, top_p=top_p, seed=seed, min_word_tokens=min_word_tokens)
+    newline_token_id = m.tokenizer('\n', add_special_tokens=False).input_ids[0]
+    replies = []
+    for b in rows:
+      row = []
+      for j in range(int(n)):
+        ids = bs.reply(b, j)
+        trunc = next((i for i, t in enumerate(ids) if t == newline_token_id), 0)      # say()'s rule: a newline at 0 truncates nothing
+        row.append(ids[:trunc] if trunc > 0 else ids)
+      replies.append(row)
+    for b, row, sc in zip(rows, replies, s.score(rows, replies, reduce='mean')):
+      out[b] = dict(texts=[m.tokenizer.batch_decode(torch.tensor([ids], dtype=torch.int64), skip_special_tokens=True)[0] for ids in row], tokens=row, **rank_order(sc))
+    self._proposal = (bs, {b: [len(ids) for ids in row] for b, row in zip(rows, replies)})
+    return out
+
+  def choose(self, b: int, j: int) -> None:
+    """Adopts reply j of the last propose() as dialogue b's turn, truncated as it was shown (DialogueSession.adopt): the dialogue then stands as
+    after a say() that had produced that reply.  One choice per dialogue and proposal; valid until the next say, propose or reset."""
+    if getattr(self, '_proposal', None) is None:
+      raise RuntimeError('choose() follows a propose()')
+    bs, keeps = self._proposal
+    if b not in keeps or not 0 <= int(j) < len(keeps[b]):
+      raise ValueError(f'the last propose() holds no reply {j} of dialogue {b}')
+    self.session.adopt(bs, b, int(j), keep=keeps[b][int(j)])
 
   def rank(self, candidates, reduce: str = 'mean'):
     """candidates[b]: None, or a list of candidate reply strings for dialogue b.  Each is tokenised without <bos> (with it when the dialogue

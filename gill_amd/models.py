@@ -851,6 +851,32 @@ class GILLModel(nn.Module):
           if int(count[(it - 1) & 1]) == 0:
             break
 
+  def _branch_decode_loop(self, h, S: int, G: int, groups: Tensor, st: Tensor, hid: Tensor, steps: Tensor, nxt: Tensor, logits: Tensor,
+                          tokens: Tensor, rule, sampler, max_len: int, L: int, len0: int) -> None:
+    """_ragged_decode_loop over S branches of cached dialogues (DialogueSession.sample): the decode step is gill_opt_decode_step_branch (the
+    branches' groups: groups = [gstart (G + 1) | gparent (G) | gplen (G)] int32 on the device), the decision gill_opt_next_token_branch; the
+    same one-iteration-late read of the active count.  hid (S, D): every branch's copy of its dialogue's hidden_last."""
+    dev = st.device
+    lib = N.lib()
+    count = torch.zeros(2, dtype=torch.int32, pin_memory=True)
+    evs = [torch.cuda.Event(), torch.cuda.Event()]
+    gstart, gparent, gplen = groups, groups[G + 1:], groups[2 * G + 1:]
+    with torch.cuda.device(dev):
+      for it in range(L):
+        if it > 0:
+          N.check(lib.gill_opt_decode_step_branch(h, N.ptr(nxt), N.ptr(st), gstart.data_ptr(), gparent.data_ptr(), gplen.data_ptr(), S, G,
+                                                  len0 + it, N.ptr(steps[it - 1]), N.current_stream()))
+          hid = steps[it - 1]
+        N.check(lib.gill_opt_next_token_branch(h, N.ptr(hid), S, C.byref(rule), max_len, C.byref(sampler) if sampler is not None else None,
+                                               N.ptr(logits), N.ptr(st), N.ptr(tokens), tokens.shape[1], N.ptr(nxt), N.current_stream()))
+        count[it & 1:(it & 1) + 1].copy_(st[6 * S:], non_blocking=True)
+        evs[it & 1].record()
+        if it > 0:
+          evs[(it - 1) & 1].synchronize()
+          self._decode_host_waits += 1
+          if int(count[(it - 1) & 1]) == 0:
+            break
+
   def _ragged_results(self, B: int, st: Tensor, tokens: Tensor, steps: Tensor, L: int, n_ret: int):
     """The state a ragged loop left -> (n_tokens (B,), n_hidden (B,) on the host, hidden (B, L, D)); raises on the rows' error flags."""
     D = steps.shape[2]

@@ -254,6 +254,50 @@ def attention_fork(q: torch.Tensor, k_new: torch.Tensor, v_new: torch.Tensor, K:
   return o
 
 
+def attention_branch(q: torch.Tensor, k_new: torch.Tensor, v_new: torch.Tensor, K: torch.Tensor, Vt: torch.Tensor, Kb: torch.Tensor,
+                     Vtb: torch.Tensor, gstart: torch.Tensor, gparent: torch.Tensor, gplen: torch.Tensor, lens: torch.Tensor,
+                     flags: Optional[torch.Tensor] = None) -> torch.Tensor:
+  """Branch decode attention: S branches, one new token each, q / k_new / v_new (S, H*d) bf16 rows (each contiguous, or the three column
+  thirds of one (S, 3*H*d) projection).  K (Bc,H,pitch,d) and Vt (Bc,H,round_up(d,32),pitch) bf16 are the main cache, READ ONLY; Kb
+  (Sb,H,bpitch,d) and Vtb (Sb,H,round_up(d,32),bpitch) bf16 the branch cache, updated IN PLACE: branch s stores its new key / value at slot
+  lens[s] - gplen[g] of row s.  gstart (G + 1), gparent (G), gplen (G) and lens (S) int32 on the device: group g holds the branches
+  gstart[g] .. gstart[g + 1] - 1 (at most 32), which attend to the slots 0 .. gplen[g] - 1 of main-cache row gparent[g], then to their own
+  row.  flags (S) int32 (optional) receives 1 where a branch was clamped or its group emptied.  Returns (S, H*d) bf16."""
+  Bc, H, pitch, d = K.shape
+  Sb, bpitch = Kb.shape[0], Kb.shape[2]
+  S, G = q.shape[0], gparent.numel()
+  ld = q.stride(0)
+  dpv = (d + 31) // 32 * 32
+  for t in (q, k_new, v_new):
+    assert t.dtype == torch.bfloat16 and t.is_cuda and tuple(t.shape) == (S, H * d) and t.stride(1) == 1 and t.stride(0) == ld
+  assert K.dtype == torch.bfloat16 and Vt.dtype == torch.bfloat16 and tuple(Vt.shape) == (Bc, H, dpv, pitch)
+  assert Kb.dtype == torch.bfloat16 and Vtb.dtype == torch.bfloat16 and tuple(Kb.shape) == (Sb, H, bpitch, d) and tuple(Vtb.shape) == (Sb, H, dpv, bpitch)
+  for t in (K, Vt, Kb, Vtb):
+    assert t.is_cuda and t.is_contiguous()
+  for t, n in ((gstart, G + 1), (gparent, G), (gplen, G), (lens, S)):
+    assert t.dtype == torch.int32 and t.is_cuda and t.numel() == n
+  assert flags is None or (flags.dtype == torch.int32 and flags.numel() == S)
+  o = torch.empty((S, H * d), dtype=torch.bfloat16, device=q.device)
+  N.check(N.lib().gill_attention_branch(q.data_ptr(), k_new.data_ptr(), v_new.data_ptr(), ld, N.ptr(K), N.ptr(Vt), N.ptr(Kb), N.ptr(Vtb),
+                                        N.ptr(gstart), N.ptr(gparent), N.ptr(gplen), N.ptr(lens), N.ptr(o), S, G, Sb, Bc, H, d, pitch, bpitch,
+                                        N.ptr(flags), N.current_stream()))
+  return o
+
+
+def kv_branch_adopt(Kb: torch.Tensor, Vtb: torch.Tensor, K: torch.Tensor, Vt: torch.Tensor, s: int, r: int, plen: int, count: int) -> None:
+  """Adopt a branch into its dialogue: the first `count` keys / values of branch row s (Kb (Sb,H,bpitch,d), Vtb (Sb,H,round_up(d,32),bpitch))
+  are copied to the slots plen .. plen + count - 1 of row r of the main cache (K, Vt), IN PLACE, with the ones-row entries of those slots
+  where round_up(d,32) > d.  plen + count <= pitch - 1 and count <= bpitch; count = 0 is legal."""
+  Bc, H, pitch, d = K.shape
+  Sb, bpitch = Kb.shape[0], Kb.shape[2]
+  dpv = (d + 31) // 32 * 32
+  assert tuple(Vt.shape) == (Bc, H, dpv, pitch) and tuple(Kb.shape) == (Sb, H, bpitch, d) and tuple(Vtb.shape) == (Sb, H, dpv, bpitch)
+  for t in (Kb, Vtb, K, Vt):
+    assert t.dtype == torch.bfloat16 and t.is_cuda and t.is_contiguous()
+  N.check(N.lib().gill_kv_branch_adopt(N.ptr(Kb), N.ptr(Vtb), N.ptr(K), N.ptr(Vt), Sb, Bc, H, d, pitch, bpitch, int(s), int(r), int(plen),
+                                       int(count), N.current_stream()))
+
+
 def _kv8_cache_checks(K8: torch.Tensor, Vt8: torch.Tensor, Kexp: torch.Tensor, Vexp: torch.Tensor):
   B, H, pitch, d = K8.shape
   assert K8.dtype == torch.uint8 and Vt8.dtype == torch.uint8 and tuple(Vt8.shape) == (B, H, (d + 31) // 32 * 32, pitch)

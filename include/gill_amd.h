@@ -347,6 +347,35 @@ int gill_attention_fork(const void* q, const void* k_new, const void* v_new, int
                         const int32_t* plen, const int32_t* cu_new, void* o, int C, int Bc, int total_new, int max_new, int H, int d, int pitch,
                         int32_t* flags, void* ws, int64_t ws_bytes, void* stream);
 
+/* Branch decode attention: S sampled continuations ("branches") of cached dialogues decode ONE new token each.  q / k_new / v_new hold S rows
+ * of ld bf16 elements (head h at column h * d), o is (S, H*d) bf16.  The main cache K (Bc,H,pitch,d) / Vt (Bc,H,round_up(d,32),pitch) is
+ * const here; the branch cache Kb (Sb,H,bpitch,d) / Vtb (Sb,H,round_up(d,32),bpitch), bpitch % 32 == 0, Sb >= S, is written: branch s owns
+ * row s.  Branches are packed in G groups of at most 32 siblings by three int32 arrays on the DEVICE: gstart (G + 1), group g holds the
+ * branches gstart[g] .. gstart[g + 1] - 1; gparent (G), the main-cache row p all of them attend to; gplen (G), that row's visible length n,
+ * 0 <= n <= pitch (the host splits a dialogue with more than 32 branches into several groups).  lens (S) int32 on the device is the branch's
+ * total position: its own count is m = lens[s] - gplen[g], in [0, bpitch - 1].
+ *   o[s] = softmax(q_s . [K[p][0..n-1]; Kb[s][0..m-1]; k_new_s] / sqrt(d)) . [V[p][0..n-1]; Vb[s][0..m-1]; v_new_s]   (the scale in fp32),
+ * and k_new_s is stored at slot m of Kb[s], v_new_s at column m of Vtb[s] (no other word of the branch cache is written); the new key and
+ * value come from the input rows, never from the slot they are stored to.  The prefix of a group is read once per (group, head), not once
+ * per branch: the siblings are the query lanes of one MFMA tile (csrc/attention_branch.hip).  A branch's output bits and the bits it stores
+ * depend only on its own q / k / v, K[p][0..n-1] / V[p][0..n-1], n, its own branch row up to m, and m: not on S, G, the group's size, its
+ * siblings, its place in the pack or the index p.  Slots of row p at or beyond n and of the branch row at or beyond m are excluded by
+ * selection whatever bits they hold.  n outside [0, pitch] or m outside [0, bpitch - 1] is clamped and flags[s] (nullable, S int32) set to 1
+ * (a clamped n flags every branch of its group); a parent outside [0, Bc) empties the group and flags its branches; a group size outside
+ * [0, 32] or a range outside [0, S] empties the group with no read through it and flags branch min(max(gstart[g], 0), S - 1); nothing outside
+ * the buffers is touched.  An unsupported d (supported: 64, 80, 128), a misaligned pointer, bpitch % 32 != 0 (or above 1024) and S < 1 are
+ * errors, reported before anything is launched.  Honours GILL_OP_REPEAT. */
+int gill_attention_branch(const void* q, const void* k_new, const void* v_new, int ld, const void* K, const void* Vt, void* Kb, void* Vtb,
+                          const int32_t* gstart, const int32_t* gparent, const int32_t* gplen, const int32_t* lens, void* o, int S, int G,
+                          int Sb, int Bc, int H, int d, int pitch, int bpitch, int32_t* flags, void* stream);
+
+/* Adopt a branch into its dialogue: copies Kb[s][h][0..count-1] to K[r][h][plen..plen+count-1] and the matching columns of Vtb[s] to Vt[r],
+ * and writes the ones-row entry Vt[r][h][d][slot] = 1 where round_up(d,32) > d, as gill_attention_append does.  s, r, plen and count are
+ * host values.  plen + count > pitch - 1, count > bpitch, s outside [0, Sb) and r outside [0, Bc) are errors that launch nothing;
+ * count = 0 is legal. */
+int gill_kv_branch_adopt(const void* Kb, const void* Vtb, void* K, void* Vt, int Sb, int Bc, int H, int d, int pitch, int bpitch, int s, int r,
+                         int plen, int count, void* stream);
+
 /* The layers over C packed candidates in fork mode, then the fused LM-head loss of every packed row.  Input as in gill_opt_extend: ids
  * (total_new) int64 on the device (an id < 0 selects row -(id + 1) of extra_rows), or, with ids NULL, embeds (total_new, D) bf16.  Packed
  * row cu_new[c] + i takes position embedding 2 + plen[c] + i and attends to the slots 0 .. plen[c] - 1 of cache row parent[c] and to the
@@ -367,6 +396,31 @@ int gill_opt_score_candidates(gill_opt* h, const int64_t* ids, const void* embed
                               const int32_t* cu_new, const int32_t* parent, const int32_t* plen, const int64_t* target, int C, int total_new,
                               int max_new, int len_bound, float* token_logprob, int32_t* token_rank, float* score_sum, int32_t* n_scored,
                               float* score_mean, float* hidden_all, int32_t* flags, void* stream);
+
+/* ---- branch decode: draw several replies per dialogue from one cached history (gill_attention_branch under the layers). ----
+ *
+ * gill_opt_branch_reserve allocates, on a bf16-cache handle, the per-layer branch cache for max_branches branches of up to branch_capacity
+ * own tokens (bpitch = round_up(branch_capacity, 32), at most 1024) and the branches' clamp flags.  A GILL_KV_E4M3 handle is an error that
+ * names the format.  max_branches is checked against every buffer a step over that many rows writes (the workspace rows max_batch * max_seq,
+ * and the projection's 3 * S * D elements).  A later larger request frees and reallocates (it waits for the device); a request that fits
+ * keeps the buffers.  Branch contents do not outlive the next reserve.  gill_opt_branch_bytes reports the size (0 before a reserve). */
+int gill_opt_branch_reserve(gill_opt* h, int max_branches, int branch_capacity);
+int64_t gill_opt_branch_bytes(const gill_opt* h);
+/* gill_opt_decode_step over S branches: new_embeds (S, 1, D) bf16, row s takes position embedding 2 + lens_dev[s]; self-attention is the
+ * projection, gill_attention_branch (groups gstart (G + 1), gparent (G), gplen (G) on the device; branch s owns row s of the branch cache)
+ * and the out-projection; hidden_out (S, D) fp32 is hidden_states[-1] of the new rows.  The w8 linears by the rule of
+ * gill_opt_decode_uses_w8(h, S).  No host wait.  Writes only the branch cache (and the branches' clamp flags); it does not allocate the main
+ * cache: a handle without one is an error, as is S beyond the reserve.  len_bound: the host's bound on max_s(lens[s]) + 1, against the
+ * position table. */
+int gill_opt_decode_step_branch(gill_opt* h, const void* new_embeds_bf16, const int32_t* lens_dev, const int32_t* gstart, const int32_t* gparent,
+                                const int32_t* gplen, int S, int G, int len_bound, float* hidden_out, void* stream);
+/* gill_opt_next_token_ragged over S branches: the same decision and state (branch s draws with key (seed, row_id[s], its decision count)),
+ * folding the branches' clamp flags (sized by the reserve, where gill_opt_next_token_ragged folds the max_batch words of the decode step). */
+int gill_opt_next_token_branch(gill_opt* h, const float* hidden, int S, const gill_decode_rule* rule, int max_steps,
+                               const gill_decode_sampler* sampler, float* logits_out, int32_t* state, int64_t* tokens, int ld,
+                               void* next_embeds_bf16, void* stream);
+/* gill_kv_branch_adopt over all layers: the first `count` own tokens of branch s become the slots plen .. plen + count - 1 of cache row r. */
+int gill_opt_branch_adopt(gill_opt* h, int s, int r, int plen, int count, void* stream);
 
 /* ---- e4m3 KV cache ("kv8"): the cache of the ragged decode step and of the extend pass at half its bytes. ----
  *
