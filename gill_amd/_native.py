@@ -186,6 +186,7 @@ SYMBOLS: Dict[str, Tuple[object, List[object]]] = {
   "gill_op_conv3x3_gn": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _f, _i, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _vp]),
   "gill_op_conv3x3_shortcut": (_i, [_vp, _i, _vp, _i, _vp, _vp, _vp, _i, _vp, _i, _vp, _vp, _i, _i, _i, _i, _i, _vp]),
   "gill_op_ffn_fused": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _vp, _vp, _vp, _vp]),
+  "gill_op_ffn_fused_ex": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _vp, _vp, _vp, _vp, _i, _i, _vp]),
   "gill_op_geglu_fp8": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _vp]),
   "gill_conv_fp8_kpad": (_i, [_i]),
   "gill_op_quant_fp8": (_i, [_vp, _f, C.c_int64, _vp, _vp]),
@@ -196,6 +197,7 @@ SYMBOLS: Dict[str, Tuple[object, List[object]]] = {
   "gill_op_ln_quant_fp8": (_i, [_vp, _i, _i, _vp, _i, _i, _f, _f, _vp, _vp]),
   "gill_op_geglu_fp8_q": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _vp]),
   "gill_op_lnproj": (_i, [_i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _vp]),
+  "gill_op_lnproj_ex": (_i, [_i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _vp, _vp]),
   "gill_op_cross_attention_folded": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp]),
   "gill_op_linear_rowstats": (_i, [_vp, _vp, _i, _vp, _vp, _vp, _vp, _vp, _i, C.POINTER(C.c_int), _i, _i, _i, _i, _vp]),
   "gill_op_ln_gemm": (_i, [_i, _vp, _vp, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _vp]),

@@ -88,15 +88,22 @@ extern "C" int gill_op_sd_inpaint_run(const gill_sd_sampler* sampler, int v_pred
 // of t, launches the kernel.  out = proj_out(ff2(geglu(ff1(LN(t)))) + t) + resid.  For tests/test_ops_gpu.py and tools; synchronises.
 // o2 / Wo / bo2 (optional, all or none): the PRE form — t := t + to_out(o2) first, inside the kernel (o2 [M][320] = the cross-attention
 // output, heads x 40; Wo [320][320], bo2 [320]: BasicTransformerBlock.attn2.to_out[0]).
-extern "C" int gill_op_ffn_fused(const void* t, const float* ln_g, const float* ln_b, const void* W1, const float* b1, const void* W2,
-                                 const float* b2, const void* Wp, const float* bp, const void* resid, void* out, float* gn_stats,
-                                 int M, int rows_per_batch, const void* o2, const void* Wo, const float* bo2, void* stream) {
+// ln_stats (optional, non-PRE form only): the caller's row-sum planes [ln_planes][R][2] (GemmArgs::row_stats layout, R = ln_rows ? ln_rows : M;
+// rows m >= R read the sums of row m - R) in place of the one plane the entry forms itself.
+static int op_ffn_fused(const void* t, const float* ln_g, const float* ln_b, const void* W1, const float* b1, const void* W2,
+                        const float* b2, const void* Wp, const float* bp, const void* resid, void* out, float* gn_stats,
+                        int M, int rows_per_batch, const void* o2, const void* Wo, const float* bo2, const float* ln_stats, int ln_planes,
+                        int ln_rows, void* stream) {
   hipStream_t s = (hipStream_t)stream;
   const XfHeads hd = xf_heads(8, 40);
   const int C = 320, inner = 4 * C, heads = hd.heads, d = hd.d, dp = hd.dp, hdp = hd.hdp;
   GILL_REQUIRE(t && ln_g && ln_b && W1 && b1 && W2 && b2 && Wp && bp && resid && out, "null argument");
   GILL_REQUIRE((o2 != nullptr) == (Wo != nullptr) && (o2 != nullptr) == (bo2 != nullptr), "o2 / Wo / bo2: all or none");
   GILL_REQUIRE(ffn_fused_supported(C, M), "ffn_fused: M must be a multiple of 128");
+  GILL_REQUIRE(ln_stats || (ln_planes == 0 && ln_rows == 0), "ffn_fused: ln_planes / ln_rows describe the caller's ln_stats");
+  GILL_REQUIRE(!ln_stats || !o2, "ffn_fused: row-sum planes belong to the form without attn2.to_out in front (that one forms its own statistics)");
+  GILL_REQUIRE(!ln_stats || (ln_planes >= 1 && ln_rows >= 0 && ln_rows <= M && (ln_rows == 0 || M <= 2 * ln_rows)),
+               "ffn_fused: ln_planes >= 1, and rows m >= ln_rows read row m - ln_rows: M <= 2 ln_rows");
   DevBuf idx, wff1, bff1, sff1, wfo, bfo, w1c, b1c, w2p, st, wpp, o2p, wop;
   if (o2) {
     GILL_TRY(wpp.alloc(sizeof(bf16_t) * (size_t)C * C));
@@ -113,10 +120,15 @@ extern "C" int gill_op_ffn_fused(const void* t, const float* ln_g, const float* 
   GILL_TRY(w1c.alloc(sizeof(bf16_t) * (size_t)8 * C * C)); GILL_TRY(b1c.alloc(sizeof(float) * 8 * C)); GILL_TRY(w2p.alloc(sizeof(bf16_t) * (size_t)4 * C * C));
   GILL_TRY(ffn_relayout_launch((const bf16_t*)wff1.p, (const float*)bff1.p, (const bf16_t*)wfo.p, (bf16_t*)w1c.p, (float*)b1c.p,
                                (bf16_t*)w2p.p, o2 ? (bf16_t*)wpp.p : nullptr, s));
-  GILL_TRY(st.alloc(sizeof(float) * (size_t)M * 2));
-  GILL_TRY(row_sums_launch((const bf16_t*)t, M, C, (float*)st.p, s));
   FfnArgs fa;
-  fa.M = M; fa.T = (const bf16_t*)t; fa.ln_stats = (const float*)st.p; fa.ln_planes = 1;
+  fa.M = M; fa.T = (const bf16_t*)t;
+  if (ln_stats) {
+    fa.ln_stats = ln_stats; fa.ln_planes = ln_planes; fa.ln_rows = ln_rows;
+  } else {
+    GILL_TRY(st.alloc(sizeof(float) * (size_t)M * 2));
+    GILL_TRY(row_sums_launch((const bf16_t*)t, M, C, (float*)st.p, s));
+    fa.ln_stats = (const float*)st.p; fa.ln_planes = 1;
+  }
   fa.W1c = (const bf16_t*)w1c.p; fa.b1c = (const float*)b1c.p; fa.W2p = (const bf16_t*)w2p.p;
   fa.Wfo = (const bf16_t*)wfo.p; fa.bo = (const float*)bfo.p; fa.resid = (const bf16_t*)resid; fa.out = (bf16_t*)out;
   fa.gn_stats = gn_stats; fa.rows_per_batch = rows_per_batch;
@@ -124,6 +136,18 @@ extern "C" int gill_op_ffn_fused(const void* t, const float* ln_g, const float* 
   for (int r = 0, rep = op_repeat(); r < rep; ++r) GILL_TRY(ffn_fused_launch(fa, s));
   GILL_CHECK_HIP(hipStreamSynchronize(s));
   return 0;
+}
+extern "C" int gill_op_ffn_fused(const void* t, const float* ln_g, const float* ln_b, const void* W1, const float* b1, const void* W2,
+                                 const float* b2, const void* Wp, const float* bp, const void* resid, void* out, float* gn_stats,
+                                 int M, int rows_per_batch, const void* o2, const void* Wo, const float* bo2, void* stream) {
+  return op_ffn_fused(t, ln_g, ln_b, W1, b1, W2, b2, Wp, bp, resid, out, gn_stats, M, rows_per_batch, o2, Wo, bo2, nullptr, 0, 0, stream);
+}
+extern "C" int gill_op_ffn_fused_ex(const void* t, const float* ln_g, const float* ln_b, const void* W1, const float* b1, const void* W2,
+                                    const float* b2, const void* Wp, const float* bp, const void* resid, void* out, float* gn_stats,
+                                    int M, int rows_per_batch, const void* o2, const void* Wo, const float* bo2, const float* ln_stats,
+                                    int ln_planes, int ln_rows, void* stream) {
+  return op_ffn_fused(t, ln_g, ln_b, W1, b1, W2, b2, Wp, bp, resid, out, gn_stats, M, rows_per_batch, o2, Wo, bo2, ln_stats, ln_planes, ln_rows,
+                      stream);
 }
 
 // Operator-level entry for the fp8 GEGLU projection (linear_fp8.hip) on NATURAL operands (diffusers parameter layouts): the loader's GEGLU recipe
@@ -191,8 +215,9 @@ extern "C" int gill_op_geglu_fp8_q(const void* x8, const void* w8, const float* 
 //   mode 0: t = W1 . x + b1;  [q | k | v] = W2 . LN(t)            x [M][320], W2 [3 * 320][320] = to_q | to_k | to_v rows
 //   mode 1: t = W1 . x + b1 + t;  q = W2 . LN(t)                  x [M][320] = the attention output (heads x 40), W2 [320][320]
 // q, k: [B][8][hw_pad][48] (q scaled by log2(e) / sqrt(40)); vt: [B][8][64][hw_pad] with row 48 = 1.  For tests and tools; synchronises.
-extern "C" int gill_op_lnproj(int mode, const void* x, void* t, const void* W1, const float* b1, const float* ln_g, const float* ln_b,
-                              const void* W2, void* q, void* k, void* vt, int B, int HW, void* stream) {
+// gn_ss (optional, mode 0 with HW % 128 == 0): [B][2][320] GroupNorm scale | shift the kernel applies to the rows of x as it loads them.
+static int op_lnproj(int mode, const void* x, void* t, const void* W1, const float* b1, const float* ln_g, const float* ln_b,
+                     const void* W2, void* q, void* k, void* vt, int B, int HW, const float* gn_ss, void* stream) {
   hipStream_t s = (hipStream_t)stream;
   const XfHeads hd = xf_heads(8, 40);
   const int C = 320, heads = hd.heads, d = hd.d, dp = hd.dp, dpv = hd.dpv, hdp = hd.hdp, M = B * HW;
@@ -210,7 +235,7 @@ extern "C" int gill_op_lnproj(int mode, const void* x, void* t, const void* W1, 
   LnProjArgs a;
   a.mode = mode; a.M = M; a.T = (bf16_t*)t; a.b1 = b1; a.W2p = (const bf16_t*)w2p.p; a.c2 = (const float*)cb.p;
   a.Cq = (bf16_t*)q; a.Ck = (bf16_t*)k; a.Cvt = (bf16_t*)vt; a.heads = heads; a.dp = dp; a.dpv = dpv; a.ntok = HW; a.ntok_pad = round_up(HW, 32);
-  a.qscale = hd.qscale;
+  a.qscale = hd.qscale; a.gn_ss = gn_ss;
   if (mode == 0) {
     a.X = (const bf16_t*)x; a.W1 = (const bf16_t*)W1;
   } else {
@@ -223,6 +248,14 @@ extern "C" int gill_op_lnproj(int mode, const void* x, void* t, const void* W1, 
   for (int r = 0, rep = op_repeat(); r < rep; ++r) GILL_TRY(lnproj_launch(a, s));
   GILL_CHECK_HIP(hipStreamSynchronize(s));
   return 0;
+}
+extern "C" int gill_op_lnproj(int mode, const void* x, void* t, const void* W1, const float* b1, const float* ln_g, const float* ln_b,
+                              const void* W2, void* q, void* k, void* vt, int B, int HW, void* stream) {
+  return op_lnproj(mode, x, t, W1, b1, ln_g, ln_b, W2, q, k, vt, B, HW, nullptr, stream);
+}
+extern "C" int gill_op_lnproj_ex(int mode, const void* x, void* t, const void* W1, const float* b1, const float* ln_g, const float* ln_b,
+                                 const void* W2, void* q, void* k, void* vt, int B, int HW, const float* gn_ss, void* stream) {
+  return op_lnproj(mode, x, t, W1, b1, ln_g, ln_b, W2, q, k, vt, B, HW, gn_ss, stream);
 }
 
 // Op-level entry of the two-GEMM cross-attention ("XALG", xf_weights.hip) on a torch-layout attn2 (to_q / to_out [C][C], to_k / to_v [C][E], heads

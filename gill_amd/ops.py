@@ -478,12 +478,15 @@ def conv3x3_fp8(x: torch.Tensor, w_oihw: torch.Tensor, bias: Optional[torch.Tens
 
 def ffn_fused(t: torch.Tensor, ln_g: torch.Tensor, ln_b: torch.Tensor, w1: torch.Tensor, b1: torch.Tensor, w2: torch.Tensor,
               b2: torch.Tensor, wp: torch.Tensor, bp: torch.Tensor, resid: torch.Tensor, rows_per_batch: int = 0,
-              o2: Optional[torch.Tensor] = None, wo: Optional[torch.Tensor] = None, bo2: Optional[torch.Tensor] = None):
+              o2: Optional[torch.Tensor] = None, wo: Optional[torch.Tensor] = None, bo2: Optional[torch.Tensor] = None,
+              ln_stats: Optional[torch.Tensor] = None, ln_rows: int = 0):
   """The feed-forward sub-block of a C = 320 transformer block + proj_out + outer residual as one kernel (csrc/ffn.hip):
   out = (t + ff2(value * gelu(gate))) @ wp.T + bp + resid with [value | gate] = LN(t) @ w1.T + b1 (diffusers layouts: w1 (2560, 320),
   w2 (320, 1280), wp (320, 320)).  t, resid (M, 320) bf16, M % 128 == 0.  Returns out (M, 320) bf16 [, GroupNorm partial sums
   (M / 64, 64, 2) fp32 when rows_per_batch > 0].  o2 / wo / bo2 (all or none): t := t + o2 @ wo.T + bo2 first, inside the kernel
-  (BasicTransformerBlock.attn2.to_out + its residual; o2 (M, 320), wo (320, 320)) — the form the UNet engine runs."""
+  (BasicTransformerBlock.attn2.to_out + its residual; o2 (M, 320), wo (320, 320)) — the form the UNet engine runs.
+  ln_stats (planes, R, 2) fp32 (not with o2): the caller's row-sum planes {sum, sum of squares} of t in place of the one plane the entry
+  forms itself, R = ln_rows or M; rows m >= R read the sums of row m - R (M <= 2 R)."""
   t, w1, w2, wp, resid = (_bf(x) for x in (t, w1, w2, wp, resid))
   M = t.shape[0]
   # outputs start as NaN: the engine hands these kernels stale arena memory, so a tile the kernel forgot to write must show in a test
@@ -493,18 +496,25 @@ def ffn_fused(t: torch.Tensor, ln_g: torch.Tensor, ln_b: torch.Tensor, w1: torch
   ln_g, ln_b, b1, b2, bp = f(ln_g), f(ln_b), f(b1), f(b2), f(bp)
   if o2 is not None:       # the PRE form: t := t + o2 @ wo.T + bo2 first, inside the kernel
     o2, wo, bo2 = _bf(o2), _bf(wo), f(bo2)
-  N.check(N.lib().gill_op_ffn_fused(N.ptr(t), N.ptr(ln_g), N.ptr(ln_b), N.ptr(w1), N.ptr(b1), N.ptr(w2), N.ptr(b2), N.ptr(wp), N.ptr(bp),
-                                    N.ptr(resid), N.ptr(out), N.ptr(stats), M, rows_per_batch, N.ptr(o2), N.ptr(wo), N.ptr(bo2),
-                                    N.current_stream()))
+  planes = 0
+  if ln_stats is not None:
+    assert ln_stats.is_cuda and ln_stats.dtype == torch.float32 and ln_stats.is_contiguous() and ln_stats.dim() == 3 and ln_stats.shape[2] == 2
+    planes = ln_stats.shape[0]
+    assert ln_stats.shape[1] == (ln_rows or M), "ln_stats: (planes, ln_rows or M, 2)"
+  N.check(N.lib().gill_op_ffn_fused_ex(N.ptr(t), N.ptr(ln_g), N.ptr(ln_b), N.ptr(w1), N.ptr(b1), N.ptr(w2), N.ptr(b2), N.ptr(wp), N.ptr(bp),
+                                       N.ptr(resid), N.ptr(out), N.ptr(stats), M, rows_per_batch, N.ptr(o2), N.ptr(wo), N.ptr(bo2),
+                                       N.ptr(ln_stats), planes, ln_rows, N.current_stream()))
   return (out, stats) if rows_per_batch else out
 
 
 def lnproj(mode: int, x: torch.Tensor, t, w1: torch.Tensor, b1: torch.Tensor, ln_g: torch.Tensor, ln_b: torch.Tensor, w2: torch.Tensor,
-           B: int, HW: int):
+           B: int, HW: int, gn_ss: Optional[torch.Tensor] = None):
   """The two projections around norm1 (mode 0) / norm2 (mode 1) of a C = 320, 8-head transformer block as one kernel (csrc/lnproj.hip).
   mode 0: t = x @ w1.T + b1; q, k, v = LN(t) @ w2.T with w2 (960, 320) = to_q | to_k | to_v.  mode 1: t = t + x @ w1.T + b1 (x = the
   attention output); q = LN(t) @ w2.T with w2 (320, 320).  Returns (t (M, 320) bf16, q, k, vt) in the attention kernels' layouts
-  (q, k (B, 8, hw_pad, 48), q pre-scaled by log2(e) / sqrt(40); vt (B, 8, 64, hw_pad) with row 48 = 1); k, vt None in mode 1."""
+  (q, k (B, 8, hw_pad, 48), q pre-scaled by log2(e) / sqrt(40); vt (B, 8, 64, hw_pad) with row 48 = 1); k, vt None in mode 1.
+  gn_ss (B, 2, 320) fp32 (mode 0, HW % 128 == 0): the block's GroupNorm as per-sample scale | shift rows, applied to the rows of x as
+  the kernel loads them (x := bf16(x * scale + shift))."""
   x, w1, w2 = (_bf(v) for v in (x, w1, w2))
   M = B * HW
   hw_pad = (HW + 31) // 32 * 32
@@ -516,8 +526,10 @@ def lnproj(mode: int, x: torch.Tensor, t, w1: torch.Tensor, b1: torch.Tensor, ln
   vt = torch.full((B, 8, 64, hw_pad), nan, device=x.device, dtype=torch.bfloat16) if mode == 0 else None
   f = lambda v: v.float().contiguous()
   b1, ln_g, ln_b = f(b1), f(ln_g), f(ln_b)
-  N.check(N.lib().gill_op_lnproj(mode, N.ptr(x), N.ptr(t), N.ptr(w1), N.ptr(b1), N.ptr(ln_g), N.ptr(ln_b), N.ptr(w2), N.ptr(q), N.ptr(k),
-                                 N.ptr(vt), B, HW, N.current_stream()))
+  if gn_ss is not None:
+    assert gn_ss.is_cuda and gn_ss.dtype == torch.float32 and gn_ss.is_contiguous() and tuple(gn_ss.shape) == (B, 2, 320)
+  N.check(N.lib().gill_op_lnproj_ex(mode, N.ptr(x), N.ptr(t), N.ptr(w1), N.ptr(b1), N.ptr(ln_g), N.ptr(ln_b), N.ptr(w2), N.ptr(q), N.ptr(k),
+                                    N.ptr(vt), B, HW, N.ptr(gn_ss), N.current_stream()))
   return t, q, k, vt
 
 

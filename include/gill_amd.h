@@ -871,6 +871,14 @@ int gill_op_ffn_fused(const void* t_bf16, const float* ln_g, const float* ln_b, 
                       const void* W2_bf16, const float* b2, const void* Wp_bf16, const float* bp, const void* resid_bf16,
                       void* out_bf16, float* gn_stats, int M, int rows_per_batch, const void* o2_bf16, const void* Wo_bf16,
                       const float* bo2, void* stream);
+/* The same with the caller's LayerNorm row-sum planes, as the engine passes the ones its producing GEMM filed: ln_stats (nullable: the entry
+ * then forms one plane itself, as gill_op_ffn_fused) [ln_planes][R][2] fp32 {sum, sum of squares} of the rows of t, added in plane order,
+ * R = ln_rows ? ln_rows : M; rows m >= R read the sums of row m - R (M <= 2 ln_rows).  Not together with o2 (that form takes the
+ * statistics in registers): an error. */
+int gill_op_ffn_fused_ex(const void* t_bf16, const float* ln_g, const float* ln_b, const void* W1_bf16, const float* b1,
+                         const void* W2_bf16, const float* b2, const void* Wp_bf16, const float* bp, const void* resid_bf16,
+                         void* out_bf16, float* gn_stats, int M, int rows_per_batch, const void* o2_bf16, const void* Wo_bf16,
+                         const float* bo2, const float* ln_stats, int ln_planes, int ln_rows, void* stream);
 
 /* BASELINE configs[4] (not a reference function): the GEGLU projection of a BasicTransformerBlock (diffusers ff.net.0; reference call site
  * gill/custom_sd.py:633-638) on CDNA4's fp8 matrix instruction — out (M, inner) bf16 = h * gelu(g), [h | g] = LayerNorm(t; ln_g, ln_b) W^T + b with
@@ -887,6 +895,11 @@ int gill_op_geglu_fp8(const void* t, const float* ln_g, const float* ln_b, const
  * Synchronises. */
 int gill_op_lnproj(int mode, const void* x_bf16, void* t_bf16, const void* W1_bf16, const float* b1, const float* ln_g, const float* ln_b,
                    const void* W2_bf16, void* q_bf16, void* k_bf16, void* vt_bf16, int B, int HW, void* stream);
+/* The same with the block's GroupNorm applied to the rows of x as the kernel loads them, the form the UNet engine runs where a sample is
+ * whole 128-row tiles: gn_ss (nullable) [B][2][320] fp32 = per sample the scale row, then the shift row; x := bf16(x * scale + shift).
+ * With a table: mode 0 and HW % 128 == 0 only (an error otherwise: nothing is launched). */
+int gill_op_lnproj_ex(int mode, const void* x_bf16, void* t_bf16, const void* W1_bf16, const float* b1, const float* ln_g, const float* ln_b,
+                      const void* W2_bf16, void* q_bf16, void* k_bf16, void* vt_bf16, int B, int HW, const float* gn_ss, void* stream);
 
 /* attn2 (cross-attention) of a UNet transformer block with heads of 80..160 features, as the two GEMMs on per-sample weights the engine
  * runs at UNet levels 1-3 (csrc/xf_weights.hip "XALG"): K and V are linear in the prompt context, so qs (g o Wq_h)^T Wk_h and Wo_h Wv_h are
